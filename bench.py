@@ -16,7 +16,11 @@ the ranks (scene replicated); each rank renders its own tiles into its own linea
 and when a frame's last sample index is done the films are summed onto rank 0 with ONE RCCL reduce over xGMI, inside
 the timed region (strong scaling: the frame is fixed).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step = wall milliseconds of one timed step,
+config).  A plain run sets up, warms up, times the steps and prints;
+`--full` adds the `roofline` object (with an instrumented launch of its own), the `cpu_baseline` (the oracle on the host's cores)
+and `film_check` (the film's digest against profiles/film_checksums.json; a mismatch fails the run); without it those are null.
+`--dump-outputs DIR` writes the film of the last timed step (see dump_film).
 """
 import argparse
 import ctypes
@@ -58,6 +62,26 @@ def film_digest(t):
     return hashlib.sha256(a.tobytes()).hexdigest(), float(a64.mean()) if a64.size else 0.0, float(a64.max()) if a64.size else 0.0, int((~fin).sum())
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 21     # 24 MB of film values + 16 MB of their indices
+
+
+def dump_film(t, out_dir):
+    """The film the timed steps left (what a caller of render_accum_device receives) as out_dir/film.npy, float32 H x W x 3.  A film
+    above DUMP_MAX_BYTES is written as a fixed sample instead: film_sample.npy (pixels x 3) and film_sample_index.npy (their row-major
+    pixel indices, float64), the pixels drawn once from a seeded generator, so two runs of the same arguments write the same pixels."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    a = t.detach().cpu().contiguous().numpy().astype(np.float32, copy=False)
+    if a.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "film.npy"), a)
+        return
+    px = a.reshape(-1, a.shape[-1])
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(out_dir, "film_sample.npy"), px[idx])
+    np.save(os.path.join(out_dir, "film_sample_index.npy"), idx.astype(np.float64))
+
+
 def find_profile(name, wl):
     """the committed counter pass (tools/profile_bench.sh -> profiles/<name>*.json) taken on exactly this workload"""
     import glob
@@ -85,8 +109,16 @@ def main():
     ap.add_argument("--sampler", default="sobol")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target CPU-baseline duration")
-    ap.add_argument("--write-film-checksum", action="store_true", help="record this run's film digest in profiles/film_checksums.json (commit it)")
+    ap.add_argument("--write-film-checksum", action="store_true", help="record this run's film digest in profiles/film_checksums.json (commit it; needs --full)")
+    ap.add_argument("--full", action="store_true", help="also the roofline (an instrumented launch of its own), the CPU baseline and the film "
+                                                        "digest checked against profiles/film_checksums.json; off: the timed steps alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the film they rendered to DIR/film.npy (float32 H x W x 3, "
+                                                          "linear sums; above 64 MB a fixed seeded sample of pixels instead)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.write_film_checksum and not args.full:
+        ap.error("--write-film-checksum needs --full")
 
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -176,12 +208,15 @@ def main():
     total = samples_per_step * args.steps
     value = total / dt / 1e6
 
+    if rank == 0 and args.dump_outputs:
+        dump_film(accum, args.dump_outputs)
+
     # ---- what the timed launches rendered: the last step's film (reduced onto rank 0) against the committed digest.  Frames are
     # bit-identical from run to run and independent of the tile sharding (disjoint tiles, deterministic in-wave schedule), so for the
     # library build the digest was recorded with, any N must reproduce the sha256; another build may sum a pixel's samples in another
     # order, then the film's mean has to agree to 1e-5.  A mismatch fails the run: a bench line over a wrong picture is worth nothing.
     film_check = None
-    if rank == 0 and frame_per_step and args.steps > 0:
+    if args.full and rank == 0 and frame_per_step:
         key = f"scene{args.scene} {W}x{H} {args.strategy}+{args.sampler} {spp_job}spp"
         sha, mean, mx, non_finite = film_digest(accum)
         path = os.path.join(ROOT, "profiles", "film_checksums.json")
@@ -201,87 +236,89 @@ def main():
 
     out = None
     if rank == 0:
-        # ---- roofline: algorithmic bytes / measured kernel time (rank 0's launches) ----
-        st = pkg.ffi.Stats()
-        sp = pkg.make_params(spp_job, args.strategy, args.sampler, shard_index=rank, shard_count=world, collect_stats=2)
-        scratch = torch.zeros((H, W, 3), dtype=torch.float32, device="cuda")
-        prod.render_accum_device(scene, cam, sp, 0, 4, scratch.data_ptr(), stream, stats=st)
-        sd = st.as_dict()
-        bps = algorithmic_bytes_per_sample(sd, spp_job)
-        avg_ms = sum(kernel_ms) / len(kernel_ms)
-        launch_samples = samples_per_step / world
-        achieved = bps * launch_samples / (avg_ms * 1e-3) / 1e9
-        algo = {"model": "production traversal (collect_stats=2): 112 B/DevNode4 visit, 48 B/triangle test, 336 B/closest hit, 16 B/spectrum, 48 B CMF",
-                "bytes_per_sample": round(bps, 1), "GBps": round(achieved, 2), "frac_of_l2_request_rate": None,
-                "bytes_per_launch": round(bps * launch_samples),
-                "per_sample": {k: round(sd[k] / max(sd["samples"], 1), 3) for k in
-                               ("closest_rays", "shadow_rays", "nodes_closest", "tris_closest", "nodes_shadow", "tris_shadow",
-                                "closest_hits", "bounces", "spectrum_evals", "textured_lookups")}}
-        # What bounds the kernel is VALU issue on a cache-resident working set, not HBM: `achieved` / `peak` / `frac` are
-        # wave-level VALU instructions per second against the chip's issue peak.  The instruction count per sample comes from the
-        # committed SQ PMC pass of THIS workload on THIS library build (tools/profile_bench.sh -> profiles/pmc_valu.json; counters
-        # cannot be read from inside the process), the duration is measured live.  The SURVEY 8(d) algorithmic-bytes figure stays as
-        # `algorithmic` (frac_of_hbm_peak is what round 1 reported as `frac`), the PMC HBM traffic as `traffic` / `hbm_*`.
-        wl = {"scene": args.scene, "width": W, "height": H, "spp": spp_job, "spp_per_step": sps,
-              "strategy": args.strategy, "sampler": args.sampler, "n_gpus": world}
-        roofline = {"bound": "valu", "achieved": None, "peak": round(PEAK_VALU_GINSTR, 1), "unit": "Gwave-instr/s", "frac": None, "traffic": None,
-                    "kernel": "pt_kernel<STATS=false,FEAT=scene feature mask,MODE>", "kernel_ms_avg": round(avg_ms, 3),
-                    "valu": None, "algorithmic": algo}
-        vj, vsrc = find_profile("pmc_valu", wl)
-        if vj:
-            try:
-                # the count belongs to a workload; a build other than the profiled one is used too, but flagged (the count moves by a few
-                # per cent between kernel versions, the duration is always live)
-                ips = vj["SQ_INSTS_VALU_per_launch"] / vj["samples_per_launch"]
-                ach = ips * launch_samples / (avg_ms * 1e-3) / 1e9
-                lane_use = vj["SQ_THREAD_CYCLES_VALU_per_launch"] / (64.0 * vj["SQ_INSTS_VALU_per_launch"])
-                roofline.update({"achieved": round(ach, 1), "frac": round(ach / PEAK_VALU_GINSTR, 4)})
-                roofline["valu"] = {"wave_instr_per_sample": round(ips, 1), "issue_frac": round(ach / PEAK_VALU_GINSTR, 4),
-                                    "lane_use": round(lane_use, 4), "useful_lane_frac": round(ach / PEAK_VALU_GINSTR * lane_use, 4),
-                                    "source": vsrc, "profiled_library": vj.get("library"),
-                                    "profile_matches_build": vj.get("library") == prod.version()}
-                wc = vj.get("SQ_WAVE_CYCLES_per_launch")
-                if wc:
-                    roofline["valu"]["wave_cycle_shares"] = {k[3:].lower(): round(vj[k + "_per_launch"] / wc, 4) for k in
-                                                             ("SQ_ACTIVE_INST_VALU", "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_SCA", "SQ_ACTIVE_INST_LDS")
-                                                             if k + "_per_launch" in vj}
-                # the memory-pipeline side of the bound (same committed passes): the vector-memory path of a CU takes one L1 tag lookup per
-                # clock; a per-lane dwordx4 gather costs up to 64 of them
-                if "TCP_TOTAL_CACHE_ACCESSES_sum_per_launch" in vj and vj.get("unprofiled_launch_ms"):
-                    n_cu, clk = 256.0, vj.get("gpu_clock_ghz", 2.4)
-                    cyc = vj["unprofiled_launch_ms"] * 1e-3 * clk * 1e9
-                    l1 = {"tag_lookups_per_clk_per_cu": round(vj["TCP_TOTAL_CACHE_ACCESSES_sum_per_launch"] / n_cu / cyc, 4), "peak": 1.0,
-                          "clock_ghz_assumed": clk}
-                    if "TA_TA_BUSY_sum_per_launch" in vj:
-                        l1["ta_busy"] = round(vj["TA_TA_BUSY_sum_per_launch"] / n_cu / cyc, 4)
-                    if "SQ_INSTS_VMEM_RD_per_launch" in vj:
-                        l1["lookups_per_wave_load"] = round(vj["TCP_TOTAL_CACHE_ACCESSES_sum_per_launch"] / vj["SQ_INSTS_VMEM_RD_per_launch"], 2)
-                        l1["wave_loads_per_sample"] = round(vj["SQ_INSTS_VMEM_RD_per_launch"] / vj["samples_per_launch"], 2)
-                    if "TCP_TCC_READ_REQ_sum_per_launch" in vj:
-                        l1["l1_hit_rate"] = round(1.0 - vj["TCP_TCC_READ_REQ_sum_per_launch"] / vj["TCP_TOTAL_CACHE_ACCESSES_sum_per_launch"], 4)
-                    roofline["l1"] = l1
-            except Exception as e:
-                roofline["valu_error"] = repr(e)
-        pj, psrc = find_profile("pmc_traffic", wl)
-        if pj and pj.get("library") == prod.version():
-            try:
-                # HBM bytes per launch from the committed rocprofv3 PMC passes (tools/profile_bench.sh: separate
-                # FETCH_SIZE / WRITE_SIZE runs of this same command, gfx950 correction applied); only valid for
-                # the workload and library build it was collected on
-                roofline["traffic"] = pj.get("hbm_bytes_per_launch")
-                roofline["traffic_source"] = psrc
-                roofline["hbm_GBps"] = round(roofline["traffic"] / (avg_ms * 1e-3) / 1e9, 1)
-                roofline["hbm_frac"] = round(roofline["hbm_GBps"] / PEAK_HBM_GBPS, 5)
-                if "TCC_HIT_sum_per_launch" in pj:
-                    req = pj["TCC_HIT_sum_per_launch"] + pj["TCC_MISS_sum_per_launch"]
-                    roofline["l2_request_GBps"] = round(req * 128.0 / (avg_ms * 1e-3) / 1e9, 1)
-                    roofline["l2_hit_rate"] = round(pj["TCC_HIT_sum_per_launch"] / req, 4)
-                    algo["frac_of_l2_request_rate"] = round(achieved / roofline["l2_request_GBps"], 4)
-            except Exception:
-                pass
+        roofline = None
+        if args.full:
+            # ---- roofline: algorithmic bytes / measured kernel time (rank 0's launches) ----
+            st = pkg.ffi.Stats()
+            sp = pkg.make_params(spp_job, args.strategy, args.sampler, shard_index=rank, shard_count=world, collect_stats=2)
+            scratch = torch.zeros((H, W, 3), dtype=torch.float32, device="cuda")
+            prod.render_accum_device(scene, cam, sp, 0, 4, scratch.data_ptr(), stream, stats=st)
+            sd = st.as_dict()
+            bps = algorithmic_bytes_per_sample(sd, spp_job)
+            avg_ms = sum(kernel_ms) / len(kernel_ms)
+            launch_samples = samples_per_step / world
+            achieved = bps * launch_samples / (avg_ms * 1e-3) / 1e9
+            algo = {"model": "production traversal (collect_stats=2): 112 B/DevNode4 visit, 48 B/triangle test, 336 B/closest hit, 16 B/spectrum, 48 B CMF",
+                    "bytes_per_sample": round(bps, 1), "GBps": round(achieved, 2), "frac_of_l2_request_rate": None,
+                    "bytes_per_launch": round(bps * launch_samples),
+                    "per_sample": {k: round(sd[k] / max(sd["samples"], 1), 3) for k in
+                                   ("closest_rays", "shadow_rays", "nodes_closest", "tris_closest", "nodes_shadow", "tris_shadow",
+                                    "closest_hits", "bounces", "spectrum_evals", "textured_lookups")}}
+            # What bounds the kernel is VALU issue on a cache-resident working set, not HBM: `achieved` / `peak` / `frac` are
+            # wave-level VALU instructions per second against the chip's issue peak.  The instruction count per sample comes from the
+            # committed SQ PMC pass of THIS workload on THIS library build (tools/profile_bench.sh -> profiles/pmc_valu.json; counters
+            # cannot be read from inside the process), the duration is measured live.  The SURVEY 8(d) algorithmic-bytes figure stays as
+            # `algorithmic` (frac_of_hbm_peak is what round 1 reported as `frac`), the PMC HBM traffic as `traffic` / `hbm_*`.
+            wl = {"scene": args.scene, "width": W, "height": H, "spp": spp_job, "spp_per_step": sps,
+                  "strategy": args.strategy, "sampler": args.sampler, "n_gpus": world}
+            roofline = {"bound": "valu", "achieved": None, "peak": round(PEAK_VALU_GINSTR, 1), "unit": "Gwave-instr/s", "frac": None, "traffic": None,
+                        "kernel": "pt_kernel<STATS=false,FEAT=scene feature mask,MODE>", "kernel_ms_avg": round(avg_ms, 3),
+                        "valu": None, "algorithmic": algo}
+            vj, vsrc = find_profile("pmc_valu", wl)
+            if vj:
+                try:
+                    # the count belongs to a workload; a build other than the profiled one is used too, but flagged (the count moves by a few
+                    # per cent between kernel versions, the duration is always live)
+                    ips = vj["SQ_INSTS_VALU_per_launch"] / vj["samples_per_launch"]
+                    ach = ips * launch_samples / (avg_ms * 1e-3) / 1e9
+                    lane_use = vj["SQ_THREAD_CYCLES_VALU_per_launch"] / (64.0 * vj["SQ_INSTS_VALU_per_launch"])
+                    roofline.update({"achieved": round(ach, 1), "frac": round(ach / PEAK_VALU_GINSTR, 4)})
+                    roofline["valu"] = {"wave_instr_per_sample": round(ips, 1), "issue_frac": round(ach / PEAK_VALU_GINSTR, 4),
+                                        "lane_use": round(lane_use, 4), "useful_lane_frac": round(ach / PEAK_VALU_GINSTR * lane_use, 4),
+                                        "source": vsrc, "profiled_library": vj.get("library"),
+                                        "profile_matches_build": vj.get("library") == prod.version()}
+                    wc = vj.get("SQ_WAVE_CYCLES_per_launch")
+                    if wc:
+                        roofline["valu"]["wave_cycle_shares"] = {k[3:].lower(): round(vj[k + "_per_launch"] / wc, 4) for k in
+                                                                 ("SQ_ACTIVE_INST_VALU", "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_SCA", "SQ_ACTIVE_INST_LDS")
+                                                                 if k + "_per_launch" in vj}
+                    # the memory-pipeline side of the bound (same committed passes): the vector-memory path of a CU takes one L1 tag lookup per
+                    # clock; a per-lane dwordx4 gather costs up to 64 of them
+                    if "TCP_TOTAL_CACHE_ACCESSES_sum_per_launch" in vj and vj.get("unprofiled_launch_ms"):
+                        n_cu, clk = 256.0, vj.get("gpu_clock_ghz", 2.4)
+                        cyc = vj["unprofiled_launch_ms"] * 1e-3 * clk * 1e9
+                        l1 = {"tag_lookups_per_clk_per_cu": round(vj["TCP_TOTAL_CACHE_ACCESSES_sum_per_launch"] / n_cu / cyc, 4), "peak": 1.0,
+                              "clock_ghz_assumed": clk}
+                        if "TA_TA_BUSY_sum_per_launch" in vj:
+                            l1["ta_busy"] = round(vj["TA_TA_BUSY_sum_per_launch"] / n_cu / cyc, 4)
+                        if "SQ_INSTS_VMEM_RD_per_launch" in vj:
+                            l1["lookups_per_wave_load"] = round(vj["TCP_TOTAL_CACHE_ACCESSES_sum_per_launch"] / vj["SQ_INSTS_VMEM_RD_per_launch"], 2)
+                            l1["wave_loads_per_sample"] = round(vj["SQ_INSTS_VMEM_RD_per_launch"] / vj["samples_per_launch"], 2)
+                        if "TCP_TCC_READ_REQ_sum_per_launch" in vj:
+                            l1["l1_hit_rate"] = round(1.0 - vj["TCP_TCC_READ_REQ_sum_per_launch"] / vj["TCP_TOTAL_CACHE_ACCESSES_sum_per_launch"], 4)
+                        roofline["l1"] = l1
+                except Exception as e:
+                    roofline["valu_error"] = repr(e)
+            pj, psrc = find_profile("pmc_traffic", wl)
+            if pj and pj.get("library") == prod.version():
+                try:
+                    # HBM bytes per launch from the committed rocprofv3 PMC passes (tools/profile_bench.sh: separate
+                    # FETCH_SIZE / WRITE_SIZE runs of this same command, gfx950 correction applied); only valid for
+                    # the workload and library build it was collected on
+                    roofline["traffic"] = pj.get("hbm_bytes_per_launch")
+                    roofline["traffic_source"] = psrc
+                    roofline["hbm_GBps"] = round(roofline["traffic"] / (avg_ms * 1e-3) / 1e9, 1)
+                    roofline["hbm_frac"] = round(roofline["hbm_GBps"] / PEAK_HBM_GBPS, 5)
+                    if "TCC_HIT_sum_per_launch" in pj:
+                        req = pj["TCC_HIT_sum_per_launch"] + pj["TCC_MISS_sum_per_launch"]
+                        roofline["l2_request_GBps"] = round(req * 128.0 / (avg_ms * 1e-3) / 1e9, 1)
+                        roofline["l2_hit_rate"] = round(pj["TCC_HIT_sum_per_launch"] / req, 4)
+                        algo["frac_of_l2_request_rate"] = round(achieved / roofline["l2_request_GBps"], 4)
+                except Exception:
+                    pass
         # ---- CPU baseline: the oracle in faithful mode on this box's host cores (rank 0, N=1 only) ----
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import ptoracle
             orc = ptoracle.Oracle(native=True)

@@ -713,13 +713,43 @@ def test_bench_n_gpus_reproduces_the_one_gpu_film_bit_for_bit():
     digests = {}
     for n in (1, 2):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "1", "--warmup", "1", "--width", "256", "--height", "200",
-                            "--spp", "64", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
+                            "--spp", "64", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
         assert r.returncode == 0, r.stderr[-2000:]
         line = [l for l in r.stdout.splitlines() if l.startswith("{") and '"metric"' in l][-1]
         j = json.loads(line)
         assert j["n_gpus"] == n and j["film_check"] and j["film_check"]["mean"] > 0.01
         digests[n] = j["film_check"]["sha256"]
     assert digests[1] == digests[2], digests
+
+
+def test_bench_dumps_the_film_of_its_timed_steps(tmp_path):
+    """bench.py --dump-outputs on a small frame, plainly and with --full: the plain line carries the headline fields and none of
+    --full's extras, both runs write the same film bit for bit (same arguments, same inputs), and it is the film whose digest --full
+    reports (`film_check.sha256`).  Child processes, like the bench runs of the test above."""
+    import hashlib
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, films = {}, {}
+    for mode in ("plain", "full"):
+        d = tmp_path / mode
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--width", "256", "--height", "200",
+                            "--spp", "64", "--dump-outputs", str(d)] + (["--full", "--no-cpu-baseline"] if mode == "full" else []),
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[mode] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{") and '"metric"' in l][-1])
+        films[mode] = np.load(d / "film.npy")
+    p, f = lines["plain"], lines["full"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert p.get(k) is not None, k
+    assert p["steps"] == 3 and p["ms_per_step"] > 0 and p["unit"] == "Msamples/s" and p["dtype"] == "f32"
+    assert p["roofline"] is None and p["cpu_baseline"] is None and p["film_check"] is None
+    assert f["roofline"] is not None and f["film_check"] is not None
+    assert films["plain"].dtype == np.float32 and films["plain"].shape == (200, 256, 3)
+    assert np.isfinite(films["plain"]).all() and films["plain"].mean() > 0.01
+    assert np.array_equal(films["plain"], films["full"])
+    assert hashlib.sha256(films["full"].tobytes()).hexdigest() == f["film_check"]["sha256"]
 
 
 def test_rr_gate_slack_is_refused_unless_unlocked(product, pkg):
