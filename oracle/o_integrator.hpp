@@ -253,7 +253,11 @@ struct PathTracer {
         Ray ray = move_forward(cam.sample_ray(px, py, uvp), RAY_EPS);
         Intersection hit;
         if (c) c->samples++;
-        auto finish = [&]() { if (c) c->sampler_draws += smp.draws; *wl_out = wl; return L; };
+        auto finish = [&]() {
+            if (c) { c->sampler_draws += smp.draws; c->max_dimension = std::max<uint64_t>(c->max_dimension, smp.dimension); }
+            *wl_out = wl;
+            return L;
+        };
         if (!scene.intersect(ray, std::numeric_limits<float>::max(), &hit, c)) {                  // base_renderer.rs:180-187
             L = L + T * infinite_radiance(ray.d, wl);
             return finish();

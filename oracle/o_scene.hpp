@@ -293,6 +293,7 @@ struct Counters {
     TraversalCounters flat_closest, flat_any;     // steps through the product's exported tree (FlatBvh)
     uint64_t closest_rays = 0, shadow_rays = 0, closest_hits = 0, bounces = 0, samples = 0, sampler_draws = 0;
     uint64_t spectrum_evals = 0, textured_lookups = 0;
+    uint64_t max_dimension = 0;                   // the highest sampler dimension a path reached (a maximum, not a sum)
     void add(const Counters& o) {
         auto a = [](TraversalCounters& x, const TraversalCounters& y) { x.nodes += y.nodes; x.items += y.items; };
         a(closest_tlas, o.closest_tlas); a(closest_blas, o.closest_blas); a(any_tlas, o.any_tlas); a(any_blas, o.any_blas);
@@ -300,6 +301,7 @@ struct Counters {
         closest_rays += o.closest_rays; shadow_rays += o.shadow_rays; closest_hits += o.closest_hits;
         bounces += o.bounces; samples += o.samples; sampler_draws += o.sampler_draws;
         spectrum_evals += o.spectrum_evals; textured_lookups += o.textured_lookups;
+        max_dimension = std::max(max_dimension, o.max_dimension);
     }
 };
 

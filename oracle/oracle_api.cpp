@@ -248,6 +248,9 @@ int ptoracle_scene_set_flat_bvh(ptoracle_scene* s, const void* nodes, uint32_t n
     return 0;
 }
 void ptoracle_reset_counters(ptoracle_scene* s) { s->counters = Counters(); }
+// the highest sampler dimension a path reached since the last reset (a maximum, so not one of the 20 sums above: callers size that buffer
+// for exactly 20 values, and a 21st would be written past its end)
+uint64_t ptoracle_get_max_dimension(const ptoracle_scene* s) { return s->counters.max_dimension; }
 
 // ---- probes ----
 int ptoracle_probe_sobol(uint32_t width, uint32_t height, uint32_t spp, uint32_t seed, const uint32_t* xys, uint32_t n,

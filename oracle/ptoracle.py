@@ -37,6 +37,8 @@ class Oracle(ffi.Backend):
         lib.ptoracle_get_counters.restype = None
         lib.ptoracle_reset_counters.argtypes = [C.c_void_p]
         lib.ptoracle_reset_counters.restype = None
+        lib.ptoracle_get_max_dimension.argtypes = [C.c_void_p]
+        lib.ptoracle_get_max_dimension.restype = C.c_uint64
         lib.ptoracle_scene_set_faithful.argtypes = [C.c_void_p, C.c_int]
         lib.ptoracle_probe_fresnel_complex.argtypes = [C.c_float, C.c_float, C.c_float]
         lib.ptoracle_probe_fresnel_complex.restype = C.c_float
@@ -108,9 +110,11 @@ class Oracle(ffi.Backend):
     def counters(self, scene, reset=True):
         v = (C.c_uint64 * 20)()
         self.lib.ptoracle_get_counters(scene.h, v)
+        out = dict(zip(self.COUNTER_NAMES, [int(x) for x in v]))
+        out["max_dimension"] = int(self.lib.ptoracle_get_max_dimension(scene.h))     # (a maximum, not one of the 20 sums)
         if reset:
             self.lib.ptoracle_reset_counters(scene.h)
-        return dict(zip(self.COUNTER_NAMES, [int(x) for x in v]))
+        return out
 
     def set_flat_bvh(self, scene, nodes, tris, root):
         """Hand the product's exported tree (Product.export_bvh) to the oracle: it is walked for step COUNTING only."""

@@ -252,3 +252,30 @@ def test_device_sincos_restatement_equals_the_host_libm(tmp_path):
     assert out["compared"] >= 36_000_000 and out["sin_mismatches"] == 0 and out["cos_mismatches"] == 0
     assert out["libm_sincosf_differs_from_sinf_cosf"] == 0 and out["out_of_range_refused"] is True
     assert out["exp_compared"] >= 36_000_000 and out["exp_mismatches"] <= 2      # expf_glibc (the optional bit-exact sigmoid, PT_SIGMOID_EXACT)
+
+
+# sampler draws per path: 3 at the camera (wavelengths, pixel offset), at most 8 per bounce (BSDF 1 + 2, light pick 1, light sample 1 + 2,
+# roulette 1).  The tail-queue record of the production kernels (csrc/pt_kernel.hpp tq_store) keeps the sampler dimension in 15 bits, which
+# api.cpp check_args guards with max_depth <= 1000: 3 + 8 * 1000 = 8003 < 2^15.
+DRAWS_AT_CAMERA, DRAWS_PER_BOUNCE = 3, 8
+
+
+@pytest.mark.parametrize("scene_id,strategy", [(36, "mis"), (36, "nee"), (21, "mis"), (21, "nee"), (34, "nee")])
+def test_deepest_sampler_dimension_fits_the_queue_record(oracle, pkg, scene_id, strategy):
+    """At max_depth = 1000 the highest sampler dimension any path reaches (the oracle's max_dimension counter) stays within the draw budget
+    above and below 2^15.  Scenes with the most draws per bounce: the clearcoat box (36) and the spot + directional + area light set
+    (21); the deep white box (34) runs its paths to hundreds of bounces."""
+    max_depth = 1000
+    assert DRAWS_AT_CAMERA + DRAWS_PER_BOUNCE * max_depth < 1 << 15
+    sc = oracle.new_scene()
+    cam = pkg.scenes.load_scene(sc, scene_id, 32, 24, tex_size=64)
+    oracle.set_faithful(sc, False)
+    oracle.counters(sc, reset=True)
+    oracle.render_accum(sc, cam, pkg.make_params(16, strategy, "sobol", max_depth=max_depth), threads=min(os.cpu_count() or 1, 16), counters=True)
+    c = oracle.counters(sc)
+    assert c["samples"] == 32 * 24 * 16
+    deepest = c["max_dimension"]
+    assert DRAWS_AT_CAMERA + DRAWS_PER_BOUNCE < deepest <= DRAWS_AT_CAMERA + DRAWS_PER_BOUNCE * max_depth, deepest
+    assert c["sampler_draws"] <= DRAWS_AT_CAMERA * c["samples"] + DRAWS_PER_BOUNCE * c["bounces"]
+    if scene_id == 34:
+        assert deepest > DRAWS_AT_CAMERA + DRAWS_PER_BOUNCE * 256       # (the box's deep paths: past the kernels' 136-dimension tables and depth 256)

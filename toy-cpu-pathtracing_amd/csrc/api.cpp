@@ -206,6 +206,8 @@ int check_args(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_
     if (!s->impl.built) return fail(MI355PT_E_NOT_BUILT, "scene not built");
     if (cam->width == 0 || cam->height == 0 || p->spp == 0) return fail(MI355PT_E_INVALID, "empty image or spp == 0");
     if (p->strategy > 2 || p->sampler > 1) return fail(MI355PT_E_INVALID, "bad strategy/sampler");
+    // the path records of the kernels' queues hold the depth in 10 bits and the sampler dimension in 15: a path draws 3 dimensions at the
+    // camera and at most 8 per bounce, so 3 + 8 * 1000 = 8003 < 2^15 (tests/test_oracle.py checks the deepest dimension the oracle's paths reach)
     if (p->max_depth > 1000u) return fail(MI355PT_E_INVALID, "max_depth > 1000 (the path records of the kernel's queues hold the depth in 10 bits and the sampler dimension in 15)");
     if (!(p->rr_gate_slack >= 0.0f && p->rr_gate_slack < 1.0f)) return fail(MI355PT_E_INVALID, "rr_gate_slack must be in [0, 1)");
     if (p->rr_gate_slack != 0.0f && !g_debug_unlocked)

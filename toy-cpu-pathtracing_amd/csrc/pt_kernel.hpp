@@ -404,29 +404,6 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
                 bsdf_classes = classes - (__ballot(mclass == MT_EMISSIVE) != 0ull ? 1u : 0u);
                 ts2 = __builtin_amdgcn_s_memtime();
             }
-            auto q_store = [&](uint32_t e, const Path& Q, const Hit& h, uint32_t pix) {
-                float4* r = q_base + (size_t)e * DEFER_F4;
-                const uint32_t fl = (Q.wl.term ? 1u : 0u) | (Q.from_camera ? 2u : 0u) | (Q.prev_spec ? 4u : 0u) | ((Q.depth & 255u) << 8) | (pix << 16);
-                r[0] = make_float4(__uint_as_float(Q.smp.morton), __uint_as_float(Q.smp.dimension), __uint_as_float(Q.smp.rkey_lo), __uint_as_float(Q.smp.rkey_hi));
-                r[1] = make_float4(Q.wl.lam0, __uint_as_float(fl), Q.T[0], Q.T[1]);
-                r[2] = make_float4(Q.T[2], Q.T[3], Q.L[0], Q.L[1]);
-                r[3] = make_float4(Q.L[2], Q.L[3], Q.rd.x, Q.rd.y);
-                r[4] = make_float4(Q.rd.z, Q.pf[0], Q.pf[1], Q.pf[2]);
-                r[5] = make_float4(Q.pf[3], Q.p_pdf, Q.prev_pos.x, Q.prev_pos.y);
-                r[6] = make_float4(Q.prev_pos.z, h.t, h.b0, h.b1);
-                r[7] = make_float4(h.b2, __uint_as_float(h.tri), __uint_as_float(h.mclass), 0.0f);
-            };
-            auto q_load = [&](uint32_t e, Path& Q, Hit& h, uint32_t& pix) {
-                const float4* r = q_base + (size_t)e * DEFER_F4;
-                const float4 a = r[0], b = r[1], c = r[2], d = r[3], e4 = r[4], f = r[5], g = r[6], hh = r[7];
-                const uint32_t fl = __float_as_uint(b.y);
-                Q.smp.morton = __float_as_uint(a.x); Q.smp.dimension = __float_as_uint(a.y); Q.smp.rkey_lo = __float_as_uint(a.z); Q.smp.rkey_hi = __float_as_uint(a.w);
-                Q.wl.lam0 = b.x; Q.wl.term = (fl & 1u) != 0u; Q.from_camera = (fl & 2u) != 0u; Q.prev_spec = (fl & 4u) != 0u; Q.depth = (fl >> 8) & 255u; pix = fl >> 16;
-                Q.T[0] = b.z; Q.T[1] = b.w; Q.T[2] = c.x; Q.T[3] = c.y; Q.L[0] = c.z; Q.L[1] = c.w; Q.L[2] = d.x; Q.L[3] = d.y;
-                Q.rd = mk3(d.z, d.w, e4.x); Q.ro = mk3(0.0f, 0.0f, 0.0f);
-                Q.pf[0] = e4.y; Q.pf[1] = e4.z; Q.pf[2] = e4.w; Q.pf[3] = f.x; Q.p_pdf = f.y; Q.prev_pos = mk3(f.z, f.w, g.x);
-                h.t = g.y; h.b0 = g.z; h.b1 = g.w; h.b2 = hh.x; h.tri = __float_as_uint(hh.y); h.mclass = __float_as_uint(hh.z);
-            };
             // the tail queue's record: what the back of the vertex still needs once the front has run — the spawning sample's f, pdf and the
             // vertex left are consumed by the front, from_camera / prev_spec are rewritten by the tail, the hit's t is never read: 20 dwords in
             // 5 float4 = 80 B.  The record's size is the queue's price: 128 -> 96 B was worth +6.5 % on C2 (the queues stream through L2 / HBM)
@@ -435,7 +412,7 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
             // sixth of 64 different ones (+1 ... 2 % over the record-major layout; a 128-entry ring where one queue suffices +0.2 ... 0.8 %)
             auto tq_store = [&](uint32_t e, const Path& Q, const Hit& h, uint32_t pix) {
                 float4* r = q_base + (size_t)(e >> 8) * (TQ_F4 * QUEUE_RING) + (e & (QR - 1u));
-                const uint32_t fl = (Q.wl.term ? 1u : 0u) | ((Q.depth & 1023u) << 1) | ((pix & 63u) << 11) | (Q.smp.dimension << 17);   // (max_depth <= 1000: api.cpp check_args)
+                const uint32_t fl = (Q.wl.term ? 1u : 0u) | ((Q.depth & 1023u) << 1) | ((pix & 63u) << 11) | (Q.smp.dimension << 17);   // (max_depth <= 1000, api.cpp check_args: dimension <= 3 + 8 * 1000 < 2^15)
                 PT_TQ_ST(r + 0u * QR, make_float4(__uint_as_float(Q.smp.morton), __uint_as_float(fl), Q.wl.lam0, __uint_as_float(h.tri)));
                 PT_TQ_ST(r + 1u * QR, make_float4(Q.T[0], Q.T[1], Q.T[2], Q.T[3]));
                 PT_TQ_ST(r + 2u * QR, make_float4(Q.L[0], Q.L[1], Q.L[2], Q.L[3]));
@@ -560,7 +537,7 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
                     const float4 a = r[0], b = r[1], c = r[2], d = r[3], e = r[4], f = r[5], g = r[6], h = r[7];
                     const uint32_t fl = __float_as_uint(b.y);
                     P.smp.morton = __float_as_uint(a.x); P.smp.dimension = __float_as_uint(a.y); P.smp.rkey_lo = __float_as_uint(a.z); P.smp.rkey_hi = __float_as_uint(a.w);
-                    P.wl.lam0 = b.x; P.wl.term = (fl & 1u) != 0u; P.from_camera = (fl & 2u) != 0u; P.prev_spec = (fl & 4u) != 0u; P.depth = (fl >> 8) & 255u; my_pix = fl >> 16;
+                    P.wl.lam0 = b.x; P.wl.term = (fl & 1u) != 0u; P.from_camera = (fl & 2u) != 0u; P.prev_spec = (fl & 4u) != 0u; P.depth = (fl >> 3) & 1023u; my_pix = fl >> 16;
                     P.T[0] = b.z; P.T[1] = b.w; P.T[2] = c.x; P.T[3] = c.y; P.L[0] = c.z; P.L[1] = c.w; P.L[2] = d.x; P.L[3] = d.y;
                     P.rd = mk3(d.z, d.w, e.x); P.ro = mk3(0.0f, 0.0f, 0.0f);
                     P.pf[0] = e.y; P.pf[1] = e.z; P.pf[2] = e.w; P.pf[3] = f.x; P.p_pdf = f.y; P.prev_pos = mk3(f.z, f.w, g.x);
@@ -573,7 +550,8 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
                 if (m_def != 0ull) {
                     if (defer_now) {
                         float4* r = q_base + (size_t)((q_tail + rank_below(m_def)) & (DEFER_RING - 1u)) * DEFER_F4;
-                        const uint32_t fl = (P.wl.term ? 1u : 0u) | (P.from_camera ? 2u : 0u) | (P.prev_spec ? 4u : 0u) | ((P.depth & 255u) << 8) | (my_pix << 16);
+                        // (flags in bits 0-2, the depth in bits 3-12: max_depth <= 1000, api.cpp check_args; the pixel from bit 16)
+                        const uint32_t fl = (P.wl.term ? 1u : 0u) | (P.from_camera ? 2u : 0u) | (P.prev_spec ? 4u : 0u) | ((P.depth & 1023u) << 3) | (my_pix << 16);
                         r[0] = make_float4(__uint_as_float(P.smp.morton), __uint_as_float(P.smp.dimension), __uint_as_float(P.smp.rkey_lo), __uint_as_float(P.smp.rkey_hi));
                         r[1] = make_float4(P.wl.lam0, __uint_as_float(fl), P.T[0], P.T[1]);
                         r[2] = make_float4(P.T[2], P.T[3], P.L[0], P.L[1]);

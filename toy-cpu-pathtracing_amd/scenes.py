@@ -116,6 +116,41 @@ def _mat4_trs_scene17():
     return (T @ (S @ R)).astype(np.float32)
 
 
+def _deep_box(scene, p, texture=False, clearcoat=False):
+    """Scenes 34-36: x, z in [-2, 2], y in [0, 4], every normal facing in; the ceiling is a ring of four quads around the emitter's opening."""
+    quad = assets._quad
+    white = scene.add_material(lambert(Spectrum.constant(1.0)))
+    a, h = 2.0, 0.6
+    floor = quad((-a, 0, a), (a, 0, a), (a, 0, -a), (-a, 0, -a), (0, 1, 0))
+    if texture:
+        # 16 x 16 checker of two near-white sRGB colours (albedo ~0.95 at every wavelength), one repeat across the floor
+        img = np.zeros((16, 16, 3), np.uint8)
+        chk = (np.add.outer(np.arange(16), np.arange(16)) // 4) % 2 == 1
+        img[chk] = (250, 246, 240); img[~chk] = (238, 246, 250)
+        floor = dict(floor, uv=np.array([[0, 0], [1, 0], [1, 1], [0, 1]], np.float32))
+        mat = scene.add_material(lambert(Spectrum.texture_albedo_srgb(scene.add_tex_rgb8(img))))
+        scene.add_instance(scene.add_mesh(assets.load_obj_semantics(floor)), mat)
+    else:
+        scene.add_instance(scene.add_mesh(floor), white)
+    walls = [quad((-a, 0, -a), (a, 0, -a), (a, 4, -a), (-a, 4, -a), (0, 0, 1)),       # back
+             quad((a, 0, a), (-a, 0, a), (-a, 4, a), (a, 4, a), (0, 0, -1)),          # front (behind the camera)
+             quad((-a, 0, a), (-a, 0, -a), (-a, 4, -a), (-a, 4, a), (1, 0, 0)),       # left
+             quad((a, 0, -a), (a, 0, a), (a, 4, a), (a, 4, -a), (-1, 0, 0)),          # right
+             quad((-a, 4, -a), (a, 4, -a), (a, 4, -h), (-a, 4, -h), (0, -1, 0)),      # ceiling ring: back strip
+             quad((-a, 4, h), (a, 4, h), (a, 4, a), (-a, 4, a), (0, -1, 0)),          # front strip
+             quad((-a, 4, -h), (-h, 4, -h), (-h, 4, h), (-a, 4, h), (0, -1, 0)),      # left strip
+             quad((h, 4, -h), (a, 4, -h), (a, 4, h), (h, 4, h), (0, -1, 0))]          # right strip
+    for w in walls:
+        scene.add_instance(scene.add_mesh(w), white)
+    if clearcoat:
+        d = MaterialDesc(); d.type = MAT_CLEARCOAT; d.color = Spectrum.rgb_albedo_srgb(0.8, 0.8, 0.8)
+        d.metallic = 1.0; d.roughness = 0.7; d.normal_tex = NONE; d.ior = 1.5; d.clearcoat_ior = 1.5
+        d.clearcoat_roughness = 0.3; d.clearcoat_tint = Spectrum.rgb_albedo_srgb(0.7, 0.8, 1.0); d.clearcoat_thickness = 0.8
+        scene.add_instance(scene.add_mesh(assets._cuboid((-1.4, 0.0, -1.4), (-0.2, 1.2, -0.2), rot_y_deg=25.0)), scene.add_material(d))
+    em = MaterialDesc(); em.type = MAT_EMISSIVE; em.color = Spectrum.lut(scene.add_lut470(p["cie_illum_d6500"])); em.intensity = 1.0; em.normal_tex = NONE
+    scene.add_instance(scene.add_mesh(quad((-h, 4, -h), (h, 4, -h), (h, 4, h), (-h, 4, h), (0, -1, 0))), scene.add_material(em))
+
+
 def load_scene(scene, scene_id, width, height, tex_size=1024, build=True):
     """load_scene_N(&mut scene, &mut camera) + scene.build(&camera) (main.rs:70-106).  Returns the camera.
     build=False: describe only (the caller builds, e.g. with Product.build_multi)."""
@@ -388,6 +423,12 @@ def load_scene(scene, scene_id, width, height, tex_size=1024, build=True):
             em.color = Spectrum.texture_unbounded_srgb(t_col)
         scene.add_instance(scene.add_mesh(panel), scene.add_material(em))
         cam = make_camera((0.0, 3.15221, 6.0), (0.0, -0.9, -3.2), (0.0, 1.0, 0.0), width, height)
+    elif scene_id in (34, 35, 36):   # not reference scenes: DEEP paths — a closed 4 x 4 x 4 box of white Lambert walls (albedo exactly 1: the
+        # throughput stays at 1, so the Russian roulette ends no path) lit by a 1.2 x 1.2 emitter set into the ceiling (1.5 % of the walls' area):
+        # most paths bounce tens to hundreds of times and a few percent pass depth 256.  35: the floor carries a spectrum texture of albedo ~0.95
+        # (the class the instrumented kernel defers); 36: a clearcoat block on the floor (the clearcoat kernels)
+        _deep_box(scene, p, texture=scene_id == 35, clearcoat=scene_id == 36)
+        cam = make_camera((0.0, 1.2, 1.9), (0.0, 0.6, -1.0), (0.0, 1.0, 0.0), width, height, fov_deg=70.0)
     else:
         raise ValueError(f"scene {scene_id} is outside the hot-path scope (SURVEY.md §8)")
     if build:
