@@ -241,6 +241,41 @@ int mi355pt_scene_build_multi(mi355pt_scene* s, const mi355pt_camera* cam, int n
 int mi355pt_render_multi(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, float* out_rgb);
 /* Sensor::to_rgb on device buffers: mean over spp, clip, Reinhard, sRGB OETF.  sensor.rs:81-88, tone_map.rs:20-28 */
 int mi355pt_film_resolve_device(const float* d_accum, uint32_t n_pixels, uint32_t spp, float* d_out_rgb, void* hip_stream);
+/* ---------------- AOV renderers ---------------- */
+/* The reference's two other renderers behind the same seam, RendererImage::<NormalRenderer | AlbedoRenderer>::render::<S>()
+ * (main.rs:155-186; `normal` is the CLI's default renderer, main.rs:38-40), as one primary-ray kernel.  Per pixel and sample index:
+ *   NORMAL          NormalRenderer::render (renderer/normal_renderer.rs:26-75): draws get_2d_pixel() only (no wavelength draw), shoots
+ *                   camera.sample_ray without the path renderers' epsilon; miss = 0; hit on an emitter = render-space shading normal * 0.5
+ *                   + 0.5; hit on a BSDF material = the shading normal AFTER interaction.shading_transform() * interaction
+ *                   (samples.rs:130-148), i.e. in its own tangent frame: (0.5, 0.5, 1.0) on every BSDF surface, as the reference has it.
+ *                   Pixel = sum / spp, stored raw (ColorSrgb<NoneToneMap>::from_rgb).
+ *   ALBEDO          AlbedoRenderer::render (renderer/albedo_renderer.rs:30-69): get_1d() -> wavelengths, get_2d_pixel(), the same ray;
+ *                   BsdfMaterial::sample_albedo_spectrum(uv, lambda) (scene/src/material/impls: Lambert albedo, SimplePbr / clearcoat
+ *                   base_color, glass / plastic 1, metal fresnel_complex(1, eta, k)) times presets::cie_illum_d6500() into
+ *                   Sensor::add_sample, exposure 1; emitters and misses add nothing.  Pixel = Sensor::to_rgb with NoneToneMap and the
+ *                   sRGB OETF (sensor.rs:81-88): mean, clip at 0 from below, OETF; values above 1 are legal and kept.
+ *   SHADING_NORMAL  EXTENSION, no reference counterpart: the reference's emitter branch of NORMAL (normal_renderer.rs:59-66) for EVERY
+ *                   hit — the render-space shading normal (through the instance's inverse-transpose, primitive/impls/triangle_mesh.rs)
+ *                   * 0.5 + 0.5; misses 0; stored raw.  The one a denoiser can use. */
+enum { MI355PT_AOV_NORMAL = 0, MI355PT_AOV_ALBEDO = 1, MI355PT_AOV_SHADING_NORMAL = 2 };
+/* RendererImage::render::<S>() for an AOV renderer (renderer.rs:101-134 with main.rs:155-186): fills out_rgb (host, W*H*3, row-major, y
+ * down) like mi355pt_render.  Of mi355pt_params, spp, seed, sampler, shard_index and shard_count are honoured; strategy, max_depth,
+ * exposure and albedo_lut are ignored; rr_gate_slack must be 0 as everywhere; collect_stats != 0 returns MI355PT_E_INVALID (there is no
+ * instrumented AOV kernel).  `illuminant_lut` is the LUT470 id of presets::cie_illum_d6500() (albedo_renderer.rs:60, as in
+ * mi355pt_scene_add_environment_light): needed for ALBEDO (MI355PT_E_INVALID on a bad id), ignored for the normal kinds.  `stats`, when
+ * given, receives samples, closest_rays, closest_hits, kernel_ms and launches; the rest is 0.  Same camera-position and device contract
+ * as mi355pt_render. */
+int mi355pt_render_aov(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, int kind, uint32_t illuminant_lut,
+                       float* out_rgb, mi355pt_stats* stats /* NULL ok */);
+/* The AOV pixel loop (normal_renderer.rs:38-70, albedo_renderer.rs:46-66) with the film resident in HBM, like
+ * mi355pt_render_accum_device: adds the linear per-pixel sums of sample indices [sample_begin, sample_end) into d_accum (device, W*H*3
+ * f32; acc_color / Sensor.accumulated_rgb) for the 8x8 tiles of the shard in `p`, other pixels untouched.  Asynchronous on `hip_stream`. */
+int mi355pt_render_aov_accum_device(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, int kind,
+                                    uint32_t illuminant_lut, uint32_t sample_begin, uint32_t sample_end, float* d_accum, void* hip_stream,
+                                    mi355pt_stats* stats /* NULL ok; non-NULL synchronises the stream */);
+/* The AOV renderers' last step on device buffers.  NORMAL / SHADING_NORMAL: acc / spp (normal_renderer.rs:71-73).  ALBEDO: Sensor::to_rgb
+ * with NoneToneMap — mean over spp, max(0), sRGB OETF (sensor.rs:81-88, tone_map.rs NoneToneMap, eotf.rs:54-61). */
+int mi355pt_aov_resolve_device(int kind, const float* d_accum, uint32_t n_pixels, uint32_t spp, float* d_out_rgb, void* hip_stream);
 /* RendererImage::save quantisation `(p*255.0) as u8`  renderer.rs:137-148 (host helper) */
 int mi355pt_quantize_u8(const float* rgb, size_t n, uint8_t* out);
 

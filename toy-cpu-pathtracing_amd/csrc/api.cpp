@@ -28,6 +28,11 @@ hipError_t launch_probe_occluded(const DevScene&, const float*, const float*, co
 hipError_t launch_probe_sincos(uint32_t, uint32_t, uint32_t, float*, float*, hipStream_t);
 uint64_t host_murmur_dim_seed(uint32_t dimension, uint32_t seed);
 int query_resident_waves(bool stats, uint32_t feat, uint32_t sampler, uint32_t strategy);
+// pt_kernels_aov.hip: the AOV renderers' primary-ray kernel (kind = MI355PT_AOV_*)
+hipError_t launch_aov(uint32_t kind, const DevScene&, const DevCamera&, const DevParams&, uint32_t illuminant_lut, const uint64_t*, float*, unsigned*,
+                      DevStats*, uint32_t feat, int grid, hipStream_t);
+int query_resident_waves_aov(uint32_t kind, uint32_t feat);
+hipError_t launch_aov_resolve(uint32_t kind, const float*, uint32_t, uint32_t, float*, hipStream_t);
 }  // namespace pt
 
 using namespace pt;
@@ -52,6 +57,7 @@ constexpr int CTX_RING = 16;
 struct LaunchCtx {
     int device = -1;                  // the device every buffer below lives on (= SceneImpl::device when the context was made)
     int waves[2][2][3] = {{{0}}};     // [instrumented][sampler][strategy]: resident waves of the kernel that combination launches (0: not asked yet)
+    int aov_waves[3] = {0, 0, 0};     // [MI355PT_AOV_*]: the same for the AOV kernel of this scene's feature set
     uint64_t* d_hash = nullptr;
     uint32_t hash_seed = 0;
     bool hash_valid = false;
@@ -201,14 +207,15 @@ int get_launch_ctx(const mi355pt_scene* sc, uint32_t seed, hipStream_t stream, L
     return MI355PT_OK;
 }
 
-int check_args(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p) {
+// `aov`: the AOV renderers ignore strategy and max_depth (mi355pt_render_aov), so they are not checked for them
+int check_args(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, bool aov = false) {
     if (!s || !cam || !p) return fail(MI355PT_E_INVALID, "null argument");
     if (!s->impl.built) return fail(MI355PT_E_NOT_BUILT, "scene not built");
     if (cam->width == 0 || cam->height == 0 || p->spp == 0) return fail(MI355PT_E_INVALID, "empty image or spp == 0");
-    if (p->strategy > 2 || p->sampler > 1) return fail(MI355PT_E_INVALID, "bad strategy/sampler");
+    if ((!aov && p->strategy > 2) || p->sampler > 1) return fail(MI355PT_E_INVALID, "bad strategy/sampler");
     // the path records of the kernels' queues hold the depth in 10 bits and the sampler dimension in 15: a path draws 3 dimensions at the
     // camera and at most 8 per bounce, so 3 + 8 * 1000 = 8003 < 2^15 (tests/test_oracle.py checks the deepest dimension the oracle's paths reach)
-    if (p->max_depth > 1000u) return fail(MI355PT_E_INVALID, "max_depth > 1000 (the path records of the kernel's queues hold the depth in 10 bits and the sampler dimension in 15)");
+    if (!aov && p->max_depth > 1000u) return fail(MI355PT_E_INVALID, "max_depth > 1000 (the path records of the kernel's queues hold the depth in 10 bits and the sampler dimension in 15)");
     if (!(p->rr_gate_slack >= 0.0f && p->rr_gate_slack < 1.0f)) return fail(MI355PT_E_INVALID, "rr_gate_slack must be in [0, 1)");
     if (p->rr_gate_slack != 0.0f && !g_debug_unlocked)
         return fail(MI355PT_E_INVALID, "mi355pt_params.rr_gate_slack must be 0 (a diagnostic: mi355pt_debug_unlock(1) in mi355pt_debug.h enables it)");
@@ -445,17 +452,26 @@ int mi355pt_scene_build(mi355pt_scene* s, const mi355pt_camera* cam) {
 }
 
 static constexpr uint32_t PT_MAX_LAUNCH_SAMPLES = 4096;
+// aov_kind < 0: the path-tracing kernels; MI355PT_AOV_*: the AOV kernel (pt_kernels_aov.hip) over the same work items and work counter —
+// but never a split sample range —, with `illuminant_lut` for the albedo kind
 static int render_accum_range(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, uint32_t s_begin, uint32_t s_end,
-                              float* d_accum, void* hip_stream, mi355pt_stats* stats, const PathOut& pout) {
-    int rc = check_args(s, cam, p);
+                              float* d_accum, void* hip_stream, mi355pt_stats* stats, const PathOut& pout, int aov_kind = -1, uint32_t illuminant_lut = 0) {
+    const bool aov = aov_kind >= 0;
+    int rc = check_args(s, cam, p, aov);
     if (rc) return rc;
     if (!d_accum || s_end > p->spp || s_begin >= s_end) return fail(MI355PT_E_INVALID, "bad sample range or null accumulator");
+    if (aov) {
+        if (aov_kind > MI355PT_AOV_SHADING_NORMAL) return fail(MI355PT_E_INVALID, "unknown AOV kind");
+        if (p->collect_stats) return fail(MI355PT_E_INVALID, "the AOV renderers have no instrumented kernel: collect_stats must be 0");
+        if (aov_kind == MI355PT_AOV_ALBEDO && illuminant_lut >= s->impl.luts.size())
+            return fail(MI355PT_E_INVALID, "illuminant_lut is not a LUT470 id of this scene (presets::cie_illum_d6500())");
+    }
     if (p->sampler == MI355PT_SAMPLER_SOBOL && !stats && s_end - s_begin > PT_MAX_LAUNCH_SAMPLES) {
         // long Sobol ranges go out as aligned blocks of 4096 sample indices: single-pixel work items over an aligned 4^6 block hash the
         // fewest digits per draw (the digits above the block join the prefix tables), and no launch runs for minutes
         for (uint32_t b = s_begin; b < s_end;) {
             const uint32_t e = std::min(s_end, (b / PT_MAX_LAUNCH_SAMPLES + 1u) * PT_MAX_LAUNCH_SAMPLES);
-            if ((rc = render_accum_range(s, cam, p, b, e, d_accum, hip_stream, nullptr, pout))) return rc;
+            if ((rc = render_accum_range(s, cam, p, b, e, d_accum, hip_stream, nullptr, pout, aov_kind, illuminant_lut))) return rc;
             b = e;
         }
         return MI355PT_OK;
@@ -463,13 +479,19 @@ static int render_accum_range(const mi355pt_scene* s, const mi355pt_camera* cam,
     hipStream_t stream = (hipStream_t)hip_stream;
     DevCamera dc = make_camera(cam);
     DevParams dp = make_params(cam, p, s_begin, s_end);
+    if (aov) { dp.exposure = 1.0f; dp.rr_gate = 1.0f; dp.strategy = 0u; dp.max_depth = 0u; dp.albedo_lut = 0u; }   // Sensor::new(spp, 1.0, NoneToneMap), albedo_renderer.rs:43-44
     uint32_t n_tiles_total = dp.tiles_x * dp.tiles_y;
     uint32_t n_tiles = n_tiles_total > dp.shard_index ? (n_tiles_total - dp.shard_index + dp.shard_count - 1) / dp.shard_count : 0;
     if (n_tiles == 0) return MI355PT_OK;
     LaunchCtx* lc; int slot;
     if ((rc = get_launch_ctx(s, p->seed, stream, &lc, &slot))) return rc;
     if (lc->device != s->impl.device) return fail(MI355PT_E_DEVICE, "launch context and scene live on different devices");
-    int waves = resident_waves(lc, stats && p->collect_stats, s->impl.features, dp.sampler, dp.strategy);
+    int waves;
+    if (aov) {
+        int& c = lc->aov_waves[aov_kind];
+        if (!c) c = query_resident_waves_aov((uint32_t)aov_kind, s->impl.features);
+        waves = c;
+    } else waves = resident_waves(lc, stats && p->collect_stats, s->impl.features, dp.sampler, dp.strategy);
     // Work items.  A work item is a 2^b x 2^b pixel block of an 8x8 tile times a range of sample indices, its (pixel, sample)
     // pairs handed to the lanes as a pool.  Sobol: the fewer pixels an item has, the fewer Morton digits vary inside it, and only
     // varying digits (minus the two that have block-level tables) are hashed per draw (pt_device.hpp sampler_index): take the
@@ -500,8 +522,9 @@ static int render_accum_range(const mi355pt_scene* s, const mi355pt_camera* cam,
     // items per resident wave, but no chunk under 16 samples (every work item rebuilds its Sobol prefix tables; measured
     // with tools/chunk_sweep.sh: one shard of 4 / 8 at 1080p is 2.2 % / 0.9 % faster with 16-sample than with 8-sample chunks)
     // (while some resident waves would have no item at all, chunks may go down to 8 samples: a 256x256 frame has 1 024 tiles)
+    // (the AOV kernel never splits: its tiles continue the film's sums in sample order, so that consecutive sample ranges compose bit for bit)
     uint32_t chunks = 1;
-    while (n_items * chunks < (uint32_t)waves * 8 && chunks * 2 <= n_samples &&
+    while (!aov && n_items * chunks < (uint32_t)waves * 8 && chunks * 2 <= n_samples &&
            (n_samples / (chunks * 2)) >= (n_items * chunks >= (uint32_t)waves ? 16u : 8u)) chunks *= 2;
 #ifdef MI355PT_TUNING
     if (const char* e = getenv("MI355PT_CHUNKS")) { uint32_t c = (uint32_t)atoi(e); if (c >= 1 && c <= n_samples) chunks = c; }
@@ -522,7 +545,7 @@ static int render_accum_range(const mi355pt_scene* s, const mi355pt_camera* cam,
     HIP_TRY(hipMemsetAsync(d_counter, 0, sizeof(unsigned), stream));
     bool want_stats = stats && p->collect_stats;
     dp.stats_mode = p->collect_stats;
-    if (want_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(DevStats), stream));
+    if (want_stats || (aov && stats)) HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(DevStats), stream));
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (stats) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, stream)); }
     int grid = (int)std::min<uint32_t>(dp.n_work, (uint32_t)waves);
@@ -535,7 +558,7 @@ static int render_accum_range(const mi355pt_scene* s, const mi355pt_camera* cam,
             lc->partial_floats = need;
         }
     }
-    if (const size_t per_wave = query_defer_bytes_per_wave()) {
+    if (const size_t per_wave = aov ? (size_t)0 : query_defer_bytes_per_wave()) {
         // (one stream at a time per scene, like d_partial: the queues are empty between launches, so consecutive launches share them)
         const size_t need = per_wave * (size_t)grid;
         if (need > lc->defer_bytes) {
@@ -545,7 +568,9 @@ static int render_accum_range(const mi355pt_scene* s, const mi355pt_camera* cam,
             lc->defer_bytes = need;
         }
     }
-    HIP_TRY(launch_pt(s->impl.dev, dc, dp, lc->d_hash, d_accum, lc->d_partial, d_counter, d_stats, want_stats, s->impl.features, grid, stream, pout, lc->d_defer));
+    if (aov) HIP_TRY(launch_aov((uint32_t)aov_kind, s->impl.dev, dc, dp, illuminant_lut, lc->d_hash, d_accum, d_counter, stats ? d_stats : nullptr,
+                                s->impl.features, grid, stream));
+    else HIP_TRY(launch_pt(s->impl.dev, dc, dp, lc->d_hash, d_accum, lc->d_partial, d_counter, d_stats, want_stats, s->impl.features, grid, stream, pout, lc->d_defer));
     if (stats) {
         HIP_TRY(hipEventRecord(e1, stream));
         HIP_TRY(hipEventSynchronize(e1));
@@ -564,6 +589,11 @@ static int render_accum_range(const mi355pt_scene* s, const mi355pt_camera* cam,
             for (int i = 0; i < 8; ++i) stats->wave_steps[i] = h.wave_steps[i];
             for (int i = 0; i < 16; ++i) stats->busy_hist[i] = h.busy_hist[i >> 3][i & 7];
             for (int i = 0; i < 12; ++i) stats->divergence[i] = h.divergence[i];
+        }
+        if (aov) {   // the AOV kernel counts its samples, primary rays and hits in every launch that is given a stats block
+            DevStats h;
+            HIP_TRY(hipMemcpy(&h, d_stats, sizeof(h), hipMemcpyDeviceToHost));
+            stats->samples = h.samples; stats->closest_rays = h.closest_rays; stats->closest_hits = h.closest_hits;
         }
         (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     }
@@ -737,6 +767,34 @@ int mi355pt_scene_info(const mi355pt_scene* s, char* buf, size_t n) {
 int mi355pt_film_resolve_device(const float* d_accum, uint32_t n_pixels, uint32_t spp, float* d_out, void* hip_stream) {
     if (!d_accum || !d_out || spp == 0) return fail(MI355PT_E_INVALID, "bad resolve arguments");
     HIP_TRY(launch_resolve(d_accum, n_pixels * 3, spp, d_out, (hipStream_t)hip_stream));
+    return MI355PT_OK;
+}
+
+int mi355pt_render_aov_accum_device(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, int kind, uint32_t illuminant_lut,
+                                    uint32_t s_begin, uint32_t s_end, float* d_accum, void* hip_stream, mi355pt_stats* stats) {
+    if (kind < MI355PT_AOV_NORMAL || kind > MI355PT_AOV_SHADING_NORMAL) return fail(MI355PT_E_INVALID, "unknown AOV kind");
+    return render_accum_range(s, cam, p, s_begin, s_end, d_accum, hip_stream, stats, PathOut{nullptr, nullptr, nullptr, 0u, 0u}, kind, illuminant_lut);
+}
+int mi355pt_aov_resolve_device(int kind, const float* d_accum, uint32_t n_pixels, uint32_t spp, float* d_out, void* hip_stream) {
+    if (kind < MI355PT_AOV_NORMAL || kind > MI355PT_AOV_SHADING_NORMAL) return fail(MI355PT_E_INVALID, "unknown AOV kind");
+    if (!d_accum || !d_out || spp == 0) return fail(MI355PT_E_INVALID, "bad resolve arguments");
+    HIP_TRY(launch_aov_resolve((uint32_t)kind, d_accum, n_pixels * 3, spp, d_out, (hipStream_t)hip_stream));
+    return MI355PT_OK;
+}
+int mi355pt_render_aov(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, int kind, uint32_t illuminant_lut, float* out_rgb,
+                       mi355pt_stats* stats) {
+    if (kind < MI355PT_AOV_NORMAL || kind > MI355PT_AOV_SHADING_NORMAL) return fail(MI355PT_E_INVALID, "unknown AOV kind");
+    int rc = check_args(s, cam, p, true);
+    if (rc) return rc;
+    if (!out_rgb) return fail(MI355PT_E_INVALID, "null output");
+    size_t n = (size_t)cam->width * cam->height * 3;
+    DevBuf<float> d_acc, d_out;
+    HIP_TRY(d_acc.alloc(n));
+    HIP_TRY(d_out.alloc(n));
+    HIP_TRY(hipMemset(d_acc.p, 0, n * sizeof(float)));
+    if ((rc = mi355pt_render_aov_accum_device(s, cam, p, kind, illuminant_lut, 0, p->spp, d_acc.p, nullptr, stats))) return rc;
+    if ((rc = mi355pt_aov_resolve_device(kind, d_acc.p, cam->width * cam->height, p->spp, d_out.p, nullptr))) return rc;
+    HIP_TRY(hipMemcpy(out_rgb, d_out.p, n * sizeof(float), hipMemcpyDeviceToHost));
     return MI355PT_OK;
 }
 

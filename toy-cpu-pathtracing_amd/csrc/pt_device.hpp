@@ -273,6 +273,7 @@ PT_DEV void wl_lams(const Wl& w, float lam[4]) {
 PT_DEV float srgb_eotf_inverse(float c) {
     return c <= 0.04045f ? c * (1.0f / 12.92f) : __builtin_amdgcn_exp2f(2.4f * __builtin_amdgcn_logf((c + 0.055f) * (1.0f / 1.055f)));
 }
+PT_DEV float srgb_oetf(float c) { return c <= 0.0031308f ? 12.92f * c : 1.055f * powf(c, 1.0f / 2.4f) - 0.055f; }   // eotf.rs:54-61
 PT_DEV float lut_value(const float* lut, float lambda) {                 // densely_sampled_spectrum.rs:57-67
     if (!(lambda >= LAMBDA_MIN && lambda <= LAMBDA_MAX)) return 0.0f;
     int idx = (int)floorf(lambda - LAMBDA_MIN);

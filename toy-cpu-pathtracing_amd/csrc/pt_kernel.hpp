@@ -671,6 +671,36 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
     if (STATS) flush_stats(stats, st);
 }
 
+// ---- the Sobol prefix tables of pt_kernel's work loop as a function, for the AOV kernel (pt_kernels_aov.hip), which takes the same work
+// items and draws with the same sampler code.  pt_kernel keeps its own inline spelling of the same statements: calling this function
+// from it changes the instruction schedule of every tuned path kernel (compared on the gfx950 disassembly), and those are measured as
+// they are.  A change to one side belongs on the other as well. ----
+// Block-uniform Sobol digit prefixes of a work item (pt_device.hpp sampler_index), where the launch shape allows them: lane d computes
+// dimensions d, d + 64, ... < n_dims for this block (job0: lane 0's job, whose pixel is the block origin) into s_hi / s_p6 and sctx is
+// pointed at them.  Single-pixel items over an aligned 4^m block of sample indices: the sample digits above m are part of the prefix.
+// The caller synchronises before the first draw.  (n_dims may be smaller than SOBOL_HI_DIMS only together with tables of SOBOL_HI_DIMS
+// entries or in a kernel that never draws a dimension from n_dims on: sampler_index reads the tables for every dimension below SOBOL_HI_DIMS.)
+PT_DEV void item_sobol_prefixes(SamplerCtx& sctx, const DevParams& prm, const LaneJob& job0, uint32_t lane, uint32_t* s_hi, uint32_t* s_p6, uint32_t n_dims) {
+    const uint32_t blk_log2 = prm.block_log2;
+    const uint32_t s_prefix = prm.sample_prefix_digits;
+    // (the tables hold the permuted prefix in 27 bits per entry: a launch shape whose prefix is wider hashes every digit instead)
+    const uint32_t hi_first_w = sobol_hi_first(prm.log2_spp, blk_log2) - s_prefix, hi_shift_w = 2u * hi_first_w - (prm.log2_spp & 1u);
+    if (prm.sampler == 1u && hi_first_w < prm.n_base4_digits && hi_first_w >= 3u &&
+        2u * prm.n_base4_digits - (prm.log2_spp & 1u) <= hi_shift_w + 27u) {
+        sctx.hi_first = sobol_hi_first(prm.log2_spp, blk_log2) - s_prefix;
+        sctx.hi_shift = 2u * sctx.hi_first - (prm.log2_spp & 1u);
+        const uint32_t tile_m = (encode_morton2_u32(job0.px, job0.py) << prm.log2_spp) | (s_prefix ? job0.s_cur : 0u);
+        for (uint32_t dmn = lane; dmn < n_dims; dmn += 64) {
+            uint32_t e = (uint32_t)(sobol_tile_hi_digits(tile_m, dmn, prm.log2_spp, prm.n_base4_digits, sctx.hi_first) >> sctx.hi_shift);   // <= 26 bits: the Morton index is a u32 and hi_shift >= 6
+            const uint64_t prefix = (uint64_t)tile_m >> sctx.hi_shift;                 // the digits above digit hi_first-1
+            e |= sobol_perm_index(prefix, dmn) << 27;
+            uint32_t e6 = 0;
+            for (uint32_t v7 = 0; v7 < 4u; ++v7) e6 |= sobol_perm_index((prefix << 2) | v7, dmn) << (5u * v7);
+            s_hi[dmn] = e; s_p6[dmn] = e6;
+        }
+        sctx.hi_lds = s_hi; sctx.p6_lds = s_p6;
+    }
+}
 // ---- launch of the production variants of one MODE: smallest compiled feature set covering `feat` ----
 inline uint32_t pick_features(uint32_t feat) {
     const uint32_t sets[] = {0u, FEAT_TEX, FEAT_DIEL, FEAT_METAL, FEAT_DIEL | FEAT_ROUGH, FEAT_DELTA | FEAT_MLIGHT, FEAT_CC, FEAT_CC | FEAT_TEX, FEAT_STD & ~FEAT_CC, FEAT_STD, FEAT_ALL};

@@ -45,7 +45,7 @@ __global__ void resolve_kernel(const float* __restrict__ accum, uint32_t n_value
         float c = accum[i] / (float)spp;
         c = fmaxf(c, 0.0f);
         c = c / (1.0f + c);
-        out[i] = c <= 0.0031308f ? 12.92f * c : 1.055f * powf(c, 1.0f / 2.4f) - 0.055f;
+        out[i] = srgb_oetf(c);
     }
 }
 

@@ -287,6 +287,20 @@ PT_DEV void regen_path(Path& P, const SamplerCtx& sctx, const DevCamera& cam, ui
     (void)need_new;
 }
 
+// Camera::sample_ray (camera.rs:51-81, filter.rs:24-29): the render-space direction through pixel (px, py) at the pixel sample uv; the
+// origin is the render-space origin.  The camera ray of regen_path above without its RAY_EPS step, for the AOV renderers
+// (pt_kernels_aov.hip).  regen_path keeps its own spelling of the same expressions: routing it through this function changes the
+// instruction schedule of every tuned path kernel (compared on the gfx950 disassembly), and those are measured as they are.
+PT_DEV f3 camera_ray_dir(const DevCamera& cam, uint32_t px, uint32_t py, f2 uv) {
+    float fx = (float)px + (uv.x * 1.0f - 1.0f * 0.5f) + 0.5f;             // filter.rs:24-29, camera.rs:68-72
+    float fy = (float)py + (uv.y * 1.0f - 1.0f * 0.5f) + 0.5f;
+    float dx = (2.0f * fx / (float)cam.width - 1.0f) * cam.aspect * cam.tan_half_fov;   // camera.rs:51-65
+    float dy = (1.0f - 2.0f * fy / (float)cam.height) * cam.tan_half_fov;
+    f3 dc = normalize(mk3(dx, dy, -1.0f));
+    f3 s = mk3(cam.s[0], cam.s[1], cam.s[2]), uu = mk3(cam.u[0], cam.u[1], cam.u[2]), ff = mk3(cam.f[0], cam.f[1], cam.f[2]);
+    return normalize(s * dc.x + uu * dc.y + (-ff) * dc.z);
+}
+
 // One path vertex in two halves.  The closest-hit result of P.ro/P.rd arrives (got/hit):
 //   shade_vertex_head  accounts emission (with the strategy's weight), applies throughput + Russian roulette, builds the shading frames
 //                      and draws the BSDF's random numbers; returns true when the path ends here, else C.cont is set;

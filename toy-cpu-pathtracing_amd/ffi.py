@@ -23,6 +23,8 @@ SPEC_TEXTURE_ILLUMINANT_SRGB, SPEC_TEXTURE_UNBOUNDED_SRGB = 6, 7
 MAT_LAMBERT, MAT_EMISSIVE, MAT_GLASS, MAT_PLASTIC, MAT_CLEARCOAT, MAT_METAL, MAT_SIMPLE_PBR = 0, 1, 2, 3, 4, 5, 6
 STRATEGY = {"pt": 0, "nee": 1, "mis": 2}
 SAMPLER = {"random": 0, "sobol": 1}
+AOV_NORMAL, AOV_ALBEDO, AOV_SHADING_NORMAL = 0, 1, 2      # MI355PT_AOV_*: the reference's NormalRenderer / AlbedoRenderer and the extension
+AOV = {"normal": AOV_NORMAL, "albedo": AOV_ALBEDO, "shading_normal": AOV_SHADING_NORMAL}
 
 
 class Spectrum(C.Structure):
@@ -125,6 +127,7 @@ DEBUG_SYMBOLS = ["debug_unlock", "scene_debug_set_lowering", "scene_export_bvh",
 ABI_SYMBOLS = [
     "scene_create", "scene_destroy", "scene_set_rgb2spec", "scene_add_lut470", "scene_add_tex_rgb8", "scene_add_mesh",
     "scene_add_material", "scene_add_instance", "scene_add_delta_light", "scene_add_environment_light", "scene_set_bvh_builder", "scene_build", "render", "render_accum_device", "film_resolve_device",
+    "render_aov", "render_aov_accum_device", "aov_resolve_device",
     "quantize_u8", "scene_info", "scene_build_multi", "render_multi", "coat_albedo_table",
     "last_error", "version",
 ]
@@ -332,6 +335,12 @@ class Product(Backend):
         lib.mi355pt_render_accum_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_uint32,
                                                     C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         lib.mi355pt_film_resolve_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "mi355pt_render_aov"):                 # (absent from an older build loaded through MI355PT_LIB)
+            lib.mi355pt_render_aov.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_int, C.c_uint32, C.POINTER(C.c_float),
+                                               C.POINTER(Stats)]
+            lib.mi355pt_render_aov_accum_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_int, C.c_uint32, C.c_uint32,
+                                                            C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+            lib.mi355pt_aov_resolve_device.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         if not hasattr(lib, "mi355pt_render_sample_log"):      # an older build loaded through MI355PT_LIB for an A/B timing run
             return
         lib.mi355pt_sample_log_records.argtypes = [C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]
@@ -360,6 +369,24 @@ class Product(Backend):
         st = Stats()
         self.check(self.lib.mi355pt_render(scene.h, C.byref(cam), C.byref(params), _ptr(out, C.c_float), C.byref(st)), "render")
         return (out, st) if want_stats else out
+
+    def render_aov(self, scene, cam, params, kind, illuminant_lut=0, want_stats=False):
+        """RendererImage::<NormalRenderer | AlbedoRenderer>::render (main.rs:155-186) -> (H, W, 3) float32.  kind: AOV_NORMAL / AOV_ALBEDO /
+        AOV_SHADING_NORMAL; illuminant_lut: the LUT470 id of presets()["cie_illum_d6500"] in this scene (albedo only)."""
+        out = np.zeros((cam.height, cam.width, 3), dtype=np.float32)
+        st = Stats()
+        self.check(self.lib.mi355pt_render_aov(scene.h, C.byref(cam), C.byref(params), kind, illuminant_lut, _ptr(out, C.c_float), C.byref(st)),
+                   "render_aov")
+        return (out, st) if want_stats else out
+
+    def render_aov_accum_device(self, scene, cam, params, kind, illuminant_lut, s_begin, s_end, d_accum_ptr, stream=None, stats=None):
+        self.check(self.lib.mi355pt_render_aov_accum_device(scene.h, C.byref(cam), C.byref(params), kind, illuminant_lut, s_begin, s_end,
+                                                            C.c_void_p(d_accum_ptr), C.c_void_p(stream or 0),
+                                                            C.byref(stats) if stats is not None else None), "render_aov_accum_device")
+
+    def aov_resolve_device(self, kind, d_accum_ptr, n_pixels, spp, d_out_ptr, stream=None):
+        self.check(self.lib.mi355pt_aov_resolve_device(kind, C.c_void_p(d_accum_ptr), n_pixels, spp, C.c_void_p(d_out_ptr), C.c_void_p(stream or 0)),
+                   "aov_resolve_device")
 
     def render_accum_device(self, scene, cam, params, s_begin, s_end, d_accum_ptr, stream=None, stats=None):
         self.check(self.lib.mi355pt_render_accum_device(scene.h, C.byref(cam), C.byref(params), s_begin, s_end, C.c_void_p(d_accum_ptr),

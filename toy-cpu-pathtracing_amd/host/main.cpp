@@ -19,7 +19,8 @@ struct Args {   // main.rs:20-53
 static void usage() {
     std::puts("Usage: mi355pt [--scene N] [-s|--spp N] [--seed N] [--filter box] [--sampler random|sobol]\n"
               "               [--renderer normal|albedo|pt|nee|mis] [--width N] [--height N] [-d|--max-depth N] [-o|--output FILE]\n"
-              "       extensions: [--albedo-lut] (clearcoat albedo from its table instead of the 64-sample estimate)  [--gpus N]");
+              "       extensions: [--albedo-lut] (clearcoat albedo from its table instead of the 64-sample estimate)  [--gpus N]\n"
+              "                   [--renderer shading-normal] (render-space shading normal of every surface: the AOV a denoiser takes)");
 }
 
 int main(int argc, char** argv) {
@@ -44,6 +45,12 @@ int main(int argc, char** argv) {
     }
     if (a.filter != "box") { std::fprintf(stderr, "error: invalid value '%s' for '--filter' (main.rs:33-37 offers only box)\n", a.filter.c_str()); return 2; }
     if (a.sampler != "random" && a.sampler != "sobol") { std::fprintf(stderr, "error: invalid value '%s' for '--sampler'\n", a.sampler.c_str()); return 2; }
+    const bool aov = a.renderer == "normal" || a.renderer == "albedo" || a.renderer == "shading-normal";
+    if (!aov && a.renderer != "pt" && a.renderer != "nee" && a.renderer != "mis") {
+        std::fprintf(stderr, "error: invalid value '%s' for '--renderer' (main.rs:38-40: normal, albedo, pt, nee, mis; extension: shading-normal)\n", a.renderer.c_str());
+        return 2;
+    }
+    if (aov && a.gpus > 1) { std::fprintf(stderr, "error: --gpus %d with --renderer %s: the AOV renderers run on one GPU\n", a.gpus, a.renderer.c_str()); return 2; }
     try {
         Camera camera(45.0f, a.width, a.height);                                        // main.rs:59-68
         Scene scene;
@@ -80,7 +87,9 @@ int main(int argc, char** argv) {
         if (a.renderer == "pt") r = SrgbRendererPt(args, 1.0f, a.max_depth);            // main.rs:188-233: exposure 1.0, Reinhard
         else if (a.renderer == "nee") r = SrgbRendererNee(args, 1.0f, a.max_depth);
         else if (a.renderer == "mis") r = SrgbRendererMis(args, 1.0f, a.max_depth);
-        else { std::fprintf(stderr, "renderer '%s' (AOV) is outside the MI355X hot-path scope: use pt, nee or mis\n", a.renderer.c_str()); return 2; }
+        else if (a.renderer == "normal") r = NormalRenderer(args);                      // main.rs:155-170
+        else if (a.renderer == "albedo") r = AlbedoRenderer(args);                      // main.rs:171-186
+        else r = ShadingNormalRenderer(args);
         RendererImage image(a.width, a.height, r);
         std::puts("Start rendering...");                                                // main.rs:166-172
         t0 = std::chrono::steady_clock::now();

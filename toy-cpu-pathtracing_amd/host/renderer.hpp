@@ -682,7 +682,12 @@ public:
     void create_primitive(const PointLightPrimitive& d) { add_light(MI355PT_LIGHT_POINT, d.intensity, 0, 0, d.spectrum, d.transform); }
     void create_primitive(const SpotLightPrimitive& d) { add_light(MI355PT_LIGHT_SPOT, d.intensity, d.angle_inner, d.angle_outer, d.spectrum, d.transform); }
     void create_primitive(const DirectionalLightPrimitive& d) { add_light(MI355PT_LIGHT_DIRECTIONAL, d.intensity, 0, 0, d.spectrum, d.transform); }
-    void build(const Camera& cam) { check(mi355pt_scene_build(s_, &cam.raw()), "mi355pt_scene_build"); }
+    // (LUTs are uploaded by mi355pt_scene_build: presets::cie_illum_d6500(), which AlbedoRenderer multiplies with — albedo_renderer.rs:60 —,
+    // is lowered before it; every scene carries that one 470-float LUT whichever renderer runs)
+    void build(const Camera& cam) {
+        d65_lut_ = lower_spectrum(presets::cie_illum_d6500()).id;
+        check(mi355pt_scene_build(s_, &cam.raw()), "mi355pt_scene_build");
+    }
     // Scene::build over the first `n_devices` GPUs of the node (mi355pt_scene_build_multi): RendererImage::render then shards the frame
     void build_multi(const Camera& cam, int n_devices) {
         std::vector<int> ids((size_t)n_devices);
@@ -691,6 +696,7 @@ public:
         multi_ = true;
     }
     bool multi() const { return multi_; }
+    uint32_t d65_lut() const { return d65_lut_; }      // LUT470 id of presets::cie_illum_d6500() (MI355PT_NONE before build())
     const mi355pt_scene* raw() const { return s_; }
 
 private:
@@ -714,15 +720,22 @@ private:
     }
     mi355pt_scene* s_ = nullptr;
     bool multi_ = false;
+    uint32_t d65_lut_ = MI355PT_NONE;
 };
 
 // ------------------------------------------------------------------ renderers (renderer/src/renderer.rs:84-149, main.rs:142-237)
 enum class SamplerKind { Random = MI355PT_SAMPLER_RANDOM, ZSobol = MI355PT_SAMPLER_SOBOL };
 struct RendererArgs { uint32_t width, height, spp, seed; const Scene* scene; const Camera* camera; };
-struct SrgbRenderer { RendererArgs args; uint32_t strategy; float exposure; uint32_t max_depth; };
+// (aov: -1 = a path renderer; MI355PT_AOV_* = NormalRenderer / AlbedoRenderer / the shading-normal extension, which take only the args)
+struct SrgbRenderer { RendererArgs args; uint32_t strategy; float exposure; uint32_t max_depth; int aov = -1; };
 inline SrgbRenderer SrgbRendererPt(RendererArgs a, float exposure, uint32_t max_depth) { return {a, MI355PT_STRATEGY_PT, exposure, max_depth}; }
 inline SrgbRenderer SrgbRendererNee(RendererArgs a, float exposure, uint32_t max_depth) { return {a, MI355PT_STRATEGY_NEE, exposure, max_depth}; }
 inline SrgbRenderer SrgbRendererMis(RendererArgs a, float exposure, uint32_t max_depth) { return {a, MI355PT_STRATEGY_MIS, exposure, max_depth}; }
+// NormalRenderer::new(args) / AlbedoRenderer::new(args) (renderer/normal_renderer.rs:17-21, albedo_renderer.rs:21-25; main.rs:155-186)
+inline SrgbRenderer NormalRenderer(RendererArgs a) { return {a, MI355PT_STRATEGY_PT, 1.0f, 0u, MI355PT_AOV_NORMAL}; }
+inline SrgbRenderer AlbedoRenderer(RendererArgs a) { return {a, MI355PT_STRATEGY_PT, 1.0f, 0u, MI355PT_AOV_ALBEDO}; }
+// extension, no reference counterpart: the render-space shading normal of every surface (MI355PT_AOV_SHADING_NORMAL)
+inline SrgbRenderer ShadingNormalRenderer(RendererArgs a) { return {a, MI355PT_STRATEGY_PT, 1.0f, 0u, MI355PT_AOV_SHADING_NORMAL}; }
 
 class RendererImage {
 public:
@@ -733,6 +746,12 @@ public:
         mi355pt_params p{};
         p.spp = r_.args.spp; p.seed = r_.args.seed; p.max_depth = r_.max_depth; p.strategy = r_.strategy; p.sampler = (uint32_t)sampler;
         p.exposure = r_.exposure; p.shard_index = 0; p.shard_count = 1; p.albedo_lut = albedo_lut ? 1u : 0u;
+        if (r_.aov >= 0) {                                  // RendererImage::<NormalRenderer | AlbedoRenderer>::render (main.rs:155-186)
+            if (r_.args.scene->multi()) throw std::runtime_error("the AOV renderers run on one GPU (mi355pt_render_multi has no AOV form)");
+            mi355pt_stats st{};
+            check(mi355pt_render_aov(r_.args.scene->raw(), &r_.args.camera->raw(), &p, r_.aov, r_.args.scene->d65_lut(), pixels_.data(), &st), "mi355pt_render_aov");
+            return st.kernel_ms * 1e-3;
+        }
         if (r_.args.scene->multi()) {                       // several GPUs from this one call: no per-launch statistics
             check(mi355pt_render_multi(r_.args.scene->raw(), &r_.args.camera->raw(), &p, pixels_.data()), "mi355pt_render_multi");
             return 0.0;
