@@ -1,6 +1,6 @@
 #!/bin/bash
-# usage (GPU box): tools/ray_bench.sh — kernel times of probe_intersect on coherent / incoherent rays, lock-step (mode 1) vs
-# dynamic fetch (mode 2); MI355PT_LIB selects a variant library
+# usage (GPU box): tools/ray_bench.sh — kernel times of probe_intersect (lock-step, 64 rays per wave) on coherent / incoherent rays;
+# MI355PT_LIB selects a variant library
 R=${GRAFT_REPO_ROOT:-$PWD}
 cd /tmp && export TMPDIR=/tmp
 rm -rf $R/gpurun_out/rb

@@ -74,8 +74,8 @@ constexpr float NODE4_PAD_REL = 1.0f / (float)(1u << PT_NODE_PAD_LOG2);   // 2^-
 // Two reasons, both in the counters: (1) a grid cell of the Cornell room is 1.8e-4, eighteen times RAY_EPS — the flat leaf boxes of the
 // walls become slabs that CONTAIN the origins of the rays leaving them, so every bounce off a wall tests the wall's own triangles again
 // (triangle tests per sample 8.4 -> 12.1 closest, 3.1 -> 6.5 shadow: +2.2 dense triangle steps per iteration); (2) the node steps themselves
-// got no faster with 43 % fewer L1 requests — like round 2's 32-byte nodes.  (An ablation that ADDS requests, PT_ABLATE_EXTRA_NODE_LOADS,
-// loses 9 % per 3 requests, but it also adds 12 live registers; the two quantisation experiments say the request count is not the lever.)
+// got no faster with 43 % fewer L1 requests — like round 2's 32-byte nodes.  (An ablation that ADDED requests to the node step, since
+// removed, lost 9 % per 3 requests, but it also added 12 live registers; the two quantisation experiments say the request count is not the lever.)
 #ifndef PT_NODE_Q16
 #define PT_NODE_Q16 0
 #endif

@@ -177,9 +177,6 @@ PT_DEV uint64_t sobol_tile_hi_digits(uint32_t tile_morton_shifted, uint32_t dime
         digit = (perm_packed(p) >> (2u * digit)) & 3u;
         out |= (uint64_t)digit << shift;
     }
-#ifdef PT_HI_BREAK
-    out ^= 0x300000000ull;
-#endif
     return out;
 }
 // permutation index (0..23) of the digit whose higher digits are `higher` (z_sobol_sampler.rs:134-145)
@@ -188,9 +185,6 @@ PT_DEV uint32_t sobol_perm_index(uint64_t higher, uint32_t dimension) {
     return (((uint32_t)(mx >> 32) * 16u) + ((uint32_t)mx % 24u)) % 24u;
 }
 PT_DEV uint64_t sampler_index(const Sampler& s, const SamplerCtx& c) {
-#ifdef PT_SOBOL_ABLATE   // timing experiment only: skips the digit permutation (wrong sequence)
-    return (uint64_t)s.morton;
-#endif
     if (c.hi_lds != nullptr && s.dimension < (uint32_t)SOBOL_HI_DIMS) {
         // tile-uniform prefix, plus the two digits below it through tile-uniform permutation indices: the permutation of digit
         // hi_first-1 depends on the prefix only, the one of digit hi_first-2 on the prefix and the 4 values of digit hi_first-1
@@ -296,25 +290,14 @@ PT_DEV float sigmoid_value(float c0, float c1, float c2, float lambda) {   // rg
 #endif
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
 }
-// (float)c / 255.0f for c = 0..255, correctly rounded at compile time: a load (the memory pipes are idle) instead of the ~10 VALU
-// instructions of an IEEE division, twelve times per bilinear lookup
-struct U8UnitTable { float v[256]; };
-constexpr U8UnitTable make_u8_unit() { U8UnitTable t{}; for (int i = 0; i < 256; ++i) t.v[i] = (float)i / 255.0f; return t; }
-__device__ constexpr U8UnitTable U8_UNIT = make_u8_unit();
-#ifndef PT_U8_VALU
-#define PT_U8_VALU 1
-#endif
 // (float)c / 255.0f in four VALU instructions and no memory round trip: q = c * fl(1/255) is off by an ulp for 126 of the 256 values; one
 // residual step q + (c - 255 q) * fl(1/255), both in fma, is the correctly rounded quotient for every c in 0..255 (checked exhaustively on
-// the host with glibc's fmaf, tests/test_abi.py).  The table variant put a dependent gather between the texel fetch and the colour maths.
+// the host with glibc's fmaf, tests/test_abi.py).  Measured against a 256-entry table of the correctly rounded quotients: the table put a
+// dependent gather between the texel fetch and the colour maths.
 PT_DEV float u8_unit(uint32_t c) {
-#if PT_U8_VALU
     const float x = (float)c, r = 1.0f / 255.0f;
     const float q = x * r;
     return fmaf(fmaf(-255.0f, q, x), r, q);
-#else
-    return U8_UNIT.v[c];
-#endif
 }
 PT_DEV void fetch_texel(const DevScene& sc, const DevTexture& t, uint32_t x, uint32_t y, float out[3]) {
     uint32_t v = sc.texels[t.offset + y * t.w + x];
@@ -341,15 +324,7 @@ PT_DEV void bilinear_rgb(const DevScene& sc, uint32_t tex, f2 uv, float out[3]) 
 // The 64 z nodes of the table (256 B) live in LDS: the search for the z cell is a chain of 6 dependent reads, then 2 more for the cell's
 // ends — LDS round trips (~100 cycles) instead of L1 ones (several hundred under this kernel's load) on the critical path of every
 // textured lookup.  Filled by the kernel's prologue (pt_kernel.hpp); the LDS allocation stays inside the same 512-B granule.
-#ifndef PT_ZNODES_LDS
-#define PT_ZNODES_LDS 1
-#endif
-#if PT_ZNODES_LDS
 static __shared__ float s_znodes[64];
-#define PT_ZNODE(sc, i) s_znodes[i]
-#else
-#define PT_ZNODE(sc, i) (sc).z_nodes[i]
-#endif
 // RgbToSpectrumTable::get for gamma-encoded sRGB input (rgb_sigmoid_polynomial.rs:87-155); table repacked to float4 cells.
 PT_DEV void rgb2spec_lookup(const DevScene& sc, const float enc[3], float c[3]) {
     float rgb[3];
@@ -364,8 +339,7 @@ PT_DEV void rgb2spec_lookup(const DevScene& sc, const float enc[3], float c[3]) 
     float r2 = mc == 0 ? rgb[2] : (mc == 1 ? rgb[0] : rgb[1]);
     float x = r1 * 63.0f / z, y = r2 * 63.0f / z;
     int xi = min((int)x, 62), yi = min((int)y, 62);
-    // first i in [0,62] with z_nodes[i+1] > z (else 62): the nodes increase monotonically -> binary search
-#if PT_ZNODES_LDS
+    // first i in [0,62] with z_nodes[i+1] > z (else 62)
     // = the number of nodes 1..63 that are not above z, at most 62 (the nodes increase monotonically; a NaN z counts them all, like the
     // reference's search that finds no node above it): two rounds of independent LDS reads — every eighth node, then the seven inside
     // the octant — instead of a chain of six dependent ones
@@ -376,15 +350,7 @@ PT_DEV void rgb2spec_lookup(const DevScene& sc, const float enc[3], float c[3]) 
 #pragma unroll
     for (int j = 1; j < 8; ++j) zi += !(s_znodes[8 * c1 + j] > z) ? 1 : 0;
     zi = min(zi, 62);
-#else
-    int lo = 0, hi = 62;
-    if (!(PT_ZNODE(sc, 63) > z)) lo = 62;
-    else {
-        while (lo < hi) { int mid = (lo + hi) >> 1; if (PT_ZNODE(sc, mid + 1) > z) hi = mid; else lo = mid + 1; }
-    }
-    int zi = lo;
-#endif
-    float zn0 = PT_ZNODE(sc, zi), zn1 = PT_ZNODE(sc, zi + 1);
+    float zn0 = s_znodes[zi], zn1 = s_znodes[zi + 1];
     float dx = x - (float)xi, dy = y - (float)yi, dz = (z - zn0) / (zn1 - zn0);
     const float4* tab = (const float4*)sc.rgb2spec;
     size_t base = (((size_t)mc * 64 + zi) * 64 + yi) * 64 + xi;
@@ -707,13 +673,10 @@ PT_DEV bool trace_any(const DevScene& sc, f3 ro, f3 rd, float t_max, uint32_t* s
 // +inf if the ray misses it.  Unused slots hold a POINT box at +FLT_MAX (bvh_builder.cpp collapse_bvh4): its slab distances are
 // +-FLT_MAX * |1/d| (|1/d| >= 1 for a unit direction), outside [0, t_lim] as long as t_lim <= 1e30: the callers' contract, see below.
 struct Node4Hits { float n[4]; int32_t link[4]; };
-// PT_NODE_SEL 1: the NEAR and FAR plane of every slab are chosen by the sign of the ray direction through the LOAD ADDRESS (the node keeps
-// lo and hi planes of an axis as two consecutive float4: near = the one at +16 B when 1/d is negative) instead of by a min / max pair per
-// child and axis after the fact: (lo - o) * inv <= (hi - o) * inv exactly when inv > 0 (rounding is monotonic), so the values are the ones
-// min / max produced, for 24 VALU instructions less per node step (of ~125).  0: the min / max form.
-#ifndef PT_NODE_SEL
-#define PT_NODE_SEL 1
-#endif
+// The NEAR and FAR plane of every slab are chosen by the sign of the ray direction through the LOAD ADDRESS (the node keeps lo and hi planes
+// of an axis as two consecutive float4: near = the one at +16 B when 1/d is negative) instead of by a min / max pair per child and axis
+// after the fact: (lo - o) * inv <= (hi - o) * inv exactly when inv > 0 (rounding is monotonic), so the values are the ones min / max
+// produced.  Measured: 24 VALU instructions less per node step (of ~125) than the min / max form.
 #if PT_NODE_Q16
 // The quantised form (layout.hpp DevNode4Q): `ro` holds (grid origin - o) / d and `inv` cell / d (walk_ray below), so a plane's distance is
 // one fma on the converted 16-bit integer.  Four requests: the x, y, z rows (lo and hi planes of the four children in ONE 16-byte row each)
@@ -722,9 +685,7 @@ PT_DEV Node4Hits node4q_step(const DevNode4Q* nodes, int32_t cur, f3 ro, f3 inv,
     const uint4* q = (const uint4*)(nodes + cur);
     const uint4 X = q[0], Y = q[1], Z = q[2];
     const int4 ch = *(const int4*)(q + 3);
-#if PT_NODE_LOADS_FIRST
-    __builtin_amdgcn_sched_barrier(0);
-#endif
+    __builtin_amdgcn_sched_barrier(0);      // loads first, see node4_step
     const bool sx = inv.x < 0.0f, sy = inv.y < 0.0f, sz = inv.z < 0.0f;        // (cell > 0: the sign of cell / d is the sign of d; -0 counts as +)
     const uint32_t nx01 = sx ? X.z : X.x, nx23 = sx ? X.w : X.y, fx01 = sx ? X.x : X.z, fx23 = sx ? X.y : X.w;
     const uint32_t ny01 = sy ? Y.z : Y.x, ny23 = sy ? Y.w : Y.y, fy01 = sy ? Y.x : Y.z, fy23 = sy ? Y.y : Y.w;
@@ -752,7 +713,6 @@ PT_DEV Node4Hits node4_step(const DevNode4* nodes, int32_t cur, f3 ro, f3 inv, f
     // CONTRACT: t_lim <= 1e30 (every caller clamps its limit once per ray, not once per step: trace_any_deferred / trace_closest_coop /
     // trace_pair_coop initialise and only ever shrink w_t / w_tmax / w_tbest from min(t, 1e30)).
     float n0, n1, n2, n3, f0, f1, f2, f3_;
-#if PT_NODE_SEL
     const char* base = (const char*)nodes;
     const uint32_t o = (uint32_t)cur << 7;
     const uint32_t ox = o + ((__float_as_uint(inv.x) >> 27) & 16u), oy = o + ((__float_as_uint(inv.y) >> 27) & 16u), oz = o + ((__float_as_uint(inv.z) >> 27) & 16u);
@@ -762,22 +722,7 @@ PT_DEV Node4Hits node4_step(const DevNode4* nodes, int32_t cur, f3 ro, f3 inv, f
     const int4 ch = *(const int4*)(base + 96 + o);
     // all seven loads of the node are issued before the first slab is evaluated: left alone, the scheduler sinks the links' load below the
     // box arithmetic (fewer live registers) and the step then waits for a SECOND L1 round trip at its very end
-#ifndef PT_NODE_LOADS_FIRST
-#define PT_NODE_LOADS_FIRST 1
-#endif
-#ifdef PT_ABLATE_EXTRA_NODE_LOADS   // timing experiment: N more 16-B requests per lane and node step (same cache line, results unused) — how
-    {                               // much does a node step's time depend on the NUMBER of L1 requests?  
-        typedef float v4f __attribute__((ext_vector_type(4)));
-        v4f extra[PT_ABLATE_EXTRA_NODE_LOADS];
-#pragma unroll
-        for (int e = 0; e < PT_ABLATE_EXTRA_NODE_LOADS; ++e) extra[e] = *(const volatile v4f*)(base + o + 112 - 16 * (e % 7));
-#pragma unroll
-        for (int e = 0; e < PT_ABLATE_EXTRA_NODE_LOADS; ++e) asm volatile("" ::"v"(extra[e]));
-    }
-#endif
-#if PT_NODE_LOADS_FIRST
     __builtin_amdgcn_sched_barrier(0);
-#endif
 #if PT_NODE_FMA     // `ro` holds -(o * inv) (walk_origin below), the boxes are padded by the host: layout.hpp
 #define PT_SLAB(C, N, F) N = fmaxf(fmaxf(fmaxf(fmaf(ax.C, inv.x, ro.x), fmaf(ay.C, inv.y, ro.y)), fmaf(az.C, inv.z, ro.z)), 0.0f); \
                          F = fminf(fminf(fminf(fmaf(bx.C, inv.x, ro.x), fmaf(by.C, inv.y, ro.y)), fmaf(bz.C, inv.z, ro.z)), t_lim);
@@ -787,43 +732,20 @@ PT_DEV Node4Hits node4_step(const DevNode4* nodes, int32_t cur, f3 ro, f3 inv, f
 #endif
     PT_SLAB(x, n0, f0) PT_SLAB(y, n1, f1) PT_SLAB(z, n2, f2) PT_SLAB(w, n3, f3_)
 #undef PT_SLAB
-#else
-    const float4* q = (const float4*)(nodes + cur);
-    // axis by axis: the interval of each child narrows as its x, y, z slabs arrive (max / min are exact, so the order does not change a
-    // result); two float4 of planes are live at a time instead of six — the traversal loop sits inside the register budget of the path state
-    n0 = 0.0f; n1 = 0.0f; n2 = 0.0f; n3 = 0.0f; f0 = t_lim; f1 = t_lim; f2 = t_lim; f3_ = t_lim;
-#define PT_AXIS4(LO, HI, O, I)                                                                                              \
-    {                                                                                                                       \
-        const float4 lo = q[LO], hi = q[HI];                                                                                \
-        float l, h;                                                                                                         \
-        l = (lo.x - O) * I; h = (hi.x - O) * I; n0 = fmaxf(n0, fminf(l, h)); f0 = fminf(f0, fmaxf(l, h));                    \
-        l = (lo.y - O) * I; h = (hi.y - O) * I; n1 = fmaxf(n1, fminf(l, h)); f1 = fminf(f1, fmaxf(l, h));                    \
-        l = (lo.z - O) * I; h = (hi.z - O) * I; n2 = fmaxf(n2, fminf(l, h)); f2 = fminf(f2, fmaxf(l, h));                    \
-        l = (lo.w - O) * I; h = (hi.w - O) * I; n3 = fmaxf(n3, fminf(l, h)); f3_ = fminf(f3_, fmaxf(l, h));                  \
-    }
-    PT_AXIS4(0, 1, ro.x, inv.x) PT_AXIS4(2, 3, ro.y, inv.y) PT_AXIS4(4, 5, ro.z, inv.z)
-#undef PT_AXIS4
-    const int4 ch = *(const int4*)(q + 6);
-#endif
     Node4Hits h;
     h.n[0] = n0 <= f0 ? n0 : INFINITY; h.n[1] = n1 <= f1 ? n1 : INFINITY; h.n[2] = n2 <= f2 ? n2 : INFINITY; h.n[3] = n3 <= f3_ ? n3 : INFINITY;
     h.link[0] = ch.x; h.link[1] = ch.y; h.link[2] = ch.z; h.link[3] = ch.w;
     return h;
 }
 // what a walking lane keeps as the "origin" of its ray: the origin itself, or with PT_NODE_FMA in the 4-wide tree the slab addend -(o * 1/d)
-#if PT_NODE_FMA && !PT_NODE_SEL
-#error "PT_NODE_FMA needs PT_NODE_SEL"
-#endif
-template <bool WIDE>
 PT_DEV f3 walk_origin(const DevScene& sc, f3 ro, f3 inv) {
-    if (WIDE && PT_NODE_Q16) return mk3((sc.grid_org[0] - ro.x) * inv.x, (sc.grid_org[1] - ro.y) * inv.y, (sc.grid_org[2] - ro.z) * inv.z);
-    if (WIDE && PT_NODE_FMA) return mk3(-(ro.x * inv.x), -(ro.y * inv.y), -(ro.z * inv.z));
+    if (PT_NODE_Q16) return mk3((sc.grid_org[0] - ro.x) * inv.x, (sc.grid_org[1] - ro.y) * inv.y, (sc.grid_org[2] - ro.z) * inv.z);
+    if (PT_NODE_FMA) return mk3(-(ro.x * inv.x), -(ro.y * inv.y), -(ro.z * inv.z));
     return ro;
 }
 // ... and as its reciprocal direction: 1 / d, or with PT_NODE_Q16 the grid cell over d
-template <bool WIDE>
 PT_DEV f3 walk_inv(const DevScene& sc, f3 inv) {
-    if (WIDE && PT_NODE_Q16) return mk3(sc.grid_cell[0] * inv.x, sc.grid_cell[1] * inv.y, sc.grid_cell[2] * inv.z);
+    if (PT_NODE_Q16) return mk3(sc.grid_cell[0] * inv.x, sc.grid_cell[1] * inv.y, sc.grid_cell[2] * inv.z);
     return inv;
 }
 PT_DEV Node4Hits wide_step(const DevScene& sc, int32_t cur, f3 wo, f3 wi, float t_lim) {
@@ -833,27 +755,19 @@ PT_DEV Node4Hits wide_step(const DevScene& sc, int32_t cur, f3 wo, f3 wi, float 
     return node4_step(sc.nodes4, cur, wo, wi, t_lim);
 #endif
 }
-// nearest child to slot 0 (PT_SORT_MODE 1) or ascending by entry distance (0); misses (+inf) are skipped by the pushes
-// stack pushes of the 4-wide step as stores-always / advance-conditionally: a slot written for a miss lies above the top and is never read
-// (the collapse bounds the need below STACK_DEPTH, so slot `sp` itself always exists); three LDS stores instead of three exec-mask regions:
-// +0.4...+0.6 % once the step was down to three compare-exchanges (0.0 before)
-#ifndef PT_PUSH_BRANCHFREE
-#define PT_PUSH_BRANCHFREE 1
-#endif
-#ifndef PT_SORT_MODE
-#define PT_SORT_MODE 1      // 0: full sorting network (5 compare-exchanges); 1: nearest child first, the rest in slot order (3): the
-                            // later pops are a little less well ordered, the step is 16 instructions shorter: +0.4...+0.7 %
-#endif
+// The nearest child to slot 0, the rest in slot order (3 compare-exchanges); misses (+inf) among 1..3 are skipped by the pushes.  Measured
+// against the full sorting network (5 compare-exchanges, ascending by entry distance): the later pops are a little less well ordered, the
+// step is 16 instructions shorter: +0.4...+0.7 %.
 PT_DEV void sort4(Node4Hits& h) {
 #define PT_CSWAP(a, b) { const bool s = h.n[b] < h.n[a]; const float tn = s ? h.n[b] : h.n[a]; const float tx = s ? h.n[a] : h.n[b]; \
                          const int32_t ln = s ? h.link[b] : h.link[a]; const int32_t lx = s ? h.link[a] : h.link[b]; h.n[a] = tn; h.n[b] = tx; h.link[a] = ln; h.link[b] = lx; }
-#if PT_SORT_MODE == 1
-    PT_CSWAP(0, 1) PT_CSWAP(0, 2) PT_CSWAP(0, 3)          // the minimum to slot 0; misses (+inf) among 1..3 are skipped by the pushes
-#else
-    PT_CSWAP(0, 1) PT_CSWAP(2, 3) PT_CSWAP(0, 2) PT_CSWAP(1, 3) PT_CSWAP(1, 2)
-#endif
+    PT_CSWAP(0, 1) PT_CSWAP(0, 2) PT_CSWAP(0, 3)
 #undef PT_CSWAP
 }
+// The callers push the children 3, 2, 1 of a sorted step farthest first, so that the nearer is popped first, as stores-always /
+// advance-conditionally: a slot written for a miss lies above the top and is never read (the collapse bounds the need below STACK_DEPTH, so
+// slot `sp` itself always exists).  Measured: three LDS stores instead of three exec-mask regions, +0.4...+0.6 % once the step was down to
+// three compare-exchanges (0.0 before).  (Written out at both places: a helper taking `sp` by reference changes the register allocation.)
 
 // Any hit with DEFERRED, DENSE triangle tests (wave-cooperative; every lane of the wave must call it, `want` = this lane has
 // a ray).  In the plain loop above a wave spends most of its any-hit VALU time on triangle steps executed for the one or
@@ -865,9 +779,6 @@ PT_DEV void sort4(Node4Hits& h) {
 constexpr uint32_t ANY_RING = 256;            // entries; a step appends <= 2 per lane, a flush leaves < 64 behind
 struct AnyLds { uint32_t* ring; uint32_t* occl; uint32_t* pair; };   // ring[ANY_RING] (tri | owner << 26), occl[2] (bit per lane), pair[64] (steal rounds)
 
-#ifndef PT_ANY_STEAL
-#define PT_ANY_STEAL 1        // idle lanes take whole subtrees off the stacks of the lanes still walking (same ray, same result)
-#endif
 #ifndef PT_STEAL_EVERY
 #define PT_STEAL_EVERY 1u
 #endif
@@ -877,7 +788,7 @@ struct AnyLds { uint32_t* ring; uint32_t* occl; uint32_t* pair; };   // ring[ANY
 #ifndef PT_STEAL_MAX_ACTIVE
 #define PT_STEAL_MAX_ACTIVE 52
 #endif
-template <bool STATS, bool WIDE>
+template <bool STATS>
 PT_DEV bool trace_any_deferred(const DevScene& sc, f3 ro, f3 rd, float t_max, bool want, uint32_t* stack, uint32_t lane, const AnyLds& L,
                                StatCounters& st) {
     if (!want) { rd = mk3(0.0f, 0.0f, 1.0f); ro = mk3(0.0f, 0.0f, 0.0f); t_max = 0.0f; }
@@ -888,9 +799,9 @@ PT_DEV bool trace_any_deferred(const DevScene& sc, f3 ro, f3 rd, float t_max, bo
     // the ray this lane is WALKING (its own, or one it is helping with) — the lane's own ray stays in ro/rd/rs for the flushes
     // (box tests only see distances up to 1e30: the unused slots of a DevNode4 are point boxes at FLT_MAX, whose slab distance FLT_MAX / |d|
     // must never fall inside [0, t_lim] — an unbounded shadow ray (t_max = FLT_MAX, directional and environment lights) would let it)
-    f3 w_ro = walk_origin<WIDE>(sc, ro, rs.inv), w_inv = walk_inv<WIDE>(sc, rs.inv); float w_tmax = fminf(t_max, 1e30f); uint32_t owner = lane;
+    f3 w_ro = walk_origin(sc, ro, rs.inv), w_inv = walk_inv(sc, rs.inv); float w_tmax = fminf(t_max, 1e30f); uint32_t owner = lane;
     int sp = 0, sb = 0;
-    int32_t cur = WIDE ? sc.root4 : sc.root;
+    int32_t cur = sc.root4;
     uint32_t leaf_off = 0;                    // triangles of the current leaf already queued
     bool done = !want;
     uint32_t head = 0, tail = 0;              // wave-uniform ring cursors
@@ -920,43 +831,20 @@ PT_DEV bool trace_any_deferred(const DevScene& sc, f3 ro, f3 rd, float t_max, bo
 
     for (;;) {
         if (!done && cur >= 0) {
-            if constexpr (WIDE) {
-                if (STATS) { st.nodes_shadow++; const int busy = __popcll(__ballot(true)); if (wave_leader()) { st.w[2]++; st.hist[8 + ((busy - 1) >> 3)]++; } }
-                const Node4Hits h = wide_step(sc, cur, w_ro, w_inv, w_tmax);
-                // any-hit needs no order: continue into the first child hit, queue the others
-                int32_t nxt = 0; bool have = false;
-    #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    if (h.n[c] < INFINITY) {
-                        if (!have) { have = true; nxt = h.link[c]; }
-                        else { stack[sp * 64] = (uint32_t)h.link[c]; ++sp; }
-                    }
+            if (STATS) { st.nodes_shadow++; const int busy = __popcll(__ballot(true)); if (wave_leader()) { st.w[2]++; st.hist[8 + ((busy - 1) >> 3)]++; } }
+            const Node4Hits h = wide_step(sc, cur, w_ro, w_inv, w_tmax);
+            // any-hit needs no order: continue into the first child hit, queue the others
+            int32_t nxt = 0; bool have = false;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (h.n[c] < INFINITY) {
+                    if (!have) { have = true; nxt = h.link[c]; }
+                    else { stack[sp * 64] = (uint32_t)h.link[c]; ++sp; }
                 }
-                if (have) cur = nxt;
-                else if (sp == sb) done = true;
-                else { --sp; cur = (int32_t)stack[sp * 64]; }
-            } else {
-                const float4* q = (const float4*)(sc.nodes + cur);
-                float4 nx = q[0], ny = q[1], nz = q[2];
-                int2 ch = *(const int2*)(q + 3);
-                if (STATS) { st.nodes_shadow++; const int busy = __popcll(__ballot(true)); if (wave_leader()) { st.w[2]++; st.hist[8 + ((busy - 1) >> 3)]++; } }
-                float l0x = (nx.x - w_ro.x) * w_inv.x, h0x = (nx.z - w_ro.x) * w_inv.x;
-                float l1x = (nx.y - w_ro.x) * w_inv.x, h1x = (nx.w - w_ro.x) * w_inv.x;
-                float l0y = (ny.x - w_ro.y) * w_inv.y, h0y = (ny.z - w_ro.y) * w_inv.y;
-                float l1y = (ny.y - w_ro.y) * w_inv.y, h1y = (ny.w - w_ro.y) * w_inv.y;
-                float l0z = (nz.x - w_ro.z) * w_inv.z, h0z = (nz.z - w_ro.z) * w_inv.z;
-                float l1z = (nz.y - w_ro.z) * w_inv.z, h1z = (nz.w - w_ro.z) * w_inv.z;
-                float n0 = fmaxf(fmaxf(fminf(l0x, h0x), fminf(l0y, h0y)), fmaxf(fminf(l0z, h0z), 0.0f));
-                float f0 = fminf(fminf(fmaxf(l0x, h0x), fmaxf(l0y, h0y)), fminf(fmaxf(l0z, h0z), w_tmax));
-                float n1 = fmaxf(fmaxf(fminf(l1x, h1x), fminf(l1y, h1y)), fmaxf(fminf(l1z, h1z), 0.0f));
-                float f1 = fminf(fminf(fmaxf(l1x, h1x), fmaxf(l1y, h1y)), fminf(fmaxf(l1z, h1z), w_tmax));
-                bool hit0 = n0 <= f0, hit1 = n1 <= f1;
-                if (hit0 && hit1) { stack[sp * 64] = (uint32_t)ch.y; ++sp; cur = ch.x; }
-                else if (hit0) cur = ch.x;
-                else if (hit1) cur = ch.y;
-                else if (sp == sb) done = true;
-                else { --sp; cur = (int32_t)stack[sp * 64]; }
             }
+            if (have) cur = nxt;
+            else if (sp == sb) done = true;
+            else { --sp; cur = (int32_t)stack[sp * 64]; }
         }
         // lanes sitting in a leaf queue up to two of its triangles per step, then move on
         const bool at_leaf = !done && cur < 0;
@@ -979,7 +867,6 @@ PT_DEV bool trace_any_deferred(const DevScene& sc, f3 ro, f3 rd, float t_max, bo
         }
         const unsigned long long m_act = __ballot(!done);
         if (m_act == 0ull) break;
-#if PT_ANY_STEAL
         // work stealing: when most of the wave idles, idle lanes take the BOTTOM stack entry (the largest pending subtree) of
         // lanes that still have one, together with that lane's working ray.  Any-hit is an OR over all subtrees, so the
         // result is unchanged; the owner's bit in occl[] is shared by everybody working on the ray.
@@ -1010,7 +897,6 @@ PT_DEV bool trace_any_deferred(const DevScene& sc, f3 ro, f3 rd, float t_max, bo
                 __syncthreads();
             }
         }
-#endif
     }
     if (tail != head) flush(tail - head);     // stragglers' last pairs (tail - head < 64 here)
     return ((L.occl[lane >> 5] >> (lane & 31u)) & 1u) != 0u;
@@ -1027,7 +913,7 @@ PT_DEV bool trace_any_deferred(const DevScene& sc, f3 ro, f3 rd, float t_max, bo
 #endif
 struct ClosestLds { uint32_t* ring; unsigned long long* best; uint32_t* pair; };   // ring[ANY_RING], best[64], pair[64]
 
-template <bool STATS, bool WIDE>
+template <bool STATS>
 PT_DEV bool trace_closest_coop(const DevScene& sc, f3 ro, f3 rd, bool want, uint32_t* stack, uint32_t lane, const ClosestLds& L, Hit& hit,
                                StatCounters& st) {
     if (!want) { rd = mk3(0.0f, 0.0f, 1.0f); ro = mk3(0.0f, 0.0f, 0.0f); }
@@ -1035,9 +921,9 @@ PT_DEV bool trace_closest_coop(const DevScene& sc, f3 ro, f3 rd, bool want, uint
     const uint32_t kpack = (uint32_t)rs.kx | ((uint32_t)rs.ky << 2) | ((uint32_t)rs.kz << 4);
     L.best[lane] = (0x7f7fffffull << 32) | 0xffffffffull;                 // (FLT_MAX, no triangle)
     __syncthreads();
-    f3 w_ro = walk_origin<WIDE>(sc, ro, rs.inv), w_inv = walk_inv<WIDE>(sc, rs.inv); float w_tbest = 1e30f; uint32_t owner = lane;             // box-test limit, see trace_any_deferred
+    f3 w_ro = walk_origin(sc, ro, rs.inv), w_inv = walk_inv(sc, rs.inv); float w_tbest = 1e30f; uint32_t owner = lane;             // box-test limit, see trace_any_deferred
     int sp = 0, sb = 0;
-    int32_t cur = WIDE ? sc.root4 : sc.root;
+    int32_t cur = sc.root4;
     uint32_t leaf_off = 0;
     bool done = !want;
     uint32_t head = 0, tail = 0;
@@ -1077,48 +963,16 @@ PT_DEV bool trace_closest_coop(const DevScene& sc, f3 ro, f3 rd, bool want, uint
 
     for (;;) {
         if (!done && cur >= 0) {
-            if constexpr (WIDE) {
-                if (STATS) { st.nodes_closest++; const int busy = __popcll(__ballot(true)); if (wave_leader()) { st.w[0]++; st.hist[0 + ((busy - 1) >> 3)]++; } }
-                Node4Hits h = wide_step(sc, cur, w_ro, w_inv, w_tbest);
-                sort4(h);
-                // nearest child next; the others go to the stack farthest first, so that the nearer of them is popped first
-#if PT_PUSH_BRANCHFREE
-                stack[sp * 64] = (uint32_t)h.link[3]; sp += h.n[3] < INFINITY ? 1 : 0;
-                stack[sp * 64] = (uint32_t)h.link[2]; sp += h.n[2] < INFINITY ? 1 : 0;
-                stack[sp * 64] = (uint32_t)h.link[1]; sp += h.n[1] < INFINITY ? 1 : 0;
-#else
-                if (h.n[3] < INFINITY) { stack[sp * 64] = (uint32_t)h.link[3]; ++sp; }
-                if (h.n[2] < INFINITY) { stack[sp * 64] = (uint32_t)h.link[2]; ++sp; }
-                if (h.n[1] < INFINITY) { stack[sp * 64] = (uint32_t)h.link[1]; ++sp; }
-#endif
-                if (h.n[0] < INFINITY) cur = h.link[0];
-                else if (sp == sb) done = true;
-                else { --sp; cur = (int32_t)stack[sp * 64]; }
-            } else {
-                const float4* q = (const float4*)(sc.nodes + cur);
-                float4 nx = q[0], ny = q[1], nz = q[2];
-                int2 ch = *(const int2*)(q + 3);
-                if (STATS) { st.nodes_closest++; const int busy = __popcll(__ballot(true)); if (wave_leader()) { st.w[0]++; st.hist[0 + ((busy - 1) >> 3)]++; } }
-                float l0x = (nx.x - w_ro.x) * w_inv.x, h0x = (nx.z - w_ro.x) * w_inv.x;
-                float l1x = (nx.y - w_ro.x) * w_inv.x, h1x = (nx.w - w_ro.x) * w_inv.x;
-                float l0y = (ny.x - w_ro.y) * w_inv.y, h0y = (ny.z - w_ro.y) * w_inv.y;
-                float l1y = (ny.y - w_ro.y) * w_inv.y, h1y = (ny.w - w_ro.y) * w_inv.y;
-                float l0z = (nz.x - w_ro.z) * w_inv.z, h0z = (nz.z - w_ro.z) * w_inv.z;
-                float l1z = (nz.y - w_ro.z) * w_inv.z, h1z = (nz.w - w_ro.z) * w_inv.z;
-                float n0 = fmaxf(fmaxf(fminf(l0x, h0x), fminf(l0y, h0y)), fmaxf(fminf(l0z, h0z), 0.0f));
-                float f0 = fminf(fminf(fmaxf(l0x, h0x), fmaxf(l0y, h0y)), fminf(fmaxf(l0z, h0z), w_tbest));
-                float n1 = fmaxf(fmaxf(fminf(l1x, h1x), fminf(l1y, h1y)), fmaxf(fminf(l1z, h1z), 0.0f));
-                float f1 = fminf(fminf(fmaxf(l1x, h1x), fmaxf(l1y, h1y)), fminf(fmaxf(l1z, h1z), w_tbest));
-                bool hit0 = n0 <= f0, hit1 = n1 <= f1;
-                if (hit0 && hit1) {
-                    bool first0 = n0 <= n1;
-                    stack[sp * 64] = (uint32_t)(first0 ? ch.y : ch.x); ++sp;
-                    cur = first0 ? ch.x : ch.y;
-                } else if (hit0) cur = ch.x;
-                else if (hit1) cur = ch.y;
-                else if (sp == sb) done = true;
-                else { --sp; cur = (int32_t)stack[sp * 64]; }
-            }
+            if (STATS) { st.nodes_closest++; const int busy = __popcll(__ballot(true)); if (wave_leader()) { st.w[0]++; st.hist[0 + ((busy - 1) >> 3)]++; } }
+            Node4Hits h = wide_step(sc, cur, w_ro, w_inv, w_tbest);
+            sort4(h);
+            // nearest child next; the others go to the stack farthest first (see sort4)
+            stack[sp * 64] = (uint32_t)h.link[3]; sp += h.n[3] < INFINITY ? 1 : 0;
+            stack[sp * 64] = (uint32_t)h.link[2]; sp += h.n[2] < INFINITY ? 1 : 0;
+            stack[sp * 64] = (uint32_t)h.link[1]; sp += h.n[1] < INFINITY ? 1 : 0;
+            if (h.n[0] < INFINITY) cur = h.link[0];
+            else if (sp == sb) done = true;
+            else { --sp; cur = (int32_t)stack[sp * 64]; }
         }
         const bool at_leaf = !done && cur < 0;
         const unsigned long long m1 = __ballot(at_leaf);
@@ -1141,7 +995,6 @@ PT_DEV bool trace_closest_coop(const DevScene& sc, f3 ro, f3 rd, bool want, uint
         }
         const unsigned long long m_act = __ballot(!done);
         if (m_act == 0ull) break;
-#if PT_ANY_STEAL
         if (++since_steal >= PT_STEAL_EVERY_CLOSEST && __popcll(m_act) <= PT_STEAL_MAX_ACTIVE) {
             const unsigned long long m_donor = __ballot(!done && sp > sb);
             if (m_donor != 0ull) {
@@ -1168,7 +1021,6 @@ PT_DEV bool trace_closest_coop(const DevScene& sc, f3 ro, f3 rd, bool want, uint
                 __syncthreads();
             }
         }
-#endif
     }
     if (tail != head) flush(tail - head);
     const unsigned long long key = L.best[lane];
@@ -1190,44 +1042,19 @@ PT_DEV bool trace_closest_coop(const DevScene& sc, f3 ro, f3 rd, bool want, uint
 // wave tests the ring densely, idle lanes steal — plus: a ray id is (owner lane | kind << 6); a lane that has both rays walks its closest-hit
 // ray first and keeps the shadow ray PENDING, to start it when it runs dry — or to hand it whole to an idle lane in a steal round, which is
 // the largest subtree there is.  Results: closest hits merge through atomicMin on (t bits << 32 | triangle), occlusion is one bit per owner.
-// the dense triangle tests of the merged traversal (64 lanes of arithmetic) run above the node steps' priority: +0.2...0.3 %, consistently
-#ifndef PT_PRIO_FLUSH
-#define PT_PRIO_FLUSH 1
-#endif
-#if PT_PRIO_FLUSH
-#define PT_PRIO_FLUSH_ENTER __builtin_amdgcn_s_setprio(2)
-#define PT_PRIO_FLUSH_EXIT __builtin_amdgcn_s_setprio(0)
-#else
-#define PT_PRIO_FLUSH_ENTER ((void)0)
-#define PT_PRIO_FLUSH_EXIT ((void)0)
-#endif
-struct PairLds { uint32_t* ring; unsigned long long* best; uint32_t* occl; uint32_t* pair; uint32_t* infl; };   // ring[ANY_RING], best[64], occl[2], pair[64], infl[2]
+// The dense triangle tests of the merged traversal (64 lanes of arithmetic) run above the node steps' priority (flush: s_setprio 2, back to 0
+// after): measured +0.2...0.3 %, consistently.
+// Measured and dropped: a straggler carry-over, in which the traversal returned with its last few closest-hit rays still
+// walking and resumed them beside the next iteration's, and with it starting a lane's shadow ray before its closest-hit ray.
+struct PairLds { uint32_t* ring; unsigned long long* best; uint32_t* occl; uint32_t* pair; uint32_t* infl; };   // ring[ANY_RING], best[64], occl[2], pair[64]; infl: unused, see below
 constexpr uint32_t RAY_ANY = 64u;             // kind bit of a ray id
 
-// STRAGGLER CARRY-OVER (CARRY > 0).  A lock-step wave pays for its deepest ray: a fifth of the merged traversal's node steps run with at most 8
-// of 64 lanes still walking a chain of dependent fetch -> test round trips that no amount of stealing shortens.  With CARRY = n
-// the traversal RETURNS when at most n lanes are still walking and all of them are on closest-hit rays with nothing pending: each of those
-// lanes saves its walking context (node link, stack window, working ray, owner: CTX_DWORDS dwords, compacted by rank into the LDS ring, which
-// is empty between calls) — the stack entries stay where they are, in the lane's own LDS column — and the OWNERS of the unfinished rays are
-// reported in `c_inflight`: such a lane skips its shading stage (its path state is untouched, its best-hit key stays in LDS) and passes
-// `c_resume` to the next call, in which the saved contexts walk on beside the next iteration's fresh rays.  The wave's other lanes shade,
-// regenerate and trace meanwhile instead of idling through the tail.  Shadow rays are never carried: a connection's contribution would have to
-// wait in registers through the shading stage (measured: -2...-6 %), so the exit waits until no lane walks or holds a shadow ray.
-// Results do not change: every ray is walked over exactly the same subtrees with the same merges, only in a different call.
-struct CarryState { unsigned long long walk; };      // wave-uniform: the lanes that hold a saved walking context (slot = rank within the mask)
-constexpr uint32_t CTX_DWORDS = 10u;
-#ifndef PT_CARRY_MIN_FRESH
-#define PT_CARRY_MIN_FRESH 32    // the early return is allowed only in calls that started at least this many fresh closest-hit rays (a wave
-                                 // that is draining its work item must not leave the traversal after every step)
-#endif
-
-// PT_SHADOW_FIRST: a lane with both rays walks its SHADOW ray first and keeps the closest-hit ray pending (the other way round by default).
-// Shadow rays cannot be carried over, closest-hit rays can: with the shadow rays started first the traversal's tail consists of closest-hit
-// rays, which is what the carry-over needs to find there.
-#ifndef PT_SHADOW_FIRST
-#define PT_SHADOW_FIRST 0
-#endif
-template <bool STATS, bool WIDE, int CARRY = 0>
+// LEFT-OVERS of the carry-over, unused: `cs`, `c_resume`, `c_inflight` (and PairLds::infl, and `susp` / `carry` / `s_infl` in pt_kernel).  Nothing
+// reads or writes them, but dropping them at the call site changes the register allocation of every production kernel with the merged
+// traversal (compared on the gfx950 assembly: +4 ... +12 B of scratch per lane in three clearcoat kernels), and those kernels are measured
+// as they are: they go with the next change that re-measures those kernels anyway.
+struct CarryState { unsigned long long walk; };
+template <bool STATS>
 PT_DEV void trace_pair_coop(const DevScene& sc, f3 c_ro, f3 c_rd, bool c_want, f3 s_ro, f3 s_rd, float s_tmax, bool s_want, uint32_t* stack,
                             uint32_t lane, const PairLds& L, Hit& hit, bool& c_found, bool& s_occluded, StatCounters& st,
                             CarryState* cs = nullptr, bool c_resume = false, bool* c_inflight = nullptr) {
@@ -1236,46 +1063,25 @@ PT_DEV void trace_pair_coop(const DevScene& sc, f3 c_ro, f3 c_rd, bool c_want, f
     const RaySetup crs = setup_ray(c_rd), srs = setup_ray(s_rd);
     const uint32_t c_kpack = (uint32_t)crs.kx | ((uint32_t)crs.ky << 2) | ((uint32_t)crs.kz << 4);
     const uint32_t s_kpack = (uint32_t)srs.kx | ((uint32_t)srs.ky << 2) | ((uint32_t)srs.kz << 4);
-    const bool c_fresh = c_want && !(CARRY > 0 && c_resume);             // a resumed owner's ray is already under way: its key in best[] stays
-    if (c_fresh || !c_want) L.best[lane] = (0x7f7fffffull << 32) | 0xffffffffull;                 // (FLT_MAX, no triangle)
-    if (lane < 2) { L.occl[lane] = 0u; if (CARRY > 0) L.infl[lane] = 0u; }
-    const int32_t root = WIDE ? sc.root4 : sc.root;
-    // the ray this lane is WALKING (box tests see distances <= 1e30, see trace_any_deferred); `pend`: its own shadow ray is still to be started;
-    // `pend_c` (CARRY): so is its own closest-hit ray, because the lane first walks on with the context it saved in the previous call
-    constexpr bool SFIRST = PT_SHADOW_FIRST != 0;
-    constexpr bool PC = CARRY > 0 || SFIRST;                              // pend_c can be set at all
-    const bool first_c = SFIRST ? (c_fresh && !s_want) : c_fresh;       // the ray the lane starts with is its closest-hit ray
-    f3 w_ro = walk_origin<WIDE>(sc, first_c ? c_ro : s_ro, first_c ? crs.inv : srs.inv), w_inv = walk_inv<WIDE>(sc, first_c ? crs.inv : srs.inv);
-    float w_t = first_c ? 1e30f : fminf(s_tmax, 1e30f);
-    uint32_t ow = first_c ? lane : (lane | RAY_ANY);
-    bool pend = !SFIRST && c_fresh && s_want, pend_c = SFIRST && c_fresh && s_want;
-    bool done = !c_fresh && !s_want;
+    L.best[lane] = (0x7f7fffffull << 32) | 0xffffffffull;                 // (FLT_MAX, no triangle)
+    if (lane < 2) L.occl[lane] = 0u;
+    const int32_t root = sc.root4;
+    // the ray this lane is WALKING (box tests see distances <= 1e30, see trace_any_deferred): its closest-hit ray if it has one; `pend`: its own
+    // shadow ray is still to be started
+    f3 w_ro = walk_origin(sc, c_want ? c_ro : s_ro, c_want ? crs.inv : srs.inv), w_inv = walk_inv(sc, c_want ? crs.inv : srs.inv);
+    float w_t = c_want ? 1e30f : fminf(s_tmax, 1e30f);
+    uint32_t ow = c_want ? lane : (lane | RAY_ANY);
+    bool pend = c_want && s_want;
+    bool done = !c_want && !s_want;
     int sp = 0, sb = 0;
     int32_t cur = root;
     uint32_t leaf_off = 0;
     uint32_t head = 0, tail = 0;
-    bool allow_carry = false, carry_exit = false;
-    if constexpr (CARRY > 0) {
-        allow_carry = __popcll(__ballot(c_fresh)) >= PT_CARRY_MIN_FRESH;
-        const unsigned long long m_ctx = cs->walk;
-        if (m_ctx != 0ull) {
-            if ((m_ctx >> lane) & 1ull) {
-                const uint32_t* c = L.ring + rank_below(m_ctx) * CTX_DWORDS;
-                const uint32_t pk = c[1];
-                cur = (int32_t)c[0]; sp = (int)(pk & 255u); sb = (int)((pk >> 8) & 255u); leaf_off = pk >> 16;
-                w_ro = mk3(__uint_as_float(c[2]), __uint_as_float(c[3]), __uint_as_float(c[4]));
-                w_inv = mk3(__uint_as_float(c[5]), __uint_as_float(c[6]), __uint_as_float(c[7]));
-                w_t = __uint_as_float(c[8]); ow = c[9];
-                pend_c = c_fresh; pend = s_want; done = false;
-            }
-            cs->walk = 0ull;
-        }
-    }
     __syncthreads();
-    if (STATS) { if (c_fresh) st.closest_rays++; if (s_want) st.shadow_rays++; }
+    if (STATS) { if (c_want) st.closest_rays++; if (s_want) st.shadow_rays++; }
 
     auto flush = [&](uint32_t n) {            // test ring entries [head, head + n), n <= 64
-        PT_PRIO_FLUSH_ENTER;
+        __builtin_amdgcn_s_setprio(2);
         const bool valid = lane < n;
         const uint32_t e = valid ? L.ring[(head + lane) & (ANY_RING - 1u)] : (lane << 25);
         const uint32_t id = e >> 25, own = id & 63u, tri = e & 0x01ffffffu;
@@ -1311,7 +1117,7 @@ PT_DEV void trace_pair_coop(const DevScene& sc, f3 c_ro, f3 c_rd, bool c_want, f
                 }
             }
         }
-        PT_PRIO_FLUSH_EXIT;
+        __builtin_amdgcn_s_setprio(0);
         head += n;
         __syncthreads();
         // feedback for the ray this lane walks: a shadow ray that is occluded is finished, a closest-hit ray prunes with the best distance so far
@@ -1323,45 +1129,14 @@ PT_DEV void trace_pair_coop(const DevScene& sc, f3 c_ro, f3 c_rd, bool c_want, f
     for (;;) {
         if (!done && cur >= 0) {
             if (STATS) { if (ow & RAY_ANY) st.nodes_shadow++; else st.nodes_closest++; const int busy = __popcll(__ballot(true)); if (wave_leader()) { st.w[0]++; st.hist[(busy - 1) >> 3]++; } }   // (the pool's steps are booked as closest-hit steps)
-            if constexpr (WIDE) {
-                Node4Hits h = wide_step(sc, cur, w_ro, w_inv, w_t);
-                sort4(h);                 // nearest first (any-hit does not need the order, and does not mind it)
-#if PT_PUSH_BRANCHFREE
-                stack[sp * 64] = (uint32_t)h.link[3]; sp += h.n[3] < INFINITY ? 1 : 0;
-                stack[sp * 64] = (uint32_t)h.link[2]; sp += h.n[2] < INFINITY ? 1 : 0;
-                stack[sp * 64] = (uint32_t)h.link[1]; sp += h.n[1] < INFINITY ? 1 : 0;
-#else
-                if (h.n[3] < INFINITY) { stack[sp * 64] = (uint32_t)h.link[3]; ++sp; }
-                if (h.n[2] < INFINITY) { stack[sp * 64] = (uint32_t)h.link[2]; ++sp; }
-                if (h.n[1] < INFINITY) { stack[sp * 64] = (uint32_t)h.link[1]; ++sp; }
-#endif
-                if (h.n[0] < INFINITY) cur = h.link[0];
-                else if (sp == sb) done = true;
-                else { --sp; cur = (int32_t)stack[sp * 64]; }
-            } else {
-                const float4* q = (const float4*)(sc.nodes + cur);
-                float4 nx = q[0], ny = q[1], nz = q[2];
-                int2 ch = *(const int2*)(q + 3);
-                float l0x = (nx.x - w_ro.x) * w_inv.x, h0x = (nx.z - w_ro.x) * w_inv.x;
-                float l1x = (nx.y - w_ro.x) * w_inv.x, h1x = (nx.w - w_ro.x) * w_inv.x;
-                float l0y = (ny.x - w_ro.y) * w_inv.y, h0y = (ny.z - w_ro.y) * w_inv.y;
-                float l1y = (ny.y - w_ro.y) * w_inv.y, h1y = (ny.w - w_ro.y) * w_inv.y;
-                float l0z = (nz.x - w_ro.z) * w_inv.z, h0z = (nz.z - w_ro.z) * w_inv.z;
-                float l1z = (nz.y - w_ro.z) * w_inv.z, h1z = (nz.w - w_ro.z) * w_inv.z;
-                float n0 = fmaxf(fmaxf(fminf(l0x, h0x), fminf(l0y, h0y)), fmaxf(fminf(l0z, h0z), 0.0f));
-                float f0 = fminf(fminf(fmaxf(l0x, h0x), fmaxf(l0y, h0y)), fminf(fmaxf(l0z, h0z), w_t));
-                float n1 = fmaxf(fmaxf(fminf(l1x, h1x), fminf(l1y, h1y)), fmaxf(fminf(l1z, h1z), 0.0f));
-                float f1 = fminf(fminf(fmaxf(l1x, h1x), fmaxf(l1y, h1y)), fminf(fmaxf(l1z, h1z), w_t));
-                bool hit0 = n0 <= f0, hit1 = n1 <= f1;
-                if (hit0 && hit1) {
-                    bool first0 = n0 <= n1;
-                    stack[sp * 64] = (uint32_t)(first0 ? ch.y : ch.x); ++sp;
-                    cur = first0 ? ch.x : ch.y;
-                } else if (hit0) cur = ch.x;
-                else if (hit1) cur = ch.y;
-                else if (sp == sb) done = true;
-                else { --sp; cur = (int32_t)stack[sp * 64]; }
-            }
+            Node4Hits h = wide_step(sc, cur, w_ro, w_inv, w_t);
+            sort4(h);                 // nearest first (any-hit does not need the order, and does not mind it)
+            stack[sp * 64] = (uint32_t)h.link[3]; sp += h.n[3] < INFINITY ? 1 : 0;
+            stack[sp * 64] = (uint32_t)h.link[2]; sp += h.n[2] < INFINITY ? 1 : 0;
+            stack[sp * 64] = (uint32_t)h.link[1]; sp += h.n[1] < INFINITY ? 1 : 0;
+            if (h.n[0] < INFINITY) cur = h.link[0];
+            else if (sp == sb) done = true;
+            else { --sp; cur = (int32_t)stack[sp * 64]; }
         }
         // lanes sitting in a leaf queue up to two of its triangles per step, then move on
         const bool at_leaf = !done && cur < 0;
@@ -1382,27 +1157,18 @@ PT_DEV void trace_pair_coop(const DevScene& sc, f3 c_ro, f3 c_rd, bool c_want, f
             __syncthreads();
             while (tail - head >= 64u) flush(64u);
         }
-        // a lane that ran dry starts its own pending ray (CARRY: the closest-hit ray it has not started yet, then the shadow ray)
-        if (PC && done && pend_c && !(SFIRST && pend)) {
-            pend_c = false; done = false;
-            w_ro = walk_origin<WIDE>(sc, c_ro, crs.inv); w_inv = walk_inv<WIDE>(sc, crs.inv); w_t = 1e30f; ow = lane;
-            cur = root; sp = sb = 0; leaf_off = 0u;
-        } else
+        // a lane that ran dry starts its own pending shadow ray
         if (done && pend) {
             pend = false; done = false;
-            w_ro = walk_origin<WIDE>(sc, s_ro, srs.inv); w_inv = walk_inv<WIDE>(sc, srs.inv); w_t = fminf(s_tmax, 1e30f); ow = lane | RAY_ANY;
+            w_ro = walk_origin(sc, s_ro, srs.inv); w_inv = walk_inv(sc, srs.inv); w_t = fminf(s_tmax, 1e30f); ow = lane | RAY_ANY;
             cur = root; sp = sb = 0; leaf_off = 0u;
         }
         const unsigned long long m_act = __ballot(!done);
         if (m_act == 0ull) break;
-        if constexpr (CARRY > 0) {
-            // the tail: few lanes left, every one of them on a closest-hit ray, nothing pending -> leave, the stragglers walk on next call
-            if (allow_carry && __popcll(m_act) <= CARRY && !__any((!done && (ow & RAY_ANY) != 0u) || pend || pend_c)) { carry_exit = true; break; }
-        }
         // work stealing: idle lanes take, from lanes that still have something to give, either the PENDING shadow ray as a whole or the
         // bottom stack entry (the largest pending subtree) together with the working ray it belongs to
         if (__popcll(m_act) <= PT_STEAL_MAX_ACTIVE) {
-            const bool donor = !done && (pend || (PC && pend_c) || sp > sb);
+            const bool donor = !done && (pend || sp > sb);
             const unsigned long long m_donor = __ballot(donor);
             if (m_donor != 0ull) {
                 if (STATS && lane == 0) st.w[7]++;       // steal rounds (mi355pt_stats.wave_steps[7])
@@ -1414,13 +1180,11 @@ PT_DEV void trace_pair_coop(const DevScene& sc, f3 c_ro, f3 c_rd, bool c_want, f
                 const bool taker = done && rank < n_pairs;
                 const uint32_t from = taker ? L.pair[rank] : lane;
                 // what this lane would give: its pending shadow ray from the root, else the bottom of its stack with its working ray
-                const bool give_c = PC && pend_c && !(SFIRST && pend);   // the own closest-hit ray not yet started (walking a carried context, or the shadow ray first)
-                const bool give_ray = pend || give_c;
-                const f3 p_inv = give_c ? crs.inv : srs.inv;                      // the pending ray a lane would give away, in walking form
-                const f3 g_inv = give_ray ? walk_inv<WIDE>(sc, p_inv) : w_inv;
-                const f3 g_ro = give_ray ? walk_origin<WIDE>(sc, give_c ? c_ro : s_ro, p_inv) : w_ro;
-                const float g_t = give_c ? 1e30f : (give_ray ? fminf(s_tmax, 1e30f) : w_t);
-                const uint32_t g_ow = give_c ? lane : (give_ray ? (lane | RAY_ANY) : ow);
+                const bool give_ray = pend;
+                const f3 g_inv = give_ray ? walk_inv(sc, srs.inv) : w_inv;
+                const f3 g_ro = give_ray ? walk_origin(sc, s_ro, srs.inv) : w_ro;
+                const float g_t = give_ray ? fminf(s_tmax, 1e30f) : w_t;
+                const uint32_t g_ow = give_ray ? (lane | RAY_ANY) : ow;
                 const int g_sb = give_ray ? -1 : sb;
                 const int d_sb = __shfl(g_sb, from);
                 const float rx = __shfl(g_ro.x, from), ry = __shfl(g_ro.y, from), rz = __shfl(g_ro.z, from);
@@ -1432,35 +1196,16 @@ PT_DEV void trace_pair_coop(const DevScene& sc, f3 c_ro, f3 c_rd, bool c_want, f
                     w_ro = mk3(rx, ry, rz); w_inv = mk3(ix, iy, iz); w_t = tb; ow = gow;
                     sp = sb = 0; leaf_off = 0u; done = false;
                 }
-                if (donor && rank < n_pairs) { if (give_c) pend_c = false; else if (give_ray) pend = false; else ++sb; }
+                if (donor && rank < n_pairs) { if (give_ray) pend = false; else ++sb; }
                 __syncthreads();
             }
         }
     }
     if (tail != head) flush(tail - head);     // stragglers' last pairs (tail - head < 64 here)
-    bool inflight = false;
-    if constexpr (CARRY > 0) {
-        if (carry_exit) {
-            // save the walkers' contexts (the ring is empty now) and mark the owners of the rays they are on
-            const unsigned long long m_walk = __ballot(!done);
-            cs->walk = m_walk;
-            if (!done) {
-                uint32_t* c = L.ring + rank_below(m_walk) * CTX_DWORDS;
-                c[0] = (uint32_t)cur; c[1] = (uint32_t)sp | ((uint32_t)sb << 8) | (leaf_off << 16);
-                c[2] = __float_as_uint(w_ro.x); c[3] = __float_as_uint(w_ro.y); c[4] = __float_as_uint(w_ro.z);
-                c[5] = __float_as_uint(w_inv.x); c[6] = __float_as_uint(w_inv.y); c[7] = __float_as_uint(w_inv.z);
-                c[8] = __float_as_uint(w_t); c[9] = ow;
-                atomicOr(&L.infl[(ow & 63u) >> 5], 1u << (ow & 31u));
-            }
-            __syncthreads();
-            inflight = c_want && (((L.infl[lane >> 5] >> (lane & 31u)) & 1u) != 0u);
-        }
-        *c_inflight = inflight;
-    }
     s_occluded = s_want && (((L.occl[lane >> 5] >> (lane & 31u)) & 1u) != 0u);
     const unsigned long long key = L.best[lane];
     const uint32_t tri = (uint32_t)key;
-    c_found = c_want && !inflight && tri != 0xffffffffu;
+    c_found = c_want && tri != 0xffffffffu;
     if (c_found) {                                                           // the winner's barycentrics
         winner_hit(sc, c_ro, c_rd, crs, tri, hit);
         if (STATS) st.closest_hits++;

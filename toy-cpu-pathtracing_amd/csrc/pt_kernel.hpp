@@ -52,25 +52,11 @@ PT_DEV void flush_stats(DevStats* stats, const StatCounters& st) {
     if (st.ties) atomicAdd(&stats->phase_cycles[9], (unsigned long long)st.ties | ((unsigned long long)st.ties_differ << 32));
 }
 
-#ifndef PT_ANY_DEFERRED
-#define PT_ANY_DEFERRED 1
-#endif
 // Wave priority by stage (s_setprio; the SIMD's issue arbitration goes by priority, then age): a wave in a traversal is a chain of dependent
 // round trips and loses nothing by yielding the issue port, a wave in the shading stage has independent work to issue — shading and hand-out
-// run at priority 3, traversals at 0: +0.9...+1.3 % (scenes 3 / 0 / 8 / 17; 0.0 on 15 / 19); the other way round -1.1 %.
-#ifndef PT_PRIO_TRAV
-#define PT_PRIO_TRAV 2             // 0: no priorities, 1: traversals high, 2: traversals low
-#endif
-#if PT_PRIO_TRAV == 1
-#define PT_PRIO_TRAV_ENTER __builtin_amdgcn_s_setprio(3)
-#define PT_PRIO_TRAV_EXIT __builtin_amdgcn_s_setprio(0)
-#elif PT_PRIO_TRAV == 2
+// run at priority 3, traversals at 0.  Measured: +0.9...+1.3 % (scenes 3 / 0 / 8 / 17; 0.0 on 15 / 19); the other way round -1.1 %.
 #define PT_PRIO_TRAV_ENTER __builtin_amdgcn_s_setprio(0)
 #define PT_PRIO_TRAV_EXIT __builtin_amdgcn_s_setprio(3)
-#else
-#define PT_PRIO_TRAV_ENTER ((void)0)
-#define PT_PRIO_TRAV_EXIT ((void)0)
-#endif
 // ONE cooperative traversal per iteration for the next closest-hit rays AND the light connections of the vertex just shaded (trace_pair_coop,
 // pt_device.hpp): a wave's step count is bounded by its deepest ray, not by the ray count, so the two traversals together cost ~20 node
 // steps instead of ~18 + ~14.  The price is the pending connection's 11 registers across one more stage, and a heavier loop where there
@@ -82,66 +68,47 @@ PT_DEV void flush_stats(DevStats* stats, const StatCounters& st) {
 //   the plain path tracer (strategy pt: no connections exist) loses 9 % with it (scene 3 2 790 vs 2 557): it has its own specialisation
 //   (MODE_PT, pt_kernels_pt.hip) without it; choosing inside one kernel at run time costs both sides (-5 % / -8 %: measured);
 //   generic-mode clearcoat kernels (random sampler with NEE / MIS): not measured, two traversals as before.
-#ifndef PT_MERGED_TRAVERSAL
-#define PT_MERGED_TRAVERSAL 1      // 0: never, 1: as measured (above), 2: every kernel
-#endif
 enum : uint32_t { MODE_GENERIC = 0, MODE_MIS_SOBOL = 1, MODE_NEE_SOBOL = 2, MODE_PT = 3 };
 template <uint32_t FEAT, uint32_t MODE> constexpr bool merged_traversal() {
-    if (PT_MERGED_TRAVERSAL != 1) return PT_MERGED_TRAVERSAL == 2;
     if (MODE == MODE_PT) return false;
     if ((FEAT & FEAT_CC) == 0u || MODE == MODE_MIS_SOBOL) return true;
     return MODE == MODE_NEE_SOBOL && FEAT != (FEAT_CC | FEAT_TEX);
 }
-#ifndef PT_CLOSEST_COOP
-#define PT_CLOSEST_COOP 1      // needs PT_ANY_DEFERRED (shares its LDS ring)
-#endif
-// Straggler carry-over of the merged traversal (trace_pair_coop, pt_device.hpp): the traversal returns when at most this many lanes are still
-// walking; the owners of the unfinished rays sit out one shading stage and their rays walk on beside the next iteration's.  0: off.
-#ifndef PT_CARRY_MAX
-#define PT_CARRY_MAX 0
-#endif
-template <uint32_t FEAT, uint32_t MODE> constexpr int carry_max() { return PT_CARRY_MAX; }
-// MATERIAL SORT BETWEEN BOUNCES, wave-local (PT_DEFER).  A wave shades all its lanes together, so an iteration in which a few lanes hit
-// the hero pays the hero's whole BSDF branch on top of the room's: measured 19-52 k of ~270-300 k cycles per iteration wherever the scene
-// has a second material class, i.e. in 84-93 % of the iterations for 8-13 % of the lanes.  With PT_DEFER a lane whose closest
+// MATERIAL SORT BETWEEN BOUNCES, wave-local (the deferral queue; defer_classes() below says which kernels have it).  A wave shades all
+// its lanes together, so an iteration in which a few lanes hit the hero pays the hero's whole BSDF branch on top of the room's: measured 19-52 k of ~270-300 k cycles per iteration wherever the scene
+// has a second material class, i.e. in 84-93 % of the iterations for 8-13 % of the lanes.  With the queue a lane whose closest
 // hit lies on a DEFERRED class (the clearcoat material in the kernels that have it, the dielectrics in theirs) does not shade: it writes its
 // path and the hit to the wave's own queue in global memory (128 B per path, a ring of 128 entries per resident wave; L2-resident) and is
 // FREE — it starts a new camera path at the top of the next iteration like a lane whose path ended, so no lane idles for the sort.  When at
-// least PT_DEFER_MIN paths wait (or the work item has no new paths left), the free lanes of the next iteration take queued paths instead of new
-// ones and the wave shades them together: the minority branch runs once for ~30 lanes instead of in every iteration for ~6.  A path only
-// ever waits in the queue of the wave that owns its pixel's LDS film tile, the order of pushes and pops is a function of the wave's own
+// least PT_DEFER_MIN paths wait (or the work item has no new paths left), the lanes that are free after the shading stage take queued paths
+// and the wave shades them at once in a second pass: the minority branch runs once for ~30 lanes instead of in every iteration for ~6
+// (measured +11...+34 %, dielectrics +-0; taking the queued paths at the top of the iteration instead, where they sit out its traversal:
+// +4 % scene 17, -5...-9 % dielectrics).  A path only ever waits in the queue of the wave that owns its pixel's LDS film tile, the order of pushes and pops is a function of the wave's own
 // deterministic schedule, and a sample's arithmetic does not depend on when it is shaded: frames stay bit-identical from run to run and
 // sample-for-sample equal to the oracle's.  (Moving paths BETWEEN waves — the usual wavefront formulation — needs 9 KB of LDS per queue or
 // float atomics on the film; sorting inside the wave's own time line needs neither.)
-#ifndef PT_DEFER
-#define PT_DEFER 2             // 0: off; 1: queued paths are taken at the top of an iteration (they sit out its traversal: +4 % scene 17, -5...-9 % dielectrics);
-#endif                         // 2: taken after the shading stage and shaded at once in a second pass (+11...+34 %, dielectrics +-0)
 #ifndef PT_DEFER_MIN
 #define PT_DEFER_MIN 56         // paths waiting before the queue is shaded (20 / 28 / 40 / 48 / 60 measured: scene 17 1 497 / 1 512 / 1 523 / 1 528 / 1 529)
 #endif
 constexpr uint32_t DEFER_RING = 128u;           // entries per wave: a drain starts at PT_DEFER_MIN waiting paths and one iteration adds at most 64
 constexpr uint32_t DEFER_F4 = 8u;               // float4 per entry
-#ifndef PT_DEFER_TEX
-#define PT_DEFER_TEX 1      // textured materials are a class of their own in the kernels without the clearcoat code
-#endif
 template <uint32_t FEAT, uint32_t MODE> constexpr uint32_t defer_classes() {    // bit c: sort class c (MT_* | 8 if the material has a spectrum texture, DevTri::pad[0]) is deferred
-    if (PT_DEFER == 0 || !merged_traversal<FEAT, MODE>()) return 0u;
+    if (!merged_traversal<FEAT, MODE>()) return 0u;
     // the clearcoat material wherever it exists (its branch is the longest: +12 % scene 17, +22 % scene 19, +34 % scene 15); in the kernels
     // without it, the materials with a spectrum texture (bilinear fetches + rgb2spec cells; C2's hero: +0.6 %, scene 4 +0.8 %; a class for
     // every textured material lost 4 % on the normal-map-only hero of scene 5).  The dielectrics alone measured +-0 (their branch is short)
     // and are not deferred.
     if ((FEAT & FEAT_CC) != 0u) return (1u << MT_CLEARCOAT) | (1u << (MT_CLEARCOAT | 8u));
-    if (PT_DEFER_TEX != 0 && (FEAT & FEAT_TEX) != 0u) return 0xff00u;
+    if ((FEAT & FEAT_TEX) != 0u) return 0xff00u;
     return 0u;
 }
 // TAIL QUEUE (PT_TAILQ): the same idea for EVERY path.  A third of the lanes that enter the shading stage end their path in its front
 // (emission, roulette) and used to idle through BSDF sampling and the light connection — 28 % of a wave's time at 65 % of its lanes.  Now the
 // shading stage is two: (1) the FRONT of the vertex for every lane that traced (emission with its weight, throughput, roulette, depth:
-// shade_vertex_head<PHASE 1>); the paths that go on are written to the wave's queue (path + hit, the 128-byte record of PT_DEFER) and ALL
-// lanes are free; (2) when 64 paths wait, one pass takes them into the free lanes and runs the back of the vertex (the surface again from
+// shade_vertex_head<PHASE 1>); the paths that go on are written to the wave's queue (path + hit) and ALL lanes are free; (2) when 64 paths wait, one pass takes them into the free lanes and runs the back of the vertex (the surface again from
 // the hit, frames, the BSDF's draws: <PHASE 2>) and the tail — BSDF sample, light connection — for a FULL wave.  Lanes left free start new
 // camera paths as before.  In the clearcoat kernels the paths whose hit is on the clearcoat material have a queue of their own, so a pass
-// shades one class (this subsumes PT_DEFER there); when a work item has nothing new left, whatever waits shares the passes.  A sample's
+// shades one class (this subsumes the deferral queue there); when a work item has nothing new left, whatever waits shares the passes.  A sample's
 // arithmetic and its sampler dimensions are what they were — the record carries the path between the two halves of ITS vertex —, the
 // queues belong to the wave that owns the pixels, the schedule is the wave's own: frames bit-identical from run to run, 166 GPU tests
 // unchanged.  Same-box A/B (round 3): **C2 2 088 -> 2 312 Msamples/s (+10.7 %), C3 +11.9 %, C4 +13.2 %, C5 1 574 -> 1 893 (+20 %)**, scene 19
@@ -156,50 +123,28 @@ template <uint32_t FEAT, uint32_t MODE> constexpr uint32_t defer_classes() {    
 #ifndef PT_TAILQ_MIN
 #define PT_TAILQ_MIN 64
 #endif
-#ifndef PT_TAILQ_CC
-#define PT_TAILQ_CC 1        // the clearcoat kernels too (two queues: one per sort class)
-#endif
-template <uint32_t FEAT, uint32_t MODE> constexpr bool tail_queue() { return PT_TAILQ != 0 && merged_traversal<FEAT, MODE>() && ((FEAT & FEAT_CC) == 0u || PT_TAILQ_CC != 0); }
+template <uint32_t FEAT, uint32_t MODE> constexpr bool tail_queue() { return PT_TAILQ != 0 && merged_traversal<FEAT, MODE>(); }    // (the clearcoat kernels too: two queues, one per sort class)
 constexpr uint32_t QUEUE_RING = (PT_TAILQ != 0) ? 256u : DEFER_RING;     // entries per wave and queue
 constexpr uint32_t QUEUE_MAX = (PT_TAILQ != 0) ? 2u : 1u;               // queues per wave (the tail queue keeps one per sort class)
-// the queue's records are written once and read once: with PT_TQ_NT their stores / loads carry the non-temporal hint, so that they do not
-// push the BVH out of the L2 (L2 hit rate 0.98 before the queues, 0.89 with them).  Measured: -4 % (C2 2 578 -> 2 481, C4 -5.6 %): the
-// records then come back from HBM instead of the L2 / Infinity Cache; off
-#ifndef PT_TQ_NT
-#define PT_TQ_NT 0
-#endif
-typedef float pt_v4f __attribute__((ext_vector_type(4)));
-#if PT_TQ_NT
-#define PT_TQ_ST(p, v) do { const float4 _v = (v); pt_v4f _w = {_v.x, _v.y, _v.z, _v.w}; __builtin_nontemporal_store(_w, (pt_v4f*)(p)); } while (0)
-#define PT_TQ_LD(p) ([&]() { const pt_v4f _w = __builtin_nontemporal_load((const pt_v4f*)(p)); return make_float4(_w.x, _w.y, _w.z, _w.w); }())
-#else
-#define PT_TQ_ST(p, v) (*(p) = (v))
-#define PT_TQ_LD(p) (*(p))
-#endif
+// (the queue's records are written once and read once, but stores / loads with the non-temporal hint, meant to keep them from pushing the
+// BVH out of the L2 — L2 hit rate 0.98 before the queues, 0.89 with them — measured -4 % (C2 2 578 -> 2 481, C4 -5.6 %): the records then
+// come back from HBM instead of the L2 / Infinity Cache)
 static_assert(PT_TAILQ == 0 || QUEUE_RING == 256u, "the tail queue's entry index keeps the queue number in bit 8");
-constexpr uint32_t TQ_F4 = 5u;                                           // float4 per record of the tail queue (80 B; PT_DEFER's record: 8)
-constexpr size_t defer_bytes_per_wave() { return (PT_DEFER || PT_TAILQ) ? (size_t)QUEUE_MAX * QUEUE_RING * DEFER_F4 * 16u : 0u; }
+constexpr uint32_t TQ_F4 = 5u;                                           // float4 per record of the tail queue (80 B; the deferral queue's record: DEFER_F4)
+constexpr size_t defer_bytes_per_wave() { return (size_t)QUEUE_MAX * QUEUE_RING * DEFER_F4 * 16u; }
 // MODE compiles the renderer strategy and the sampler in (MODE_GENERIC reads them from DevParams): the branches on
 // prm.strategy / the sampler mode fold away, worth +2.5 % on C2 (MIS + Sobol), +1.3 % on C5 (NEE + Sobol).
-// Which tree the cooperative traversals walk (both are on the device; the plain traversals of the probes and of the canonical-count
-// mode walk the BVH2).  The 4-wide tree halves the dependent node round trips per ray (18 -> ~10 wave steps per closest-hit trace): +3...4.5 %
+// The cooperative traversals walk the 4-wide tree (both trees are on the device; the plain traversals of the probes and of the canonical-count
+// mode walk the BVH2).  Measured: it halves the dependent node round trips per ray (18 -> ~10 wave steps per closest-hit trace): +3...4.5 %
 // on every kernel, and +4.7 % on the kernel specialised for textured Lambert scenes (C2's) once that kernel stopped spilling around the wider
-// step (round 2: machine LICM off, see the Makefile; before that the same tree cost it 4 % and it kept the BVH2).  PT_WIDE_BVH=0 builds the
-// BVH2 form for A/B runs.
-#ifndef PT_WIDE_BVH
-#define PT_WIDE_BVH 1
-#endif
-template <uint32_t FEAT> constexpr bool wide_bvh() { return PT_WIDE_BVH != 0; }
+// step (round 2: machine LICM off, see the Makefile; before that the same tree cost it 4 % and it kept the BVH2).
 // Waves per SIMD of the clearcoat kernels.  Round 2: 3 (168 VGPRs) with the spawning sample's record parked in LDS.  Since the material sort
-// moved most clearcoat shading into dedicated passes (PT_DEFER), the common iteration is the room's: the kernels whose clearcoat code is not
+// moved most clearcoat shading into dedicated passes, the common iteration is the room's: the kernels whose clearcoat code is not
 // ALSO carrying the texture code gain from a fourth wave (128 VGPRs, no parking: the LDS is needed for 16 waves) — scene 17 NEE (C5) +1.8 %,
 // scene 19 (all-features kernel) +3.6 %, scenes 16 / 17 MIS +0 ... 0.5 %; the clearcoat + texture set loses 5.8 % (scene 15: 276 B of scratch) and stays at 3.
-#ifndef PT_CC_WAVES_SEL
-#define PT_CC_WAVES_SEL 1
-#endif
 template <uint32_t FEAT> constexpr int kernel_min_waves() {
     if ((FEAT & FEAT_CC) == 0u) return PT_MIN_WAVES;
-    if (PT_CC_WAVES_SEL != 0 && FEAT != (FEAT_CC | FEAT_TEX)) return 4;
+    if (FEAT != (FEAT_CC | FEAT_TEX)) return 4;
     return PT_MIN_WAVES_CC;
 }
 template <bool STATS, uint32_t FEAT, uint32_t MODE = MODE_GENERIC>
@@ -214,27 +159,20 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
     __shared__ uint32_t s_hi[SOBOL_HI_DIMS];
     __shared__ uint32_t s_p6[SOBOL_HI_DIMS];
     __shared__ unsigned s_work;
-#ifndef PT_PARK_LDS
-#define PT_PARK_LDS 1
-#endif
     // The clearcoat kernels run 12 waves per CU, so each has 3.4 KB of LDS the 16-wave kernels do not: the record of the BSDF sample that
     // spawned the ray in flight (f, pdf, the vertex left: 8 dwords per lane, read only at the start of the next vertex's shading) waits there
     // during the traversals instead of in registers the allocator would spill to scratch
-    constexpr bool PARK = PT_PARK_LDS != 0 && (FEAT & FEAT_CC) != 0u && kernel_min_waves<FEAT>() <= 3;
+    constexpr bool PARK = (FEAT & FEAT_CC) != 0u && kernel_min_waves<FEAT>() <= 3;
     __shared__ float s_park[PARK ? 8 * 64 : 1];
     __shared__ uint8_t s_perm[96];
-#if PT_ANY_DEFERRED
     __shared__ uint32_t s_ring[ANY_RING];
     __shared__ uint32_t s_occl[2];
     __shared__ uint32_t s_pair[64];
     const AnyLds any_lds{s_ring, s_occl, s_pair};
-#if PT_CLOSEST_COOP
     __shared__ unsigned long long s_best[64];
     const ClosestLds closest_lds{s_ring, s_best, s_pair};
     __shared__ uint32_t s_infl[2];
     const PairLds pair_lds{s_ring, s_best, s_occl, s_pair, s_infl};
-#endif
-#endif
     DevParams prm = prm_in;
     if constexpr (MODE == MODE_MIS_SOBOL) { prm.strategy = 2u; prm.sampler = 1u; }
     if constexpr (MODE == MODE_NEE_SOBOL) { prm.strategy = 1u; prm.sampler = 1u; }
@@ -262,9 +200,7 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
     uint32_t* stack = s_stack + lane;
     // murmur(dimension, seed) comes straight from its 1 KB global table (L1-resident): the LDS it used holds the tile's film
     for (uint32_t k = lane; k < 96u; k += 64u) s_perm[k] = (uint8_t)((perm_packed(k >> 2) >> (2u * (k & 3u))) & 3u);
-#if PT_ZNODES_LDS
     if constexpr ((FEAT & (FEAT_TEX | FEAT_EMTEX | FEAT_ENV)) != 0u) s_znodes[lane] = sc.z_nodes[lane];   // rgb2spec_lookup's z search (pt_device.hpp)
-#endif
     __syncthreads();
     SamplerCtx sctx{prm.sampler, prm.seed, prm.log2_spp, prm.n_base4_digits, cam.width, dim_hash_tab, nullptr, 0u, 0u, nullptr, s_perm};
     StatCounters st{};
@@ -316,12 +252,10 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
         park(P);
         bool active = false;
         constexpr bool MERGED = merged_traversal<FEAT, MODE>();
-        constexpr int CARRY = MERGED ? carry_max<FEAT, MODE>() : 0;
         ShadowReq sh{};                                            // merged form: the light connection of the vertex just shaded, traced together with the NEXT closest-hit ray
         // merged form: a path that ended with a light connection pending stays for one more iteration (`dying`) in which only the connection
         // is traced, instead of a separate any-hit traversal at the end of the iteration (rare; keeps one traversal instance in the kernel);
-        // `susp` (carry-over): this lane's closest-hit ray is still in flight, the lane sits out the shading stage
-        bool dying = false, susp = false;
+        bool dying = false, susp = false;                         // (`susp`, `carry`: always false / unused — left-overs, see trace_pair_coop)
         CarryState carry{0ull};
         constexpr bool TAILQ = !STATS && tail_queue<FEAT, MODE>();       // (the instrumented kernels keep the plain shading stage)
         constexpr uint32_t DEFER = TAILQ ? 0u : defer_classes<FEAT, MODE>();
@@ -343,19 +277,8 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
             unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, ts4 = 0, tsa = 0, tsb = 0;
             uint32_t bsdf_classes = 0u;
             if (STATS) ts0 = __builtin_amdgcn_s_memtime();
-            // deferral queue: when enough paths wait (or nothing new is left to start), this iteration's free lanes take them
-            bool popped = false, drain = false;
+            bool popped = false;                            // deferral queue: this lane took a queued path (in the second shading pass)
             uint32_t pop_e = 0u;
-            if constexpr (DEFER != 0u) {
-                const uint32_t q_count = q_tail - q_head;
-                drain = PT_DEFER == 1 && !(STATS && prm.stats_mode == 1u) && (q_count >= (uint32_t)PT_DEFER_MIN || (pool_next >= pool_size && q_count != 0u));
-                if (drain) {
-                    const unsigned long long m_free = __ballot(!active);
-                    const uint32_t r = rank_below(m_free);
-                    if (!active && r < q_count) { popped = true; active = true; pop_e = (q_head + r) & (DEFER_RING - 1u); }   // its record is read after the traversal
-                    q_head += min((uint32_t)__popcll(m_free), q_count);
-                }
-            }
             const unsigned long long m_needy = __ballot(!active);
             if (m_needy != 0ull && pool_next < pool_size) {
                 const uint32_t idx = pool_next + rank_below(m_needy);
@@ -370,8 +293,8 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
             }
             if (!__any(active)) {
                 if (pool_next >= pool_size && q_tail == q_head && q2_tail == q2_head) break;
-                // (PT_DEFER 2 takes queued paths AFTER the shading stage: with nothing left to start, an iteration without rays still has to get there)
-                if (!(((DEFER != 0u && PT_DEFER == 2) || TAILQ) && pool_next >= pool_size)) continue;
+                // (queued paths are taken AFTER the shading stage: with nothing left to start, an iteration without rays still has to get there)
+                if (!((DEFER != 0u || TAILQ) && pool_next >= pool_size)) continue;
             }
             if (STATS) { ts1 = __builtin_amdgcn_s_memtime(); if (lane == 0) st.w[4]++; if (active) st.w[5]++; }
             Hit hit{};
@@ -383,7 +306,7 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
                 bool occluded = false;
                 if (STATS && sh.on) st.w[6]++;
                 PT_PRIO_TRAV_ENTER;
-                trace_pair_coop<STATS, wide_bvh<FEAT>(), CARRY>(sc, P.ro, P.rd, active && !dying && !popped, sh.o, sh.d, sh.t, sh.on, stack, lane, pair_lds, hit, got, occluded, st, &carry, susp, &susp);
+                trace_pair_coop<STATS>(sc, P.ro, P.rd, active && !dying && !popped, sh.o, sh.d, sh.t, sh.on, stack, lane, pair_lds, hit, got, occluded, st, &carry, susp, &susp);
                 PT_PRIO_TRAV_EXIT;
                 if (sh.on && !occluded) {
 #pragma unroll
@@ -391,7 +314,7 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
                 }
                 sh = ShadowReq{};      // consumed: every field dead from here on, for every lane — none of them is carried through the shading stage (+2 % on scenes 0 / 8)
             }
-            else { PT_PRIO_TRAV_ENTER; got = trace_closest_coop<STATS, wide_bvh<FEAT>()>(sc, P.ro, P.rd, active, stack, lane, closest_lds, hit, st); PT_PRIO_TRAV_EXIT; }
+            else { PT_PRIO_TRAV_ENTER; got = trace_closest_coop<STATS>(sc, P.ro, P.rd, active, stack, lane, closest_lds, hit, st); PT_PRIO_TRAV_EXIT; }
             if (STATS) {
                 // material divergence of the shading stage (mi355pt_stats.divergence): classes among the lanes that shade a surface
                 const uint32_t mclass = (active && got) ? sc.materials[__float_as_uint(((const float4*)(sc.shade + hit.tri))[4].z)].type : 8u;
@@ -413,15 +336,15 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
             auto tq_store = [&](uint32_t e, const Path& Q, const Hit& h, uint32_t pix) {
                 float4* r = q_base + (size_t)(e >> 8) * (TQ_F4 * QUEUE_RING) + (e & (QR - 1u));
                 const uint32_t fl = (Q.wl.term ? 1u : 0u) | ((Q.depth & 1023u) << 1) | ((pix & 63u) << 11) | (Q.smp.dimension << 17);   // (max_depth <= 1000, api.cpp check_args: dimension <= 3 + 8 * 1000 < 2^15)
-                PT_TQ_ST(r + 0u * QR, make_float4(__uint_as_float(Q.smp.morton), __uint_as_float(fl), Q.wl.lam0, __uint_as_float(h.tri)));
-                PT_TQ_ST(r + 1u * QR, make_float4(Q.T[0], Q.T[1], Q.T[2], Q.T[3]));
-                PT_TQ_ST(r + 2u * QR, make_float4(Q.L[0], Q.L[1], Q.L[2], Q.L[3]));
-                PT_TQ_ST(r + 3u * QR, make_float4(Q.rd.x, Q.rd.y, Q.rd.z, h.b0));
-                PT_TQ_ST(r + 4u * QR, make_float4(h.b1, h.b2, __uint_as_float(Q.smp.rkey_lo), __uint_as_float(Q.smp.rkey_hi)));
+                r[0u * QR] = make_float4(__uint_as_float(Q.smp.morton), __uint_as_float(fl), Q.wl.lam0, __uint_as_float(h.tri));
+                r[1u * QR] = make_float4(Q.T[0], Q.T[1], Q.T[2], Q.T[3]);
+                r[2u * QR] = make_float4(Q.L[0], Q.L[1], Q.L[2], Q.L[3]);
+                r[3u * QR] = make_float4(Q.rd.x, Q.rd.y, Q.rd.z, h.b0);
+                r[4u * QR] = make_float4(h.b1, h.b2, __uint_as_float(Q.smp.rkey_lo), __uint_as_float(Q.smp.rkey_hi));
             };
             auto tq_load = [&](uint32_t e, Path& Q, Hit& h, uint32_t& pix) {
                 const float4* r = q_base + (size_t)(e >> 8) * (TQ_F4 * QUEUE_RING) + (e & (QR - 1u));
-                const float4 a = PT_TQ_LD(r + 0u * QR), b = PT_TQ_LD(r + 1u * QR), c = PT_TQ_LD(r + 2u * QR), d = PT_TQ_LD(r + 3u * QR), e4 = PT_TQ_LD(r + 4u * QR);
+                const float4 a = r[0u * QR], b = r[1u * QR], c = r[2u * QR], d = r[3u * QR], e4 = r[4u * QR];
                 const uint32_t fl = __float_as_uint(a.y);
                 Q.smp.morton = __float_as_uint(a.x); Q.smp.dimension = fl >> 17; Q.smp.rkey_lo = __float_as_uint(e4.z); Q.smp.rkey_hi = __float_as_uint(e4.w);
                 Q.wl.lam0 = a.z; Q.wl.term = (fl & 1u) != 0u; Q.depth = (fl >> 1) & 1023u; pix = (fl >> 11) & 63u;
@@ -432,6 +355,31 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
 #pragma unroll
                 for (int i = 0; i < 4; ++i) Q.pf[i] = 0.0f;
                 Q.p_pdf = 0.0f; Q.prev_pos = mk3(0.0f, 0.0f, 0.0f);
+            };
+            // the deferral queue's record (the instrumented kernels): the whole path, the hit and the pixel, record-major, 8 float4 = 128 B
+            auto dq_store = [&](uint32_t e, const Path& Q, const Hit& h, uint32_t pix) {
+                float4* r = q_base + (size_t)e * DEFER_F4;
+                // (flags in bits 0-2, the depth in bits 3-12: max_depth <= 1000, api.cpp check_args; the pixel from bit 16)
+                const uint32_t fl = (Q.wl.term ? 1u : 0u) | (Q.from_camera ? 2u : 0u) | (Q.prev_spec ? 4u : 0u) | ((Q.depth & 1023u) << 3) | (pix << 16);
+                r[0] = make_float4(__uint_as_float(Q.smp.morton), __uint_as_float(Q.smp.dimension), __uint_as_float(Q.smp.rkey_lo), __uint_as_float(Q.smp.rkey_hi));
+                r[1] = make_float4(Q.wl.lam0, __uint_as_float(fl), Q.T[0], Q.T[1]);
+                r[2] = make_float4(Q.T[2], Q.T[3], Q.L[0], Q.L[1]);
+                r[3] = make_float4(Q.L[2], Q.L[3], Q.rd.x, Q.rd.y);
+                r[4] = make_float4(Q.rd.z, Q.pf[0], Q.pf[1], Q.pf[2]);
+                r[5] = make_float4(Q.pf[3], Q.p_pdf, Q.prev_pos.x, Q.prev_pos.y);
+                r[6] = make_float4(Q.prev_pos.z, h.t, h.b0, h.b1);
+                r[7] = make_float4(h.b2, __uint_as_float(h.tri), __uint_as_float(h.mclass), 0.0f);
+            };
+            auto dq_load = [&](uint32_t e, Path& Q, Hit& h, uint32_t& pix) {
+                const float4* r = q_base + (size_t)e * DEFER_F4;
+                const float4 a = r[0], b = r[1], c = r[2], d = r[3], e4 = r[4], f = r[5], g = r[6], h4 = r[7];
+                const uint32_t fl = __float_as_uint(b.y);
+                Q.smp.morton = __float_as_uint(a.x); Q.smp.dimension = __float_as_uint(a.y); Q.smp.rkey_lo = __float_as_uint(a.z); Q.smp.rkey_hi = __float_as_uint(a.w);
+                Q.wl.lam0 = b.x; Q.wl.term = (fl & 1u) != 0u; Q.from_camera = (fl & 2u) != 0u; Q.prev_spec = (fl & 4u) != 0u; Q.depth = (fl >> 3) & 1023u; pix = fl >> 16;
+                Q.T[0] = b.z; Q.T[1] = b.w; Q.T[2] = c.x; Q.T[3] = c.y; Q.L[0] = c.z; Q.L[1] = c.w; Q.L[2] = d.x; Q.L[3] = d.y;
+                Q.rd = mk3(d.z, d.w, e4.x); Q.ro = mk3(0.0f, 0.0f, 0.0f);
+                Q.pf[0] = e4.y; Q.pf[1] = e4.z; Q.pf[2] = e4.w; Q.pf[3] = f.x; Q.p_pdf = f.y; Q.prev_pos = mk3(f.z, f.w, g.x);
+                h.t = g.y; h.b0 = g.z; h.b1 = g.w; h.b2 = h4.x; h.tri = __float_as_uint(h4.y); h.mclass = __float_as_uint(h4.z);
             };
             auto finish_path = [&]() {            // Sensor::add_sample of a finished path into the work item's LDS film tile (+ the per-sample log)
                 if (pout.L != nullptr) {
@@ -489,7 +437,7 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
                     bool ep = false;
                     if constexpr ((FEAT & FEAT_CC) != 0u) {
                         ShadeCtx C;
-                        C.cont = false; C.need_cc = false; C.cc_fc = 0.0f; C.cc_alpha_c = 0.0f; C.cc_r0c = 0.0f; C.wo_nm = mk3(0, 0, 1); C.mc_key = 0ull;
+                        shade_ctx_idle_cc(C);
                         if (take) {
                             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                             tq_load(e, P, hit, my_pix);
@@ -519,9 +467,9 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
                     if (take && ep) { finish_path(); active = false; }
                 }
             } else
-            // The shading stage.  PT_DEFER 2 runs it a second time in the iterations that shade the deferral queue: the lanes the first pass
-            // freed (ended paths, deferred hits) take queued paths and shade them at once, so a queued path rejoins the NEXT traversal
-            // with its next ray like everybody else (PT_DEFER 1 pops at the top of the iteration and lets those lanes sit out a traversal).
+            // The shading stage.  It runs a second time in the iterations that shade the deferral queue: the lanes the first pass freed
+            // (ended paths, deferred hits) take queued paths and shade them at once, so a queued path rejoins the NEXT traversal with its
+            // next ray like everybody else.
             for (int pass = 0;; ++pass) {
             const bool mine = pass == 0 || popped;     // the lanes this pass works on
             bool end_path = pass == 0 && MERGED && dying;           // a dying path's last connection has just been resolved
@@ -530,36 +478,18 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
                 unpark(P);
             }
             if constexpr (DEFER != 0u) {
-                // queued paths join here: path state, hit and pixel of the lanes that popped (PT_DEFER 1: registers dead during the traversal)
+                // queued paths join here: path state, hit and pixel of the lanes that popped
                 if (popped) {
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                    const float4* r = q_base + (size_t)pop_e * DEFER_F4;
-                    const float4 a = r[0], b = r[1], c = r[2], d = r[3], e = r[4], f = r[5], g = r[6], h = r[7];
-                    const uint32_t fl = __float_as_uint(b.y);
-                    P.smp.morton = __float_as_uint(a.x); P.smp.dimension = __float_as_uint(a.y); P.smp.rkey_lo = __float_as_uint(a.z); P.smp.rkey_hi = __float_as_uint(a.w);
-                    P.wl.lam0 = b.x; P.wl.term = (fl & 1u) != 0u; P.from_camera = (fl & 2u) != 0u; P.prev_spec = (fl & 4u) != 0u; P.depth = (fl >> 3) & 1023u; my_pix = fl >> 16;
-                    P.T[0] = b.z; P.T[1] = b.w; P.T[2] = c.x; P.T[3] = c.y; P.L[0] = c.z; P.L[1] = c.w; P.L[2] = d.x; P.L[3] = d.y;
-                    P.rd = mk3(d.z, d.w, e.x); P.ro = mk3(0.0f, 0.0f, 0.0f);
-                    P.pf[0] = e.y; P.pf[1] = e.z; P.pf[2] = e.w; P.pf[3] = f.x; P.p_pdf = f.y; P.prev_pos = mk3(f.z, f.w, g.x);
-                    hit.t = g.y; hit.b0 = g.z; hit.b1 = g.w; hit.b2 = h.x; hit.tri = __float_as_uint(h.y); hit.mclass = __float_as_uint(h.z);
+                    dq_load(pop_e, P, hit, my_pix);
                     got = true;
                 }
-                // and the lanes whose hit is on a deferred material leave (unless this is the iteration that shades the queue)
-                const bool defer_now = pass == 0 && !drain && !(STATS && prm.stats_mode == 1u) && active && !dying && !susp && !popped && got && ((DEFER >> (hit.mclass & 31u)) & 1u) != 0u;
+                // and the lanes whose hit is on a deferred material leave
+                const bool defer_now = pass == 0 && !(STATS && prm.stats_mode == 1u) && active && !dying && !susp && !popped && got && ((DEFER >> (hit.mclass & 31u)) & 1u) != 0u;
                 const unsigned long long m_def = __ballot(defer_now);
                 if (m_def != 0ull) {
                     if (defer_now) {
-                        float4* r = q_base + (size_t)((q_tail + rank_below(m_def)) & (DEFER_RING - 1u)) * DEFER_F4;
-                        // (flags in bits 0-2, the depth in bits 3-12: max_depth <= 1000, api.cpp check_args; the pixel from bit 16)
-                        const uint32_t fl = (P.wl.term ? 1u : 0u) | (P.from_camera ? 2u : 0u) | (P.prev_spec ? 4u : 0u) | ((P.depth & 1023u) << 3) | (my_pix << 16);
-                        r[0] = make_float4(__uint_as_float(P.smp.morton), __uint_as_float(P.smp.dimension), __uint_as_float(P.smp.rkey_lo), __uint_as_float(P.smp.rkey_hi));
-                        r[1] = make_float4(P.wl.lam0, __uint_as_float(fl), P.T[0], P.T[1]);
-                        r[2] = make_float4(P.T[2], P.T[3], P.L[0], P.L[1]);
-                        r[3] = make_float4(P.L[2], P.L[3], P.rd.x, P.rd.y);
-                        r[4] = make_float4(P.rd.z, P.pf[0], P.pf[1], P.pf[2]);
-                        r[5] = make_float4(P.pf[3], P.p_pdf, P.prev_pos.x, P.prev_pos.y);
-                        r[6] = make_float4(P.prev_pos.z, hit.t, hit.b0, hit.b1);
-                        r[7] = make_float4(hit.b2, __uint_as_float(hit.tri), __uint_as_float(hit.mclass), 0.0f);
+                        dq_store((q_tail + rank_below(m_def)) & (DEFER_RING - 1u), P, hit, my_pix);
                         active = false;                                      // free: a new path (or a queued one) next
                     }
                     q_tail += (uint32_t)__popcll(m_def);
@@ -569,7 +499,7 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
             const bool shade_now = mine && active && !(MERGED && (dying || susp));
             if constexpr ((FEAT & FEAT_CC) != 0u) {
                 ShadeCtx C;
-                C.cont = false; C.need_cc = false; C.cc_fc = 0.0f; C.cc_alpha_c = 0.0f; C.cc_r0c = 0.0f; C.wo_nm = mk3(0, 0, 1); C.mc_key = 0ull;
+                shade_ctx_idle_cc(C);
                 if (shade_now) end_path = shade_vertex_head<STATS, FEAT>(P, sc, prm, sctx, got, hit, sh, st, tsa, C);
                 // the coat's 64-sample directional albedo, estimated by the whole wave for the lanes that need it
                 const bool want_mc = shade_now && C.cont && C.need_cc;
@@ -605,7 +535,7 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
                     if (STATS && now) st.w[6]++;
                     bool occluded = false;
                     if (canonical) { if (now) occluded = trace_any<STATS>(sc, sh.o, sh.d, sh.t, stack, st); }
-                    else { PT_PRIO_TRAV_ENTER; occluded = trace_any_deferred<STATS, wide_bvh<FEAT>()>(sc, sh.o, sh.d, sh.t, now, stack, lane, any_lds, st); PT_PRIO_TRAV_EXIT; }
+                    else { PT_PRIO_TRAV_ENTER; occluded = trace_any_deferred<STATS>(sc, sh.o, sh.d, sh.t, now, stack, lane, any_lds, st); PT_PRIO_TRAV_EXIT; }
                     if (now && !occluded) {
 #pragma unroll
                         for (int i = 0; i < 4; ++i) P.L[i] = P.L[i] + sh.c[i];
@@ -628,7 +558,7 @@ __global__ __launch_bounds__(64, kernel_min_waves<FEAT>()) void pt_kernel(DevSce
                 active = false;
             }
             // a second pass for the deferral queue?
-            if constexpr (DEFER != 0u && PT_DEFER == 2) {
+            if constexpr (DEFER != 0u) {
                 if (pass != 0 || (STATS && prm.stats_mode == 1u)) break;
                 const uint32_t q_count = q_tail - q_head;
                 if (!(q_count >= (uint32_t)PT_DEFER_MIN || (pool_next >= pool_size && q_count != 0u))) break;

@@ -19,7 +19,7 @@
 //    of the lanes idled through that tail and a minority material's branch ran in every iteration).  Alternatives built and measured on MI355X:
 //    a lane pool with vote-driven batched shading (516 vs 654 Msamples/s), one merged shadow+closest traversal loop
 //    per iteration (670 vs 851), packed-f32 slab tests (-5 %): slower.  Persistent traversal with dynamic ray fetch
-//    (experiments/probe_intersect_dyn.inc, wave-local ray batches): 1.16-1.55x on the stand-alone traversal kernel for
+//    (wave-local ray batches): 1.16-1.55x on the stand-alone traversal kernel for
 //    incoherent rays, 0.6x for coherent ones — not enough to pay for streaming path state through HBM;
 //  * shadow rays use deferred, dense triangle tests (trace_any_deferred, pt_device.hpp): lanes only walk nodes and
 //    queue (triangle, lane) pairs in an LDS ring, the wave tests 64 pairs at a time (any-hit is order independent).
@@ -112,11 +112,6 @@ __global__ __launch_bounds__(64) void probe_occluded_kernel(DevScene sc, const f
     f3 ro = mk3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd = mk3(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
     out[i] = trace_any<false>(sc, ro, rd, tmax[i], s_stack + threadIdx.x, st) ? 1 : 0;
 }
-
-
-#ifdef PT_EXPERIMENTS
-#include "experiments/probe_intersect_dyn.inc"
-#endif
 
 // dst += src over a film (multi-device gather: the films of the other devices' tile shards, disjoint from this device's own)
 __global__ void film_add_kernel(float* __restrict__ dst, const float* __restrict__ src, size_t n4) {
@@ -217,21 +212,6 @@ hipError_t launch_probe_sobol(uint32_t width, uint32_t seed, uint32_t log2_spp, 
 }
 hipError_t launch_probe_intersect(const DevScene& sc, const float* o, const float* d, uint32_t n, float* t, uint32_t* inst, uint32_t* tri, float* nrm,
                                   hipStream_t stream) {
-#ifdef PT_EXPERIMENTS
-    const char* mode = getenv("MI355PT_TRAV");
-    if (mode && mode[0] == '2') {
-        static unsigned* d_ctr = nullptr;
-        if (!d_ctr && hipMalloc((void**)&d_ctr, sizeof(unsigned)) != hipSuccess) return hipErrorOutOfMemory;
-        (void)hipMemsetAsync(d_ctr, 0, sizeof(unsigned), stream);
-        if (nrm) (void)hipMemsetAsync(nrm, 0, sizeof(float) * 3 * (size_t)n, stream);
-        int nb = 0, dev = 0; hipDeviceProp_t prop;
-        (void)hipGetDevice(&dev); (void)hipGetDeviceProperties(&prop, dev);
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, probe_intersect_dyn_kernel, 64, 0);
-        int grid = std::min<int>((int)((n + 63) / 64), nb * prop.multiProcessorCount);
-        hipLaunchKernelGGL(probe_intersect_dyn_kernel, dim3(grid), dim3(64), 0, stream, sc, o, d, n, t, inst, tri, d_ctr);
-        return hipGetLastError();
-    }
-#endif
     hipLaunchKernelGGL(probe_intersect_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, sc, o, d, n, t, inst, tri, nrm);
     return hipGetLastError();
 }

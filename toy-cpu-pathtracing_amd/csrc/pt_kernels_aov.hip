@@ -71,9 +71,7 @@ __global__ __launch_bounds__(64, PT_MIN_WAVES) void aov_kernel(DevScene sc, DevC
     const uint32_t lane = threadIdx.x;
     uint32_t* stack = s_stack + lane;
     for (uint32_t k = lane; k < 96u; k += 64u) s_perm[k] = (uint8_t)((perm_packed(k >> 2) >> (2u * (k & 3u))) & 3u);
-#if PT_ZNODES_LDS
     if constexpr (KIND == AOV_ALBEDO && (FEAT & FEAT_TEX) != 0u) s_znodes[lane] = sc.z_nodes[lane];   // rgb2spec_lookup's z search (pt_device.hpp)
-#endif
     __syncthreads();
     SamplerCtx sctx{prm.sampler, prm.seed, prm.log2_spp, prm.n_base4_digits, cam.width, dim_hash_tab, nullptr, 0u, 0u, nullptr, s_perm};
     StatCounters st{};
@@ -114,7 +112,7 @@ __global__ __launch_bounds__(64, PT_MIN_WAVES) void aov_kernel(DevScene sc, DevC
             }
             Hit hit{};
             PT_PRIO_TRAV_ENTER;
-            const bool got = trace_closest_coop<false, wide_bvh<FEAT>()>(sc, mk3(0.0f, 0.0f, 0.0f), rd, active, stack, lane, closest_lds, hit, st);
+            const bool got = trace_closest_coop<false>(sc, mk3(0.0f, 0.0f, 0.0f), rd, active, stack, lane, closest_lds, hit, st);
             PT_PRIO_TRAV_EXIT;
             n_samples += (unsigned long long)__popcll(__ballot(active));
             n_hits += (unsigned long long)__popcll(__ballot(got));

@@ -320,6 +320,11 @@ struct ShadeCtx {
     bool need_cc; float cc_alpha_c, cc_r0c, cc_thick, cc_metallic, cc_rough_b, cc_fc; uint64_t mc_key;
 };
 
+// What the clearcoat kernels read of a lane's ShadeCtx whether or not the lane shaded (the coat's cooperative estimate runs for the whole wave)
+PT_DEV void shade_ctx_idle_cc(ShadeCtx& C) {
+    C.cont = false; C.need_cc = false; C.cc_fc = 0.0f; C.cc_alpha_c = 0.0f; C.cc_r0c = 0.0f; C.wo_nm = mk3(0, 0, 1); C.mc_key = 0ull;
+}
+
 // PHASE (the tail queue of pt_kernel.hpp, PT_TAILQ): 0 = the whole first half; 1 = only its front — emission with the strategy's weight,
 // throughput, Russian roulette, the depth test: what decides whether the path goes on —; 2 = only its back for a path that went on — the
 // surface again from the hit, shading frames, the BSDF's random numbers — whose result feeds shade_vertex_tail.  1 then 2 on the same
