@@ -288,4 +288,11 @@ const char* mi355pt_version(void);
 #ifdef __cplusplus
 }
 #endif
+
+/* ---------------- denoiser ---------------- */
+/* EXTENSION, no reference counterpart: the consumer of the ALBEDO and SHADING_NORMAL films — mi355pt_denoise_params,
+ * mi355pt_denoise_params_default, mi355pt_denoise_scratch_bytes, mi355pt_denoise_device and mi355pt_denoise: an edge-avoiding a-trous
+ * filter over the linear film of a path renderer, on device buffers.  Declared in its own header, which this one always includes. */
+#include "mi355pt_denoise.h"
+
 #endif /* MI355PT_H */

@@ -33,6 +33,12 @@ hipError_t launch_aov(uint32_t kind, const DevScene&, const DevCamera&, const De
                       DevStats*, uint32_t feat, int grid, hipStream_t);
 int query_resident_waves_aov(uint32_t kind, uint32_t feat);
 hipError_t launch_aov_resolve(uint32_t kind, const float*, uint32_t, uint32_t, float*, hipStream_t);
+// pt_kernels_denoise.hip: the a-trous denoiser (include/mi355pt_denoise.h)
+size_t denoise_scratch_bytes(uint32_t width, uint32_t height);
+uint32_t denoise_grid_blocks(uint32_t width, uint32_t height);
+hipError_t launch_denoise(const float* d_beauty, uint32_t spp_b, const float* d_albedo, uint32_t spp_a, const float* d_normal, uint32_t spp_n,
+                          uint32_t width, uint32_t height, uint32_t levels, float sigma_color, float sigma_normal, float sigma_albedo,
+                          float albedo_eps, void* d_scratch, float* d_out, hipStream_t);
 }  // namespace pt
 
 using namespace pt;
@@ -795,6 +801,60 @@ int mi355pt_render_aov(const mi355pt_scene* s, const mi355pt_camera* cam, const 
     if ((rc = mi355pt_render_aov_accum_device(s, cam, p, kind, illuminant_lut, 0, p->spp, d_acc.p, nullptr, stats))) return rc;
     if ((rc = mi355pt_aov_resolve_device(kind, d_acc.p, cam->width * cam->height, p->spp, d_out.p, nullptr))) return rc;
     HIP_TRY(hipMemcpy(out_rgb, d_out.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    return MI355PT_OK;
+}
+
+// ---------------- denoiser (include/mi355pt_denoise.h) ----------------
+
+void mi355pt_denoise_params_default(mi355pt_denoise_params* out) {
+    if (!out) return;
+    out->levels = 5; out->sigma_color = 1.0f; out->sigma_normal = 0.5f; out->sigma_albedo = 0.3f; out->albedo_eps = 0.01f;
+}
+size_t mi355pt_denoise_scratch_bytes(uint32_t width, uint32_t height) { return denoise_scratch_bytes(width, height); }
+
+// every check of mi355pt_denoise_device / mi355pt_denoise that does not concern the scratch; host arithmetic only
+static int denoise_check(const float* beauty, uint32_t spp_b, const float* albedo, uint32_t spp_a, const float* normal, uint32_t spp_n, uint32_t width,
+                         uint32_t height, const mi355pt_denoise_params* dp, const float* out) {
+    if (!beauty || !out || !dp) return fail(MI355PT_E_INVALID, "denoise: null beauty, output or params pointer");
+    if (dp->levels < 1 || dp->levels > 8) return fail(MI355PT_E_INVALID, "denoise: levels must be 1 .. 8 (mi355pt_denoise_params_default fills the struct)");
+    const float pos[4] = {dp->sigma_color, dp->sigma_normal, dp->sigma_albedo, dp->albedo_eps};
+    for (float v : pos)
+        if (!(std::isfinite(v) && v > 0.0f)) return fail(MI355PT_E_INVALID, "denoise: sigma_color, sigma_normal, sigma_albedo and albedo_eps must be finite and > 0");
+    if (spp_b == 0 || (albedo && spp_a == 0) || (normal && spp_n == 0)) return fail(MI355PT_E_INVALID, "denoise: spp of a given buffer is 0");
+    if (width == 0 || height == 0) return fail(MI355PT_E_INVALID, "denoise: zero width or height");
+    if (denoise_grid_blocks(width, height) == 0 || denoise_scratch_bytes(width, height) == 0) return fail(MI355PT_E_INVALID, "denoise: frame too large");
+    if (out == beauty || out == albedo || out == normal) return fail(MI355PT_E_INVALID, "denoise: the output must not be one of the inputs");
+    return MI355PT_OK;
+}
+
+int mi355pt_denoise_device(const float* d_beauty, uint32_t spp_b, const float* d_albedo, uint32_t spp_a, const float* d_normal, uint32_t spp_n,
+                           uint32_t width, uint32_t height, const mi355pt_denoise_params* dp, void* d_scratch, size_t scratch_bytes, float* d_out,
+                           void* hip_stream) {
+    int rc = denoise_check(d_beauty, spp_b, d_albedo, spp_a, d_normal, spp_n, width, height, dp, d_out);
+    if (rc) return rc;
+    if (!d_scratch || scratch_bytes < denoise_scratch_bytes(width, height)) return fail(MI355PT_E_INVALID, "denoise: scratch missing or smaller than mi355pt_denoise_scratch_bytes");
+    if (((uintptr_t)d_scratch & 15u) != 0) return fail(MI355PT_E_INVALID, "denoise: scratch is not 16-byte aligned");
+    HIP_TRY(launch_denoise(d_beauty, spp_b, d_albedo, spp_a, d_normal, spp_n, width, height, dp->levels, dp->sigma_color, dp->sigma_normal,
+                           dp->sigma_albedo, dp->albedo_eps, d_scratch, d_out, (hipStream_t)hip_stream));
+    return MI355PT_OK;
+}
+
+int mi355pt_denoise(const float* beauty, uint32_t spp_b, const float* albedo, uint32_t spp_a, const float* normal, uint32_t spp_n, uint32_t width,
+                    uint32_t height, const mi355pt_denoise_params* dp, float* out) {
+    int rc = denoise_check(beauty, spp_b, albedo, spp_a, normal, spp_n, width, height, dp, out);
+    if (rc) return rc;
+    const size_t n = (size_t)width * height * 3, scratch_bytes = denoise_scratch_bytes(width, height);
+    DevBuf<float> d_b, d_a, d_n, d_out;
+    DevBuf<unsigned char> d_scratch;
+    HIP_TRY(d_b.alloc(n));
+    HIP_TRY(d_out.alloc(n));
+    HIP_TRY(d_scratch.alloc(scratch_bytes));
+    HIP_TRY(hipMemcpy(d_b.p, beauty, n * sizeof(float), hipMemcpyHostToDevice));
+    if (albedo) { HIP_TRY(d_a.alloc(n)); HIP_TRY(hipMemcpy(d_a.p, albedo, n * sizeof(float), hipMemcpyHostToDevice)); }
+    if (normal) { HIP_TRY(d_n.alloc(n)); HIP_TRY(hipMemcpy(d_n.p, normal, n * sizeof(float), hipMemcpyHostToDevice)); }
+    if ((rc = mi355pt_denoise_device(d_b.p, spp_b, albedo ? d_a.p : nullptr, spp_a, normal ? d_n.p : nullptr, spp_n, width, height, dp, d_scratch.p,
+                                     scratch_bytes, d_out.p, nullptr))) return rc;
+    HIP_TRY(hipMemcpy(out, d_out.p, n * sizeof(float), hipMemcpyDeviceToHost));      // (synchronises the default stream)
     return MI355PT_OK;
 }
 

@@ -107,6 +107,12 @@ class Stats(C.Structure):
         return d
 
 
+class DenoiseParams(C.Structure):
+    """mi355pt_denoise_params (include/mi355pt_denoise.h); Product.denoise_params_default() fills it — a zeroed one is refused"""
+    _fields_ = [("levels", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float),
+                ("albedo_eps", C.c_float)]
+
+
 def make_camera(position, direction, up, width, height, fov_deg=45.0):
     return Camera((C.c_float * 3)(*position), (C.c_float * 3)(*direction), (C.c_float * 3)(*up), fov_deg, width, height)
 
@@ -131,6 +137,8 @@ ABI_SYMBOLS = [
     "quantize_u8", "scene_info", "scene_build_multi", "render_multi", "coat_albedo_table",
     "last_error", "version",
 ]
+# ... include/mi355pt_denoise.h, the denoiser block mi355pt.h includes (tests/test_denoise.py checks these the same way)
+DENOISE_SYMBOLS = ["denoise_params_default", "denoise_scratch_bytes", "denoise_device", "denoise"]
 
 
 class Backend:
@@ -341,6 +349,13 @@ class Product(Backend):
             lib.mi355pt_render_aov_accum_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_int, C.c_uint32, C.c_uint32,
                                                             C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
             lib.mi355pt_aov_resolve_device.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "mi355pt_denoise_device"):             # (absent from an older build loaded through MI355PT_LIB)
+            lib.mi355pt_denoise_params_default.argtypes = [C.POINTER(DenoiseParams)]; lib.mi355pt_denoise_params_default.restype = None
+            lib.mi355pt_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]; lib.mi355pt_denoise_scratch_bytes.restype = C.c_size_t
+            lib.mi355pt_denoise_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                   C.POINTER(DenoiseParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+            lib.mi355pt_denoise.argtypes = [C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float), C.c_uint32,
+                                            C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), C.POINTER(C.c_float)]
         if not hasattr(lib, "mi355pt_render_sample_log"):      # an older build loaded through MI355PT_LIB for an A/B timing run
             return
         lib.mi355pt_sample_log_records.argtypes = [C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]
@@ -387,6 +402,37 @@ class Product(Backend):
     def aov_resolve_device(self, kind, d_accum_ptr, n_pixels, spp, d_out_ptr, stream=None):
         self.check(self.lib.mi355pt_aov_resolve_device(kind, C.c_void_p(d_accum_ptr), n_pixels, spp, C.c_void_p(d_out_ptr), C.c_void_p(stream or 0)),
                    "aov_resolve_device")
+
+    # ---- the denoiser (include/mi355pt_denoise.h): an a-trous filter over the linear beauty film, guided by the albedo / shading-normal films ----
+    def denoise_params_default(self):
+        p = DenoiseParams()
+        self.lib.mi355pt_denoise_params_default(C.byref(p))
+        return p
+
+    def denoise_scratch_bytes(self, width, height):
+        return int(self.lib.mi355pt_denoise_scratch_bytes(width, height))
+
+    def denoise_device(self, d_beauty_ptr, spp_beauty, d_albedo_ptr, spp_albedo, d_normal_ptr, spp_normal, width, height, params, d_scratch_ptr,
+                       scratch_bytes, d_out_ptr, stream=None):
+        """mi355pt_denoise_device on device pointers (films of linear SUMS, W*H*3 f32; albedo / normal pointer None or 0 = not given);
+        asynchronous on `stream`.  The output is a linear mean: resolve it with film_resolve_device(.., spp=1, ..)."""
+        self.check(self.lib.mi355pt_denoise_device(C.c_void_p(d_beauty_ptr), spp_beauty, C.c_void_p(d_albedo_ptr or 0), spp_albedo,
+                                                   C.c_void_p(d_normal_ptr or 0), spp_normal, width, height, C.byref(params),
+                                                   C.c_void_p(d_scratch_ptr), scratch_bytes, C.c_void_p(d_out_ptr), C.c_void_p(stream or 0)),
+                   "denoise_device")
+
+    def denoise(self, beauty, spp_beauty, albedo=None, spp_albedo=0, normal=None, spp_normal=0, params=None):
+        """mi355pt_denoise on host arrays (H, W, 3) of linear sums -> (H, W, 3) float32 linear mean"""
+        b = np.ascontiguousarray(beauty, dtype=np.float32)
+        assert b.ndim == 3 and b.shape[2] == 3
+        a = None if albedo is None else np.ascontiguousarray(albedo, dtype=np.float32)
+        n = None if normal is None else np.ascontiguousarray(normal, dtype=np.float32)
+        assert all(g is None or g.shape == b.shape for g in (a, n))
+        params = params if params is not None else self.denoise_params_default()
+        out = np.zeros(b.shape, dtype=np.float32)
+        self.check(self.lib.mi355pt_denoise(_ptr(b, C.c_float), spp_beauty, _ptr(a, C.c_float), spp_albedo, _ptr(n, C.c_float), spp_normal,
+                                            b.shape[1], b.shape[0], C.byref(params), _ptr(out, C.c_float)), "denoise")
+        return out
 
     def render_accum_device(self, scene, cam, params, s_begin, s_end, d_accum_ptr, stream=None, stats=None):
         self.check(self.lib.mi355pt_render_accum_device(scene.h, C.byref(cam), C.byref(params), s_begin, s_end, C.c_void_p(d_accum_ptr),

@@ -5,6 +5,8 @@
 #include <cstdlib>
 #include <string>
 
+#include <hip/hip_runtime_api.h>   // --denoise only: the films of that path stay on the device (hipMalloc / hipMemcpy / hipFree, no kernels here)
+
 #include "scenes.hpp"
 
 using namespace renderer;
@@ -14,13 +16,47 @@ struct Args {   // main.rs:20-53
     std::string filter = "box", sampler = "random", renderer = "normal", output = "output.png";
     // not in the reference's CLI: the coat-albedo table option (mi355pt_params.albedo_lut) and the number of GPUs of this node to shard the frame over
     bool albedo_lut = false; int gpus = 1;
+    // not in the reference's CLI either: the a-trous denoiser (mi355pt_denoise.h) behind a path renderer, and the spp of its two guide films
+    bool denoise = false; uint32_t denoise_guide_spp = 64;
 };
+
+// --denoise: the beauty film at --spp, the albedo and shading-normal films at --denoise-guide-spp (converged guides cost a few percent of
+// the frame; guides as noisy as the frame hurt), mi355pt_denoise_device, then Sensor::to_rgb on the result as a film with spp 1.
+// Everything stays on the device until the resolved frame is copied into `pixels`.  Returns the device seconds of the beauty launch.
+struct DeviceFilm {
+    float* p = nullptr;
+    explicit DeviceFilm(size_t bytes) {
+        if (hipMalloc((void**)&p, bytes) != hipSuccess || hipMemset(p, 0, bytes) != hipSuccess) throw std::runtime_error("mi355pt: device allocation failed");
+    }
+    ~DeviceFilm() { (void)hipFree(p); }
+    DeviceFilm(const DeviceFilm&) = delete;
+    DeviceFilm& operator=(const DeviceFilm&) = delete;
+};
+static double render_denoised(const Scene& scene, const Camera& camera, mi355pt_params p, uint32_t guide_spp, std::vector<float>& pixels) {
+    const mi355pt_camera& cam = camera.raw();
+    const uint32_t n_pixels = cam.width * cam.height;
+    const size_t film_bytes = (size_t)n_pixels * 3 * sizeof(float), scratch_bytes = mi355pt_denoise_scratch_bytes(cam.width, cam.height);
+    DeviceFilm beauty(film_bytes), albedo(film_bytes), normal(film_bytes), out(film_bytes), rgb(film_bytes), scratch(scratch_bytes);
+    mi355pt_stats st{};
+    check(mi355pt_render_accum_device(scene.raw(), &cam, &p, 0, p.spp, beauty.p, nullptr, &st), "mi355pt_render_accum_device");
+    mi355pt_params g = p;
+    g.spp = guide_spp;
+    check(mi355pt_render_aov_accum_device(scene.raw(), &cam, &g, MI355PT_AOV_ALBEDO, scene.d65_lut(), 0, guide_spp, albedo.p, nullptr, nullptr), "mi355pt_render_aov_accum_device");
+    check(mi355pt_render_aov_accum_device(scene.raw(), &cam, &g, MI355PT_AOV_SHADING_NORMAL, scene.d65_lut(), 0, guide_spp, normal.p, nullptr, nullptr), "mi355pt_render_aov_accum_device");
+    mi355pt_denoise_params dp;
+    mi355pt_denoise_params_default(&dp);
+    check(mi355pt_denoise_device(beauty.p, p.spp, albedo.p, guide_spp, normal.p, guide_spp, cam.width, cam.height, &dp, scratch.p, scratch_bytes, out.p, nullptr), "mi355pt_denoise_device");
+    check(mi355pt_film_resolve_device(out.p, n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
+    if (hipMemcpy(pixels.data(), rgb.p, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the frame back failed");
+    return st.kernel_ms * 1e-3;
+}
 
 static void usage() {
     std::puts("Usage: mi355pt [--scene N] [-s|--spp N] [--seed N] [--filter box] [--sampler random|sobol]\n"
               "               [--renderer normal|albedo|pt|nee|mis] [--width N] [--height N] [-d|--max-depth N] [-o|--output FILE]\n"
               "       extensions: [--albedo-lut] (clearcoat albedo from its table instead of the 64-sample estimate)  [--gpus N]\n"
-              "                   [--renderer shading-normal] (render-space shading normal of every surface: the AOV a denoiser takes)");
+              "                   [--renderer shading-normal] (render-space shading normal of every surface: the AOV a denoiser takes)\n"
+              "                   [--denoise] (pt|nee|mis: a-trous filter guided by the albedo and shading-normal films)  [--denoise-guide-spp N] (64)");
 }
 
 int main(int argc, char** argv) {
@@ -40,6 +76,8 @@ int main(int argc, char** argv) {
         else if (k == "-o" || k == "--output") a.output = val();
         else if (k == "--albedo-lut") a.albedo_lut = true;
         else if (k == "--gpus") a.gpus = std::stoi(val());
+        else if (k == "--denoise") a.denoise = true;
+        else if (k == "--denoise-guide-spp") a.denoise_guide_spp = (uint32_t)std::stoul(val());
         else if (k == "-h" || k == "--help") { usage(); return 0; }
         else { std::fprintf(stderr, "error: unexpected argument '%s'\n", k.c_str()); usage(); return 2; }
     }
@@ -51,6 +89,9 @@ int main(int argc, char** argv) {
         return 2;
     }
     if (aov && a.gpus > 1) { std::fprintf(stderr, "error: --gpus %d with --renderer %s: the AOV renderers run on one GPU\n", a.gpus, a.renderer.c_str()); return 2; }
+    if (a.denoise && aov) { std::fprintf(stderr, "error: --denoise with --renderer %s: the denoiser filters the frame of a path renderer (pt, nee, mis)\n", a.renderer.c_str()); return 2; }
+    if (a.denoise && a.gpus > 1) { std::fprintf(stderr, "error: --denoise with --gpus %d: the denoiser runs on one GPU\n", a.gpus); return 2; }
+    if (a.denoise && (a.denoise_guide_spp == 0 || a.spp == 0)) { std::fprintf(stderr, "error: --denoise needs --spp and --denoise-guide-spp above 0\n"); return 2; }
     try {
         Camera camera(45.0f, a.width, a.height);                                        // main.rs:59-68
         Scene scene;
@@ -93,10 +134,13 @@ int main(int argc, char** argv) {
         RendererImage image(a.width, a.height, r);
         std::puts("Start rendering...");                                                // main.rs:166-172
         t0 = std::chrono::steady_clock::now();
-        double kernel_s = image.render(a.sampler == "sobol" ? SamplerKind::ZSobol : SamplerKind::Random, a.albedo_lut);
+        const SamplerKind sampler = a.sampler == "sobol" ? SamplerKind::ZSobol : SamplerKind::Random;
+        double kernel_s = a.denoise ? render_denoised(scene, camera, image.params(sampler, a.albedo_lut), a.denoise_guide_spp, image.pixels_mut())
+                                    : image.render(sampler, a.albedo_lut);
         double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         std::printf("Finish rendering: %.3f seconds.\n", wall);
-        if (kernel_s > 0.0) std::printf("(device %.3f s, %.1f Msamples/s)\n", kernel_s, (double)a.width * a.height * a.spp / kernel_s / 1e6);
+        if (kernel_s > 0.0 && a.denoise) std::printf("(beauty launch alone: device %.3f s, %.1f Msamples/s; the guide films and the filter are in the wall time above)\n", kernel_s, (double)a.width * a.height * a.spp / kernel_s / 1e6);
+        else if (kernel_s > 0.0) std::printf("(device %.3f s, %.1f Msamples/s)\n", kernel_s, (double)a.width * a.height * a.spp / kernel_s / 1e6);
         image.save(a.output);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "mi355pt: %s\n", e.what());

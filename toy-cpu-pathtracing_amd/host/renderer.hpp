@@ -742,10 +742,14 @@ public:
     RendererImage(uint32_t w, uint32_t h, SrgbRenderer r) : pixels_((size_t)w * h * 3, 0.0f), w_(w), h_(h), r_(r) {}
     // RendererImage::render::<S>() — the seam: one call into the HIP library fills `pixels`
     // (albedo_lut: mi355pt_params.albedo_lut, an option outside the reference's CLI; 0 = the reference's estimator)
-    double render(SamplerKind sampler, bool albedo_lut = false) {
+    mi355pt_params params(SamplerKind sampler, bool albedo_lut = false) const {
         mi355pt_params p{};
         p.spp = r_.args.spp; p.seed = r_.args.seed; p.max_depth = r_.max_depth; p.strategy = r_.strategy; p.sampler = (uint32_t)sampler;
         p.exposure = r_.exposure; p.shard_index = 0; p.shard_count = 1; p.albedo_lut = albedo_lut ? 1u : 0u;
+        return p;
+    }
+    double render(SamplerKind sampler, bool albedo_lut = false) {
+        const mi355pt_params p = params(sampler, albedo_lut);
         if (r_.aov >= 0) {                                  // RendererImage::<NormalRenderer | AlbedoRenderer>::render (main.rs:155-186)
             if (r_.args.scene->multi()) throw std::runtime_error("the AOV renderers run on one GPU (mi355pt_render_multi has no AOV form)");
             mi355pt_stats st{};
@@ -761,6 +765,7 @@ public:
         return st.kernel_ms * 1e-3;
     }
     const std::vector<float>& pixels() const { return pixels_; }
+    std::vector<float>& pixels_mut() { return pixels_; }      // for a caller that fills the frame itself (the CLI's --denoise path)
     // RendererImage::save (renderer.rs:137-148): (p*255.0) as u8, PNG
     void save(const std::string& path) const;
 private:
