@@ -481,7 +481,7 @@ def test_shards_tile_the_frame(product, pkg):
                                                (3, 96, 64, 512), (0, 64, 48, 2048)])   # odd log2(spp): the half digit at the bottom of the index
 def test_launch_shape_does_not_change_the_frame(product, oracle, pkg, scene_id, w, h, spp):
     """The launcher picks the work-item shape from the number of sample indices per launch (8x8 tiles for short launches,
-    4x4 / 2x2 / 1x1 pixel blocks for longer ones, api.cpp): the film of the whole job in ONE launch must equal the film
+    4x4 / 2x2 / 1x1 pixel blocks for longer ones, launch_plan.hpp): the film of the whole job in ONE launch must equal the film
     accumulated over launches of 64 (and of 16) sample indices up to float summation order, shards included, and must match
     the oracle's frame like any other."""
     import torch

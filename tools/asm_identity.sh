@@ -1,7 +1,9 @@
 #!/usr/bin/env bash
 # Is the device code of this tree the same as that of another revision?  For every .hip translation unit of csrc/Makefile's SRCS, compile
 # the revision and the working tree to device assembly with exactly the flags the Makefile gives that unit (taken from `make -n`, per-target
-# additions included) plus --cuda-device-only -S, and compare the two after dropping the __hip_cuid_<hash> lines (they hash the source text).
+# additions included) plus --cuda-device-only -S, and compare the two after dropping the __hip_cuid_<hash> lines (they hash the source text)
+# and the ordinal of the function in its unit from the block labels (.LBB<function>_<block>, .Lfunc_end<function>: a kernel that is removed
+# renumbers every kernel after it).
 # Needs hipcc, no GPU.  The gate of a refactor that claims to delete only compile-time-dead code.
 #
 #   tools/asm_identity.sh <git-rev> [unit.hip ...]       (default: every unit)
@@ -35,8 +37,10 @@ compile() {         # <tree> <out> [unit ...]
     asm_commands "$@" | (cd "$tree/$csrc" && xargs -r -P "$jobs" -d '\n' -I{} sh -c '{}')
 }
 
+# the assembly without what differs between two compilations of the same code
+clean() { grep -v __hip_cuid_ "$1" | sed -E 's/BB[0-9]+_([0-9]+)/BB_\1/g; s/\.Lfunc_(begin|end)[0-9]+/.Lfunc_\1/g; s/[ \t]+;/ ;/g'; }
 # every line of a function's body, prefixed with the function's label
-functions() { grep -v __hip_cuid_ "$1" | awk '/^[^ \t;.][^ \t]*:[ \t]*; @/ { f = $1 } f != "" { print f "\t" $0 } /^\.Lfunc_end/ { f = "" }'; }
+functions() { clean "$1" | awk '/^[^ \t;.][^ \t]*:[ \t]*; @/ { f = $1 } f != "" { print f "\t" $0 } /^\.Lfunc_end/ { f = "" }'; }
 
 base=$work/$rev
 rm -rf "$work/tree-$rev" && mkdir -p "$work/tree-$rev"
@@ -52,9 +56,9 @@ for s in "$cand"/*.s; do
     [ $# -eq 0 ] || [[ " $* " == *" $(basename "$s" .s) "* ]] || continue
     u=$(basename "$s" .s)
     if [ ! -f "$base/$u.s" ]; then echo "NEW        $u (not in ${rev:0:12})"; status=1
-    elif cmp -s <(grep -v __hip_cuid_ "$base/$u.s") <(grep -v __hip_cuid_ "$s"); then echo "identical  $u"
+    elif cmp -s <(clean "$base/$u.s") <(clean "$s"); then echo "identical  $u"
     else
-        echo "DIFFERENT  $u ($(diff <(grep -v __hip_cuid_ "$base/$u.s") <(grep -v __hip_cuid_ "$s") | grep -c '^[<>]') lines), in the functions:"; status=1
+        echo "DIFFERENT  $u ($(diff <(clean "$base/$u.s") <(clean "$s") | grep -c '^[<>]') lines), in the functions:"; status=1
         diff <(functions "$base/$u.s") <(functions "$s") | grep '^[<>]' | cut -f1 | cut -c3- | sort -u | c++filt | cut -c1-160 | sed 's/^/             /' || true
     fi
 done

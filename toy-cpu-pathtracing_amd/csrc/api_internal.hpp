@@ -1,0 +1,89 @@
+// What api.cpp (include/mi355pt.h, mi355pt_denoise.h) and api_debug.cpp (include/mi355pt_debug.h) share.  Not installed, not an ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../../include/mi355pt.h"
+#include "launch.hpp"
+#include "launch_plan.hpp"
+#include "scene.hpp"
+
+namespace pt {
+
+// Per-scene launch resources, allocated once (no hipMalloc/hipFree/sync on the launch path, so a caller can queue
+// launches on its own stream or capture them): the MurmurHash(dimension, seed) table per seed and a ring of work
+// counters / stats blocks so that back-to-back asynchronous launches never share a counter.
+constexpr int CTX_RING = 16;
+struct LaunchCtx {
+    int device = -1;                  // the device every buffer below lives on (= SceneImpl::device when the context was made)
+    int waves[2][2][3] = {{{0}}};     // [instrumented][sampler][strategy]: resident waves of the kernel that combination launches (0: not asked yet)
+    int aov_waves[3] = {0, 0, 0};     // [MI355PT_AOV_*]: the same for the AOV kernel of this scene's feature set
+    uint64_t* d_hash = nullptr;
+    uint32_t hash_seed = 0;
+    bool hash_valid = false;
+    unsigned* d_counters = nullptr;   // CTX_RING counters
+    DevStats* d_stats = nullptr;      // CTX_RING blocks
+    float* d_defer = nullptr;         // the resident waves' deferral queues (pt_kernel.hpp defer_bytes_per_wave), sized for the largest grid seen
+    size_t defer_bytes = 0;
+    float* d_partial = nullptr;       // per-chunk film tiles of split launches (tiles * chunks * 64 * 3 floats), grown on demand;
+    size_t partial_bytes = 0;         // reused by consecutive launches: one stream at a time per scene
+    int next = 0;
+    ~LaunchCtx() {
+        // freed with the owning device current (a scene rebuilt on another device drops its context from there)
+        int cur = -1;
+        const bool swap = device >= 0 && hipGetDevice(&cur) == hipSuccess && cur != device && hipSetDevice(device) == hipSuccess;
+        (void)hipFree(d_hash); (void)hipFree(d_counters); (void)hipFree(d_stats); (void)hipFree(d_partial); (void)hipFree(d_defer);
+        if (swap) (void)hipSetDevice(cur);
+    }
+};
+// One device's share of a multi-device scene (mi355pt_scene_build_multi): a full replica of the scene on that device plus
+// the stream, film and event mi355pt_render_multi drives it with.  Replica 0 is the scene object itself.
+struct MultiPart {
+    int device = -1;
+    mi355pt_scene* scene = nullptr;      // owned unless it is the parent (part 0)
+    hipStream_t stream = nullptr;
+    hipEvent_t done = nullptr;
+    float* d_film = nullptr;             // full-frame linear film of this device's tile shard
+    float* d_pack = nullptr;             // parts 1..: the shard's tiles as a compact film (tile-major, 192 floats per tile) — what crosses xGMI
+    float* d_stage = nullptr;            // part 0 only: one landing area per peer for those compact films
+    float* d_out = nullptr;              // part 0 only: resolved frame
+    size_t film_floats = 0, pack_floats = 0, stage_floats = 0;
+};
+
+}  // namespace pt
+
+struct mi355pt_scene {
+    pt::SceneImpl impl;
+    mutable pt::LaunchCtx* ctx = nullptr;
+    mutable std::vector<pt::MultiPart> parts;   // empty unless built with mi355pt_scene_build_multi
+    ~mi355pt_scene();
+};
+
+namespace pt {
+
+extern bool g_debug_unlocked;      // mi355pt_debug_unlock: lets mi355pt_params.rr_gate_slack through
+int fail(int code, const std::string& msg);   // sets the thread's mi355pt_last_error (api.cpp) and returns `code`
+#define HIP_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        hipError_t _e = (expr);                                                                         \
+        if (_e != hipSuccess) return fail(MI355PT_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    ~DevBuf() { (void)hipFree(p); }
+    hipError_t alloc(size_t n) { return hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)); }
+};
+
+// `aov`: the AOV renderers ignore strategy and max_depth (mi355pt_render_aov), so they are not checked for them
+int check_args(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, bool aov = false);
+// aov_kind < 0: the path-tracing kernels; MI355PT_AOV_*: the AOV kernel (pt_kernels_aov.hip) over the same work items and work counter —
+// but never a split sample range —, with `illuminant_lut` for the albedo kind
+int render_accum_range(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, uint32_t s_begin, uint32_t s_end,
+                       float* d_accum, void* hip_stream, mi355pt_stats* stats, const PathOut& pout, int aov_kind = -1, uint32_t illuminant_lut = 0);
+
+}  // namespace pt

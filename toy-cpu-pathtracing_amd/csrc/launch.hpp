@@ -1,0 +1,61 @@
+// Every host-callable function a .hip translation unit defines for api.cpp / api_debug.cpp, declared ONCE: the callers and the defining
+// units include this header, so a signature that drifts is a compile error (and PathOut, a kernel parameter, has one definition).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "layout.hpp"
+
+namespace pt {
+
+// Per-sample log (mi355pt_render_sample_log): when L != nullptr every finished path of the launch also writes its spectral radiance,
+// wavelengths and wavelength pdfs to slot ((tile_k * 64 + pixel in tile) * n_s + (sample index - s_base)).  A wave-uniform branch at
+// path end in the PRODUCTION kernel: the per-sample parity tests read what the benchmarked binary computed, in its own launch shape.
+struct PathOut { float* L; float* lam; float* pdf; uint32_t s_base, n_s; };
+
+// pt_kernels.hip: the path-tracing kernels (n_tiles: 8x8 tiles of the launch's shard, launch_plan.hpp), film resolve, multi-device gather, probes
+hipError_t launch_pt(const DevScene&, const DevCamera&, const DevParams&, uint32_t n_tiles, const uint64_t* d_hash, float* d_accum, float* d_partial,
+                     unsigned* d_counter, DevStats* d_stats, bool stats, uint32_t feat, int grid, hipStream_t, const PathOut&, float* d_defer);
+size_t query_defer_bytes_per_wave();
+hipError_t launch_resolve(const float* d_accum, uint32_t n_values, uint32_t spp, float* d_out, hipStream_t);
+hipError_t launch_film_pack(const float* film, uint32_t w, uint32_t h, uint32_t shard_index, uint32_t shard_count, uint32_t n_tiles, float* packed, hipStream_t);
+hipError_t launch_film_unpack(float* film, uint32_t w, uint32_t h, uint32_t shard_index, uint32_t shard_count, uint32_t n_tiles, const float* packed, hipStream_t);
+hipError_t launch_probe_sobol(uint32_t width, uint32_t seed, uint32_t log2_spp, uint32_t nb4, const uint32_t* d_xys, uint32_t n, const uint8_t* d_pat,
+                              uint32_t n_pat, uint32_t per, uint32_t* d_out, hipStream_t);
+hipError_t launch_probe_intersect(const DevScene&, const float* o, const float* d, uint32_t n, float* t, uint32_t* inst, uint32_t* tri, float* nrm, hipStream_t);
+hipError_t launch_probe_occluded(const DevScene&, const float* o, const float* d, const float* tmax, uint32_t n, uint8_t* out, hipStream_t);
+hipError_t launch_probe_sincos(uint32_t first, uint32_t stride, uint32_t n, float* out_s, float* out_c, hipStream_t);
+uint64_t host_murmur_dim_seed(uint32_t dimension, uint32_t seed);
+int query_resident_waves(bool stats, uint32_t feat, uint32_t sampler, uint32_t strategy);
+// pt_kernels_aov.hip: the AOV renderers' primary-ray kernel (kind = MI355PT_AOV_*)
+hipError_t launch_aov(uint32_t kind, const DevScene&, const DevCamera&, const DevParams&, uint32_t illuminant_lut, const uint64_t* d_hash, float* d_accum,
+                      unsigned* d_counter, DevStats* d_stats, uint32_t feat, int grid, hipStream_t);
+int query_resident_waves_aov(uint32_t kind, uint32_t feat);
+hipError_t launch_aov_resolve(uint32_t kind, const float* d_accum, uint32_t n_values, uint32_t spp, float* d_out, hipStream_t);
+// pt_kernels_denoise.hip: the a-trous denoiser (include/mi355pt_denoise.h)
+size_t denoise_scratch_bytes(uint32_t width, uint32_t height);
+uint32_t denoise_grid_blocks(uint32_t width, uint32_t height);
+hipError_t launch_denoise(const float* d_beauty, uint32_t spp_b, const float* d_albedo, uint32_t spp_a, const float* d_normal, uint32_t spp_n,
+                          uint32_t width, uint32_t height, uint32_t levels, float sigma_color, float sigma_normal, float sigma_albedo,
+                          float albedo_eps, void* d_scratch, float* d_out, hipStream_t);
+
+// Resident 64-thread blocks (= waves) of `kernel` on the current device: the persistent grid size of the EXACT instantiation a launch takes
+// (the register count, and so the occupancy, differs between instantiations and between translation units with their own backend flags).
+// Each translation unit answers for the kernels it holds.  per_cu <= 0 (no answer): 8 blocks per CU.
+inline int resident_waves_per_device(int per_cu) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 2048;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 2048;
+    return prop.multiProcessorCount * (per_cu > 0 ? per_cu : 8);
+}
+template <typename Kernel>
+int resident_waves_of(Kernel kernel) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, 0) != hipSuccess) per_cu = 0;
+    return resident_waves_per_device(per_cu);
+}
+
+}  // namespace pt

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "launch.hpp"
 #include "layout.hpp"
 #include "pt_device.hpp"
 #include "pt_path.hpp"
@@ -645,7 +646,6 @@ struct PtLaunchArgs {
 // clearcoat code run at 4 waves per SIMD and gain from sinking / the AMDGPU pressure trackers, the clearcoat sets (3 waves per SIMD) lose.
 #define PT_FOR_EACH_PLAIN_SET(X) X(0u) X(FEAT_TEX) X(FEAT_DIEL) X(FEAT_METAL) X(FEAT_DIEL | FEAT_ROUGH) X(FEAT_DELTA | FEAT_MLIGHT) X(FEAT_STD & ~FEAT_CC)
 #define PT_FOR_EACH_CC_SET(X) X(FEAT_CC) X(FEAT_CC | FEAT_TEX) X(FEAT_STD) X(FEAT_ALL)
-#define PT_FOR_EACH_FEATURE_SET(X) PT_FOR_EACH_PLAIN_SET(X) PT_FOR_EACH_CC_SET(X)
 #define PT_CASE(F) case (F): hipLaunchKernelGGL((pt_kernel<false, (F), MODE>), dim3(a.grid), dim3(64), 0, a.stream, a.sc, a.cam, a.prm, a.d_hash, a.d_accum, a.d_partial, a.d_counter, a.d_stats, a.pout, a.d_defer); break;
 template <uint32_t MODE>
 void launch_pt_plain(const PtLaunchArgs& a, uint32_t feat) {
@@ -660,36 +660,30 @@ template <uint32_t MODE>
 void launch_pt_mode(const PtLaunchArgs& a, uint32_t feat) {
     if (pick_features(feat) & FEAT_CC) launch_pt_cc<MODE>(a, feat); else launch_pt_plain<MODE>(a, feat);
 }
-// resident waves per CU of the EXACT instantiation a launch takes (launch bounds: 4 waves/SIMD, clearcoat variants 3; the register count and
-// so the occupancy can differ between the MODE specialisations, which live in different translation units with their own backend flags):
-// the persistent grid size.  Each translation unit answers for the kernels it holds.
-#define PT_OCC_CASE(F) case (F): e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pt_kernel<false, (F), MODE>, 64, 0); break;
+// resident waves on the current device of the EXACT instantiation a launch takes (launch bounds: 4 waves/SIMD, clearcoat variants 3; the
+// register count and so the occupancy can differ between the MODE specialisations, which live in different translation units with their own
+// backend flags): the persistent grid size (launch.hpp resident_waves_of).  Each translation unit answers for the kernels it holds.
+#define PT_WAVES_CASE(F) case (F): return resident_waves_of(pt_kernel<false, (F), MODE>);
 template <uint32_t MODE>
-int occupancy_pt_plain(uint32_t feat) {
-    int per_cu = 0;
-    hipError_t e = hipErrorUnknown;
-    switch (pick_features(feat)) { PT_FOR_EACH_PLAIN_SET(PT_OCC_CASE) default: break; }
-    return (e == hipSuccess && per_cu > 0) ? per_cu : 8;
+int resident_waves_pt_plain(uint32_t feat) {
+    switch (pick_features(feat)) { PT_FOR_EACH_PLAIN_SET(PT_WAVES_CASE) default: return resident_waves_per_device(0); }
 }
 template <uint32_t MODE>
-int occupancy_pt_cc(uint32_t feat) {
-    int per_cu = 0;
-    hipError_t e = hipErrorUnknown;
-    switch (pick_features(feat)) { PT_FOR_EACH_CC_SET(PT_OCC_CASE) default: break; }
-    return (e == hipSuccess && per_cu > 0) ? per_cu : 8;
+int resident_waves_pt_cc(uint32_t feat) {
+    switch (pick_features(feat)) { PT_FOR_EACH_CC_SET(PT_WAVES_CASE) default: return resident_waves_per_device(0); }
 }
-#undef PT_OCC_CASE
+#undef PT_WAVES_CASE
 template <uint32_t MODE>
-int occupancy_pt_mode(uint32_t feat) { return (pick_features(feat) & FEAT_CC) ? occupancy_pt_cc<MODE>(feat) : occupancy_pt_plain<MODE>(feat); }
+int resident_waves_pt_mode(uint32_t feat) { return (pick_features(feat) & FEAT_CC) ? resident_waves_pt_cc<MODE>(feat) : resident_waves_pt_plain<MODE>(feat); }
 void launch_pt_mis_sobol(const PtLaunchArgs& a, uint32_t feat);      // pt_kernels_mis.hip (plain sets; forwards the clearcoat sets)
 void launch_pt_mis_sobol_cc(const PtLaunchArgs& a, uint32_t feat);   // pt_kernels_mis_cc.hip
 void launch_pt_nee_sobol(const PtLaunchArgs& a, uint32_t feat);      // pt_kernels_nee.hip
 void launch_pt_nee_sobol_cc(const PtLaunchArgs& a, uint32_t feat);   // pt_kernels_nee_cc.hip
 void launch_pt_strategy_pt(const PtLaunchArgs& a, uint32_t feat);    // pt_kernels_pt.hip (the plain path tracer, either sampler)
-int occupancy_pt_mis_sobol(uint32_t feat);
-int occupancy_pt_mis_sobol_cc(uint32_t feat);
-int occupancy_pt_nee_sobol(uint32_t feat);
-int occupancy_pt_nee_sobol_cc(uint32_t feat);
-int occupancy_pt_strategy_pt(uint32_t feat);
+int resident_waves_pt_mis_sobol(uint32_t feat);
+int resident_waves_pt_mis_sobol_cc(uint32_t feat);
+int resident_waves_pt_nee_sobol(uint32_t feat);
+int resident_waves_pt_nee_sobol_cc(uint32_t feat);
+int resident_waves_pt_strategy_pt(uint32_t feat);
 
 }  // namespace pt

@@ -38,7 +38,7 @@
 namespace pt {
 
 // Sensor::to_rgb (sensor.rs:81-88) + ReinhardToneMap (tone_map.rs:20-28) + sRGB OETF (eotf.rs:54-61)
-__global__ void resolve_kernel(const float* __restrict__ accum, uint32_t n_values, float inv_unused, uint32_t spp, float* __restrict__ out) {
+__global__ void resolve_kernel(const float* __restrict__ accum, uint32_t n_values, uint32_t spp, float* __restrict__ out) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t stride = gridDim.x * blockDim.x;
     for (; i < n_values; i += stride) {
@@ -113,16 +113,6 @@ __global__ __launch_bounds__(64) void probe_occluded_kernel(DevScene sc, const f
     out[i] = trace_any<false>(sc, ro, rd, tmax[i], s_stack + threadIdx.x, st) ? 1 : 0;
 }
 
-// dst += src over a film (multi-device gather: the films of the other devices' tile shards, disjoint from this device's own)
-__global__ void film_add_kernel(float* __restrict__ dst, const float* __restrict__ src, size_t n4) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (; i < n4; i += stride) {
-        float4 a = ((const float4*)dst)[i], b = ((const float4*)src)[i];
-        ((float4*)dst)[i] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-    }
-}
-
 // Multi-device gather (mi355pt_render_multi): a device's shard of the frame as a COMPACT film — its 8x8 tiles in shard order (tile k of the
 // shard = frame tile shard_index + k * shard_count), 64 pixels x 3 floats each, pixels outside the frame 0 — so that 1/N of the film
 // crosses xGMI per peer instead of the whole frame; and the inverse on the gathering device (the shards' tiles are disjoint: plain stores).
@@ -164,10 +154,11 @@ __global__ void combine_kernel(DevCamera cam, DevParams prm, const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------
-// launch wrappers (host side, called from api.cpp)
+// launch wrappers (host side, declared in launch.hpp for api.cpp / api_debug.cpp)
 // ---------------------------------------------------------------------------------------------
-hipError_t launch_pt(const DevScene& sc, const DevCamera& cam, const DevParams& prm, const uint64_t* d_hash, float* d_accum, float* d_partial,
-                     unsigned* d_counter, DevStats* d_stats, bool stats, uint32_t feat, int grid, hipStream_t stream, const PathOut& pout, float* d_defer) {
+hipError_t launch_pt(const DevScene& sc, const DevCamera& cam, const DevParams& prm, uint32_t n_tiles, const uint64_t* d_hash, float* d_accum,
+                     float* d_partial, unsigned* d_counter, DevStats* d_stats, bool stats, uint32_t feat, int grid, hipStream_t stream,
+                     const PathOut& pout, float* d_defer) {
     const PtLaunchArgs a{sc, cam, prm, d_hash, d_accum, d_partial, d_counter, d_stats, grid, stream, pout, (float4*)d_defer};
     if (stats) {
         // two instrumented variants: scenes without the clearcoat code get the one whose traversal has the production form (merged, 4 waves
@@ -180,16 +171,8 @@ hipError_t launch_pt(const DevScene& sc, const DevCamera& cam, const DevParams& 
     else if (prm.sampler == 1u && prm.strategy == 1u) launch_pt_nee_sobol(a, feat);
     else if (prm.strategy == 0u) launch_pt_strategy_pt(a, feat);
     else launch_pt_mode<MODE_GENERIC>(a, feat);
-    if (prm.chunks > 1) {
-        const uint32_t n_tiles = (prm.n_work / prm.chunks) >> (6u - 2u * prm.block_log2);   // n_work = tiles * blocks per tile * chunks
+    if (prm.chunks > 1)
         hipLaunchKernelGGL(combine_kernel, dim3(n_tiles), dim3(64), 0, stream, cam, prm, (const float*)d_partial, d_accum, n_tiles);
-    }
-    return hipGetLastError();
-}
-hipError_t launch_film_add(float* dst, const float* src, size_t n_floats, hipStream_t stream) {   // n_floats % 4 == 0 (padded by the caller)
-    const size_t n4 = n_floats / 4;
-    int grid = (int)std::min<size_t>((n4 + 255) / 256, 4096);
-    hipLaunchKernelGGL(film_add_kernel, dim3(grid), dim3(256), 0, stream, dst, src, n4);
     return hipGetLastError();
 }
 hipError_t launch_film_pack(const float* film, uint32_t w, uint32_t h, uint32_t shard_index, uint32_t shard_count, uint32_t n_tiles, float* packed, hipStream_t stream) {
@@ -202,7 +185,7 @@ hipError_t launch_film_unpack(float* film, uint32_t w, uint32_t h, uint32_t shar
 }
 hipError_t launch_resolve(const float* d_accum, uint32_t n_values, uint32_t spp, float* d_out, hipStream_t stream) {
     int grid = (int)std::min<uint32_t>((n_values + 255) / 256, 2048u);
-    hipLaunchKernelGGL(resolve_kernel, dim3(grid), dim3(256), 0, stream, d_accum, n_values, 0.0f, spp, d_out);
+    hipLaunchKernelGGL(resolve_kernel, dim3(grid), dim3(256), 0, stream, d_accum, n_values, spp, d_out);
     return hipGetLastError();
 }
 hipError_t launch_probe_sobol(uint32_t width, uint32_t seed, uint32_t log2_spp, uint32_t nb4, const uint32_t* d_xys, uint32_t n,
@@ -224,29 +207,20 @@ hipError_t launch_probe_occluded(const DevScene& sc, const float* o, const float
     return hipGetLastError();
 }
 
-}  // namespace pt
 
-namespace pt {
 uint64_t host_murmur_dim_seed(uint32_t dimension, uint32_t seed) { return murmur_dim_seed(dimension, seed); }
 size_t query_defer_bytes_per_wave() { return defer_bytes_per_wave(); }     // the deferral queues of pt_kernel.hpp (0: compiled out)
 // resident 64-thread blocks (= waves) on the current device of the EXACT kernel instantiation launch_pt takes for (stats, feat, sampler,
 // strategy): the persistent grid size.  The MODE specialisations are separate translation units with their own backend flags, so their
 // register counts — and with them the occupancy — need not be those of the generic variant.  Cached per scene and device (api.cpp LaunchCtx).
 int query_resident_waves(bool stats, uint32_t feat, uint32_t sampler, uint32_t strategy) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 2048;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 2048;
-    int per_cu = 0;
     if (stats) {
-        hipError_t e;
-        if ((feat & (FEAT_CC | FEAT_EMTEX)) == 0u) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pt_kernel<true, FEAT_STD & ~FEAT_CC, MODE_GENERIC>, 64, 0);
-        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pt_kernel<true, FEAT_ALL, MODE_GENERIC>, 64, 0);
-        if (e != hipSuccess || per_cu <= 0) per_cu = 8;
-    } else if (sampler == 1u && strategy == 2u) per_cu = occupancy_pt_mis_sobol(feat);
-    else if (sampler == 1u && strategy == 1u) per_cu = occupancy_pt_nee_sobol(feat);
-    else if (strategy == 0u) per_cu = occupancy_pt_strategy_pt(feat);
-    else per_cu = occupancy_pt_mode<MODE_GENERIC>(feat);
-    return prop.multiProcessorCount * per_cu;
+        if ((feat & (FEAT_CC | FEAT_EMTEX)) == 0u) return resident_waves_of(pt_kernel<true, FEAT_STD & ~FEAT_CC, MODE_GENERIC>);
+        return resident_waves_of(pt_kernel<true, FEAT_ALL, MODE_GENERIC>);
+    }
+    if (sampler == 1u && strategy == 2u) return resident_waves_pt_mis_sobol(feat);
+    if (sampler == 1u && strategy == 1u) return resident_waves_pt_nee_sobol(feat);
+    if (strategy == 0u) return resident_waves_pt_strategy_pt(feat);
+    return resident_waves_pt_mode<MODE_GENERIC>(feat);
 }
 }  // namespace pt

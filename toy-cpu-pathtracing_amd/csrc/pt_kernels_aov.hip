@@ -174,7 +174,7 @@ __global__ void aov_resolve_kernel(uint32_t kind, const float* __restrict__ accu
     }
 }
 
-// ---- host side (called from api.cpp) ----
+// ---- host side (declared in launch.hpp for api.cpp) ----
 // the instantiation a (kind, scene feature set) launches: texture code only in the albedo kernel of a scene with spectrum textures
 #define PT_AOV_DISPATCH(X)                                                          \
     if (kind == AOV_NORMAL) { X(AOV_NORMAL, 0u) }                                   \
@@ -192,17 +192,9 @@ hipError_t launch_aov(uint32_t kind, const DevScene& sc, const DevCamera& cam, c
 }
 // resident 64-thread blocks (= waves) of that instantiation on the current device: the persistent grid size
 int query_resident_waves_aov(uint32_t kind, uint32_t feat) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 2048;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 2048;
-    int per_cu = 0;
-    hipError_t e = hipErrorUnknown;
-#define PT_AOV_OCC(K, F) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, aov_kernel<K, F>, 64, 0);
-    PT_AOV_DISPATCH(PT_AOV_OCC)
-#undef PT_AOV_OCC
-    if (e != hipSuccess || per_cu <= 0) per_cu = 8;
-    return prop.multiProcessorCount * per_cu;
+#define PT_AOV_WAVES(K, F) return resident_waves_of(aov_kernel<K, F>);
+    PT_AOV_DISPATCH(PT_AOV_WAVES)
+#undef PT_AOV_WAVES
 }
 hipError_t launch_aov_resolve(uint32_t kind, const float* d_accum, uint32_t n_values, uint32_t spp, float* d_out, hipStream_t stream) {
     if (n_values == 0u) return hipSuccess;

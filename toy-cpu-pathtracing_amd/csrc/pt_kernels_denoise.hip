@@ -20,6 +20,8 @@
 #include <cfloat>
 #include <cstdint>
 
+#include "launch.hpp"
+
 namespace pt {
 
 namespace {
@@ -138,7 +140,7 @@ __global__ __launch_bounds__(DN_BLOCK_X * DN_BLOCK_Y) void denoise_level_kernel(
 
 }  // namespace
 
-// ---- host side (called from api.cpp, which has checked every argument) ----
+// ---- host side (declared in launch.hpp; called from api.cpp, which has checked every argument) ----
 size_t denoise_scratch_bytes(uint32_t width, uint32_t height) {
     const unsigned __int128 b = (unsigned __int128)width * height * 64u;
     return b > (unsigned __int128)SIZE_MAX ? 0 : (size_t)b;

@@ -1,6 +1,7 @@
 // Path state and the per-vertex stages of BaseSrgbRenderer::render (renderer/src/renderer/base_renderer.rs:146-280) as
 // device functions shared by the kernel variants in pt_kernels.hip.  All state lives in registers.
 #pragma once
+#include "launch.hpp"
 #include "pt_device.hpp"
 #include "pt_ggx.hpp"
 
@@ -1147,11 +1148,7 @@ PT_DEV bool shade_vertex_tail(Path& P, const DevScene& sc, const DevParams& prm,
     return end_path;
 }
 
-// Per-sample log (mi355pt_render_sample_log): when L != nullptr every finished path of the launch also writes its spectral radiance,
-// wavelengths and wavelength pdfs to slot ((tile_k * 64 + pixel in tile) * n_s + (sample index - s_base)).  A wave-uniform branch at
-// path end in the PRODUCTION kernel: the per-sample parity tests read what the benchmarked binary computed, in its own launch shape.
-struct PathOut { float* L; float* lam; float* pdf; uint32_t s_base, n_s; };
-
+// the per-sample log's record of one finished path (PathOut: launch.hpp)
 PT_DEV void sample_log(const Path& P, const PathOut& pout, size_t slot) {
     const float pdf0 = 1.0f / (LAMBDA_MAX - LAMBDA_MIN);
     float lam[4];

@@ -38,11 +38,6 @@ bool build_bvh_gpu(const std::vector<BuildTri>& tris, BvhOut* out, double* devic
 
 constexpr size_t BVH_GPU_AUTO_TRIS = 1u << 17;   // "auto": scenes from 131 072 triangles on are built on the GPU
 
-struct DeviceBuffers {
-    void* ptrs[16] = {nullptr};
-    int n = 0;
-};
-
 struct SceneImpl {
     // ---- description ----
     std::vector<float> table;                 // reference layout [64][3][64][64][64][3]
@@ -62,7 +57,6 @@ struct SceneImpl {
     float build_cam_pos[3] = {0, 0, 0};   // camera position baked into the render-space records (world -> render translation)
     DevScene dev{};
     std::vector<void*> allocs;
-    uint32_t cmf_lut[3] = {0, 0, 0};
     int bvh_depth = 0;
     size_t bvh4_nodes = 0;        // nodes of the collapsed tree (DevNode4)
     int bvh_builder = 0;          // MI355PT_BVH_AUTO / _HOST / _GPU (mi355pt_scene_set_bvh_builder)
@@ -87,9 +81,5 @@ struct SceneImpl {
 
 // mi355pt_coat_albedo_table (scene.cpp): E(cos theta_o) of the clearcoat's directional-albedo estimator, 64 entries
 void coat_albedo_table(float alpha, float r0, float out[64]);
-
-// baked CIE 1931 colour matching functions shipped with the library (data/presets470.bin rows cie_x/y/z)
-const float* builtin_cmf_xyz();   // 3*470 floats or nullptr if not loaded
-bool load_builtin_cmf(std::string* err);
 
 }  // namespace pt
