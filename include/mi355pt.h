@@ -230,6 +230,16 @@ int mi355pt_render(const mi355pt_scene* s, const mi355pt_camera* cam, const mi35
 int mi355pt_render_accum_device(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p,
                                 uint32_t sample_begin, uint32_t sample_end, float* d_accum, void* hip_stream,
                                 mi355pt_stats* stats /* NULL ok; non-NULL synchronises the stream */);
+/* EXTENSION, no reference counterpart: mi355pt_render_accum_device over an EXPLICIT LIST of the frame's 8x8 tiles (tile t = column t %
+ * tiles_x, row t / tiles_x, tiles_x = ceil(W / 8): the numbering of shard_index) — adds the sums of [sample_begin, sample_end) into d_accum
+ * on the pixels of the listed tiles, every other pixel untouched.  `tiles` is a HOST array, copied; it must be strictly ascending with
+ * every index below the frame's tile count, p->shard_count must be 0 or 1 and p->collect_stats 0 (there is no instrumented tile-list
+ * kernel): otherwise MI355PT_E_INVALID, before anything touches the device.  n_tiles = 0 does nothing.  The list of ALL tiles gives
+ * mi355pt_render_accum_device's film bit for bit; a shorter list may split the sample range differently (another summation order).
+ * `stats`, when given, receives kernel_ms and launches and synchronises the stream.  What the adaptive driver (below) renders its passes with. */
+int mi355pt_render_accum_tiles_device(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, const uint32_t* tiles,
+                                      uint32_t n_tiles, uint32_t sample_begin, uint32_t sample_end, float* d_accum, void* hip_stream,
+                                      mi355pt_stats* stats /* NULL ok; non-NULL synchronises the stream */);
 /* The seam as main.rs:228 calls it — ONE call from ONE process — over several GPUs of the node (north star: "pixel tiles shard
  * across the 8 GPUs of one node").  mi355pt_scene_build_multi replaces mi355pt_scene_build: the scene (< 30 MB) is replicated on
  * every listed device (ids may repeat, which rehearses the path on fewer GPUs).  mi355pt_render_multi = mi355pt_render: the frame's
@@ -294,5 +304,12 @@ const char* mi355pt_version(void);
  * mi355pt_denoise_params_default, mi355pt_denoise_scratch_bytes, mi355pt_denoise_device and mi355pt_denoise: an edge-avoiding a-trous
  * filter over the linear film of a path renderer, on device buffers.  Declared in its own header, which this one always includes. */
 #include "mi355pt_denoise.h"
+
+/* ---------------- adaptive sampling ---------------- */
+/* EXTENSION, no reference counterpart: samples where the noise is — mi355pt_adaptive_params, mi355pt_adaptive_result,
+ * mi355pt_adaptive_scratch_bytes, mi355pt_adaptive_step_device (a per-tile noise estimate from the film and a half film, and the list of tiles
+ * above a threshold), mi355pt_film_normalize_tiles_device, mi355pt_render_adaptive_device and mi355pt_render_adaptive (the driver, over
+ * mi355pt_render_accum_tiles_device above).  Declared in its own header, which this one always includes. */
+#include "mi355pt_adaptive.h"
 
 #endif /* MI355PT_H */

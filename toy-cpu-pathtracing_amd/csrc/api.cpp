@@ -55,7 +55,8 @@ int get_launch_ctx(const mi355pt_scene* sc, uint32_t seed, LaunchCtx** out, int*
 }
 
 // a buffer of the launch context that must hold `need` bytes: an earlier launch on `stream` may still be using the old one
-int grow_device_buffer(float** ptr, size_t* have, size_t need, hipStream_t stream) {
+template <typename T>
+int grow_device_buffer(T** ptr, size_t* have, size_t need, hipStream_t stream) {
     if (need <= *have) return MI355PT_OK;
     HIP_TRY(hipStreamSynchronize(stream));
     (void)hipFree(*ptr); *ptr = nullptr; *have = 0;
@@ -180,6 +181,60 @@ int pt::render_accum_range(const mi355pt_scene* s, const mi355pt_camera* cam, co
     }
     return for_each_launch_range(p->sampler, stats != nullptr, s_begin, s_end, [&](uint32_t b, uint32_t e) {
         return launch_range(s, cam, p, b, e, d_accum, (hipStream_t)hip_stream, stats, pout, aov_kind, illuminant_lut);
+    });
+}
+
+// one launch of the tile-list kernels over d_list[0 .. n_list) (device memory, n_list > 0; arguments checked): launch_range for a list.
+// The shape is planned with the resident waves of the PLAIN kernel of the same mode: chunks and block size — the frame's bits — then equal
+// plan_launch's for a list of all tiles, whatever occupancy the tile-list instantiation has (a grid that does not fit waits its turn: the
+// work items are independent).
+static int launch_range_tiles(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, const uint32_t* d_list, uint32_t n_list,
+                              uint32_t s_begin, uint32_t s_end, float* d_accum, hipStream_t stream, mi355pt_stats* stats) {
+    int rc;
+    LaunchCtx* lc; int slot;
+    if ((rc = get_launch_ctx(s, p->seed, &lc, &slot))) return rc;
+    if (lc->device != s->impl.device) return fail(MI355PT_E_DEVICE, "launch context and scene live on different devices");
+    int& waves = lc->waves[0][p->sampler & 1u][p->strategy < 3u ? p->strategy : 0u];
+    if (!waves) waves = query_resident_waves(false, s->impl.features, p->sampler, p->strategy);
+    const DevCamera dc = make_camera(cam);
+    LaunchPlan plan = plan_launch_tiles(cam, p, s_begin, s_end, waves, n_list);
+    DevParams& dp = plan.params;
+    set_tile_list(dp, d_list);
+    dp.stats_mode = 0u;
+    unsigned* d_counter = lc->d_counters + slot;
+    HIP_TRY(hipMemsetAsync(d_counter, 0, sizeof(unsigned), stream));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (stats) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, stream)); }
+    if ((rc = grow_device_buffer(&lc->d_partial, &lc->partial_bytes, plan.partial_floats * sizeof(float), stream))) return rc;
+    if ((rc = grow_device_buffer(&lc->d_defer, &lc->defer_bytes, query_defer_bytes_per_wave() * (size_t)plan.grid, stream))) return rc;
+    HIP_TRY(launch_pt_tiles(s->impl.dev, dc, dp, n_list, lc->d_hash, d_accum, lc->d_partial, d_counter, s->impl.features, plan.grid, stream, lc->d_defer));
+    if (stats) {
+        HIP_TRY(hipEventRecord(e1, stream));
+        HIP_TRY(hipEventSynchronize(e1));
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        std::memset(stats, 0, sizeof(*stats));
+        stats->kernel_ms = ms; stats->launches = 1;
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    }
+    return MI355PT_OK;
+}
+
+// what the tile-list entry and the adaptive driver ask of (scene, camera, params) beyond check_args
+static int check_tiles_args(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p) {
+    int rc = check_args(s, cam, p);
+    if (rc) return rc;
+    if (p->shard_count > 1u) return fail(MI355PT_E_INVALID, "tile lists name tiles of the whole frame: shard_count must be 0 or 1");
+    if (p->collect_stats) return fail(MI355PT_E_INVALID, "there is no instrumented tile-list kernel: collect_stats must be 0");
+    if (adaptive_tile_count(cam->width, cam->height) == 0u) return fail(MI355PT_E_INVALID, "the frame has 2^31 tiles or more");
+    return MI355PT_OK;
+}
+
+// [s_begin, s_end) of the tiles d_list[0 .. n_list) (device memory) into d_accum; arguments checked
+static int render_accum_tiles(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, const uint32_t* d_list, uint32_t n_list,
+                              uint32_t s_begin, uint32_t s_end, float* d_accum, hipStream_t stream, mi355pt_stats* stats) {
+    return for_each_launch_range(p->sampler, stats != nullptr, s_begin, s_end, [&](uint32_t b, uint32_t e) {
+        return launch_range_tiles(s, cam, p, d_list, n_list, b, e, d_accum, stream, stats);
     });
 }
 
@@ -379,6 +434,29 @@ int mi355pt_scene_build(mi355pt_scene* s, const mi355pt_camera* cam) {
 int mi355pt_render_accum_device(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, uint32_t s_begin, uint32_t s_end,
                                 float* d_accum, void* hip_stream, mi355pt_stats* stats) {
     return render_accum_range(s, cam, p, s_begin, s_end, d_accum, hip_stream, stats, PathOut{nullptr, nullptr, nullptr, 0u, 0u});
+}
+
+int mi355pt_render_accum_tiles_device(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, const uint32_t* tiles, uint32_t n_tiles,
+                                      uint32_t s_begin, uint32_t s_end, float* d_accum, void* hip_stream, mi355pt_stats* stats) {
+    int rc = check_tiles_args(s, cam, p);
+    if (rc) return rc;
+    if (!d_accum || s_end > p->spp || s_begin >= s_end) return fail(MI355PT_E_INVALID, "bad sample range or null accumulator");
+    if (n_tiles && !tiles) return fail(MI355PT_E_INVALID, "null tile list");
+    const uint32_t total = adaptive_tile_count(cam->width, cam->height);
+    for (uint32_t k = 0; k < n_tiles; ++k) {
+        if (tiles[k] >= total) return fail(MI355PT_E_INVALID, "tile index at or beyond the frame's tile count");
+        if (k && tiles[k] <= tiles[k - 1]) return fail(MI355PT_E_INVALID, "the tile list must be strictly ascending");
+    }
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (n_tiles == 0) return MI355PT_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    LaunchCtx* lc; int slot;
+    if ((rc = get_launch_ctx(s, p->seed, &lc, &slot))) return rc;
+    if ((rc = grow_device_buffer(&lc->d_tiles, &lc->tiles_bytes, (size_t)n_tiles * sizeof(uint32_t), stream))) return rc;
+    // (ordered on the stream after an earlier launch that may still read the buffer; the caller's array is free again when this returns)
+    HIP_TRY(hipMemcpyAsync(lc->d_tiles, tiles, (size_t)n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return render_accum_tiles(s, cam, p, lc->d_tiles, n_tiles, s_begin, s_end, d_accum, stream, stats);
 }
 
 
@@ -599,6 +677,121 @@ int mi355pt_denoise(const float* beauty, uint32_t spp_b, const float* albedo, ui
     if ((rc = mi355pt_denoise_device(d_b.p, spp_b, albedo ? d_a.p : nullptr, spp_a, normal ? d_n.p : nullptr, spp_n, width, height, dp, d_scratch.p,
                                      scratch_bytes, d_out.p, nullptr))) return rc;
     HIP_TRY(hipMemcpy(out, d_out.p, n * sizeof(float), hipMemcpyDeviceToHost));      // (synchronises the default stream)
+    return MI355PT_OK;
+}
+
+// ---------------- adaptive sampling (include/mi355pt_adaptive.h) ----------------
+
+size_t mi355pt_adaptive_scratch_bytes(uint32_t width, uint32_t height) { return adaptive_scratch_bytes(width, height); }
+
+static int adaptive_check_params(const mi355pt_adaptive_params* ap) {
+    if (!ap) return fail(MI355PT_E_INVALID, "adaptive: null params pointer");
+    if (!(std::isfinite(ap->threshold) && ap->threshold > 0.0f)) return fail(MI355PT_E_INVALID, "adaptive: threshold must be finite and > 0 (it has no default)");
+    if (!(std::isfinite(ap->dark_eps) && ap->dark_eps > 0.0f)) return fail(MI355PT_E_INVALID, "adaptive: dark_eps must be finite and > 0");
+    if (ap->min_spp < 2u || (ap->min_spp & (ap->min_spp - 1u)) != 0u) return fail(MI355PT_E_INVALID, "adaptive: min_spp must be a power of two >= 2");
+    return MI355PT_OK;
+}
+static int adaptive_check_scratch(uint32_t width, uint32_t height, const void* d_scratch, size_t scratch_bytes) {
+    if (width == 0 || height == 0 || adaptive_tile_count(width, height) == 0u) return fail(MI355PT_E_INVALID, "adaptive: zero width or height, or a frame of 2^31 tiles or more");
+    if (!d_scratch || scratch_bytes < adaptive_scratch_bytes(width, height)) return fail(MI355PT_E_INVALID, "adaptive: scratch missing or smaller than mi355pt_adaptive_scratch_bytes");
+    if (((uintptr_t)d_scratch & 3u) != 0) return fail(MI355PT_E_INVALID, "adaptive: scratch is not 4-byte aligned");
+    return MI355PT_OK;
+}
+
+int mi355pt_adaptive_step_device(const float* d_film, float* d_half, uint32_t width, uint32_t height, uint32_t* d_tile_spp, float* d_tile_err,
+                                 const mi355pt_adaptive_params* ap, uint32_t level_spp, uint32_t max_spp, void* d_scratch, size_t scratch_bytes,
+                                 uint32_t* d_list, uint32_t* d_count, void* hip_stream) {
+    int rc = adaptive_check_params(ap);
+    if (rc) return rc;
+    if (!d_film || !d_half || !d_tile_spp || !d_tile_err || !d_list || !d_count) return fail(MI355PT_E_INVALID, "adaptive: null buffer");
+    if (level_spp == 0u || (level_spp & 1u) != 0u) return fail(MI355PT_E_INVALID, "adaptive: level_spp must be even and > 0");
+    if (max_spp < level_spp) return fail(MI355PT_E_INVALID, "adaptive: max_spp is below level_spp");
+    if ((rc = adaptive_check_scratch(width, height, d_scratch, scratch_bytes))) return rc;
+    HIP_TRY(launch_adaptive_step(d_film, d_half, width, height, d_tile_spp, d_tile_err, ap->threshold, ap->dark_eps, level_spp, max_spp, d_scratch, d_list,
+                                 d_count, (hipStream_t)hip_stream));
+    return MI355PT_OK;
+}
+
+int mi355pt_film_normalize_tiles_device(const float* d_film, const uint32_t* d_tile_spp, uint32_t width, uint32_t height, float* d_mean, void* hip_stream) {
+    if (!d_film || !d_tile_spp || !d_mean) return fail(MI355PT_E_INVALID, "normalize: null buffer");
+    if (width == 0 || height == 0 || adaptive_tile_count(width, height) == 0u) return fail(MI355PT_E_INVALID, "normalize: zero width or height, or a frame of 2^31 tiles or more");
+    HIP_TRY(launch_normalize_tiles(d_film, d_tile_spp, width, height, d_mean, (hipStream_t)hip_stream));
+    return MI355PT_OK;
+}
+
+// every check of the two drivers that does not concern the device buffers
+static int adaptive_check_render(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, const mi355pt_adaptive_params* ap) {
+    int rc = check_tiles_args(s, cam, p);
+    if (rc) return rc;
+    if ((rc = adaptive_check_params(ap))) return rc;
+    if ((p->spp & (p->spp - 1u)) != 0u || p->spp < ap->min_spp) return fail(MI355PT_E_INVALID, "adaptive: spp (the maximum) must be a power of two >= min_spp");
+    return MI355PT_OK;
+}
+
+int mi355pt_render_adaptive_device(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, const mi355pt_adaptive_params* ap,
+                                   float* d_film, float* d_half, uint32_t* d_tile_spp, float* d_tile_err, uint32_t* d_list, void* d_scratch,
+                                   size_t scratch_bytes, void* hip_stream, mi355pt_adaptive_result* result) {
+    int rc = adaptive_check_render(s, cam, p, ap);
+    if (rc) return rc;
+    if (!d_film || !d_half || !d_tile_spp || !d_tile_err || !d_list) return fail(MI355PT_E_INVALID, "adaptive: null buffer");
+    if ((rc = adaptive_check_scratch(cam->width, cam->height, d_scratch, scratch_bytes))) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const uint32_t W = cam->width, H = cam->height, n_tiles = adaptive_tile_count(W, H), tiles_x = (W + 7u) / 8u;
+    const uint32_t min_spp = ap->min_spp, max_spp = p->spp;
+    const size_t film_bytes = (size_t)W * H * 3 * sizeof(float);
+    uint32_t* d_count = (uint32_t*)((char*)d_scratch + adaptive_scratch_bytes(W, H) - 16u);     // the scratch's last 16 bytes
+    const PathOut no_log{nullptr, nullptr, nullptr, 0u, 0u};
+    // 1 - 4: every tile at min_spp, H = [0, min / 2), F = [0, min)
+    HIP_TRY(hipMemsetAsync(d_film, 0, film_bytes, stream));
+    HIP_TRY(hipMemsetAsync(d_half, 0, film_bytes, stream));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_tile_spp, (int)min_spp, n_tiles, stream));
+    if ((rc = render_accum_range(s, cam, p, 0u, min_spp / 2u, d_half, hip_stream, nullptr, no_log))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_film, d_half, film_bytes, hipMemcpyDeviceToDevice, stream));
+    if ((rc = render_accum_range(s, cam, p, min_spp / 2u, min_spp, d_film, hip_stream, nullptr, no_log))) return rc;
+    // 5: step, count, the listed tiles' next samples
+    uint32_t passes = 0;
+    for (uint32_t level = min_spp; level <= max_spp; level *= 2u) {
+        HIP_TRY(launch_adaptive_step(d_film, d_half, W, H, d_tile_spp, d_tile_err, ap->threshold, ap->dark_eps, level, max_spp, d_scratch, d_list, d_count, stream));
+        ++passes;
+        uint32_t count = 0;
+        HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (count == 0u) break;                              // (at level == max_spp always: the step activates nothing there)
+        if (count > n_tiles) return fail(MI355PT_E_DEVICE, "adaptive: the step returned more tiles than the frame has");
+        if ((rc = render_accum_tiles(s, cam, p, d_list, count, level, 2u * level, d_film, stream, nullptr))) return rc;
+    }
+    if (result) {
+        std::vector<uint32_t> spp(n_tiles);
+        HIP_TRY(hipMemcpyAsync(spp.data(), d_tile_spp, (size_t)n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        result->passes = passes; result->tiles_at_max = 0; result->total_samples = 0;
+        for (uint32_t t = 0; t < n_tiles; ++t) {
+            const uint32_t tw = std::min(8u, W - (t % tiles_x) * 8u), th = std::min(8u, H - (t / tiles_x) * 8u);
+            result->total_samples += (uint64_t)spp[t] * tw * th;
+            result->tiles_at_max += spp[t] == max_spp ? 1u : 0u;
+        }
+    }
+    return MI355PT_OK;
+}
+
+int mi355pt_render_adaptive(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, const mi355pt_adaptive_params* ap, float* out_rgb,
+                            uint32_t* out_tile_spp, mi355pt_adaptive_result* result) {
+    int rc = adaptive_check_render(s, cam, p, ap);
+    if (rc) return rc;
+    if (!out_rgb) return fail(MI355PT_E_INVALID, "null output");
+    const uint32_t W = cam->width, H = cam->height, n_tiles = adaptive_tile_count(W, H);
+    const size_t n = (size_t)W * H * 3, scratch_bytes = adaptive_scratch_bytes(W, H);
+    DevBuf<float> d_film, d_half, d_err;
+    DevBuf<uint32_t> d_spp, d_list;
+    DevBuf<unsigned char> d_scratch;
+    HIP_TRY(d_film.alloc(n)); HIP_TRY(d_half.alloc(n)); HIP_TRY(d_err.alloc(n_tiles)); HIP_TRY(d_spp.alloc(n_tiles)); HIP_TRY(d_list.alloc(n_tiles));
+    HIP_TRY(d_scratch.alloc(scratch_bytes));
+    if ((rc = mi355pt_render_adaptive_device(s, cam, p, ap, d_film.p, d_half.p, d_spp.p, d_err.p, d_list.p, d_scratch.p, scratch_bytes, nullptr, result))) return rc;
+    // the half film has done its work: it takes the means, and the film the resolved frame
+    if ((rc = mi355pt_film_normalize_tiles_device(d_film.p, d_spp.p, W, H, d_half.p, nullptr))) return rc;
+    if ((rc = mi355pt_film_resolve_device(d_half.p, W * H, 1u, d_film.p, nullptr))) return rc;
+    HIP_TRY(hipMemcpy(out_rgb, d_film.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_tile_spp) HIP_TRY(hipMemcpy(out_tile_spp, d_spp.p, (size_t)n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return MI355PT_OK;
 }
 

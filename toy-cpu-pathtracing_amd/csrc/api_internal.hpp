@@ -30,12 +30,14 @@ struct LaunchCtx {
     size_t defer_bytes = 0;
     float* d_partial = nullptr;       // per-chunk film tiles of split launches (tiles * chunks * 64 * 3 floats), grown on demand;
     size_t partial_bytes = 0;         // reused by consecutive launches: one stream at a time per scene
+    uint32_t* d_tiles = nullptr;      // mi355pt_render_accum_tiles_device: the caller's host list on the device, grown on demand
+    size_t tiles_bytes = 0;
     int next = 0;
     ~LaunchCtx() {
         // freed with the owning device current (a scene rebuilt on another device drops its context from there)
         int cur = -1;
         const bool swap = device >= 0 && hipGetDevice(&cur) == hipSuccess && cur != device && hipSetDevice(device) == hipSuccess;
-        (void)hipFree(d_hash); (void)hipFree(d_counters); (void)hipFree(d_stats); (void)hipFree(d_partial); (void)hipFree(d_defer);
+        (void)hipFree(d_hash); (void)hipFree(d_counters); (void)hipFree(d_stats); (void)hipFree(d_partial); (void)hipFree(d_defer); (void)hipFree(d_tiles);
         if (swap) (void)hipSetDevice(cur);
     }
 };

@@ -40,6 +40,17 @@ uint32_t denoise_grid_blocks(uint32_t width, uint32_t height);
 hipError_t launch_denoise(const float* d_beauty, uint32_t spp_b, const float* d_albedo, uint32_t spp_a, const float* d_normal, uint32_t spp_n,
                           uint32_t width, uint32_t height, uint32_t levels, float sigma_color, float sigma_normal, float sigma_albedo,
                           float albedo_eps, void* d_scratch, float* d_out, hipStream_t);
+// pt_kernels_tiles.hip (+ _mis, _mis_cc, _nee, _nee_cc, _pt): the production path kernels over an explicit tile list — prm carries the device
+// list (layout.hpp set_tile_list) and the plan of launch_plan.hpp plan_launch_tiles over its n_list entries; no instrumented variant, no sample log
+hipError_t launch_pt_tiles(const DevScene&, const DevCamera&, const DevParams&, uint32_t n_list, const uint64_t* d_hash, float* d_accum, float* d_partial,
+                           unsigned* d_counter, uint32_t feat, int grid, hipStream_t, float* d_defer);
+// pt_kernels_adaptive.hip: adaptive sampling's noise step and the per-tile normalisation (include/mi355pt_adaptive.h)
+uint32_t adaptive_tile_count(uint32_t width, uint32_t height);      // 0: empty frame, or 2^31 tiles and more
+size_t adaptive_scratch_bytes(uint32_t width, uint32_t height);
+hipError_t launch_adaptive_step(const float* d_film, float* d_half, uint32_t width, uint32_t height, uint32_t* d_tile_spp, float* d_tile_err,
+                                float threshold, float dark_eps, uint32_t level_spp, uint32_t max_spp, void* d_scratch, uint32_t* d_list,
+                                uint32_t* d_count, hipStream_t);
+hipError_t launch_normalize_tiles(const float* d_film, const uint32_t* d_tile_spp, uint32_t width, uint32_t height, float* d_mean, hipStream_t);
 
 // Resident 64-thread blocks (= waves) of `kernel` on the current device: the persistent grid size of the EXACT instantiation a launch takes
 // (the register count, and so the occupancy, differs between instantiations and between translation units with their own backend flags).

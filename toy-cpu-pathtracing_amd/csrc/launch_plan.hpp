@@ -112,10 +112,11 @@ struct LaunchPlan {
 
 // One launch over the sample indices [s_begin, s_end) on a device that holds `waves` resident waves of the kernel.
 // aov: the AOV kernel (pt_kernels_aov.hip) — the same work items, but never a split sample range
-inline LaunchPlan plan_launch(const mi355pt_camera* cam, const mi355pt_params* p, uint32_t s_begin, uint32_t s_end, int waves, bool aov) {
+// n_tiles: the 8x8 tiles the launch covers (plan_launch: the shard's; plan_launch_tiles: the entries of a list) — the shape depends on their
+// NUMBER only
+inline LaunchPlan plan_launch_over(const mi355pt_camera* cam, const mi355pt_params* p, uint32_t s_begin, uint32_t s_end, int waves, bool aov, uint32_t n_tiles) {
     DevParams dp = make_params(cam, p, s_begin, s_end);
     if (aov) { dp.exposure = 1.0f; dp.rr_gate = 1.0f; dp.strategy = 0u; dp.max_depth = 0u; dp.albedo_lut = 0u; }   // Sensor::new(spp, 1.0, NoneToneMap), albedo_renderer.rs:43-44
-    const uint32_t n_tiles = shard_tile_count(cam->width, cam->height, p->shard_index, p->shard_count);
     // Work items.  A work item is a 2^b x 2^b pixel block of an 8x8 tile times a range of sample indices, its (pixel, sample)
     // pairs handed to the lanes as a pool.  Sobol: the fewer pixels an item has, the fewer Morton digits vary inside it, and only
     // varying digits (minus the two that have block-level tables) are hashed per draw (pt_device.hpp sampler_index): take the
@@ -167,6 +168,16 @@ inline LaunchPlan plan_launch(const mi355pt_camera* cam, const mi355pt_params* p
     const int grid = (int)std::min<uint32_t>(dp.n_work, (uint32_t)waves);
     // one slot per 8x8 tile and chunk, whatever the block size
     return LaunchPlan{dp, n_tiles, grid, dp.chunks > 1 ? (size_t)n_tiles * dp.chunks * 64u * 3u : (size_t)0};
+}
+inline LaunchPlan plan_launch(const mi355pt_camera* cam, const mi355pt_params* p, uint32_t s_begin, uint32_t s_end, int waves, bool aov) {
+    return plan_launch_over(cam, p, s_begin, s_end, waves, aov, shard_tile_count(cam->width, cam->height, p->shard_index, p->shard_count));
+}
+// One launch of the tile-list kernels (pt_kernel_tiles.hpp) over n_list tiles of the whole frame (p->shard_count 0 or 1): tile_k counts the
+// list's entries, so the shape is that of a shard with n_list tiles — and, for n_list = every tile of the frame, field for field
+// plan_launch's whole-frame plan: a list of all tiles renders today's frame bit for bit.  The launcher puts the list's device address into
+// params (layout.hpp set_tile_list) in place of the shard pair.
+inline LaunchPlan plan_launch_tiles(const mi355pt_camera* cam, const mi355pt_params* p, uint32_t s_begin, uint32_t s_end, int waves, uint32_t n_list) {
+    return plan_launch_over(cam, p, s_begin, s_end, waves, false, n_list);
 }
 
 }  // namespace pt

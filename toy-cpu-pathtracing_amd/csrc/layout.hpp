@@ -13,6 +13,7 @@
 //   rgb2spec     [3][64][64][64] float4 (c0,c1,c2,0) + 64 z nodes
 //   textures     RGBA8 (one dword per texel)
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -252,7 +253,8 @@ struct DevParams {
     float exposure;
     uint32_t log2_spp, n_base4_digits;     // ZSobolSampler::new (z_sobol_sampler.rs:179-196)
     uint32_t sample_begin, sample_end;
-    uint32_t shard_index, shard_count;
+    uint32_t shard_index, shard_count;      // the tiles of the launch: frame tile shard_index + k * shard_count — or, for the tile-list kernels
+                                            // (pt_kernel_tiles.hpp), the two halves of a device pointer to the list (tile_list below)
     uint32_t tiles_x, tiles_y;
     uint32_t n_work;                        // tiles * sample chunks handled by this launch
     uint32_t chunks, chunk_size;            // sample-range split per tile (1 = none)
@@ -265,6 +267,14 @@ struct DevParams {
     float rr_gate;                          // Russian roulette is skipped when max(T) >= rr_gate (1 = the reference; mi355pt_params.rr_gate_slack)
     float xyz_to_rgb[9];                    // row-major sRGB matrix (gamut.rs:50-63)
 };
+// The tile-list kernels take frame tile list[k] (device memory) where the others compute shard_index + k * shard_count.  The pointer
+// travels in that pair's eight bytes (offset 40, 8-aligned), low half first, so that DevParams — a by-value argument of every kernel —
+// keeps its type and layout: declaring a union there instead changed the compiled code of every existing kernel.
+static_assert(offsetof(DevParams, shard_index) == 40 && offsetof(DevParams, shard_count) == 44, "the shard pair carries the tile-list pointer");
+PT_HD inline void set_tile_list(DevParams& p, const uint32_t* list) {
+    p.shard_index = (uint32_t)((uint64_t)(uintptr_t)list & 0xffffffffu); p.shard_count = (uint32_t)((uint64_t)(uintptr_t)list >> 32);
+}
+PT_HD inline const uint32_t* tile_list(const DevParams& p) { return (const uint32_t*)(uintptr_t)(((uint64_t)p.shard_count << 32) | p.shard_index); }
 
 // Scene feature bits: the host picks the smallest kernel specialisation that covers the scene's materials, so a
 // Lambert-only Cornell box does not carry the registers and code of the clearcoat / dielectric / texture paths.

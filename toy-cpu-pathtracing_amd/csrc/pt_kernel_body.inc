@@ -1,0 +1,453 @@
+// The body of the sample-loop kernel: the text between the braces of pt_kernel (pt_kernel.hpp) and of pt_kernel_tiles (pt_kernel_tiles.hpp),
+// which differ in ONE thing, how a work item finds its 8x8 tile — PT_LANE_JOB names the function (lane_job: the shard's arithmetic
+// progression; lane_job_tiles: an explicit list).  Included, not called: even a helper called from pt_kernel changes the schedule of every
+// tuned kernel, and those are measured as they are (tools/asm_identity.sh compares the device assembly with a revision's).
+// Expects the kernel's parameters (sc, cam, prm_in, dim_hash_tab, accum, partial, work_counter, stats, pout, defer_buf) and STATS, FEAT, MODE.
+    __shared__ uint32_t s_stack[STACK_DEPTH * 64];
+#ifndef PT_FILM_PIX
+#define PT_FILM_PIX 64
+#endif
+    __shared__ float s_film[PT_FILM_PIX * 3];                 // the work item's 8x8 film tile
+    __shared__ uint32_t s_hi[SOBOL_HI_DIMS];
+    __shared__ uint32_t s_p6[SOBOL_HI_DIMS];
+    __shared__ unsigned s_work;
+    // The clearcoat kernels run 12 waves per CU, so each has 3.4 KB of LDS the 16-wave kernels do not: the record of the BSDF sample that
+    // spawned the ray in flight (f, pdf, the vertex left: 8 dwords per lane, read only at the start of the next vertex's shading) waits there
+    // during the traversals instead of in registers the allocator would spill to scratch
+    constexpr bool PARK = (FEAT & FEAT_CC) != 0u && kernel_min_waves<FEAT>() <= 3;
+    __shared__ float s_park[PARK ? 8 * 64 : 1];
+    __shared__ uint8_t s_perm[96];
+    __shared__ uint32_t s_ring[ANY_RING];
+    __shared__ uint32_t s_occl[2];
+    __shared__ uint32_t s_pair[64];
+    const AnyLds any_lds{s_ring, s_occl, s_pair};
+    __shared__ unsigned long long s_best[64];
+    const ClosestLds closest_lds{s_ring, s_best, s_pair};
+    __shared__ uint32_t s_infl[2];
+    const PairLds pair_lds{s_ring, s_best, s_occl, s_pair, s_infl};
+    DevParams prm = prm_in;
+    if constexpr (MODE == MODE_MIS_SOBOL) { prm.strategy = 2u; prm.sampler = 1u; }
+    if constexpr (MODE == MODE_NEE_SOBOL) { prm.strategy = 1u; prm.sampler = 1u; }
+    if constexpr (MODE == MODE_PT) prm.strategy = 0u;                      // either sampler
+    const uint32_t lane = threadIdx.x;
+    auto park = [&](Path& Q, bool mine = true) {      // `mine`: this lane's record is stored (a second shading pass only stores the lanes it shaded)
+        if constexpr (PARK) {
+            if (mine) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) s_park[i * 64 + lane] = Q.pf[i];
+                s_park[4 * 64 + lane] = Q.p_pdf; s_park[5 * 64 + lane] = Q.prev_pos.x; s_park[6 * 64 + lane] = Q.prev_pos.y; s_park[7 * 64 + lane] = Q.prev_pos.z;
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) Q.pf[i] = 0.0f;
+            Q.p_pdf = 0.0f; Q.prev_pos = mk3(0.0f, 0.0f, 0.0f);
+        }
+    };
+    auto unpark = [&](Path& Q) {
+        if constexpr (PARK) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) Q.pf[i] = s_park[i * 64 + lane];
+            Q.p_pdf = s_park[4 * 64 + lane]; Q.prev_pos = mk3(s_park[5 * 64 + lane], s_park[6 * 64 + lane], s_park[7 * 64 + lane]);
+        }
+    };
+    uint32_t* stack = s_stack + lane;
+    // murmur(dimension, seed) comes straight from its 1 KB global table (L1-resident): the LDS it used holds the tile's film
+    for (uint32_t k = lane; k < 96u; k += 64u) s_perm[k] = (uint8_t)((perm_packed(k >> 2) >> (2u * (k & 3u))) & 3u);
+    if constexpr ((FEAT & (FEAT_TEX | FEAT_EMTEX | FEAT_ENV)) != 0u) s_znodes[lane] = sc.z_nodes[lane];   // rgb2spec_lookup's z search (pt_device.hpp)
+    __syncthreads();
+    SamplerCtx sctx{prm.sampler, prm.seed, prm.log2_spp, prm.n_base4_digits, cam.width, dim_hash_tab, nullptr, 0u, 0u, nullptr, s_perm};
+    StatCounters st{};
+    unsigned long long tp[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long dvc[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // mi355pt_stats.divergence[4..11]
+    unsigned long long t_loop0 = 0;
+    if (STATS) t_loop0 = __builtin_amdgcn_s_memtime();
+
+    for (;;) {
+        if (lane == 0) s_work = atomicAdd(work_counter, 1u);
+        __syncthreads();
+        const uint32_t work = s_work;
+        __syncthreads();
+        if (work >= prm.n_work) break;
+        // this lane's own pixel of the tile (film write-back) and the work item's wave-uniform sample range
+        const LaneJob job = PT_LANE_JOB(work, lane, cam, prm);
+        const LaneJob job0 = PT_LANE_JOB(work, 0u, cam, prm);
+        const uint32_t blk_log2 = prm.block_log2, blk_mask = (1u << blk_log2) - 1u;
+        const uint32_t s_prefix = prm.sample_prefix_digits;
+        // (the tables hold the permuted prefix in 27 bits per entry: a launch shape whose prefix is wider hashes every digit instead)
+        const uint32_t hi_first_w = sobol_hi_first(prm.log2_spp, blk_log2) - s_prefix, hi_shift_w = 2u * hi_first_w - (prm.log2_spp & 1u);
+        if (prm.sampler == 1u && hi_first_w < prm.n_base4_digits && hi_first_w >= 3u &&
+            2u * prm.n_base4_digits - (prm.log2_spp & 1u) <= hi_shift_w + 27u) {
+            // block-uniform Sobol digit prefixes: lane d computes dimension d for this block (lane 0's pixel is the block origin).
+            // Single-pixel items over an aligned 4^m block of sample indices: the sample digits above m are part of the prefix.
+            sctx.hi_first = sobol_hi_first(prm.log2_spp, blk_log2) - s_prefix;
+            sctx.hi_shift = 2u * sctx.hi_first - (prm.log2_spp & 1u);
+            const uint32_t tile_m = (encode_morton2_u32(job0.px, job0.py) << prm.log2_spp) | (s_prefix ? job0.s_cur : 0u);
+            for (uint32_t dmn = lane; dmn < (uint32_t)SOBOL_HI_DIMS; dmn += 64) {
+                uint32_t e = (uint32_t)(sobol_tile_hi_digits(tile_m, dmn, prm.log2_spp, prm.n_base4_digits, sctx.hi_first) >> sctx.hi_shift);   // <= 26 bits: the Morton index is a u32 and hi_shift >= 6
+                const uint64_t prefix = (uint64_t)tile_m >> sctx.hi_shift;                 // the digits above digit hi_first-1
+                e |= sobol_perm_index(prefix, dmn) << 27;
+                uint32_t e6 = 0;
+                for (uint32_t v7 = 0; v7 < 4u; ++v7) e6 |= sobol_perm_index((prefix << 2) | v7, dmn) << (5u * v7);
+                s_hi[dmn] = e; s_p6[dmn] = e6;
+            }
+            sctx.hi_lds = s_hi; sctx.p6_lds = s_p6;
+        }
+        // The work item's paths form a pool of (pixel, sample) pairs, sample-major.  A lane whose path ended takes the next pair,
+        // whichever pixel of the tile it belongs to: no lane idles while another still has samples of "its" pixel to do.  The
+        // tile's film lives in LDS (ds_add_f32); the hand-out order is a function of the wave's own deterministic schedule.
+        if (lane < PT_FILM_PIX) { s_film[3 * lane] = 0.0f; s_film[3 * lane + 1] = 0.0f; s_film[3 * lane + 2] = 0.0f; }
+        __syncthreads();
+        const uint32_t n_s = job0.s_end > job0.s_cur ? job0.s_end - job0.s_cur : 0u;
+        const uint32_t pool_size = n_s << (2u * blk_log2);
+        uint32_t pool_next = 0u;                                   // wave-uniform
+        uint32_t my_pix = lane;
+        Path P{};
+        park(P);
+        bool active = false;
+        constexpr bool MERGED = merged_traversal<FEAT, MODE>();
+        ShadowReq sh{};                                            // merged form: the light connection of the vertex just shaded, traced together with the NEXT closest-hit ray
+        // merged form: a path that ended with a light connection pending stays for one more iteration (`dying`) in which only the connection
+        // is traced, instead of a separate any-hit traversal at the end of the iteration (rare; keeps one traversal instance in the kernel);
+        bool dying = false, susp = false;                         // (`susp`, `carry`: always false / unused — left-overs, see trace_pair_coop)
+        CarryState carry{0ull};
+        constexpr bool TAILQ = !STATS && tail_queue<FEAT, MODE>();       // (the instrumented kernels keep the plain shading stage)
+        constexpr uint32_t DEFER = TAILQ ? 0u : defer_classes<FEAT, MODE>();
+        float4* const q_base = (DEFER != 0u || TAILQ) ? defer_buf + (size_t)blockIdx.x * (QUEUE_MAX * QUEUE_RING * DEFER_F4) : nullptr;     // this wave's queue(s)
+        uint32_t q_head = 0u, q_tail = 0u;                         // wave-uniform; the queue is empty between work items
+        // tail queue: a second queue for the paths whose hit is on a sort class of its own (defer_classes), so that a pass shades one class
+        // (the clearcoat material in the kernels that have it: its branch is the long one.  A second queue for every class but plain Lambert
+        // was measured on the kernels without clearcoat and LOSES — scene 3 2 312 -> 2 063, scene 8 2 097 -> 1 932: a class that is a tenth of
+        // the hits fills its queue every ~16 iterations and leaves up to 63 paths to be bounced out in sparse passes when a work item ends)
+        constexpr uint32_t TQ_CLASSES = (TAILQ && (FEAT & FEAT_CC) != 0u) ? ((1u << MT_CLEARCOAT) | (1u << (MT_CLEARCOAT | 8u))) : 0u;
+        uint32_t q2_head = 0u, q2_tail = 0u;
+        // entries per ring: with one queue at most 127 paths ever wait (a pass starts at 64, an iteration adds at most 64 and every lane is
+        // free after the front), with two at most 191 in both together — the smaller ring keeps the records closer to the L2
+#ifndef PT_TAILQ_RING1
+#define PT_TAILQ_RING1 128u
+#endif
+        constexpr uint32_t QR = (TQ_CLASSES != 0u) ? QUEUE_RING : PT_TAILQ_RING1;
+        while (true) {
+            unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, ts4 = 0, tsa = 0, tsb = 0;
+            uint32_t bsdf_classes = 0u;
+            if (STATS) ts0 = __builtin_amdgcn_s_memtime();
+            bool popped = false;                            // deferral queue: this lane took a queued path (in the second shading pass)
+            uint32_t pop_e = 0u;
+            const unsigned long long m_needy = __ballot(!active);
+            if (m_needy != 0ull && pool_next < pool_size) {
+                const uint32_t idx = pool_next + rank_below(m_needy);
+                if (!active && idx < pool_size) {
+                    const uint32_t pix = idx & ((1u << (2u * blk_log2)) - 1u);
+                    const uint32_t px = job0.px + (pix & blk_mask), py = job0.py + (pix >> blk_log2);
+                    const uint32_t smp_i = job0.s_cur + (idx >> (2u * blk_log2));
+                    const bool valid = px < cam.width && py < cam.height;
+                    if (valid) { active = true; my_pix = pix; regen_path<STATS>(P, sctx, cam, px, py, smp_i, st); }
+                }
+                pool_next = min(pool_next + (uint32_t)__popcll(m_needy), pool_size);
+            }
+            if (!__any(active)) {
+                if (pool_next >= pool_size && q_tail == q_head && q2_tail == q2_head) break;
+                // (queued paths are taken AFTER the shading stage: with nothing left to start, an iteration without rays still has to get there)
+                if (!((DEFER != 0u || TAILQ) && pool_next >= pool_size)) continue;
+            }
+            if (STATS) { ts1 = __builtin_amdgcn_s_memtime(); if (lane == 0) st.w[4]++; if (active) st.w[5]++; }
+            Hit hit{};
+            bool got = false;
+            const bool canonical = STATS && prm.stats_mode == 1u;                    // plain per-lane traversals in the reference's order (step counts)
+            if (canonical) { if (active) got = trace_closest<STATS>(sc, P.ro, P.rd, 3.402823466e+38f, stack, hit, st); }
+            else if constexpr (MERGED) {
+                // ONE traversal for this iteration's closest-hit rays and the light connections the previous shading left pending
+                bool occluded = false;
+                if (STATS && sh.on) st.w[6]++;
+                PT_PRIO_TRAV_ENTER;
+                trace_pair_coop<STATS>(sc, P.ro, P.rd, active && !dying && !popped, sh.o, sh.d, sh.t, sh.on, stack, lane, pair_lds, hit, got, occluded, st, &carry, susp, &susp);
+                PT_PRIO_TRAV_EXIT;
+                if (sh.on && !occluded) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) P.L[i] = P.L[i] + sh.c[i];
+                }
+                sh = ShadowReq{};      // consumed: every field dead from here on, for every lane — none of them is carried through the shading stage (+2 % on scenes 0 / 8)
+            }
+            else { PT_PRIO_TRAV_ENTER; got = trace_closest_coop<STATS>(sc, P.ro, P.rd, active, stack, lane, closest_lds, hit, st); PT_PRIO_TRAV_EXIT; }
+            if (STATS) {
+                // material divergence of the shading stage (mi355pt_stats.divergence): classes among the lanes that shade a surface
+                const uint32_t mclass = (active && got) ? sc.materials[__float_as_uint(((const float4*)(sc.shade + hit.tri))[4].z)].type : 8u;
+                uint32_t classes = 0u, largest = 0u, lanes = 0u;
+                for (uint32_t c = 0u; c < 8u; ++c) {
+                    const uint32_t n = (uint32_t)__popcll(__ballot(mclass == c));
+                    classes += n ? 1u : 0u; largest = max(largest, n); lanes += n;
+                }
+                if (lane == 0 && lanes) { st.dv[0]++; st.dv[1] += classes; st.dv[2] += lanes; st.dv[3] += largest; }
+                bsdf_classes = classes - (__ballot(mclass == MT_EMISSIVE) != 0ull ? 1u : 0u);
+                ts2 = __builtin_amdgcn_s_memtime();
+            }
+            // the tail queue's record: what the back of the vertex still needs once the front has run — the spawning sample's f, pdf and the
+            // vertex left are consumed by the front, from_camera / prev_spec are rewritten by the tail, the hit's t is never read: 20 dwords in
+            // 5 float4 = 80 B.  The record's size is the queue's price: 128 -> 96 B was worth +6.5 % on C2 (the queues stream through L2 / HBM)
+            // Layout: FIELD-major inside a ring (float4 k of entry e at ring base + k * ring + e): the entries of one push / pop are
+            // consecutive, so each of the five store / load instructions of a wave covers 64 x 16 B = eight whole 128-byte lines instead of a
+            // sixth of 64 different ones (+1 ... 2 % over the record-major layout; a 128-entry ring where one queue suffices +0.2 ... 0.8 %)
+            auto tq_store = [&](uint32_t e, const Path& Q, const Hit& h, uint32_t pix) {
+                float4* r = q_base + (size_t)(e >> 8) * (TQ_F4 * QUEUE_RING) + (e & (QR - 1u));
+                const uint32_t fl = (Q.wl.term ? 1u : 0u) | ((Q.depth & 1023u) << 1) | ((pix & 63u) << 11) | (Q.smp.dimension << 17);   // (max_depth <= 1000, api.cpp check_args: dimension <= 3 + 8 * 1000 < 2^15)
+                r[0u * QR] = make_float4(__uint_as_float(Q.smp.morton), __uint_as_float(fl), Q.wl.lam0, __uint_as_float(h.tri));
+                r[1u * QR] = make_float4(Q.T[0], Q.T[1], Q.T[2], Q.T[3]);
+                r[2u * QR] = make_float4(Q.L[0], Q.L[1], Q.L[2], Q.L[3]);
+                r[3u * QR] = make_float4(Q.rd.x, Q.rd.y, Q.rd.z, h.b0);
+                r[4u * QR] = make_float4(h.b1, h.b2, __uint_as_float(Q.smp.rkey_lo), __uint_as_float(Q.smp.rkey_hi));
+            };
+            auto tq_load = [&](uint32_t e, Path& Q, Hit& h, uint32_t& pix) {
+                const float4* r = q_base + (size_t)(e >> 8) * (TQ_F4 * QUEUE_RING) + (e & (QR - 1u));
+                const float4 a = r[0u * QR], b = r[1u * QR], c = r[2u * QR], d = r[3u * QR], e4 = r[4u * QR];
+                const uint32_t fl = __float_as_uint(a.y);
+                Q.smp.morton = __float_as_uint(a.x); Q.smp.dimension = fl >> 17; Q.smp.rkey_lo = __float_as_uint(e4.z); Q.smp.rkey_hi = __float_as_uint(e4.w);
+                Q.wl.lam0 = a.z; Q.wl.term = (fl & 1u) != 0u; Q.depth = (fl >> 1) & 1023u; pix = (fl >> 11) & 63u;
+                Q.from_camera = false; Q.prev_spec = false;
+                Q.T[0] = b.x; Q.T[1] = b.y; Q.T[2] = b.z; Q.T[3] = b.w; Q.L[0] = c.x; Q.L[1] = c.y; Q.L[2] = c.z; Q.L[3] = c.w;
+                Q.rd = mk3(d.x, d.y, d.z); Q.ro = mk3(0.0f, 0.0f, 0.0f);
+                h.b0 = d.w; h.b1 = e4.x; h.b2 = e4.y; h.tri = __float_as_uint(a.w); h.mclass = 0u; h.t = 0.0f;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) Q.pf[i] = 0.0f;
+                Q.p_pdf = 0.0f; Q.prev_pos = mk3(0.0f, 0.0f, 0.0f);
+            };
+            // the deferral queue's record (the instrumented kernels): the whole path, the hit and the pixel, record-major, 8 float4 = 128 B
+            auto dq_store = [&](uint32_t e, const Path& Q, const Hit& h, uint32_t pix) {
+                float4* r = q_base + (size_t)e * DEFER_F4;
+                // (flags in bits 0-2, the depth in bits 3-12: max_depth <= 1000, api.cpp check_args; the pixel from bit 16)
+                const uint32_t fl = (Q.wl.term ? 1u : 0u) | (Q.from_camera ? 2u : 0u) | (Q.prev_spec ? 4u : 0u) | ((Q.depth & 1023u) << 3) | (pix << 16);
+                r[0] = make_float4(__uint_as_float(Q.smp.morton), __uint_as_float(Q.smp.dimension), __uint_as_float(Q.smp.rkey_lo), __uint_as_float(Q.smp.rkey_hi));
+                r[1] = make_float4(Q.wl.lam0, __uint_as_float(fl), Q.T[0], Q.T[1]);
+                r[2] = make_float4(Q.T[2], Q.T[3], Q.L[0], Q.L[1]);
+                r[3] = make_float4(Q.L[2], Q.L[3], Q.rd.x, Q.rd.y);
+                r[4] = make_float4(Q.rd.z, Q.pf[0], Q.pf[1], Q.pf[2]);
+                r[5] = make_float4(Q.pf[3], Q.p_pdf, Q.prev_pos.x, Q.prev_pos.y);
+                r[6] = make_float4(Q.prev_pos.z, h.t, h.b0, h.b1);
+                r[7] = make_float4(h.b2, __uint_as_float(h.tri), __uint_as_float(h.mclass), 0.0f);
+            };
+            auto dq_load = [&](uint32_t e, Path& Q, Hit& h, uint32_t& pix) {
+                const float4* r = q_base + (size_t)e * DEFER_F4;
+                const float4 a = r[0], b = r[1], c = r[2], d = r[3], e4 = r[4], f = r[5], g = r[6], h4 = r[7];
+                const uint32_t fl = __float_as_uint(b.y);
+                Q.smp.morton = __float_as_uint(a.x); Q.smp.dimension = __float_as_uint(a.y); Q.smp.rkey_lo = __float_as_uint(a.z); Q.smp.rkey_hi = __float_as_uint(a.w);
+                Q.wl.lam0 = b.x; Q.wl.term = (fl & 1u) != 0u; Q.from_camera = (fl & 2u) != 0u; Q.prev_spec = (fl & 4u) != 0u; Q.depth = (fl >> 3) & 1023u; pix = fl >> 16;
+                Q.T[0] = b.z; Q.T[1] = b.w; Q.T[2] = c.x; Q.T[3] = c.y; Q.L[0] = c.z; Q.L[1] = c.w; Q.L[2] = d.x; Q.L[3] = d.y;
+                Q.rd = mk3(d.z, d.w, e4.x); Q.ro = mk3(0.0f, 0.0f, 0.0f);
+                Q.pf[0] = e4.y; Q.pf[1] = e4.z; Q.pf[2] = e4.w; Q.pf[3] = f.x; Q.p_pdf = f.y; Q.prev_pos = mk3(f.z, f.w, g.x);
+                h.t = g.y; h.b0 = g.z; h.b1 = g.w; h.b2 = h4.x; h.tri = __float_as_uint(h4.y); h.mclass = __float_as_uint(h4.z);
+            };
+            auto finish_path = [&]() {            // Sensor::add_sample of a finished path into the work item's LDS film tile (+ the per-sample log)
+                if (pout.L != nullptr) {
+                    const uint32_t px = job0.px + (my_pix & blk_mask), py = job0.py + (my_pix >> blk_log2);
+                    const uint32_t tile_k = (work / prm.chunks) >> (6u - 2u * blk_log2);
+                    const uint32_t smp_i = P.smp.morton & ((1u << prm.log2_spp) - 1u);
+                    sample_log(P, pout, ((size_t)tile_k * 64u + ((py & 7u) * 8u + (px & 7u))) * pout.n_s + (smp_i - pout.s_base));
+                }
+                float r, g, b;
+                film_rgb(P, sc, prm, r, g, b);
+                atomicAdd(&s_film[3 * my_pix], r); atomicAdd(&s_film[3 * my_pix + 1], g); atomicAdd(&s_film[3 * my_pix + 2], b);
+            };
+            if constexpr (TAILQ) {
+                // front of the vertex for every lane that traced: does the path go on?
+                bool end_path = dying;                         // (a dying path's last connection has just been resolved)
+                const bool front = active && !dying && !susp;
+                unpark(P);
+                {
+                    ShadeCtx C0;
+                    C0.cont = false;
+                    if (front) end_path = shade_vertex_head<STATS, FEAT, 1>(P, sc, prm, sctx, got, hit, sh, st, tsa, C0);
+                }
+                dying = false;
+                // the paths that go on wait in the queue of their sort class; their lanes are free
+                const bool go_on = front && !end_path;
+                const bool cls2 = TQ_CLASSES != 0u && ((TQ_CLASSES >> (hit.mclass & 31u)) & 1u) != 0u;
+                const unsigned long long m_on1 = __ballot(go_on && !cls2), m_on2 = TQ_CLASSES != 0u ? __ballot(go_on && cls2) : 0ull;
+                if ((m_on1 | m_on2) != 0ull) {
+                    if (go_on) {
+                        const uint32_t e = cls2 ? QUEUE_RING + ((q2_tail + rank_below(m_on2)) & (QR - 1u)) : ((q_tail + rank_below(m_on1)) & (QR - 1u));
+                        tq_store(e, P, hit, my_pix);
+                        active = false;
+                    }
+                    q_tail += (uint32_t)__popcll(m_on1); q2_tail += (uint32_t)__popcll(m_on2);
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                }
+                if (active && end_path) { finish_path(); active = false; }
+                park(P, false);                                 // (nothing of these lanes' records is needed any more: the queue has them)
+                if (STATS) ts3 = ts4 = __builtin_amdgcn_s_memtime();
+                // the back of the vertex and its tail for a full wave of queued paths — of ONE class while new paths still arrive (the class
+                // with its own queue first); when the work item has nothing new left, whatever waits in either queue shares the passes
+                const bool draining = pool_next >= pool_size;
+                const uint32_t c2 = q2_tail - q2_head, c1 = q_tail - q_head;
+                const bool full2 = TQ_CLASSES != 0u && c2 >= (uint32_t)PT_TAILQ_MIN, full1 = c1 >= (uint32_t)PT_TAILQ_MIN;
+                if (full2 || full1 || (draining && (c1 | c2) != 0u)) {
+                    const unsigned long long m_free = __ballot(!active);
+                    const uint32_t n_free = (uint32_t)__popcll(m_free), r = rank_below(m_free);
+                    // lanes 0 .. n2-1 of the free lanes take from queue 2, the next n1 from queue 1
+                    const uint32_t n2 = (full2 || (draining && !full1)) ? min(n_free, c2) : 0u;
+                    const uint32_t n1 = (!full2 || draining) ? min(n_free - n2, c1) : 0u;
+                    const bool take2 = !active && r < n2, take1 = !active && !take2 && r - n2 < n1;
+                    const bool take = take1 || take2;
+                    const uint32_t e = take2 ? QUEUE_RING + ((q2_head + r) & (QR - 1u)) : ((q_head + (r - n2)) & (QR - 1u));
+                    q2_head += n2; q_head += n1;
+                    bool ep = false;
+                    if constexpr ((FEAT & FEAT_CC) != 0u) {
+                        ShadeCtx C;
+                        shade_ctx_idle_cc(C);
+                        if (take) {
+                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                            tq_load(e, P, hit, my_pix);
+                            active = true;
+                            shade_vertex_head<STATS, FEAT, 2>(P, sc, prm, sctx, true, hit, sh, st, tsa, C);
+                        }
+                        // the coat's 64-sample directional albedo, estimated by the whole wave for the lanes that need it
+                        const bool want_mc = take && C.cont && C.need_cc;
+                        const float fc_mc = coat_directional_albedo_coop(want_mc, C.cc_alpha_c, C.cc_r0c, C.wo_nm, C.mc_key, lane);
+                        if (want_mc) C.cc_fc = fc_mc;
+                        if (take && C.cont) ep = shade_vertex_tail<STATS, FEAT>(P, sc, prm, sctx, sh, st, tsb, C);
+                    } else if (take) {
+                        // (ONE divergent region for the back of the head and the tail: ShadeCtx must not cross a re-convergence point in the
+                        // kernels that run 4 waves per SIMD — the split form of this block cost them 12 %)
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                        tq_load(e, P, hit, my_pix);
+                        active = true;
+                        ShadeCtx C;
+                        C.cont = false; C.need_cc = false; C.cc_fc = 0.0f;
+                        shade_vertex_head<STATS, FEAT, 2>(P, sc, prm, sctx, true, hit, sh, st, tsa, C);
+                        if (C.cont) ep = shade_vertex_tail<STATS, FEAT>(P, sc, prm, sctx, sh, st, tsb, C);
+                    }
+                    park(P, take);
+                    if (sh.on && sh.c[0] == 0.0f && sh.c[1] == 0.0f && sh.c[2] == 0.0f && sh.c[3] == 0.0f) sh.on = false;
+                    if (!active) sh.on = false;
+                    if (take) { dying = sh.on && ep; if (dying) ep = false; }
+                    if (take && ep) { finish_path(); active = false; }
+                }
+            } else
+            // The shading stage.  It runs a second time in the iterations that shade the deferral queue: the lanes the first pass freed
+            // (ended paths, deferred hits) take queued paths and shade them at once, so a queued path rejoins the NEXT traversal with its
+            // next ray like everybody else.
+            for (int pass = 0;; ++pass) {
+            const bool mine = pass == 0 || popped;     // the lanes this pass works on
+            bool end_path = pass == 0 && MERGED && dying;           // a dying path's last connection has just been resolved
+            if (pass == 0) {
+                if constexpr (!MERGED) sh = ShadowReq{};
+                unpark(P);
+            }
+            if constexpr (DEFER != 0u) {
+                // queued paths join here: path state, hit and pixel of the lanes that popped
+                if (popped) {
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                    dq_load(pop_e, P, hit, my_pix);
+                    got = true;
+                }
+                // and the lanes whose hit is on a deferred material leave
+                const bool defer_now = pass == 0 && !(STATS && prm.stats_mode == 1u) && active && !dying && !susp && !popped && got && ((DEFER >> (hit.mclass & 31u)) & 1u) != 0u;
+                const unsigned long long m_def = __ballot(defer_now);
+                if (m_def != 0ull) {
+                    if (defer_now) {
+                        dq_store((q_tail + rank_below(m_def)) & (DEFER_RING - 1u), P, hit, my_pix);
+                        active = false;                                      // free: a new path (or a queued one) next
+                    }
+                    q_tail += (uint32_t)__popcll(m_def);
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                }
+            }
+            const bool shade_now = mine && active && !(MERGED && (dying || susp));
+            if constexpr ((FEAT & FEAT_CC) != 0u) {
+                ShadeCtx C;
+                shade_ctx_idle_cc(C);
+                if (shade_now) end_path = shade_vertex_head<STATS, FEAT>(P, sc, prm, sctx, got, hit, sh, st, tsa, C);
+                // the coat's 64-sample directional albedo, estimated by the whole wave for the lanes that need it
+                const bool want_mc = shade_now && C.cont && C.need_cc;
+                const float fc_mc = coat_directional_albedo_coop(want_mc, C.cc_alpha_c, C.cc_r0c, C.wo_nm, C.mc_key, lane);
+                if (want_mc) C.cc_fc = fc_mc;
+                if (shade_now && C.cont) end_path = shade_vertex_tail<STATS, FEAT>(P, sc, prm, sctx, sh, st, tsb, C);
+            } else {
+                if (shade_now) end_path = shade_vertex<STATS, FEAT>(P, sc, prm, sctx, got, hit, sh, st, tsa, tsb);
+            }
+            park(P, mine);
+            if (STATS) {
+                ts3 = __builtin_amdgcn_s_memtime();
+                // the stamps inside shade_vertex are taken by the lanes that reach them: make them wave-level (first lane that has one)
+                unsigned long long ma = __ballot(tsa != 0ull), mb = __ballot(tsb != 0ull);
+                if (ma) { int l = (int)__ffsll((long long)ma) - 1; tsa = ((unsigned long long)__shfl((uint32_t)(tsa >> 32), l) << 32) | __shfl((uint32_t)tsa, l); }
+                if (mb) { int l = (int)__ffsll((long long)mb) - 1; tsb = ((unsigned long long)__shfl((uint32_t)(tsb >> 32), l) << 32) | __shfl((uint32_t)tsb, l); }
+            }
+            // a light connection whose contribution is exactly zero (light behind the surface, f == 0) cannot change L whatever the
+            // visibility test says: the production path does not trace it (the canonical-count mode does, like the reference)
+            if (!canonical && sh.on && sh.c[0] == 0.0f && sh.c[1] == 0.0f && sh.c[2] == 0.0f && sh.c[3] == 0.0f) sh.on = false;
+            if (!active) sh.on = false;
+            if (MERGED && !canonical) {
+                // merged form: the connection of a CONTINUING path waits for the next iteration's traversal; a path that ends here with a
+                // connection pending (a failed BSDF sample after the light was sampled: rare) lives on for that traversal alone
+                if (mine) {
+                    dying = sh.on && end_path;
+                    if (dying) end_path = false;
+                }
+            } else {
+                // two traversals per iteration — and everything in the canonical-count mode: the connection is traced now
+                const bool now = sh.on;
+                if (__any(now)) {
+                    if (STATS && now) st.w[6]++;
+                    bool occluded = false;
+                    if (canonical) { if (now) occluded = trace_any<STATS>(sc, sh.o, sh.d, sh.t, stack, st); }
+                    else { PT_PRIO_TRAV_ENTER; occluded = trace_any_deferred<STATS>(sc, sh.o, sh.d, sh.t, now, stack, lane, any_lds, st); PT_PRIO_TRAV_EXIT; }
+                    if (now && !occluded) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) P.L[i] = P.L[i] + sh.c[i];
+                    }
+                    if (now) sh.on = false;
+                }
+            }
+            if (STATS) ts4 = __builtin_amdgcn_s_memtime();
+            if (mine && active && end_path) {
+                if (pout.L != nullptr) {
+                    // per-sample log (see PathOut): the sample index is the low log2(spp) bits of the lane's Morton index (spp a power of two)
+                    const uint32_t px = job0.px + (my_pix & blk_mask), py = job0.py + (my_pix >> blk_log2);
+                    const uint32_t tile_k = (work / prm.chunks) >> (6u - 2u * blk_log2);
+                    const uint32_t smp_i = P.smp.morton & ((1u << prm.log2_spp) - 1u);
+                    sample_log(P, pout, ((size_t)tile_k * 64u + ((py & 7u) * 8u + (px & 7u))) * pout.n_s + (smp_i - pout.s_base));
+                }
+                float r, g, b;
+                film_rgb(P, sc, prm, r, g, b);
+                atomicAdd(&s_film[3 * my_pix], r); atomicAdd(&s_film[3 * my_pix + 1], g); atomicAdd(&s_film[3 * my_pix + 2], b);
+                active = false;
+            }
+            // a second pass for the deferral queue?
+            if constexpr (DEFER != 0u) {
+                if (pass != 0 || (STATS && prm.stats_mode == 1u)) break;
+                const uint32_t q_count = q_tail - q_head;
+                if (!(q_count >= (uint32_t)PT_DEFER_MIN || (pool_next >= pool_size && q_count != 0u))) break;
+                const unsigned long long m_free = __ballot(!active);
+                if (m_free == 0ull) break;
+                const uint32_t r = rank_below(m_free);
+                popped = !active && r < q_count;
+                if (popped) { active = true; dying = false; pop_e = (q_head + r) & (DEFER_RING - 1u); }
+                q_head += min((uint32_t)__popcll(m_free), q_count);
+            } else break;
+            }
+            if (STATS) {
+                unsigned long long ts5 = __builtin_amdgcn_s_memtime();
+                dvc[min(bsdf_classes, 3u)] += 1ull; dvc[4 + min(bsdf_classes, 3u)] += ts3 - ts2;
+                tp[0] += ts1 - ts0; tp[1] += ts2 - ts1; tp[2] += ts3 - ts2; tp[3] += ts4 - ts3; tp[4] += ts5 - ts4;
+                if (tsa) { tp[6] += tsa - ts2; if (tsb) { tp[7] += tsb - tsa; tp[8] += ts3 - tsb; } else tp[7] += ts3 - tsa; } else tp[6] += ts3 - ts2;
+            }
+        }
+        __syncthreads();
+        if (job.valid) {
+            size_t o = ((size_t)job.py * cam.width + job.px) * 3;
+            const float fr = s_film[3 * lane], fg = s_film[3 * lane + 1], fb = s_film[3 * lane + 2];
+            if (prm.chunks == 1) { accum[o] += fr; accum[o + 1] += fg; accum[o + 2] += fb; }
+            else {
+                // the sample range of this tile is split over several work items: each writes its own slot, combine_kernel adds the
+                // slots to the film in chunk order (no float atomics: frames stay bit-identical from run to run)
+                // (slots are laid out per 8x8 tile and chunk whatever the block size, see combine_kernel)
+                const uint32_t tile_k = (work / prm.chunks) >> (6u - 2u * blk_log2), chunk = work % prm.chunks;
+                float* slot = partial + (((size_t)tile_k * prm.chunks + chunk) * 64u + ((job.py & 7u) * 8u + (job.px & 7u))) * 3u;
+                slot[0] = fr; slot[1] = fg; slot[2] = fb;
+            }
+        }
+        __syncthreads();
+    }
+    if (STATS && lane == 0) {
+        tp[5] = __builtin_amdgcn_s_memtime() - t_loop0;
+        for (int i = 0; i < 10; ++i) atomicAdd(&stats->phase_cycles[i], tp[i]);
+        for (int i = 0; i < 8; ++i) atomicAdd(&stats->divergence[4 + i], dvc[i]);
+    }
+    if (STATS) flush_stats(stats, st);

@@ -113,6 +113,16 @@ class DenoiseParams(C.Structure):
                 ("albedo_eps", C.c_float)]
 
 
+class AdaptiveParams(C.Structure):
+    """mi355pt_adaptive_params (include/mi355pt_adaptive.h): threshold has no default, and a zeroed struct is refused"""
+    _fields_ = [("threshold", C.c_float), ("dark_eps", C.c_float), ("min_spp", C.c_uint32)]
+
+
+class AdaptiveResult(C.Structure):
+    """mi355pt_adaptive_result"""
+    _fields_ = [("passes", C.c_uint32), ("tiles_at_max", C.c_uint32), ("total_samples", C.c_uint64)]
+
+
 def make_camera(position, direction, up, width, height, fov_deg=45.0):
     return Camera((C.c_float * 3)(*position), (C.c_float * 3)(*direction), (C.c_float * 3)(*up), fov_deg, width, height)
 
@@ -133,12 +143,15 @@ DEBUG_SYMBOLS = ["debug_unlock", "scene_debug_set_lowering", "scene_export_bvh",
 ABI_SYMBOLS = [
     "scene_create", "scene_destroy", "scene_set_rgb2spec", "scene_add_lut470", "scene_add_tex_rgb8", "scene_add_mesh",
     "scene_add_material", "scene_add_instance", "scene_add_delta_light", "scene_add_environment_light", "scene_set_bvh_builder", "scene_build", "render", "render_accum_device", "film_resolve_device",
+    "render_accum_tiles_device",
     "render_aov", "render_aov_accum_device", "aov_resolve_device",
     "quantize_u8", "scene_info", "scene_build_multi", "render_multi", "coat_albedo_table",
     "last_error", "version",
 ]
 # ... include/mi355pt_denoise.h, the denoiser block mi355pt.h includes (tests/test_denoise.py checks these the same way)
 DENOISE_SYMBOLS = ["denoise_params_default", "denoise_scratch_bytes", "denoise_device", "denoise"]
+# ... and include/mi355pt_adaptive.h, the adaptive-sampling block mi355pt.h includes (tests/test_adaptive.py)
+ADAPTIVE_SYMBOLS = ["adaptive_scratch_bytes", "adaptive_step_device", "film_normalize_tiles_device", "render_adaptive_device", "render_adaptive"]
 
 
 class Backend:
@@ -356,6 +369,17 @@ class Product(Backend):
                                                    C.POINTER(DenoiseParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
             lib.mi355pt_denoise.argtypes = [C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float), C.c_uint32,
                                             C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), C.POINTER(C.c_float)]
+        if hasattr(lib, "mi355pt_render_adaptive_device"):     # (absent from an older build loaded through MI355PT_LIB)
+            lib.mi355pt_render_accum_tiles_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(C.c_uint32), C.c_uint32,
+                                                              C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+            lib.mi355pt_adaptive_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]; lib.mi355pt_adaptive_scratch_bytes.restype = C.c_size_t
+            lib.mi355pt_adaptive_step_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(AdaptiveParams),
+                                                         C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.mi355pt_film_normalize_tiles_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+            lib.mi355pt_render_adaptive_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AdaptiveParams)] + [C.c_void_p] * 6 + \
+                [C.c_size_t, C.c_void_p, C.POINTER(AdaptiveResult)]
+            lib.mi355pt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AdaptiveParams), C.POINTER(C.c_float),
+                                                    C.POINTER(C.c_uint32), C.POINTER(AdaptiveResult)]
         if not hasattr(lib, "mi355pt_render_sample_log"):      # an older build loaded through MI355PT_LIB for an A/B timing run
             return
         lib.mi355pt_sample_log_records.argtypes = [C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]
@@ -438,6 +462,48 @@ class Product(Backend):
         self.check(self.lib.mi355pt_render_accum_device(scene.h, C.byref(cam), C.byref(params), s_begin, s_end, C.c_void_p(d_accum_ptr),
                                                         C.c_void_p(stream or 0), C.byref(stats) if stats is not None else None),
                    "render_accum_device")
+
+    # ---- adaptive sampling (include/mi355pt_adaptive.h) and the tile-list render it is built on ----
+    def render_accum_tiles_device(self, scene, cam, params, tiles, s_begin, s_end, d_accum_ptr, stream=None, stats=None):
+        """mi355pt_render_accum_tiles_device: `tiles` is a host sequence of frame tile indices (strictly ascending)"""
+        t = np.ascontiguousarray(tiles, dtype=np.uint32).reshape(-1)
+        self.check(self.lib.mi355pt_render_accum_tiles_device(scene.h, C.byref(cam), C.byref(params), _ptr(t, C.c_uint32), t.size, s_begin, s_end,
+                                                              C.c_void_p(d_accum_ptr), C.c_void_p(stream or 0),
+                                                              C.byref(stats) if stats is not None else None), "render_accum_tiles_device")
+
+    def adaptive_scratch_bytes(self, width, height):
+        return int(self.lib.mi355pt_adaptive_scratch_bytes(width, height))
+
+    def adaptive_step_device(self, d_film_ptr, d_half_ptr, width, height, d_tile_spp_ptr, d_tile_err_ptr, params, level_spp, max_spp, d_scratch_ptr,
+                             scratch_bytes, d_list_ptr, d_count_ptr, stream=None):
+        """mi355pt_adaptive_step_device on device pointers; asynchronous on `stream`"""
+        self.check(self.lib.mi355pt_adaptive_step_device(C.c_void_p(d_film_ptr), C.c_void_p(d_half_ptr), width, height, C.c_void_p(d_tile_spp_ptr),
+                                                         C.c_void_p(d_tile_err_ptr), C.byref(params), level_spp, max_spp, C.c_void_p(d_scratch_ptr),
+                                                         scratch_bytes, C.c_void_p(d_list_ptr), C.c_void_p(d_count_ptr), C.c_void_p(stream or 0)),
+                   "adaptive_step_device")
+
+    def film_normalize_tiles_device(self, d_film_ptr, d_tile_spp_ptr, width, height, d_mean_ptr, stream=None):
+        self.check(self.lib.mi355pt_film_normalize_tiles_device(C.c_void_p(d_film_ptr), C.c_void_p(d_tile_spp_ptr), width, height, C.c_void_p(d_mean_ptr),
+                                                                C.c_void_p(stream or 0)), "film_normalize_tiles_device")
+
+    def render_adaptive_device(self, scene, cam, params, adaptive, d_film_ptr, d_half_ptr, d_tile_spp_ptr, d_tile_err_ptr, d_list_ptr, d_scratch_ptr,
+                               scratch_bytes, stream=None):
+        """mi355pt_render_adaptive_device -> AdaptiveResult (passes, tiles_at_max, total_samples)"""
+        res = AdaptiveResult()
+        self.check(self.lib.mi355pt_render_adaptive_device(scene.h, C.byref(cam), C.byref(params), C.byref(adaptive), C.c_void_p(d_film_ptr),
+                                                           C.c_void_p(d_half_ptr), C.c_void_p(d_tile_spp_ptr), C.c_void_p(d_tile_err_ptr),
+                                                           C.c_void_p(d_list_ptr), C.c_void_p(d_scratch_ptr), scratch_bytes, C.c_void_p(stream or 0),
+                                                           C.byref(res)), "render_adaptive_device")
+        return res
+
+    def render_adaptive(self, scene, cam, params, adaptive):
+        """mi355pt_render_adaptive -> ((H, W, 3) float32 tone-mapped sRGB, (tiles_y, tiles_x) uint32 samples per tile, AdaptiveResult)"""
+        out = np.zeros((cam.height, cam.width, 3), dtype=np.float32)
+        spp = np.zeros(((cam.height + 7) // 8, (cam.width + 7) // 8), dtype=np.uint32)
+        res = AdaptiveResult()
+        self.check(self.lib.mi355pt_render_adaptive(scene.h, C.byref(cam), C.byref(params), C.byref(adaptive), _ptr(out, C.c_float),
+                                                    _ptr(spp, C.c_uint32), C.byref(res)), "render_adaptive")
+        return out, spp, res
 
     def render_sample_log(self, scene, cam, params, s_begin, s_end, want_accum=False):
         """mi355pt_render_sample_log: every finished path of the production launch(es) for [s_begin, s_end) of the shard in `params`.

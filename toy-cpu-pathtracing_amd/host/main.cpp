@@ -1,11 +1,12 @@
 // mi355pt — command line mirroring renderer/src/main.rs:20-140 (clap flags, defaults and flow), with
 // RendererImage::render running on the MI355X through libmi355pt.so instead of the rayon pixel loop.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
 
-#include <hip/hip_runtime_api.h>   // --denoise only: the films of that path stay on the device (hipMalloc / hipMemcpy / hipFree, no kernels here)
+#include <hip/hip_runtime_api.h>   // --denoise and --adaptive-threshold: the films of those paths stay on the device (hipMalloc / hipMemcpy / hipFree, no kernels here)
 
 #include "scenes.hpp"
 
@@ -18,6 +19,10 @@ struct Args {   // main.rs:20-53
     bool albedo_lut = false; int gpus = 1;
     // not in the reference's CLI either: the a-trous denoiser (mi355pt_denoise.h) behind a path renderer, and the spp of its two guide films
     bool denoise = false; uint32_t denoise_guide_spp = 64;
+    // nor is adaptive sampling (mi355pt_adaptive.h): --spp becomes the maximum.  The threshold has no default (0 = not adaptive).
+    // dark_eps 1e-3 is a CHOICE, not a measurement: a thousandth of the radiance of a mid-grey pixel, so that black pixels neither divide
+    // by zero nor dominate a tile's estimate
+    float adaptive_threshold = 0.0f, adaptive_dark_eps = 1e-3f; uint32_t adaptive_min_spp = 16; std::string spp_map;
 };
 
 // --denoise: the beauty film at --spp, the albedo and shading-normal films at --denoise-guide-spp (converged guides cost a few percent of
@@ -51,12 +56,60 @@ static double render_denoised(const Scene& scene, const Camera& camera, mi355pt_
     return st.kernel_ms * 1e-3;
 }
 
+// --adaptive-threshold: mi355pt_render_adaptive_device with --spp as the maximum, the per-tile means (a film with spp 1), optionally the
+// denoiser on them, then Sensor::to_rgb.  --spp-map writes the samples per tile as a grey picture, log2(tile_spp / min) / log2(max / min).
+static void render_adaptive(const Scene& scene, const Camera& camera, mi355pt_params p, const Args& a, std::vector<float>& pixels) {
+    const mi355pt_camera& cam = camera.raw();
+    const uint32_t n_pixels = cam.width * cam.height, tiles_x = (cam.width + 7) / 8, n_tiles = tiles_x * ((cam.height + 7) / 8);
+    const size_t film_bytes = (size_t)n_pixels * 3 * sizeof(float), tile_bytes = (size_t)n_tiles * 4, scratch_bytes = mi355pt_adaptive_scratch_bytes(cam.width, cam.height);
+    DeviceFilm film(film_bytes), half(film_bytes), rgb(film_bytes), tile_spp(tile_bytes), tile_err(tile_bytes), list(tile_bytes), scratch(scratch_bytes);
+    const mi355pt_adaptive_params ap{a.adaptive_threshold, a.adaptive_dark_eps, a.adaptive_min_spp};
+    mi355pt_adaptive_result res{};
+    check(mi355pt_render_adaptive_device(scene.raw(), &cam, &p, &ap, film.p, half.p, (uint32_t*)tile_spp.p, tile_err.p, (uint32_t*)list.p, scratch.p, scratch_bytes,
+                                         nullptr, &res), "mi355pt_render_adaptive_device");
+    check(mi355pt_film_normalize_tiles_device(film.p, (const uint32_t*)tile_spp.p, cam.width, cam.height, half.p, nullptr), "mi355pt_film_normalize_tiles_device");
+    if (a.denoise) {
+        const uint32_t guide_spp = a.denoise_guide_spp;
+        const size_t dn_bytes = mi355pt_denoise_scratch_bytes(cam.width, cam.height);
+        DeviceFilm albedo(film_bytes), normal(film_bytes), dn_scratch(dn_bytes);
+        mi355pt_params g = p;
+        g.spp = guide_spp;
+        check(mi355pt_render_aov_accum_device(scene.raw(), &cam, &g, MI355PT_AOV_ALBEDO, scene.d65_lut(), 0, guide_spp, albedo.p, nullptr, nullptr), "mi355pt_render_aov_accum_device");
+        check(mi355pt_render_aov_accum_device(scene.raw(), &cam, &g, MI355PT_AOV_SHADING_NORMAL, scene.d65_lut(), 0, guide_spp, normal.p, nullptr, nullptr), "mi355pt_render_aov_accum_device");
+        mi355pt_denoise_params dp;
+        mi355pt_denoise_params_default(&dp);
+        check(mi355pt_denoise_device(half.p, 1, albedo.p, guide_spp, normal.p, guide_spp, cam.width, cam.height, &dp, dn_scratch.p, dn_bytes, film.p, nullptr), "mi355pt_denoise_device");
+        check(mi355pt_film_resolve_device(film.p, n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
+    } else {
+        check(mi355pt_film_resolve_device(half.p, n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
+    }
+    if (hipMemcpy(pixels.data(), rgb.p, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the frame back failed");
+    std::printf("(adaptive: %u passes, mean %.1f spp of at most %u, %u of %u tiles at the maximum)\n", res.passes, (double)res.total_samples / n_pixels, p.spp,
+                res.tiles_at_max, n_tiles);
+    if (!a.spp_map.empty()) {
+        std::vector<uint32_t> spp(n_tiles);
+        if (hipMemcpy(spp.data(), tile_spp.p, tile_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the tile counts back failed");
+        const double span = std::log2((double)p.spp / ap.min_spp);
+        std::vector<uint8_t> grey((size_t)n_pixels * 3);
+        for (uint32_t y = 0; y < cam.height; ++y)
+            for (uint32_t x = 0; x < cam.width; ++x) {
+                const double g = span > 0.0 ? std::log2((double)spp[(y / 8) * tiles_x + x / 8] / ap.min_spp) / span : 0.0;
+                const uint8_t v = (uint8_t)(g * 255.0);
+                uint8_t* o = &grey[((size_t)y * cam.width + x) * 3];
+                o[0] = o[1] = o[2] = v;
+            }
+        write_png_rgb8(a.spp_map, grey.data(), cam.width, cam.height);
+    }
+}
+
 static void usage() {
     std::puts("Usage: mi355pt [--scene N] [-s|--spp N] [--seed N] [--filter box] [--sampler random|sobol]\n"
               "               [--renderer normal|albedo|pt|nee|mis] [--width N] [--height N] [-d|--max-depth N] [-o|--output FILE]\n"
               "       extensions: [--albedo-lut] (clearcoat albedo from its table instead of the 64-sample estimate)  [--gpus N]\n"
               "                   [--renderer shading-normal] (render-space shading normal of every surface: the AOV a denoiser takes)\n"
-              "                   [--denoise] (pt|nee|mis: a-trous filter guided by the albedo and shading-normal films)  [--denoise-guide-spp N] (64)");
+              "                   [--denoise] (pt|nee|mis: a-trous filter guided by the albedo and shading-normal films)  [--denoise-guide-spp N] (64)\n"
+              "                   [--adaptive-threshold X] (pt|nee|mis: samples where the per-tile noise estimate is above X; --spp is the maximum)\n"
+              "                   [--adaptive-min-spp N] (16)  [--adaptive-dark-eps E] (1e-3)  [--spp-map FILE] (samples per tile as a grey picture)");
 }
 
 int main(int argc, char** argv) {
@@ -78,6 +131,10 @@ int main(int argc, char** argv) {
         else if (k == "--gpus") a.gpus = std::stoi(val());
         else if (k == "--denoise") a.denoise = true;
         else if (k == "--denoise-guide-spp") a.denoise_guide_spp = (uint32_t)std::stoul(val());
+        else if (k == "--adaptive-threshold") a.adaptive_threshold = std::stof(val());
+        else if (k == "--adaptive-min-spp") a.adaptive_min_spp = (uint32_t)std::stoul(val());
+        else if (k == "--adaptive-dark-eps") a.adaptive_dark_eps = std::stof(val());
+        else if (k == "--spp-map") a.spp_map = val();
         else if (k == "-h" || k == "--help") { usage(); return 0; }
         else { std::fprintf(stderr, "error: unexpected argument '%s'\n", k.c_str()); usage(); return 2; }
     }
@@ -92,6 +149,15 @@ int main(int argc, char** argv) {
     if (a.denoise && aov) { std::fprintf(stderr, "error: --denoise with --renderer %s: the denoiser filters the frame of a path renderer (pt, nee, mis)\n", a.renderer.c_str()); return 2; }
     if (a.denoise && a.gpus > 1) { std::fprintf(stderr, "error: --denoise with --gpus %d: the denoiser runs on one GPU\n", a.gpus); return 2; }
     if (a.denoise && (a.denoise_guide_spp == 0 || a.spp == 0)) { std::fprintf(stderr, "error: --denoise needs --spp and --denoise-guide-spp above 0\n"); return 2; }
+    const bool adaptive = a.adaptive_threshold != 0.0f;
+    if (!adaptive && !a.spp_map.empty()) { std::fprintf(stderr, "error: --spp-map needs --adaptive-threshold\n"); return 2; }
+    if (adaptive && aov) { std::fprintf(stderr, "error: --adaptive-threshold with --renderer %s: adaptive sampling is for the path renderers (pt, nee, mis)\n", a.renderer.c_str()); return 2; }
+    if (adaptive && a.gpus > 1) { std::fprintf(stderr, "error: --adaptive-threshold with --gpus %d: adaptive sampling runs on one GPU\n", a.gpus); return 2; }
+    if (adaptive && (!(a.adaptive_threshold > 0.0f) || !(a.adaptive_dark_eps > 0.0f) || a.adaptive_min_spp < 2 || (a.adaptive_min_spp & (a.adaptive_min_spp - 1)) != 0 ||
+                     (a.spp & (a.spp - 1)) != 0 || a.spp < a.adaptive_min_spp)) {
+        std::fprintf(stderr, "error: --adaptive-threshold and --adaptive-dark-eps must be above 0, --adaptive-min-spp a power of two from 2, --spp (the maximum) a power of two from --adaptive-min-spp\n");
+        return 2;
+    }
     try {
         Camera camera(45.0f, a.width, a.height);                                        // main.rs:59-68
         Scene scene;
@@ -135,7 +201,9 @@ int main(int argc, char** argv) {
         std::puts("Start rendering...");                                                // main.rs:166-172
         t0 = std::chrono::steady_clock::now();
         const SamplerKind sampler = a.sampler == "sobol" ? SamplerKind::ZSobol : SamplerKind::Random;
-        double kernel_s = a.denoise ? render_denoised(scene, camera, image.params(sampler, a.albedo_lut), a.denoise_guide_spp, image.pixels_mut())
+        double kernel_s = 0.0;
+        if (adaptive) render_adaptive(scene, camera, image.params(sampler, a.albedo_lut), a, image.pixels_mut());
+        else kernel_s = a.denoise ? render_denoised(scene, camera, image.params(sampler, a.albedo_lut), a.denoise_guide_spp, image.pixels_mut())
                                     : image.render(sampler, a.albedo_lut);
         double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         std::printf("Finish rendering: %.3f seconds.\n", wall);
