@@ -24,6 +24,9 @@ TX, TY = 6, 3
 NT = TX * TY
 CASES = [(3, "mis", "sobol"), (17, "nee", "sobol"), (8, "pt", "sobol"), (3, "mis", "random")]   # deferral class, clearcoat units, MODE_PT, generic mode
 CASE_IDS = [f"scene{s}-{st}-{sa}" for s, st, sa in CASES]
+# with CASES, every (mode, feature-set class) pair once: the units CASES leaves out (MIS clearcoat, plain NEE, generic and pt clearcoat)
+ALL_UNITS = CASES + [(17, "mis", "sobol"), (3, "nee", "sobol"), (17, "pt", "sobol"), (17, "mis", "random")]
+ALL_UNIT_IDS = [f"scene{s}-{st}-{sa}" for s, st, sa in ALL_UNITS]
 SPARSE = [2, 5, 11, 17]                     # 5 and 11 in the narrow right-hand column, 17 the bottom-right corner
 DARK_EPS = 1e-3
 FACTOR, FLOOR = 8.0, 2.0 ** -22
@@ -162,8 +165,10 @@ def adaptive_params(pkg, threshold, min_spp=MIN_SPP):
 
 
 # ---------------------------------------------------------------- 1, 2: tile lists
-@pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
+@pytest.mark.parametrize("case", ALL_UNITS, ids=ALL_UNIT_IDS)
 def test_list_of_all_tiles_is_bit_equal_to_the_plain_render(rigs, case):
+    """Every translation unit's kernels launched once through the plain lookup and once through the tile-list lookup (pt_kernels.hip
+    find_pt_kernel): an empty or crossed slot of that table shows here."""
     r = rigs(case)
     f = r.zeros()
     r.tiles(f, np.arange(NT), 0, 16)

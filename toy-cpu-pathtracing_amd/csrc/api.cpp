@@ -119,11 +119,16 @@ mi355pt_scene::~mi355pt_scene() {
     delete ctx;
 }
 
-// one launch of render_accum_range (arguments checked): plan -> context / buffers -> memsets -> launch -> stats
+// one launch of a sample range (arguments checked): plan -> context / buffers -> memsets -> launch -> stats.  d_list != nullptr: the tile-list
+// kernels over d_list[0 .. n_list) (device memory, n_list > 0; no AOV kind, no instrumentation, no sample log).
+// Their shape is planned with the resident waves of the PLAIN kernel of the same mode: chunks and block size — the frame's bits — then equal
+// plan_launch's for a list of all tiles, whatever occupancy the tile-list instantiation has (a grid that does not fit waits its turn: the
+// work items are independent).
 static int launch_range(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, uint32_t s_begin, uint32_t s_end, float* d_accum,
-                        hipStream_t stream, mi355pt_stats* stats, const PathOut& pout, int aov_kind, uint32_t illuminant_lut) {
+                        hipStream_t stream, mi355pt_stats* stats, const PathOut& pout, int aov_kind, uint32_t illuminant_lut, const uint32_t* d_list,
+                        uint32_t n_list) {
     const bool aov = aov_kind >= 0;
-    if (shard_tile_count(cam->width, cam->height, p->shard_index, p->shard_count) == 0) return MI355PT_OK;
+    if (!d_list && shard_tile_count(cam->width, cam->height, p->shard_index, p->shard_count) == 0) return MI355PT_OK;
     int rc;
     LaunchCtx* lc; int slot;
     if ((rc = get_launch_ctx(s, p->seed, &lc, &slot))) return rc;
@@ -132,10 +137,11 @@ static int launch_range(const mi355pt_scene* s, const mi355pt_camera* cam, const
     // the persistent grid of the exact kernel of this scene's feature set on this scene's device: asked once, then cached
     int& waves = aov ? lc->aov_waves[aov_kind] : lc->waves[want_stats ? 1 : 0][p->sampler & 1u][p->strategy < 3u ? p->strategy : 0u];
     if (!waves) waves = aov ? query_resident_waves_aov((uint32_t)aov_kind, s->impl.features)
-                            : query_resident_waves(want_stats, s->impl.features, p->sampler, p->strategy);
+                            : query_resident_waves(select_kernel(false, want_stats, s->impl.features, p->sampler, p->strategy));
     const DevCamera dc = make_camera(cam);
-    LaunchPlan plan = plan_launch(cam, p, s_begin, s_end, waves, aov);
+    LaunchPlan plan = d_list ? plan_launch_tiles(cam, p, s_begin, s_end, waves, n_list) : plan_launch(cam, p, s_begin, s_end, waves, aov);
     DevParams& dp = plan.params;
+    if (d_list) set_tile_list(dp, d_list);
     unsigned* d_counter = lc->d_counters + slot;
     DevStats* d_stats = lc->d_stats + slot;
     HIP_TRY(hipMemsetAsync(d_counter, 0, sizeof(unsigned), stream));
@@ -148,8 +154,8 @@ static int launch_range(const mi355pt_scene* s, const mi355pt_camera* cam, const
     if ((rc = grow_device_buffer(&lc->d_defer, &lc->defer_bytes, aov ? (size_t)0 : query_defer_bytes_per_wave() * (size_t)plan.grid, stream))) return rc;
     if (aov) HIP_TRY(launch_aov((uint32_t)aov_kind, s->impl.dev, dc, dp, illuminant_lut, lc->d_hash, d_accum, d_counter, stats ? d_stats : nullptr,
                                 s->impl.features, plan.grid, stream));
-    else HIP_TRY(launch_pt(s->impl.dev, dc, dp, plan.n_tiles, lc->d_hash, d_accum, lc->d_partial, d_counter, d_stats, want_stats, s->impl.features,
-                           plan.grid, stream, pout, lc->d_defer));
+    else HIP_TRY(launch_pt(select_kernel(d_list != nullptr, want_stats, s->impl.features, p->sampler, p->strategy), s->impl.dev, dc, dp, plan.n_tiles,
+                           lc->d_hash, d_accum, lc->d_partial, d_counter, d_list ? nullptr : d_stats, plan.grid, stream, pout, lc->d_defer));
     if (stats) {
         HIP_TRY(hipEventRecord(e1, stream));
         HIP_TRY(hipEventSynchronize(e1));
@@ -167,6 +173,15 @@ static int launch_range(const mi355pt_scene* s, const mi355pt_camera* cam, const
     return MI355PT_OK;   // stats == NULL: fully asynchronous on `stream`
 }
 
+// the launches of [s_begin, s_end) into d_accum, arguments checked; with d_list, of the tiles d_list[0 .. n_list) (device memory)
+static int launch_ranges(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, uint32_t s_begin, uint32_t s_end, float* d_accum,
+                         hipStream_t stream, mi355pt_stats* stats, const uint32_t* d_list, uint32_t n_list,
+                         const PathOut& pout = PathOut{nullptr, nullptr, nullptr, 0u, 0u}, int aov_kind = -1, uint32_t illuminant_lut = 0) {
+    return for_each_launch_range(p->sampler, stats != nullptr, s_begin, s_end, [&](uint32_t b, uint32_t e) {
+        return launch_range(s, cam, p, b, e, d_accum, stream, stats, pout, aov_kind, illuminant_lut, d_list, n_list);
+    });
+}
+
 int pt::render_accum_range(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, uint32_t s_begin, uint32_t s_end,
                            float* d_accum, void* hip_stream, mi355pt_stats* stats, const PathOut& pout, int aov_kind, uint32_t illuminant_lut) {
     const bool aov = aov_kind >= 0;
@@ -179,45 +194,7 @@ int pt::render_accum_range(const mi355pt_scene* s, const mi355pt_camera* cam, co
         if (aov_kind == MI355PT_AOV_ALBEDO && illuminant_lut >= s->impl.luts.size())
             return fail(MI355PT_E_INVALID, "illuminant_lut is not a LUT470 id of this scene (presets::cie_illum_d6500())");
     }
-    return for_each_launch_range(p->sampler, stats != nullptr, s_begin, s_end, [&](uint32_t b, uint32_t e) {
-        return launch_range(s, cam, p, b, e, d_accum, (hipStream_t)hip_stream, stats, pout, aov_kind, illuminant_lut);
-    });
-}
-
-// one launch of the tile-list kernels over d_list[0 .. n_list) (device memory, n_list > 0; arguments checked): launch_range for a list.
-// The shape is planned with the resident waves of the PLAIN kernel of the same mode: chunks and block size — the frame's bits — then equal
-// plan_launch's for a list of all tiles, whatever occupancy the tile-list instantiation has (a grid that does not fit waits its turn: the
-// work items are independent).
-static int launch_range_tiles(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, const uint32_t* d_list, uint32_t n_list,
-                              uint32_t s_begin, uint32_t s_end, float* d_accum, hipStream_t stream, mi355pt_stats* stats) {
-    int rc;
-    LaunchCtx* lc; int slot;
-    if ((rc = get_launch_ctx(s, p->seed, &lc, &slot))) return rc;
-    if (lc->device != s->impl.device) return fail(MI355PT_E_DEVICE, "launch context and scene live on different devices");
-    int& waves = lc->waves[0][p->sampler & 1u][p->strategy < 3u ? p->strategy : 0u];
-    if (!waves) waves = query_resident_waves(false, s->impl.features, p->sampler, p->strategy);
-    const DevCamera dc = make_camera(cam);
-    LaunchPlan plan = plan_launch_tiles(cam, p, s_begin, s_end, waves, n_list);
-    DevParams& dp = plan.params;
-    set_tile_list(dp, d_list);
-    dp.stats_mode = 0u;
-    unsigned* d_counter = lc->d_counters + slot;
-    HIP_TRY(hipMemsetAsync(d_counter, 0, sizeof(unsigned), stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (stats) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, stream)); }
-    if ((rc = grow_device_buffer(&lc->d_partial, &lc->partial_bytes, plan.partial_floats * sizeof(float), stream))) return rc;
-    if ((rc = grow_device_buffer(&lc->d_defer, &lc->defer_bytes, query_defer_bytes_per_wave() * (size_t)plan.grid, stream))) return rc;
-    HIP_TRY(launch_pt_tiles(s->impl.dev, dc, dp, n_list, lc->d_hash, d_accum, lc->d_partial, d_counter, s->impl.features, plan.grid, stream, lc->d_defer));
-    if (stats) {
-        HIP_TRY(hipEventRecord(e1, stream));
-        HIP_TRY(hipEventSynchronize(e1));
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        std::memset(stats, 0, sizeof(*stats));
-        stats->kernel_ms = ms; stats->launches = 1;
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    }
-    return MI355PT_OK;
+    return launch_ranges(s, cam, p, s_begin, s_end, d_accum, (hipStream_t)hip_stream, stats, nullptr, 0u, pout, aov_kind, illuminant_lut);
 }
 
 // what the tile-list entry and the adaptive driver ask of (scene, camera, params) beyond check_args
@@ -228,14 +205,6 @@ static int check_tiles_args(const mi355pt_scene* s, const mi355pt_camera* cam, c
     if (p->collect_stats) return fail(MI355PT_E_INVALID, "there is no instrumented tile-list kernel: collect_stats must be 0");
     if (adaptive_tile_count(cam->width, cam->height) == 0u) return fail(MI355PT_E_INVALID, "the frame has 2^31 tiles or more");
     return MI355PT_OK;
-}
-
-// [s_begin, s_end) of the tiles d_list[0 .. n_list) (device memory) into d_accum; arguments checked
-static int render_accum_tiles(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, const uint32_t* d_list, uint32_t n_list,
-                              uint32_t s_begin, uint32_t s_end, float* d_accum, hipStream_t stream, mi355pt_stats* stats) {
-    return for_each_launch_range(p->sampler, stats != nullptr, s_begin, s_end, [&](uint32_t b, uint32_t e) {
-        return launch_range_tiles(s, cam, p, d_list, n_list, b, e, d_accum, stream, stats);
-    });
 }
 
 extern "C" {
@@ -456,7 +425,7 @@ int mi355pt_render_accum_tiles_device(const mi355pt_scene* s, const mi355pt_came
     // (ordered on the stream after an earlier launch that may still read the buffer; the caller's array is free again when this returns)
     HIP_TRY(hipMemcpyAsync(lc->d_tiles, tiles, (size_t)n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    return render_accum_tiles(s, cam, p, lc->d_tiles, n_tiles, s_begin, s_end, d_accum, stream, stats);
+    return launch_ranges(s, cam, p, s_begin, s_end, d_accum, stream, stats, lc->d_tiles, n_tiles);
 }
 
 
@@ -758,7 +727,7 @@ int mi355pt_render_adaptive_device(const mi355pt_scene* s, const mi355pt_camera*
         HIP_TRY(hipStreamSynchronize(stream));
         if (count == 0u) break;                              // (at level == max_spp always: the step activates nothing there)
         if (count > n_tiles) return fail(MI355PT_E_DEVICE, "adaptive: the step returned more tiles than the frame has");
-        if ((rc = render_accum_tiles(s, cam, p, d_list, count, level, 2u * level, d_film, stream, nullptr))) return rc;
+        if ((rc = launch_ranges(s, cam, p, level, 2u * level, d_film, stream, nullptr, d_list, count))) return rc;
     }
     if (result) {
         std::vector<uint32_t> spp(n_tiles);

@@ -6,6 +6,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "launch_plan.hpp"
 #include "layout.hpp"
 
 namespace pt {
@@ -15,9 +16,14 @@ namespace pt {
 // path end in the PRODUCTION kernel: the per-sample parity tests read what the benchmarked binary computed, in its own launch shape.
 struct PathOut { float* L; float* lam; float* pdf; uint32_t s_base, n_s; };
 
-// pt_kernels.hip: the path-tracing kernels (n_tiles: 8x8 tiles of the launch's shard, launch_plan.hpp), film resolve, multi-device gather, probes
-hipError_t launch_pt(const DevScene&, const DevCamera&, const DevParams&, uint32_t n_tiles, const uint64_t* d_hash, float* d_accum, float* d_partial,
-                     unsigned* d_counter, DevStats* d_stats, bool stats, uint32_t feat, int grid, hipStream_t, const PathOut&, float* d_defer);
+// pt_kernels.hip: the path-tracing kernels, film resolve, multi-device gather, probes.
+// launch_pt: the kernel `key` names (launch_plan.hpp select_kernel), wherever it is compiled, and the matching combine kernel when the sample
+// range is split; hipErrorInvalidDeviceFunction when no such kernel is built.  n_tiles: the 8x8 tiles of the launch's shard (plan_launch) or,
+// with key.tiles, the entries of the device list that prm carries (layout.hpp set_tile_list, plan_launch_tiles): the production kernels over
+// an explicit tile list, which have no instrumented variant and write no sample log.
+hipError_t launch_pt(const KernelKey& key, const DevScene&, const DevCamera&, const DevParams&, uint32_t n_tiles, const uint64_t* d_hash, float* d_accum,
+                     float* d_partial, unsigned* d_counter, DevStats* d_stats, int grid, hipStream_t, const PathOut&, float* d_defer);
+int query_resident_waves(const KernelKey& key);      // of the very kernel launch_pt takes for `key`
 size_t query_defer_bytes_per_wave();
 hipError_t launch_resolve(const float* d_accum, uint32_t n_values, uint32_t spp, float* d_out, hipStream_t);
 hipError_t launch_film_pack(const float* film, uint32_t w, uint32_t h, uint32_t shard_index, uint32_t shard_count, uint32_t n_tiles, float* packed, hipStream_t);
@@ -28,7 +34,6 @@ hipError_t launch_probe_intersect(const DevScene&, const float* o, const float* 
 hipError_t launch_probe_occluded(const DevScene&, const float* o, const float* d, const float* tmax, uint32_t n, uint8_t* out, hipStream_t);
 hipError_t launch_probe_sincos(uint32_t first, uint32_t stride, uint32_t n, float* out_s, float* out_c, hipStream_t);
 uint64_t host_murmur_dim_seed(uint32_t dimension, uint32_t seed);
-int query_resident_waves(bool stats, uint32_t feat, uint32_t sampler, uint32_t strategy);
 // pt_kernels_aov.hip: the AOV renderers' primary-ray kernel (kind = MI355PT_AOV_*)
 hipError_t launch_aov(uint32_t kind, const DevScene&, const DevCamera&, const DevParams&, uint32_t illuminant_lut, const uint64_t* d_hash, float* d_accum,
                       unsigned* d_counter, DevStats* d_stats, uint32_t feat, int grid, hipStream_t);
@@ -40,10 +45,6 @@ uint32_t denoise_grid_blocks(uint32_t width, uint32_t height);
 hipError_t launch_denoise(const float* d_beauty, uint32_t spp_b, const float* d_albedo, uint32_t spp_a, const float* d_normal, uint32_t spp_n,
                           uint32_t width, uint32_t height, uint32_t levels, float sigma_color, float sigma_normal, float sigma_albedo,
                           float albedo_eps, void* d_scratch, float* d_out, hipStream_t);
-// pt_kernels_tiles.hip (+ _mis, _mis_cc, _nee, _nee_cc, _pt): the production path kernels over an explicit tile list — prm carries the device
-// list (layout.hpp set_tile_list) and the plan of launch_plan.hpp plan_launch_tiles over its n_list entries; no instrumented variant, no sample log
-hipError_t launch_pt_tiles(const DevScene&, const DevCamera&, const DevParams&, uint32_t n_list, const uint64_t* d_hash, float* d_accum, float* d_partial,
-                           unsigned* d_counter, uint32_t feat, int grid, hipStream_t, float* d_defer);
 // pt_kernels_adaptive.hip: adaptive sampling's noise step and the per-tile normalisation (include/mi355pt_adaptive.h)
 uint32_t adaptive_tile_count(uint32_t width, uint32_t height);      // 0: empty frame, or 2^31 tiles and more
 size_t adaptive_scratch_bytes(uint32_t width, uint32_t height);
@@ -54,7 +55,7 @@ hipError_t launch_normalize_tiles(const float* d_film, const uint32_t* d_tile_sp
 
 // Resident 64-thread blocks (= waves) of `kernel` on the current device: the persistent grid size of the EXACT instantiation a launch takes
 // (the register count, and so the occupancy, differs between instantiations and between translation units with their own backend flags).
-// Each translation unit answers for the kernels it holds.  per_cu <= 0 (no answer): 8 blocks per CU.
+// per_cu <= 0 (no answer): 8 blocks per CU.
 inline int resident_waves_per_device(int per_cu) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 2048;

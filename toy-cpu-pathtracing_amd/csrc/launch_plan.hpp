@@ -1,6 +1,7 @@
 // The shape of a launch as a pure function of (camera, params, sample range, resident waves): the tiles of the shard, the pixel block and
 // sample chunk of a work item, the Sobol prefix digits, the grid.  Host only — integer arithmetic on the C ABI's structs and layout.hpp's,
 // no HIP — so that tests/test_launch_plan.py checks what the kernels' lane_job and prefix-table code rely on without a GPU.
+// And WHICH path kernel the launch takes (select_kernel, at the end), as pure: the one statement of that choice, tests/test_kernel_select.py.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -178,6 +179,43 @@ inline LaunchPlan plan_launch(const mi355pt_camera* cam, const mi355pt_params* p
 // params (layout.hpp set_tile_list) in place of the shard pair.
 inline LaunchPlan plan_launch_tiles(const mi355pt_camera* cam, const mi355pt_params* p, uint32_t s_begin, uint32_t s_end, int waves, uint32_t n_list) {
     return plan_launch_over(cam, p, s_begin, s_end, waves, false, n_list);
+}
+
+// ---- which path kernel a launch takes (tests/test_kernel_select.py) ----
+// MODE compiles the renderer strategy and the sampler into the kernel (pt_kernel.hpp); MODE_GENERIC reads them from DevParams.
+enum : uint32_t { MODE_GENERIC = 0, MODE_MIS_SOBOL = 1, MODE_NEE_SOBOL = 2, MODE_PT = 3, MODE_COUNT = 4 };
+// The compiled feature sets, ONE ordered list in two classes: P(set) for the sets without the clearcoat code, then C(set) for those with it.
+// The classes are compiled in separate translation units with their own backend options (Makefile): the plain sets run at 4 waves per SIMD
+// and gain from sinking / the AMDGPU pressure trackers, the clearcoat sets (3 waves per SIMD) lose.  A scene runs the FIRST set of the list
+// that covers its features (pick_features), so within a class a set stands before every set that contains it.
+#define PT_FOR_EACH_SET(P, C)                                                                                                          \
+    P(0u) P(FEAT_TEX) P(FEAT_DIEL) P(FEAT_METAL) P(FEAT_DIEL | FEAT_ROUGH) P(FEAT_DELTA | FEAT_MLIGHT) P(FEAT_STD & ~FEAT_CC)           \
+    C(FEAT_CC) C(FEAT_CC | FEAT_TEX) C(FEAT_STD) C(FEAT_ALL)
+#define PT_NO_SET(F)
+#define PT_FOR_EACH_PLAIN_SET(X) PT_FOR_EACH_SET(X, PT_NO_SET)
+#define PT_FOR_EACH_CC_SET(X) PT_FOR_EACH_SET(PT_NO_SET, X)
+#define PT_SET_ENTRY(F) (F),
+inline constexpr uint32_t FEATURE_SETS[] = {PT_FOR_EACH_SET(PT_SET_ENTRY, PT_SET_ENTRY)};
+inline constexpr uint32_t PLAIN_SETS[] = {PT_FOR_EACH_PLAIN_SET(PT_SET_ENTRY)};
+inline constexpr uint32_t CC_SETS[] = {PT_FOR_EACH_CC_SET(PT_SET_ENTRY)};
+#undef PT_SET_ENTRY
+// smallest compiled feature set covering `feat`
+inline uint32_t pick_features(uint32_t feat) {
+    for (uint32_t s : FEATURE_SETS) if ((feat & ~s) == 0u) return s;
+    return FEAT_ALL;
+}
+// One kernel instantiation: pt_kernel_tiles<set, mode> (tiles), pt_kernel<stats, set, mode> otherwise.  The clearcoat class is set & FEAT_CC.
+struct KernelKey { bool tiles, stats; uint32_t mode, set; };
+// The kernel of a launch over the shard's tiles or over a tile list (tiles), with the instrumentation or without (stats), for a scene with
+// the features `feat`.  The two instrumented variants are generic-mode kernels: scenes without the clearcoat code get the one whose traversal
+// has the production form (merged, 4 waves per SIMD), so that the lane-use diagnostics describe what the benchmarked kernels do.  There is no
+// instrumented tile-list kernel: the key says what was asked for, the lookup (pt_kernels.hip find_pt_kernel) finds nothing for it.
+inline KernelKey select_kernel(bool tiles, bool stats, uint32_t feat, uint32_t sampler, uint32_t strategy) {
+    if (stats) return KernelKey{tiles, true, MODE_GENERIC, (feat & (FEAT_CC | FEAT_EMTEX)) == 0u ? FEAT_STD & ~FEAT_CC : FEAT_ALL};
+    const uint32_t mode = sampler == MI355PT_SAMPLER_SOBOL && strategy == MI355PT_STRATEGY_MIS ? MODE_MIS_SOBOL
+                        : sampler == MI355PT_SAMPLER_SOBOL && strategy == MI355PT_STRATEGY_NEE ? MODE_NEE_SOBOL
+                        : strategy == MI355PT_STRATEGY_PT ? MODE_PT : MODE_GENERIC;
+    return KernelKey{tiles, false, mode, pick_features(feat)};
 }
 
 }  // namespace pt

@@ -1,10 +1,12 @@
-// The sample-loop kernel template (see pt_kernels.hip for the design notes).  A header so that the specialisations by
-// MODE are compiled in separate translation units (pt_kernels.hip: generic + instrumented + probe; pt_kernels_mis.hip,
-// pt_kernels_nee.hip), in parallel.
+// The sample-loop kernel template (see pt_kernels.hip for the design notes).  A header so that the specialisations by MODE and feature-set
+// class are compiled in separate translation units, in parallel and with their own backend options (Makefile): pt_kernels.hip (generic +
+// instrumented), pt_kernels_mis[_cc].hip, pt_kernels_nee[_cc].hip, pt_kernels_pt.hip.  Each unit is a PT_KERNELS_PLAIN / PT_KERNELS_CC line per class it
+// holds (below) and nothing else; which instantiation a launch takes is decided once, in launch_plan.hpp select_kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "launch.hpp"
+#include "launch_plan.hpp"
 #include "layout.hpp"
 #include "pt_device.hpp"
 #include "pt_path.hpp"
@@ -19,13 +21,15 @@ namespace pt {
 #endif
 // work item -> lane assignment
 struct LaneJob { uint32_t px, py, s_cur, s_end; bool valid; };
-PT_DEV LaneJob lane_job(uint32_t work, uint32_t lane, const DevCamera& cam, const DevParams& prm) {
+// tile_of(tile_k): the frame tile of the launch's tile_k-th tile (lane_job: of the shard; pt_kernel_tiles.hpp lane_job_tiles: of the list)
+template <typename TileOf>
+PT_DEV LaneJob lane_job_at(uint32_t work, uint32_t lane, const DevCamera& cam, const DevParams& prm, TileOf tile_of) {
     LaneJob j{0, 0, 0, 0, false};
     // work = ((tile * blocks per tile) + block) * chunks + chunk; lanes >= 4^b own no pixel of the block
     const uint32_t b = prm.block_log2, bside = 1u << b;
     uint32_t item = work / prm.chunks, chunk = work % prm.chunks;
     uint32_t tile_k = item >> (6u - 2u * b), blk = item & ((64u >> (2u * b)) - 1u);
-    uint32_t tile = prm.shard_index + tile_k * prm.shard_count;
+    uint32_t tile = tile_of(tile_k);
     uint32_t tx = tile % prm.tiles_x, ty = tile / prm.tiles_x;
     uint32_t bx = blk & ((8u >> b) - 1u), by = blk >> (3u - b);
     j.px = tx * 8 + bx * bside + (lane & (bside - 1u)); j.py = ty * 8 + by * bside + ((lane >> b) & (bside - 1u));
@@ -33,6 +37,9 @@ PT_DEV LaneJob lane_job(uint32_t work, uint32_t lane, const DevCamera& cam, cons
     j.s_cur = prm.sample_begin + chunk * prm.chunk_size;
     j.s_end = min(j.s_cur + prm.chunk_size, prm.sample_end);
     return j;
+}
+PT_DEV LaneJob lane_job(uint32_t work, uint32_t lane, const DevCamera& cam, const DevParams& prm) {
+    return lane_job_at(work, lane, cam, prm, [&](uint32_t tile_k) { return prm.shard_index + tile_k * prm.shard_count; });
 }
 
 PT_DEV void flush_stats(DevStats* stats, const StatCounters& st) {
@@ -69,7 +76,7 @@ PT_DEV void flush_stats(DevStats* stats, const StatCounters& st) {
 //   the plain path tracer (strategy pt: no connections exist) loses 9 % with it (scene 3 2 790 vs 2 557): it has its own specialisation
 //   (MODE_PT, pt_kernels_pt.hip) without it; choosing inside one kernel at run time costs both sides (-5 % / -8 %: measured);
 //   generic-mode clearcoat kernels (random sampler with NEE / MIS): not measured, two traversals as before.
-enum : uint32_t { MODE_GENERIC = 0, MODE_MIS_SOBOL = 1, MODE_NEE_SOBOL = 2, MODE_PT = 3 };
+// (MODE_*: launch_plan.hpp)
 template <uint32_t FEAT, uint32_t MODE> constexpr bool merged_traversal() {
     if (MODE == MODE_PT) return false;
     if ((FEAT & FEAT_CC) == 0u || MODE == MODE_MIS_SOBOL) return true;
@@ -187,58 +194,23 @@ PT_DEV void item_sobol_prefixes(SamplerCtx& sctx, const DevParams& prm, const La
         sctx.hi_lds = s_hi; sctx.p6_lds = s_p6;
     }
 }
-// ---- launch of the production variants of one MODE: smallest compiled feature set covering `feat` ----
-inline uint32_t pick_features(uint32_t feat) {
-    const uint32_t sets[] = {0u, FEAT_TEX, FEAT_DIEL, FEAT_METAL, FEAT_DIEL | FEAT_ROUGH, FEAT_DELTA | FEAT_MLIGHT, FEAT_CC, FEAT_CC | FEAT_TEX, FEAT_STD & ~FEAT_CC, FEAT_STD, FEAT_ALL};
-    for (uint32_t s : sets) if ((feat & ~s) == 0u) return s;
-    return FEAT_ALL;
-}
-struct PtLaunchArgs {
-    DevScene sc; DevCamera cam; DevParams prm; const uint64_t* d_hash; float* d_accum; float* d_partial; unsigned* d_counter; DevStats* d_stats;
-    int grid; hipStream_t stream; PathOut pout; float4* d_defer;
-};
-// The feature sets in two classes, compiled in separate translation units with their own backend options (Makefile): the sets without the
-// clearcoat code run at 4 waves per SIMD and gain from sinking / the AMDGPU pressure trackers, the clearcoat sets (3 waves per SIMD) lose.
-#define PT_FOR_EACH_PLAIN_SET(X) X(0u) X(FEAT_TEX) X(FEAT_DIEL) X(FEAT_METAL) X(FEAT_DIEL | FEAT_ROUGH) X(FEAT_DELTA | FEAT_MLIGHT) X(FEAT_STD & ~FEAT_CC)
-#define PT_FOR_EACH_CC_SET(X) X(FEAT_CC) X(FEAT_CC | FEAT_TEX) X(FEAT_STD) X(FEAT_ALL)
-#define PT_CASE(F) case (F): hipLaunchKernelGGL((pt_kernel<false, (F), MODE>), dim3(a.grid), dim3(64), 0, a.stream, a.sc, a.cam, a.prm, a.d_hash, a.d_accum, a.d_partial, a.d_counter, a.d_stats, a.pout, a.d_defer); break;
-template <uint32_t MODE>
-void launch_pt_plain(const PtLaunchArgs& a, uint32_t feat) {
-    switch (pick_features(feat)) { PT_FOR_EACH_PLAIN_SET(PT_CASE) default: break; }
-}
-template <uint32_t MODE>
-void launch_pt_cc(const PtLaunchArgs& a, uint32_t feat) {
-    switch (pick_features(feat)) { PT_FOR_EACH_CC_SET(PT_CASE) default: break; }
-}
-#undef PT_CASE
-template <uint32_t MODE>
-void launch_pt_mode(const PtLaunchArgs& a, uint32_t feat) {
-    if (pick_features(feat) & FEAT_CC) launch_pt_cc<MODE>(a, feat); else launch_pt_plain<MODE>(a, feat);
-}
-// resident waves on the current device of the EXACT instantiation a launch takes (launch bounds: 4 waves/SIMD, clearcoat variants 3; the
-// register count and so the occupancy can differ between the MODE specialisations, which live in different translation units with their own
-// backend flags): the persistent grid size (launch.hpp resident_waves_of).  Each translation unit answers for the kernels it holds.
-#define PT_WAVES_CASE(F) case (F): return resident_waves_of(pt_kernel<false, (F), MODE>);
-template <uint32_t MODE>
-int resident_waves_pt_plain(uint32_t feat) {
-    switch (pick_features(feat)) { PT_FOR_EACH_PLAIN_SET(PT_WAVES_CASE) default: return resident_waves_per_device(0); }
-}
-template <uint32_t MODE>
-int resident_waves_pt_cc(uint32_t feat) {
-    switch (pick_features(feat)) { PT_FOR_EACH_CC_SET(PT_WAVES_CASE) default: return resident_waves_per_device(0); }
-}
-#undef PT_WAVES_CASE
-template <uint32_t MODE>
-int resident_waves_pt_mode(uint32_t feat) { return (pick_features(feat) & FEAT_CC) ? resident_waves_pt_cc<MODE>(feat) : resident_waves_pt_plain<MODE>(feat); }
-void launch_pt_mis_sobol(const PtLaunchArgs& a, uint32_t feat);      // pt_kernels_mis.hip (plain sets; forwards the clearcoat sets)
-void launch_pt_mis_sobol_cc(const PtLaunchArgs& a, uint32_t feat);   // pt_kernels_mis_cc.hip
-void launch_pt_nee_sobol(const PtLaunchArgs& a, uint32_t feat);      // pt_kernels_nee.hip
-void launch_pt_nee_sobol_cc(const PtLaunchArgs& a, uint32_t feat);   // pt_kernels_nee_cc.hip
-void launch_pt_strategy_pt(const PtLaunchArgs& a, uint32_t feat);    // pt_kernels_pt.hip (the plain path tracer, either sampler)
-int resident_waves_pt_mis_sobol(uint32_t feat);
-int resident_waves_pt_mis_sobol_cc(uint32_t feat);
-int resident_waves_pt_nee_sobol(uint32_t feat);
-int resident_waves_pt_nee_sobol_cc(uint32_t feat);
-int resident_waves_pt_strategy_pt(uint32_t feat);
+// ---- the instantiations, by address ----
+// pt_kernel and pt_kernel_tiles (pt_kernel_tiles.hpp) share their parameter list: one pointer type for every path kernel.
+using PtKernel = void (*)(DevScene, DevCamera, DevParams, const uint64_t*, float*, float*, unsigned*, DevStats*, PathOut, float4*);
+// The production instantiation of the feature set `set` among those of one (plain or tile-list kernel, MODE, feature-set class); nullptr:
+// not a set of that class.  Each is specialised — and its kernels with it instantiated — in exactly one translation unit, whose whole text
+// is the line PT_KERNELS_PLAIN(mode) or PT_KERNELS_CC(mode) (pt_kernel_tiles.hpp: PT_KERNELS_TILES_*).  pt_kernels.hip's find_pt_kernel is
+// the lookup over all of them: launch and occupancy query take the pointer from there.
+template <bool TILES, uint32_t MODE, bool CC> PtKernel production_kernel(uint32_t set);
+#define PT_PRODUCTION_KERNELS(TILES, MODE_, CC, FOR_EACH_SET, CASE)                       \
+    namespace pt {                                                                        \
+    template <> PtKernel production_kernel<TILES, MODE_, CC>(uint32_t set) {              \
+        constexpr uint32_t MODE = MODE_;                                                  \
+        switch (set) { FOR_EACH_SET(CASE) default: return nullptr; }                      \
+    }                                                                                     \
+    }
+#define PT_KERNEL_CASE(F) case (F): return pt_kernel<false, (F), MODE>;
+#define PT_KERNELS_PLAIN(M) PT_PRODUCTION_KERNELS(false, M, false, PT_FOR_EACH_PLAIN_SET, PT_KERNEL_CASE)
+#define PT_KERNELS_CC(M) PT_PRODUCTION_KERNELS(false, M, true, PT_FOR_EACH_CC_SET, PT_KERNEL_CASE)
 
 }  // namespace pt

@@ -153,26 +153,45 @@ __global__ void combine_kernel(DevCamera cam, DevParams prm, const float* __rest
     accum[o] += r; accum[o + 1] += g; accum[o + 2] += b;
 }
 
+// the instrumented variants, both generic-mode kernels (launch_plan.hpp select_kernel says which scenes take which); nullptr: no such variant
+static PtKernel instrumented_kernel(uint32_t set) {
+    if (set == (FEAT_STD & ~FEAT_CC)) return pt_kernel<true, FEAT_STD & ~FEAT_CC, MODE_GENERIC>;
+    return set == FEAT_ALL ? pt_kernel<true, FEAT_ALL, MODE_GENERIC> : nullptr;
+}
+
+}  // namespace pt
+
+// the production kernels of this unit: the generic mode (strategy and sampler read from DevParams), both feature-set classes
+PT_KERNELS_CC(MODE_GENERIC)
+PT_KERNELS_PLAIN(MODE_GENERIC)
+
+namespace pt {
+
+__global__ void combine_tiles_kernel(DevCamera cam, DevParams prm, const float* __restrict__ partial, float* __restrict__ accum, uint32_t n_list);   // pt_kernels_tiles.hip
+
 // ---------------------------------------------------------------------------------------------
 // launch wrappers (host side, declared in launch.hpp for api.cpp / api_debug.cpp)
 // ---------------------------------------------------------------------------------------------
-hipError_t launch_pt(const DevScene& sc, const DevCamera& cam, const DevParams& prm, uint32_t n_tiles, const uint64_t* d_hash, float* d_accum,
-                     float* d_partial, unsigned* d_counter, DevStats* d_stats, bool stats, uint32_t feat, int grid, hipStream_t stream,
-                     const PathOut& pout, float* d_defer) {
-    const PtLaunchArgs a{sc, cam, prm, d_hash, d_accum, d_partial, d_counter, d_stats, grid, stream, pout, (float4*)d_defer};
-    if (stats) {
-        // two instrumented variants: scenes without the clearcoat code get the one whose traversal has the production form (merged, 4 waves
-        // per SIMD), so that the lane-use diagnostics describe what the benchmarked kernels do
-        if ((feat & (FEAT_CC | FEAT_EMTEX)) == 0u)
-            hipLaunchKernelGGL((pt_kernel<true, FEAT_STD & ~FEAT_CC, MODE_GENERIC>), dim3(grid), dim3(64), 0, stream, sc, cam, prm, d_hash, d_accum, d_partial, d_counter, d_stats, pout, a.d_defer);
-        else
-            hipLaunchKernelGGL((pt_kernel<true, FEAT_ALL>), dim3(grid), dim3(64), 0, stream, sc, cam, prm, d_hash, d_accum, d_partial, d_counter, d_stats, pout, a.d_defer);
-    } else if (prm.sampler == 1u && prm.strategy == 2u) launch_pt_mis_sobol(a, feat);
-    else if (prm.sampler == 1u && prm.strategy == 1u) launch_pt_nee_sobol(a, feat);
-    else if (prm.strategy == 0u) launch_pt_strategy_pt(a, feat);
-    else launch_pt_mode<MODE_GENERIC>(a, feat);
+// The instantiation a key (launch_plan.hpp select_kernel) names, wherever it is compiled; nullptr: there is none (an instrumented tile-list
+// kernel, a set that is not in the list of its class).  The ONE place a launch and its occupancy query take their kernel from.
+static PtKernel find_pt_kernel(const KernelKey& key) {
+    if (key.stats) return !key.tiles && key.mode == MODE_GENERIC ? instrumented_kernel(key.set) : nullptr;
+    // [MODE_*][tile list][clearcoat class]: one entry per translation unit's share of the production kernels
+    using Unit = PtKernel (*)(uint32_t set);
+#define PT_UNITS_OF(M) {{production_kernel<false, M, false>, production_kernel<false, M, true>}, {production_kernel<true, M, false>, production_kernel<true, M, true>}}
+    static const Unit units[MODE_COUNT][2][2] = {PT_UNITS_OF(MODE_GENERIC), PT_UNITS_OF(MODE_MIS_SOBOL), PT_UNITS_OF(MODE_NEE_SOBOL), PT_UNITS_OF(MODE_PT)};
+#undef PT_UNITS_OF
+    static_assert(MODE_GENERIC == 0 && MODE_MIS_SOBOL == 1 && MODE_NEE_SOBOL == 2 && MODE_PT == 3, "units[] is indexed by MODE");
+    return key.mode < MODE_COUNT ? units[key.mode][key.tiles ? 1 : 0][(key.set & FEAT_CC) ? 1 : 0](key.set) : nullptr;
+}
+hipError_t launch_pt(const KernelKey& key, const DevScene& sc, const DevCamera& cam, const DevParams& prm, uint32_t n_tiles, const uint64_t* d_hash,
+                     float* d_accum, float* d_partial, unsigned* d_counter, DevStats* d_stats, int grid, hipStream_t stream, const PathOut& pout,
+                     float* d_defer) {
+    const PtKernel kernel = find_pt_kernel(key);
+    if (!kernel) return hipErrorInvalidDeviceFunction;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, stream, sc, cam, prm, d_hash, d_accum, d_partial, d_counter, d_stats, pout, (float4*)d_defer);
     if (prm.chunks > 1)
-        hipLaunchKernelGGL(combine_kernel, dim3(n_tiles), dim3(64), 0, stream, cam, prm, (const float*)d_partial, d_accum, n_tiles);
+        hipLaunchKernelGGL(key.tiles ? combine_tiles_kernel : combine_kernel, dim3(n_tiles), dim3(64), 0, stream, cam, prm, (const float*)d_partial, d_accum, n_tiles);
     return hipGetLastError();
 }
 hipError_t launch_film_pack(const float* film, uint32_t w, uint32_t h, uint32_t shard_index, uint32_t shard_count, uint32_t n_tiles, float* packed, hipStream_t stream) {
@@ -210,17 +229,11 @@ hipError_t launch_probe_occluded(const DevScene& sc, const float* o, const float
 
 uint64_t host_murmur_dim_seed(uint32_t dimension, uint32_t seed) { return murmur_dim_seed(dimension, seed); }
 size_t query_defer_bytes_per_wave() { return defer_bytes_per_wave(); }     // the deferral queues of pt_kernel.hpp (0: compiled out)
-// resident 64-thread blocks (= waves) on the current device of the EXACT kernel instantiation launch_pt takes for (stats, feat, sampler,
-// strategy): the persistent grid size.  The MODE specialisations are separate translation units with their own backend flags, so their
-// register counts — and with them the occupancy — need not be those of the generic variant.  Cached per scene and device (api.cpp LaunchCtx).
-int query_resident_waves(bool stats, uint32_t feat, uint32_t sampler, uint32_t strategy) {
-    if (stats) {
-        if ((feat & (FEAT_CC | FEAT_EMTEX)) == 0u) return resident_waves_of(pt_kernel<true, FEAT_STD & ~FEAT_CC, MODE_GENERIC>);
-        return resident_waves_of(pt_kernel<true, FEAT_ALL, MODE_GENERIC>);
-    }
-    if (sampler == 1u && strategy == 2u) return resident_waves_pt_mis_sobol(feat);
-    if (sampler == 1u && strategy == 1u) return resident_waves_pt_nee_sobol(feat);
-    if (strategy == 0u) return resident_waves_pt_strategy_pt(feat);
-    return resident_waves_pt_mode<MODE_GENERIC>(feat);
+// resident 64-thread blocks (= waves) on the current device of the kernel instantiation launch_pt takes for `key`, through the same lookup:
+// the persistent grid size.  The MODE specialisations are separate translation units with their own backend flags, so their register
+// counts — and with them the occupancy — need not be those of the generic variant.  Cached per scene and device (api.cpp LaunchCtx).
+int query_resident_waves(const KernelKey& key) {
+    const PtKernel kernel = find_pt_kernel(key);
+    return kernel ? resident_waves_of(kernel) : resident_waves_per_device(0);
 }
 }  // namespace pt

@@ -176,26 +176,21 @@ __global__ void aov_resolve_kernel(uint32_t kind, const float* __restrict__ accu
 
 // ---- host side (declared in launch.hpp for api.cpp) ----
 // the instantiation a (kind, scene feature set) launches: texture code only in the albedo kernel of a scene with spectrum textures
-#define PT_AOV_DISPATCH(X)                                                          \
-    if (kind == AOV_NORMAL) { X(AOV_NORMAL, 0u) }                                   \
-    else if (kind == AOV_SHADING_NORMAL) { X(AOV_SHADING_NORMAL, 0u) }              \
-    else if ((feat & FEAT_TEX) != 0u) { X(AOV_ALBEDO, FEAT_TEX) }                   \
-    else { X(AOV_ALBEDO, 0u) }
+using AovKernel = void (*)(DevScene, DevCamera, DevParams, uint32_t, const uint64_t*, float*, unsigned*, DevStats*);
+static AovKernel find_aov_kernel(uint32_t kind, uint32_t feat) {
+    if (kind == AOV_NORMAL) return aov_kernel<AOV_NORMAL, 0u>;
+    if (kind == AOV_SHADING_NORMAL) return aov_kernel<AOV_SHADING_NORMAL, 0u>;
+    return (feat & FEAT_TEX) != 0u ? aov_kernel<AOV_ALBEDO, FEAT_TEX> : aov_kernel<AOV_ALBEDO, 0u>;
+}
 
 hipError_t launch_aov(uint32_t kind, const DevScene& sc, const DevCamera& cam, const DevParams& prm, uint32_t illuminant_lut, const uint64_t* d_hash,
                       float* d_accum, unsigned* d_counter, DevStats* d_stats, uint32_t feat, int grid, hipStream_t stream) {
     if (prm.chunks != 1u) return hipErrorInvalidValue;      // (a pixel's sum is sequential in the sample index: see the top of this file)
-#define PT_AOV_LAUNCH(K, F) hipLaunchKernelGGL((aov_kernel<K, F>), dim3(grid), dim3(64), 0, stream, sc, cam, prm, illuminant_lut, d_hash, d_accum, d_counter, d_stats);
-    PT_AOV_DISPATCH(PT_AOV_LAUNCH)
-#undef PT_AOV_LAUNCH
+    hipLaunchKernelGGL(find_aov_kernel(kind, feat), dim3(grid), dim3(64), 0, stream, sc, cam, prm, illuminant_lut, d_hash, d_accum, d_counter, d_stats);
     return hipGetLastError();
 }
 // resident 64-thread blocks (= waves) of that instantiation on the current device: the persistent grid size
-int query_resident_waves_aov(uint32_t kind, uint32_t feat) {
-#define PT_AOV_WAVES(K, F) return resident_waves_of(aov_kernel<K, F>);
-    PT_AOV_DISPATCH(PT_AOV_WAVES)
-#undef PT_AOV_WAVES
-}
+int query_resident_waves_aov(uint32_t kind, uint32_t feat) { return resident_waves_of(find_aov_kernel(kind, feat)); }
 hipError_t launch_aov_resolve(uint32_t kind, const float* d_accum, uint32_t n_values, uint32_t spp, float* d_out, hipStream_t stream) {
     if (n_values == 0u) return hipSuccess;
     int grid = (int)std::min<uint32_t>((n_values + 255) / 256, 2048u);

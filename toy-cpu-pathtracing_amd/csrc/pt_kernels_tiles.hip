@@ -1,5 +1,5 @@
 // Path renders over an explicit tile list: the generic-mode instantiations of pt_kernel_tiles (pt_kernel_tiles.hpp; strategy and sampler
-// read from DevParams, like pt_kernels.hip's), the combine kernel for lists and the launcher api.cpp calls (launch.hpp).
+// read from DevParams, like pt_kernels.hip's) and the combine kernel for lists (launched by pt_kernels.hip's launch_pt).
 #include <hip/hip_runtime.h>
 
 #include "pt_kernel_tiles.hpp"
@@ -23,18 +23,7 @@ __global__ void combine_tiles_kernel(DevCamera cam, DevParams prm, const float* 
     accum[o] += r; accum[o + 1] += g; accum[o + 2] += b;
 }
 
-hipError_t launch_pt_tiles(const DevScene& sc, const DevCamera& cam, const DevParams& prm, uint32_t n_list, const uint64_t* d_hash, float* d_accum,
-                           float* d_partial, unsigned* d_counter, uint32_t feat, int grid, hipStream_t stream, float* d_defer) {
-    const PtLaunchArgs a{sc, cam, prm, d_hash, d_accum, d_partial, d_counter, nullptr, grid, stream, PathOut{nullptr, nullptr, nullptr, 0u, 0u}, (float4*)d_defer};
-    // the MODE of launch_pt (pt_kernels.hip) for the same strategy and sampler
-    if (prm.sampler == 1u && prm.strategy == 2u) launch_pt_tiles_mis_sobol(a, feat);
-    else if (prm.sampler == 1u && prm.strategy == 1u) launch_pt_tiles_nee_sobol(a, feat);
-    else if (prm.strategy == 0u) launch_pt_tiles_strategy_pt(a, feat);
-    else if (pick_features(feat) & FEAT_CC) launch_pt_tiles_cc<MODE_GENERIC>(a, feat);
-    else launch_pt_tiles_plain<MODE_GENERIC>(a, feat);
-    if (prm.chunks > 1)
-        hipLaunchKernelGGL(combine_tiles_kernel, dim3(n_list), dim3(64), 0, stream, cam, prm, (const float*)d_partial, d_accum, n_list);
-    return hipGetLastError();
-}
-
 }  // namespace pt
+
+PT_KERNELS_TILES_CC(MODE_GENERIC)
+PT_KERNELS_TILES_PLAIN(MODE_GENERIC)

@@ -1,6 +1,4 @@
 // pt_kernel_tiles (pt_kernel_tiles.hpp), MIS + ZSobol: the feature sets with the clearcoat code, with the backend options of
 // pt_kernels_mis_cc.hip (Makefile).
 #include "pt_kernel_tiles.hpp"
-namespace pt {
-void launch_pt_tiles_mis_sobol_cc(const PtLaunchArgs& a, uint32_t feat) { launch_pt_tiles_cc<MODE_MIS_SOBOL>(a, feat); }
-}  // namespace pt
+PT_KERNELS_TILES_CC(MODE_MIS_SOBOL)
