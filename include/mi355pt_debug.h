@@ -21,6 +21,16 @@ int mi355pt_debug_unlock(int on);
  *   intersected again in its mesh's local space; 1 never the local array; 2 in addition every instance through the full matrix path. */
 int mi355pt_scene_debug_set_lowering(mi355pt_scene* s, int mode);
 
+/* What mi355pt_scene_build would lower this scene to for `cam`, without a device: the lowering's two stages around the HOST tree builder
+ * (whatever mi355pt_scene_set_bvh_builder says), nothing uploaded, the scene - built or not - left as it is.  digests[i] is the FNV-1a-64
+ * of the raw bytes of one array, in upload order, and the last one that of the scalars (the non-pointer fields of the device's scene record
+ * in declaration order, the feature bits, the degenerate count, the BVH2 depth, the 4-wide node count, the stack need, the collapse
+ * method); pointers inside hashed records count as null.  names_buf receives one name per digest, each followed by a newline, then the
+ * text mi355pt_scene_info would give without its three *_ms fields.  *n: capacity of digests on entry, their number on return (also when
+ * a buffer is too small, which is refused).  tests/golden/scene_lowering_digests.json holds the values of the test scenes. */
+int mi355pt_scene_debug_lowering_digest(const mi355pt_scene* s, const mi355pt_camera* cam, char* names_buf, size_t names_len,
+                                        uint64_t* digests, uint32_t* n);
+
 /* ---------------- probes (parity tests; same device code as the render path) ---------------- */
 /* The built acceleration structure as the device holds it (no reference counterpart; the reference's is scene/src/bvh.rs:300-343):
  * node records of 64 B {bx[4] = lo0.x lo1.x hi0.x hi1.x, by[4], bz[4], int32 child[2] (>= 0 node index, < 0 leaf:

@@ -21,6 +21,7 @@ int pt::fail(int code, const std::string& msg) { g_err = msg; return code; }
 static const uint32_t CIE_CMF_BITS[470 * 4] = {
 #include "cie_cmf.inc"
 };
+void pt::cie_cmf4(float out[470 * 4]) { std::memcpy(out, CIE_CMF_BITS, sizeof(CIE_CMF_BITS)); }
 
 namespace {
 
@@ -331,7 +332,6 @@ int mi355pt_scene_add_material(mi355pt_scene* s, const mi355pt_material_desc* d,
             return fail(MI355PT_E_INVALID, "material type not implemented on the device yet");
     }
     im.materials.push_back(m);
-    im.mat_descs.push_back(*d);
     *out = (uint32_t)im.materials.size() - 1;
     return MI355PT_OK;
 }
@@ -345,8 +345,6 @@ int mi355pt_scene_add_delta_light(mi355pt_scene* s, const mi355pt_light_desc* d)
     m.type = MT_EMISSIVE; m.normal_tex = 0xffffffffu; m.metallic_tex = m.roughness_tex = m.cc_thickness_tex = 0xffffffffu; m.intensity = 1.0f; m.intensity_avg = 1.0f;
     if ((rc = im.lower_spectrum(d->spectrum, &m.color, false, &err))) return fail(rc, "light spectrum: " + err);
     im.materials.push_back(m);
-    mi355pt_material_desc md{}; md.type = MI355PT_MAT_EMISSIVE; md.color = d->spectrum; md.intensity = 1.0f; md.normal_tex = MI355PT_NONE; md.intensity_tex = MI355PT_NONE;
-    im.mat_descs.push_back(md);
     HostDeltaLight hl{*d, (uint32_t)im.materials.size() - 1, (uint32_t)im.instances.size()};
     im.delta_lights.push_back(hl);
     return MI355PT_OK;
@@ -364,8 +362,6 @@ int mi355pt_scene_add_environment_light(mi355pt_scene* s, float intensity, const
     DevMaterial m{};                         // hidden emissive material: the integrated RgbIlluminantSpectrum, filled in at build()
     m.type = MT_EMISSIVE; m.normal_tex = 0xffffffffu; m.metallic_tex = m.roughness_tex = m.cc_thickness_tex = 0xffffffffu; m.intensity = 1.0f; m.intensity_avg = 1.0f; m.color.kind = SPK_CONSTANT;
     im.materials.push_back(m);
-    mi355pt_material_desc md{}; md.type = MI355PT_MAT_EMISSIVE; md.intensity = 1.0f; md.normal_tex = MI355PT_NONE; md.intensity_tex = MI355PT_NONE;
-    im.mat_descs.push_back(md);
     mi355pt_light_desc ld{}; ld.kind = LK_ENV; ld.intensity = intensity; std::memcpy(ld.local_to_world, l2w, sizeof(float) * 16);
     im.delta_lights.push_back(HostDeltaLight{ld, (uint32_t)im.materials.size() - 1, (uint32_t)im.instances.size(), (uint32_t)im.envs.size() - 1});
     return MI355PT_OK;
@@ -392,7 +388,7 @@ int mi355pt_scene_build(mi355pt_scene* s, const mi355pt_camera* cam) {
     if (!s || !cam) return fail(MI355PT_E_INVALID, "null argument");
     std::string err;
     float cmf[470 * 4];
-    std::memcpy(cmf, CIE_CMF_BITS, sizeof(cmf));
+    cie_cmf4(cmf);
     int rc = s->impl.build(cam, cmf, &err);
     // the launch context belongs to the old build: another feature set launches other kernels (cached grid sizes), another device makes its
     // buffers foreign memory — get_launch_ctx makes a new one, on the build's device, at the next render
@@ -455,7 +451,7 @@ int mi355pt_scene_build_multi(mi355pt_scene* s, const mi355pt_camera* cam, int n
             m.scene = new (std::nothrow) mi355pt_scene();
             if (!m.scene) { rc = fail(MI355PT_E_INVALID, "allocation failed"); break; }
             SceneImpl& d = m.scene->impl; const SceneImpl& o = s->impl;       // the description, not the lowered state
-            d.table = o.table; d.luts = o.luts; d.textures = o.textures; d.meshes = o.meshes; d.mat_descs = o.mat_descs; d.materials = o.materials;
+            d.table = o.table; d.luts = o.luts; d.textures = o.textures; d.meshes = o.meshes; d.materials = o.materials;
             d.instances = o.instances; d.envs = o.envs; d.delta_lights = o.delta_lights; d.bvh_builder = o.bvh_builder; d.lowering = o.lowering;
         }
         rc = mi355pt_scene_build(m.scene, cam);
@@ -547,7 +543,7 @@ int mi355pt_render_multi(const mi355pt_scene* s, const mi355pt_camera* cam, cons
 int mi355pt_scene_info(const mi355pt_scene* s, char* buf, size_t n) {
     if (!s || !buf || n == 0) return fail(MI355PT_E_INVALID, "null argument");
     if (!s->impl.built) return fail(MI355PT_E_INVALID, "scene not built");
-    std::snprintf(buf, n, "%s features=%u", s->impl.info.c_str(), s->impl.features);
+    std::snprintf(buf, n, "%s", s->impl.info.c_str());
     return MI355PT_OK;
 }
 int mi355pt_film_resolve_device(const float* d_accum, uint32_t n_pixels, uint32_t spp, float* d_out, void* hip_stream) {

@@ -9,6 +9,7 @@
 
 #include "../../include/mi355pt_debug.h"
 #include "api_internal.hpp"
+#include "scene_lower.hpp"
 
 using namespace pt;
 
@@ -20,6 +21,31 @@ int mi355pt_scene_debug_set_lowering(mi355pt_scene* s, int mode) {
     if (!s) return fail(MI355PT_E_INVALID, "null argument");
     if (mode < 0 || mode > 2) return fail(MI355PT_E_INVALID, "unknown lowering mode");
     s->impl.lowering = mode;
+    return MI355PT_OK;
+}
+
+int mi355pt_scene_debug_lowering_digest(const mi355pt_scene* s, const mi355pt_camera* cam, char* names_buf, size_t names_len, uint64_t* digests, uint32_t* n) {
+    if (!s || !cam || !names_buf || !digests || !n) return fail(MI355PT_E_INVALID, "null argument");
+    // SceneImpl::build without its three device steps: no query, the host builder, no upload
+    std::string err;
+    int rc;
+    LoweredGeometry geo; BvhOut bvh; LoweredScene ls; LowerReport rep;
+    if ((rc = lower_geometry(s->impl, cam, &geo, &err))) return fail(rc, err);
+    build_bvh(geo.build_tris, &bvh);
+    if (bvh.max_depth >= STACK_DEPTH) return fail(MI355PT_E_INVALID, "BVH deeper than the traversal stack");
+    float cmf[470 * 4];
+    cie_cmf4(cmf);
+    if ((rc = lower_scene(s->impl, std::move(geo), std::move(bvh), cmf, &ls, &rep, &err)) || (rc = lower_tree4(&ls, &rep, &err))) return fail(rc, err);
+    std::vector<std::string> names; std::vector<uint64_t> dig;
+    lowering_digests(ls, rep, &names, &dig);
+    std::string text;
+    for (const std::string& nm : names) text += nm + "\n";
+    text += lowering_info(ls, rep, false, nullptr);
+    const uint32_t cap = *n;
+    *n = (uint32_t)dig.size();
+    if (cap < dig.size() || names_len < text.size() + 1) return fail(MI355PT_E_INVALID, "digest or name buffer too small");
+    std::memcpy(digests, dig.data(), dig.size() * sizeof(uint64_t));
+    std::memcpy(names_buf, text.c_str(), text.size() + 1);
     return MI355PT_OK;
 }
 

@@ -67,6 +67,7 @@ struct mi355pt_scene {
 namespace pt {
 
 extern bool g_debug_unlocked;      // mi355pt_debug_unlock: lets mi355pt_params.rr_gate_slack through
+void cie_cmf4(float out[470 * 4]);   // the CIE colour matching functions SceneImpl::build takes: [470][4] (xbar, ybar, zbar, 0) (api.cpp)
 int fail(int code, const std::string& msg);   // sets the thread's mi355pt_last_error (api.cpp) and returns `code`
 #define HIP_TRY(expr)                                                                                   \
     do {                                                                                                \

@@ -1,4 +1,4 @@
-// Data layout shared by the host lowering (scene.cpp) and the gfx950 kernels (pt_kernels.hip).
+// Data layout shared by the host lowering (scene_lower.cpp) and the gfx950 kernels (pt_kernels.hip).
 //
 // Everything the sample loop touches lives in HBM as flat, 16-byte-aligned records sized for
 // whole dwordx4 gathers (lanes of a wave traverse independently, so node/triangle fetches are
@@ -42,7 +42,7 @@ struct alignas(16) DevNode {
     uint32_t pad[2];
 };
 static_assert(sizeof(DevNode) == 64, "node must be 64 B");
-// The tree the wave-cooperative traversals walk: the BVH2 collapsed to up to FOUR children per node (scene.cpp collapse_bvh4).  A wave's
+// The tree the wave-cooperative traversals walk: the BVH2 collapsed to up to FOUR children per node (bvh_builder.cpp collapse_bvh4).  A wave's
 // node steps per ray are bounded below by the depth of the path it follows (stealing spreads the breadth of a traversal over idle lanes, not
 // its depth): 18 steps for rays that need 10 on average in the BVH2.  Half the levels = half the dependent fetch -> test -> fetch round trips.
 // Children are collapsed only where the per-lane LDS stack (STACK_DEPTH entries) provably cannot overflow: a node with k children
@@ -56,7 +56,7 @@ static_assert(sizeof(DevNode4) == 128, "wide node must be 128 B");
 // PT_NODE_FMA 1: the slab distances of the 4-wide step are ONE fma per plane, plane * (1/d) + (-(o * (1/d))), instead of a subtraction and a
 // multiplication ((plane - o) * (1/d)).  The fma form cancels: its absolute error is u * |o / d| + u * |t| (u = 2^-24), i.e. up to 2 u * max(|o|, |plane|)
 // measured in space, where the two-step form has 2 u * |t|.  The host therefore pads every box of the DevNode4 tree by NODE4_PAD_REL x the largest
-// coordinate magnitude of the scene (2 x that bound) when it uploads the tree (scene.cpp): the padded test can only visit MORE nodes than the
+// coordinate magnitude of the scene (2 x that bound) when it lowers the tree (scene_lower.cpp): the padded test can only visit MORE nodes than the
 // exact one, and which triangle a ray hits is decided by the unchanged watertight triangle test.  The BVH2 records (probes, canonical counts) stay exact.
 #ifndef PT_NODE_FMA
 #define PT_NODE_FMA 1        // measured (round 3, same box): pad 2^-20 +0.1...0.25 %, pad 2^-22 +0.55...0.75 % (scenes 3 / 8 / 10)
@@ -126,7 +126,7 @@ using DevTriLocal = DevTri;    // the same record with LOCAL-space positions in 
 
 struct alignas(16) DevInstance {
     float m[12];       // local_to_render: columns x, y, z, w (the xyz of each; the bottom row is 0 0 0 1)
-    float inv[12];     // glam Mat4::inverse(local_to_render), same layout (scene.cpp mat4_inverse_glam)
+    float inv[12];     // glam Mat4::inverse(local_to_render), same layout (scene_lower.cpp mat4_inverse_glam)
     uint32_t identity; // 1: the 3x3 parts of both are exactly the identity (a translation): the multiplies are exact and skipped
     uint32_t pad[3];
 };

@@ -1,6 +1,7 @@
 // Host-side scene: stores what the C ABI hands over, lowers it to the flat HBM layout of layout.hpp
 // (single render-space BVH over all instances, leaf-ordered triangles, per-triangle shading records,
 // light tables) and owns the device buffers.  Replaces Scene::build (scene/src/scene.rs:64-76).
+// The lowering itself is scene_lower.hpp (pure host code); scene.cpp is what needs a device.
 #pragma once
 #include <string>
 #include <vector>
@@ -38,6 +39,8 @@ bool build_bvh_gpu(const std::vector<BuildTri>& tris, BvhOut* out, double* devic
 
 constexpr size_t BVH_GPU_AUTO_TRIS = 1u << 17;   // "auto": scenes from 131 072 triangles on are built on the GPU
 
+struct LoweredScene;   // scene_lower.hpp
+
 struct SceneImpl {
     // ---- description ----
     std::vector<float> table;                 // reference layout [64][3][64][64][64][3]
@@ -45,41 +48,33 @@ struct SceneImpl {
     struct Tex { std::vector<uint8_t> rgb; uint32_t w, h; };
     std::vector<Tex> textures;
     std::vector<HostMesh> meshes;
-    std::vector<mi355pt_material_desc> mat_descs;
     std::vector<DevMaterial> materials;
     std::vector<HostInstance> instances;
     struct HostEnv { float intensity = 1.0f; uint32_t w = 0, h = 0, illuminant_lut = 0; std::vector<float> rgb; float l2w[16]; };
     std::vector<HostEnv> envs;                  // environment lights in creation order (HostDeltaLight::d.angle_inner carries the index)
     std::vector<HostDeltaLight> delta_lights;   // creation order; after_instances = instances.size() at creation (light_sampler.rs:163-180)
-    // ---- lowered ----
+    int bvh_builder = 0;          // MI355PT_BVH_AUTO / _HOST / _GPU (mi355pt_scene_set_bvh_builder)
+    int lowering = 0;             // mi355pt_scene_debug_set_lowering: 0 auto, 1 never the local triangle array, 2 also every instance through the full matrix path
+    // ---- built ----
     bool built = false;
     int device = -1;              // the HIP device build() uploaded to: render calls must run with it current
     float build_cam_pos[3] = {0, 0, 0};   // camera position baked into the render-space records (world -> render translation)
     DevScene dev{};
     std::vector<void*> allocs;
-    int bvh_depth = 0;
-    size_t bvh4_nodes = 0;        // nodes of the collapsed tree (DevNode4)
-    int bvh_builder = 0;          // MI355PT_BVH_AUTO / _HOST / _GPU (mi355pt_scene_set_bvh_builder)
-    int bvh_builder_used = 1;     // what build() took
-    size_t n_degenerate = 0;      // triangles with an exactly zero cross product: never hit (ray.rs:49-56), left out of the tree
-    int lowering = 0;             // mi355pt_scene_debug_set_lowering: 0 auto, 1 never the local triangle array, 2 also every instance through the full matrix path
-    double collapse_ms = 0.0;     // host time of the 2-wide -> 4-wide collapse
-    const char* collapse_method = "";   // "dp" or "greedy" (scene_info)
-    int bvh4_stack_need = 0;      // worst-case per-lane stack entries the collapsed tree can need (< STACK_DEPTH, validated)
-    double bvh_build_ms = 0.0;    // wall time of the BVH build inside build(); bvh_device_ms: device part of a GPU build
-    double bvh_device_ms = 0.0;
     uint32_t features = FEAT_ALL;   // FEAT_* bits the scene's materials need (kernel specialisation)
-    std::string info;
+    std::string info;             // mi355pt_scene_info
 
     ~SceneImpl();
     void release();
     // RgbSigmoidPolynomial::from(ColorSrgb) on the host (rgb_sigmoid_polynomial.rs:87-155)
     bool table_lookup_srgb(const float rgb_encoded[3], float c[3], bool linear = false) const;
     int lower_spectrum(const mi355pt_spectrum& in, DevSpectrum* out, int allow_texture /* 0 no, 1 Albedo type, 2 every SpectrumType */, std::string* err) const;
-    int build(const mi355pt_camera* cam, const float* cmf_xyz /*3*470*/, std::string* err);
+    // release(), the device query, lower_geometry, the tree build (host or GPU), lower_scene + lower_tree4, upload, the info string
+    int build(const mi355pt_camera* cam, const float* cmf4 /*470*4*/, std::string* err);
+    int upload(const LoweredScene& ls, std::string* err);   // the one place that allocates device memory and copies to it
 };
 
-// mi355pt_coat_albedo_table (scene.cpp): E(cos theta_o) of the clearcoat's directional-albedo estimator, 64 entries
+// mi355pt_coat_albedo_table (scene_lower.cpp): E(cos theta_o) of the clearcoat's directional-albedo estimator, 64 entries
 void coat_albedo_table(float alpha, float r0, float out[64]);
 
 }  // namespace pt

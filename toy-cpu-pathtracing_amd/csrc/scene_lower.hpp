@@ -1,0 +1,82 @@
+// Scene lowering, the part that needs no device: description + camera -> the host arrays SceneImpl::build uploads (layout.hpp).
+// Host-only and pure: no HIP header, no environment variable, no clock — the same description gives the same bytes, on any machine
+// with the same libm (tests/test_scene_lowering.py holds the digests).  Two stages around the BVH2 build, which the caller owns:
+//
+//   lower_geometry   description + camera -> records in creation order, the builder's input       (stage A)
+//   [ build_bvh / build_bvh_gpu: scene.cpp picks one ]
+//   lower_scene      geometry + BVH2      -> everything in leaf order, every table and scalar      (stage B)
+//   lower_tree4      ... and the 4-wide tree the traversals walk; a call of its own so that the caller can time the collapse
+#pragma once
+#include <array>
+#include <string>
+#include <vector>
+
+#include "scene.hpp"
+
+namespace pt {
+
+// Stage A's result.  Triangle records are in creation order (instance by instance); build_tris / kept leave out the degenerate ones.
+struct LoweredGeometry {
+    std::vector<DevInstance> instances;
+    std::vector<DevTri> tris;                  // render-space vertices
+    std::vector<DevTriLocal> tris_local;       // the mesh's own vertices
+    std::vector<DevTriShade> shade;
+    std::vector<BuildTri> build_tris;          // bounds of the triangles the tree is built over
+    std::vector<uint32_t> kept;                // build index -> triangle
+    size_t n_degenerate = 0;                   // triangles with an exactly zero cross product: never hit (ray.rs:49-56), left out of the tree
+    std::vector<DevLight> lights;              // area lights and delta / environment lights, in creation order
+    std::vector<DevLightTri> light_tris;
+    std::vector<float> light_uvs;              // 6 per light triangle (original vertex order), zeros without texcoords
+    std::vector<uint32_t> env_light_index;     // position of environment light k in the light list
+    std::vector<std::array<float, 16>> env_l2r;
+    bool tris_are_local = false;               // every instance is the same pure translation: the traversals test the local vertices
+    float shared_iw[3] = {0, 0, 0}, shared_mw[3] = {0, 0, 0};   // that translation's inverse / forward offsets
+};
+
+// Everything SceneImpl::upload needs and nothing else: the arrays in upload order, then what DevScene holds besides pointers.
+struct LoweredScene {
+    std::vector<DevNode> nodes;
+#if PT_NODE_Q16
+    std::vector<DevNode4Q> nodes4;
+#else
+    std::vector<DevNode4> nodes4;
+#endif
+    std::vector<DevTri> tris_render;
+    std::vector<DevTriShade> shade;
+    std::vector<DevInstance> instances;
+    std::vector<DevTriLocal> tris_local;
+    std::vector<float> cc_albedo;
+    std::vector<DevMaterial> materials;        // the device copy: texture descriptors, clearcoat table offsets, the environment lights' spectra
+    std::vector<DevLight> lights;
+    std::vector<DevLightTri> light_tris;
+    std::vector<float> light_uvs, luts, cmf, rgb2spec, z_nodes;
+    std::vector<uint32_t> texels;
+    std::vector<DevTexture> textures;
+    struct EnvTables { std::vector<float> texels, marginal, conditional; };
+    std::vector<EnvTables> env_tables;
+    std::vector<DevEnv> envs;                  // the three pointers of each are null: upload fills them in
+    DevScene dev{};                            // every non-pointer field; the pointers are null
+    uint32_t features = 0;                     // FEAT_* bits the scene needs (kernel specialisation)
+};
+
+// What lowering found out along the way: scene_info's numbers that are not in DevScene.
+struct LowerReport {
+    size_t n_degenerate = 0;
+    int bvh_depth = 0;
+    int stack_need = 0;                        // worst-case per-lane stack entries the collapsed tree can need (< STACK_DEPTH, validated)
+    const char* collapse_method = "";          // "dp" or "greedy"
+};
+
+// Stage A.  Errors (MI355PT_E_INVALID): "scene has no instances", "singular instance transform", "scene has no triangles", "too many triangles".
+int lower_geometry(const SceneImpl& scene, const mi355pt_camera* cam, LoweredGeometry* out, std::string* err);
+// Stage B.  Consumes the geometry and the tree (their arrays move into *out); cmf4: [470][4].
+int lower_scene(const SceneImpl& scene, LoweredGeometry&& geo, BvhOut&& bvh, const float* cmf4, LoweredScene* out, LowerReport* rep, std::string* err);
+int lower_tree4(LoweredScene* ls, LowerReport* rep, std::string* err);   // ls->nodes -> ls->nodes4 (+ root4, n_nodes4, the Q16 grid)
+
+// scene_info's text; ms = {bvh_ms, bvh_device_ms, collapse_ms} or null to leave the three timings out (what the digests are recorded with)
+std::string lowering_info(const LoweredScene& ls, const LowerReport& rep, bool gpu_builder, const double* ms);
+
+// FNV-1a-64 of every array of `ls` in upload order, then of the scalars (DevScene's non-pointer fields, features, the report); names[i] names digests[i].
+void lowering_digests(const LoweredScene& ls, const LowerReport& rep, std::vector<std::string>* names, std::vector<uint64_t>* digests);
+
+}  // namespace pt

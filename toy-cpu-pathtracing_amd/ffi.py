@@ -138,7 +138,7 @@ def _ptr(a, ty):
 
 
 # every symbol include/mi355pt.h declares (tests/test_abi.py checks the built library exports all of them) ...
-DEBUG_SYMBOLS = ["debug_unlock", "scene_debug_set_lowering", "scene_export_bvh", "probe_bvh_collapse", "probe_bvh_collapse_nodes", "probe_sobol", "probe_sincos", "probe_intersect", "probe_occluded",
+DEBUG_SYMBOLS = ["debug_unlock", "scene_debug_set_lowering", "scene_debug_lowering_digest", "scene_export_bvh", "probe_bvh_collapse", "probe_bvh_collapse_nodes", "probe_sobol", "probe_sincos", "probe_intersect", "probe_occluded",
                  "sample_log_records", "render_sample_log", "probe_radiance"]     # ... and include/mi355pt_debug.h
 ABI_SYMBOLS = [
     "scene_create", "scene_destroy", "scene_set_rgb2spec", "scene_add_lut470", "scene_add_tex_rgb8", "scene_add_mesh",
@@ -309,6 +309,17 @@ class SceneHandle:
         fn = self.b.fn("scene_debug_set_lowering")
         fn.argtypes = [C.c_void_p, C.c_int]
         self.b.check(fn(self.h, {"auto": 0, "no_local_tris": 1, "general": 2}[mode]), "scene_debug_set_lowering")
+
+    def debug_lowering_digest(self, cam):
+        """mi355pt_scene_debug_lowering_digest (host only, product only) -> ({array name: FNV-1a-64 as 16 hex digits}, in upload order with
+        "scalars" last, and scene_info's text without the *_ms fields)"""
+        fn = self.b.fn("scene_debug_lowering_digest")
+        fn.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+        text = C.create_string_buffer(4096); dig = (C.c_uint64 * 128)(); n = C.c_uint32(128)
+        self.b.check(fn(self.h, C.byref(cam), text, 4096, dig, C.byref(n)), "scene_debug_lowering_digest")
+        *names, info = text.value.decode().split("\n")
+        assert len(names) == n.value
+        return {nm: f"{dig[i]:016x}" for i, nm in enumerate(names)}, info
 
     def build(self, cam):
         self.b.check(self.b.fn("scene_build")(self.h, C.byref(cam)), "scene_build")
