@@ -152,10 +152,12 @@ static int launch_range(const mi355pt_scene* s, const mi355pt_camera* cam, const
     if (stats) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, stream)); }
     if ((rc = grow_device_buffer(&lc->d_partial, &lc->partial_bytes, plan.partial_floats * sizeof(float), stream))) return rc;
     // (one stream at a time per scene, like d_partial: the queues are empty between launches, so consecutive launches share them)
-    if ((rc = grow_device_buffer(&lc->d_defer, &lc->defer_bytes, aov ? (size_t)0 : query_defer_bytes_per_wave() * (size_t)plan.grid, stream))) return rc;
+    // (sized by what the selected kernel's queues use per wave; the buffer only grows: a context that launches several kernels holds the largest)
+    const KernelKey key = select_kernel(d_list != nullptr, want_stats, s->impl.features, p->sampler, p->strategy);
+    if ((rc = grow_device_buffer(&lc->d_defer, &lc->defer_bytes, aov ? (size_t)0 : query_defer_bytes_per_wave(key) * (size_t)plan.grid, stream))) return rc;
     if (aov) HIP_TRY(launch_aov((uint32_t)aov_kind, s->impl.dev, dc, dp, illuminant_lut, lc->d_hash, d_accum, d_counter, stats ? d_stats : nullptr,
                                 s->impl.features, plan.grid, stream));
-    else HIP_TRY(launch_pt(select_kernel(d_list != nullptr, want_stats, s->impl.features, p->sampler, p->strategy), s->impl.dev, dc, dp, plan.n_tiles,
+    else HIP_TRY(launch_pt(key, s->impl.dev, dc, dp, plan.n_tiles,
                            lc->d_hash, d_accum, lc->d_partial, d_counter, d_list ? nullptr : d_stats, plan.grid, stream, pout, lc->d_defer));
     if (stats) {
         HIP_TRY(hipEventRecord(e1, stream));

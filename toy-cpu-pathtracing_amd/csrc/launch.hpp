@@ -24,7 +24,7 @@ struct PathOut { float* L; float* lam; float* pdf; uint32_t s_base, n_s; };
 hipError_t launch_pt(const KernelKey& key, const DevScene&, const DevCamera&, const DevParams&, uint32_t n_tiles, const uint64_t* d_hash, float* d_accum,
                      float* d_partial, unsigned* d_counter, DevStats* d_stats, int grid, hipStream_t, const PathOut&, float* d_defer);
 int query_resident_waves(const KernelKey& key);      // of the very kernel launch_pt takes for `key`
-size_t query_defer_bytes_per_wave();
+size_t query_defer_bytes_per_wave(const KernelKey& key);
 hipError_t launch_resolve(const float* d_accum, uint32_t n_values, uint32_t spp, float* d_out, hipStream_t);
 hipError_t launch_film_pack(const float* film, uint32_t w, uint32_t h, uint32_t shard_index, uint32_t shard_count, uint32_t n_tiles, float* packed, hipStream_t);
 hipError_t launch_film_unpack(float* film, uint32_t w, uint32_t h, uint32_t shard_index, uint32_t shard_count, uint32_t n_tiles, const float* packed, hipStream_t);

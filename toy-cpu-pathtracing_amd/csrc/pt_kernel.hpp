@@ -10,6 +10,7 @@
 #include "layout.hpp"
 #include "pt_device.hpp"
 #include "pt_path.hpp"
+#include "tail_queue_plan.hpp"
 
 namespace pt {
 
@@ -77,11 +78,13 @@ PT_DEV void flush_stats(DevStats* stats, const StatCounters& st) {
 //   (MODE_PT, pt_kernels_pt.hip) without it; choosing inside one kernel at run time costs both sides (-5 % / -8 %: measured);
 //   generic-mode clearcoat kernels (random sampler with NEE / MIS): not measured, two traversals as before.
 // (MODE_*: launch_plan.hpp)
-template <uint32_t FEAT, uint32_t MODE> constexpr bool merged_traversal() {
+// (the *_of functions: the same statements on values, for the launcher's queue size, queue_bytes_per_wave below)
+constexpr bool merged_traversal_of(uint32_t FEAT, uint32_t MODE) {
     if (MODE == MODE_PT) return false;
     if ((FEAT & FEAT_CC) == 0u || MODE == MODE_MIS_SOBOL) return true;
     return MODE == MODE_NEE_SOBOL && FEAT != (FEAT_CC | FEAT_TEX);
 }
+template <uint32_t FEAT, uint32_t MODE> constexpr bool merged_traversal() { return merged_traversal_of(FEAT, MODE); }
 // MATERIAL SORT BETWEEN BOUNCES, wave-local (the deferral queue; defer_classes() below says which kernels have it).  A wave shades all
 // its lanes together, so an iteration in which a few lanes hit the hero pays the hero's whole BSDF branch on top of the room's: measured 19-52 k of ~270-300 k cycles per iteration wherever the scene
 // has a second material class, i.e. in 84-93 % of the iterations for 8-13 % of the lanes.  With the queue a lane whose closest
@@ -100,8 +103,8 @@ template <uint32_t FEAT, uint32_t MODE> constexpr bool merged_traversal() {
 #endif
 constexpr uint32_t DEFER_RING = 128u;           // entries per wave: a drain starts at PT_DEFER_MIN waiting paths and one iteration adds at most 64
 constexpr uint32_t DEFER_F4 = 8u;               // float4 per entry
-template <uint32_t FEAT, uint32_t MODE> constexpr uint32_t defer_classes() {    // bit c: sort class c (MT_* | 8 if the material has a spectrum texture, DevTri::pad[0]) is deferred
-    if (!merged_traversal<FEAT, MODE>()) return 0u;
+constexpr uint32_t defer_classes_of(uint32_t FEAT, uint32_t MODE) {    // bit c: sort class c (MT_* | 8 if the material has a spectrum texture, DevTri::pad[0]) is deferred
+    if (!merged_traversal_of(FEAT, MODE)) return 0u;
     // the clearcoat material wherever it exists (its branch is the longest: +12 % scene 17, +22 % scene 19, +34 % scene 15); in the kernels
     // without it, the materials with a spectrum texture (bilinear fetches + rgb2spec cells; C2's hero: +0.6 %, scene 4 +0.8 %; a class for
     // every textured material lost 4 % on the normal-map-only hero of scene 5).  The dielectrics alone measured +-0 (their branch is short)
@@ -110,6 +113,7 @@ template <uint32_t FEAT, uint32_t MODE> constexpr uint32_t defer_classes() {    
     if ((FEAT & FEAT_TEX) != 0u) return 0xff00u;
     return 0u;
 }
+template <uint32_t FEAT, uint32_t MODE> constexpr uint32_t defer_classes() { return defer_classes_of(FEAT, MODE); }
 // TAIL QUEUE (PT_TAILQ): the same idea for EVERY path.  A third of the lanes that enter the shading stage end their path in its front
 // (emission, roulette) and used to idle through BSDF sampling and the light connection — 28 % of a wave's time at 65 % of its lanes.  Now the
 // shading stage is two: (1) the FRONT of the vertex for every lane that traced (emission with its weight, throughput, roulette, depth:
@@ -125,21 +129,41 @@ template <uint32_t FEAT, uint32_t MODE> constexpr uint32_t defer_classes() {    
 // (a class that is a tenth of the hits leaves up to 63 paths to be bounced out in sparse passes at the end of every work item); writing
 // the pass with the back of the head and the tail in two divergent regions instead of one costs those kernels 12 % (ShadeCtx across a
 // re-convergence point at 128 VGPRs, as round 1 found for the fused shader).
+// Each queue is a STACK (tail_queue_plan.hpp has the index arithmetic, tests/test_tail_queue_plan.py runs it on the CPU): a pass pops the
+// NEWEST records.  Popped first in, first out — the queues were rings once — a pass read the OLDEST records, written one or two iterations
+// earlier, and the head walked round every slot of every wave's queue: 512 waves x 10 KB per XCD against a 4 MB L2, every record a miss in
+// both directions.  Newest first, most of a pass's records are the ones the front has just stored, and the bottom of the
+// stack goes cold until the work item drains.  The order of the pops is still a function of the wave's own state, so frames stay
+// bit-identical from run to run; a pixel's samples reach the LDS film tile in another order than with the rings, so the film's float sums
+// differ from that build's in the last bits (per-sample values do not: tests/test_tail_queue_order_gpu.py).
 #ifndef PT_TAILQ
 #define PT_TAILQ 1
 #endif
 #ifndef PT_TAILQ_MIN
 #define PT_TAILQ_MIN 64
 #endif
-template <uint32_t FEAT, uint32_t MODE> constexpr bool tail_queue() { return PT_TAILQ != 0 && merged_traversal<FEAT, MODE>(); }    // (the clearcoat kernels too: two queues, one per sort class)
-constexpr uint32_t QUEUE_RING = (PT_TAILQ != 0) ? 256u : DEFER_RING;     // entries per wave and queue
+constexpr bool tail_queue_of(uint32_t FEAT, uint32_t MODE) { return PT_TAILQ != 0 && merged_traversal_of(FEAT, MODE); }    // (the clearcoat kernels too: two queues, one per sort class)
+template <uint32_t FEAT, uint32_t MODE> constexpr bool tail_queue() { return tail_queue_of(FEAT, MODE); }
+constexpr uint32_t QUEUE_RING = (PT_TAILQ != 0) ? 256u : DEFER_RING;     // entries per wave and queue (the capacity of a stack of the two-queue kernels; of the deferral ring)
 constexpr uint32_t QUEUE_MAX = (PT_TAILQ != 0) ? 2u : 1u;               // queues per wave (the tail queue keeps one per sort class)
 // (the queue's records are written once and read once, but stores / loads with the non-temporal hint, meant to keep them from pushing the
 // BVH out of the L2 — L2 hit rate 0.98 before the queues, 0.89 with them — measured -4 % (C2 2 578 -> 2 481, C4 -5.6 %): the records then
 // come back from HBM instead of the L2 / Infinity Cache)
 static_assert(PT_TAILQ == 0 || QUEUE_RING == 256u, "the tail queue's entry index keeps the queue number in bit 8");
 constexpr uint32_t TQ_F4 = 5u;                                           // float4 per record of the tail queue (80 B; the deferral queue's record: DEFER_F4)
-constexpr size_t defer_bytes_per_wave() { return (size_t)QUEUE_MAX * QUEUE_RING * DEFER_F4 * 16u; }
+// entries of the stack where one queue suffices: at most 127 paths ever wait there (tail_queue_plan.hpp), and the smaller stack keeps the
+// records closer to the L2
+#ifndef PT_TAILQ_RING1
+#define PT_TAILQ_RING1 128u
+#endif
+// Queue memory of one resident wave of pt_kernel<STATS, FEAT, MODE> / pt_kernel_tiles<FEAT, MODE> (STATS = false), in bytes: what that
+// kernel's queues hold and nothing more — 10 KB for one stack (5 float4 x 128 entries), 40 KB for the clearcoat kernels' two (2 x 5 x 256),
+// 16 KB for the instrumented kernels' deferral ring, 0 for a kernel without a queue.  The ONE statement of the per-wave stride: the kernel
+// body places its queues with it (q_base) and the launcher sizes the buffer with it for the kernel it selected (query_defer_bytes_per_wave).
+constexpr size_t queue_bytes_per_wave(bool STATS, uint32_t FEAT, uint32_t MODE) {
+    if (!STATS && tail_queue_of(FEAT, MODE)) return (size_t)16u * TQ_F4 * ((FEAT & FEAT_CC) != 0u ? QUEUE_MAX * QUEUE_RING : PT_TAILQ_RING1);
+    return defer_classes_of(FEAT, MODE) != 0u ? (size_t)16u * DEFER_F4 * DEFER_RING : (size_t)0;
+}
 // MODE compiles the renderer strategy and the sampler in (MODE_GENERIC reads them from DevParams): the branches on
 // prm.strategy / the sampler mode fold away, worth +2.5 % on C2 (MIS + Sobol), +1.3 % on C5 (NEE + Sobol).
 // The cooperative traversals walk the 4-wide tree (both trees are on the device; the plain traversals of the probes and of the canonical-count

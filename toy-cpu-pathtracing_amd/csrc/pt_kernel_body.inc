@@ -111,19 +111,16 @@
         CarryState carry{0ull};
         constexpr bool TAILQ = !STATS && tail_queue<FEAT, MODE>();       // (the instrumented kernels keep the plain shading stage)
         constexpr uint32_t DEFER = TAILQ ? 0u : defer_classes<FEAT, MODE>();
-        float4* const q_base = (DEFER != 0u || TAILQ) ? defer_buf + (size_t)blockIdx.x * (QUEUE_MAX * QUEUE_RING * DEFER_F4) : nullptr;     // this wave's queue(s)
-        uint32_t q_head = 0u, q_tail = 0u;                         // wave-uniform; the queue is empty between work items
+        float4* const q_base = (DEFER != 0u || TAILQ) ? defer_buf + (size_t)blockIdx.x * (queue_bytes_per_wave(STATS, FEAT, MODE) / 16u) : nullptr;     // this wave's queue(s)
+        uint32_t q_head = 0u, q_tail = 0u;                         // the deferral queue (a ring); wave-uniform; the queue is empty between work items
+        uint32_t q_count = 0u, q2_count = 0u;                      // the tail queue(s) (stacks, tail_queue_plan.hpp): records waiting; wave-uniform; 0 between work items
         // tail queue: a second queue for the paths whose hit is on a sort class of its own (defer_classes), so that a pass shades one class
         // (the clearcoat material in the kernels that have it: its branch is the long one.  A second queue for every class but plain Lambert
         // was measured on the kernels without clearcoat and LOSES — scene 3 2 312 -> 2 063, scene 8 2 097 -> 1 932: a class that is a tenth of
         // the hits fills its queue every ~16 iterations and leaves up to 63 paths to be bounced out in sparse passes when a work item ends)
         constexpr uint32_t TQ_CLASSES = (TAILQ && (FEAT & FEAT_CC) != 0u) ? ((1u << MT_CLEARCOAT) | (1u << (MT_CLEARCOAT | 8u))) : 0u;
-        uint32_t q2_head = 0u, q2_tail = 0u;
-        // entries per ring: with one queue at most 127 paths ever wait (a pass starts at 64, an iteration adds at most 64 and every lane is
-        // free after the front), with two at most 191 in both together — the smaller ring keeps the records closer to the L2
-#ifndef PT_TAILQ_RING1
-#define PT_TAILQ_RING1 128u
-#endif
+        // entries per stack: with one queue at most 127 paths ever wait (a pass starts at 64, an iteration adds at most 64 and every lane is
+        // free after the front), with two at most 191 in both together — the smaller stack keeps the records closer to the L2
         constexpr uint32_t QR = (TQ_CLASSES != 0u) ? QUEUE_RING : PT_TAILQ_RING1;
         while (true) {
             unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, ts4 = 0, tsa = 0, tsb = 0;
@@ -144,7 +141,7 @@
                 pool_next = min(pool_next + (uint32_t)__popcll(m_needy), pool_size);
             }
             if (!__any(active)) {
-                if (pool_next >= pool_size && q_tail == q_head && q2_tail == q2_head) break;
+                if (pool_next >= pool_size && q_tail == q_head && (q_count | q2_count) == 0u) break;
                 // (queued paths are taken AFTER the shading stage: with nothing left to start, an iteration without rays still has to get there)
                 if (!((DEFER != 0u || TAILQ) && pool_next >= pool_size)) continue;
             }
@@ -182,9 +179,9 @@
             // the tail queue's record: what the back of the vertex still needs once the front has run — the spawning sample's f, pdf and the
             // vertex left are consumed by the front, from_camera / prev_spec are rewritten by the tail, the hit's t is never read: 20 dwords in
             // 5 float4 = 80 B.  The record's size is the queue's price: 128 -> 96 B was worth +6.5 % on C2 (the queues stream through L2 / HBM)
-            // Layout: FIELD-major inside a ring (float4 k of entry e at ring base + k * ring + e): the entries of one push / pop are
+            // Layout: FIELD-major inside a stack (float4 k of entry e at stack base + k * capacity + e): the entries of one push / pop are
             // consecutive, so each of the five store / load instructions of a wave covers 64 x 16 B = eight whole 128-byte lines instead of a
-            // sixth of 64 different ones (+1 ... 2 % over the record-major layout; a 128-entry ring where one queue suffices +0.2 ... 0.8 %)
+            // sixth of 64 different ones (+1 ... 2 % over the record-major layout; 128 entries where one queue suffices +0.2 ... 0.8 %)
             auto tq_store = [&](uint32_t e, const Path& Q, const Hit& h, uint32_t pix) {
                 float4* r = q_base + (size_t)(e >> 8) * (TQ_F4 * QUEUE_RING) + (e & (QR - 1u));
                 const uint32_t fl = (Q.wl.term ? 1u : 0u) | ((Q.depth & 1023u) << 1) | ((pix & 63u) << 11) | (Q.smp.dimension << 17);   // (max_depth <= 1000, api.cpp check_args: dimension <= 3 + 8 * 1000 < 2^15)
@@ -261,11 +258,12 @@
                 const unsigned long long m_on1 = __ballot(go_on && !cls2), m_on2 = TQ_CLASSES != 0u ? __ballot(go_on && cls2) : 0ull;
                 if ((m_on1 | m_on2) != 0ull) {
                     if (go_on) {
-                        const uint32_t e = cls2 ? QUEUE_RING + ((q2_tail + rank_below(m_on2)) & (QR - 1u)) : ((q_tail + rank_below(m_on1)) & (QR - 1u));
+                        // (on top of the stack: consecutive ranks, consecutive entries)
+                        const uint32_t e = cls2 ? QUEUE_RING + tq_push_slot(q2_count, rank_below(m_on2)) : tq_push_slot(q_count, rank_below(m_on1));
                         tq_store(e, P, hit, my_pix);
                         active = false;
                     }
-                    q_tail += (uint32_t)__popcll(m_on1); q2_tail += (uint32_t)__popcll(m_on2);
+                    q_count += (uint32_t)__popcll(m_on1); q2_count += (uint32_t)__popcll(m_on2);
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 }
                 if (active && end_path) { finish_path(); active = false; }
@@ -274,18 +272,18 @@
                 // the back of the vertex and its tail for a full wave of queued paths — of ONE class while new paths still arrive (the class
                 // with its own queue first); when the work item has nothing new left, whatever waits in either queue shares the passes
                 const bool draining = pool_next >= pool_size;
-                const uint32_t c2 = q2_tail - q2_head, c1 = q_tail - q_head;
-                const bool full2 = TQ_CLASSES != 0u && c2 >= (uint32_t)PT_TAILQ_MIN, full1 = c1 >= (uint32_t)PT_TAILQ_MIN;
-                if (full2 || full1 || (draining && (c1 | c2) != 0u)) {
+                // A pass takes the NEWEST records (tail_queue_plan.hpp): mostly the ones the front above has just stored, read back while their
+                // lines are still in the L2, instead of the oldest, written an iteration or two ago and evicted since
+                if (tq_pass_due(q_count, q2_count, draining, TQ_CLASSES != 0u, (uint32_t)PT_TAILQ_MIN)) {
                     const unsigned long long m_free = __ballot(!active);
                     const uint32_t n_free = (uint32_t)__popcll(m_free), r = rank_below(m_free);
                     // lanes 0 .. n2-1 of the free lanes take from queue 2, the next n1 from queue 1
-                    const uint32_t n2 = (full2 || (draining && !full1)) ? min(n_free, c2) : 0u;
-                    const uint32_t n1 = (!full2 || draining) ? min(n_free - n2, c1) : 0u;
+                    const TqTake tk = tq_pass_take(q_count, q2_count, n_free, draining, TQ_CLASSES != 0u, (uint32_t)PT_TAILQ_MIN);
+                    const uint32_t n2 = tk.n2, n1 = tk.n1;
                     const bool take2 = !active && r < n2, take1 = !active && !take2 && r - n2 < n1;
                     const bool take = take1 || take2;
-                    const uint32_t e = take2 ? QUEUE_RING + ((q2_head + r) & (QR - 1u)) : ((q_head + (r - n2)) & (QR - 1u));
-                    q2_head += n2; q_head += n1;
+                    const uint32_t e = take2 ? QUEUE_RING + tq_pop_slot(q2_count, n2, r) : tq_pop_slot(q_count, n1, r - n2);
+                    q2_count -= n2; q_count -= n1;
                     bool ep = false;
                     if constexpr ((FEAT & FEAT_CC) != 0u) {
                         ShadeCtx C;

@@ -228,7 +228,8 @@ hipError_t launch_probe_occluded(const DevScene& sc, const float* o, const float
 
 
 uint64_t host_murmur_dim_seed(uint32_t dimension, uint32_t seed) { return murmur_dim_seed(dimension, seed); }
-size_t query_defer_bytes_per_wave() { return defer_bytes_per_wave(); }     // the deferral queues of pt_kernel.hpp (0: compiled out)
+// the queue memory a resident wave of the kernel launch_pt takes for `key` uses (pt_kernel.hpp queue_bytes_per_wave: the kernel's own stride)
+size_t query_defer_bytes_per_wave(const KernelKey& key) { return queue_bytes_per_wave(key.stats, key.set, key.mode); }
 // resident 64-thread blocks (= waves) on the current device of the kernel instantiation launch_pt takes for `key`, through the same lookup:
 // the persistent grid size.  The MODE specialisations are separate translation units with their own backend flags, so their register
 // counts — and with them the occupancy — need not be those of the generic variant.  Cached per scene and device (api.cpp LaunchCtx).

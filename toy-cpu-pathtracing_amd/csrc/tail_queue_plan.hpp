@@ -1,0 +1,39 @@
+// The tail queue's index arithmetic (pt_kernel.hpp TAIL QUEUE, pt_kernel_body.inc): which slot a push writes, which slots a pass reads and
+// how many records a pass takes from each of a wave's queues.  Plain integer functions of the wave-uniform counts — no HIP, no state — so
+// that tests/test_tail_queue_plan.py runs a wave's schedule on them without a GPU (constexpr: callable from the kernels as they stand).
+//
+// Each queue is a STACK: `count` records wait in slots [0, count).  A push of n records writes slots [count, count + n), a pass that takes
+// n reads slots [count - n, count) — the newest, which the front of the vertex stored a few hundred instructions earlier and which are
+// still in the L2; the bottom of the stack goes cold until the work item drains.  Consecutive ranks map to consecutive slots in both
+// directions: with the field-major layout of the records every store / load instruction of a wave covers whole 128-byte lines.
+//
+// Occupancy: a pass starts as soon as a queue holds pass_min (64) records, takes min(free lanes, count) and every lane is free after the
+// front, so a queue holds at most 63 after a pass and an iteration adds at most 64: with one queue count <= 127; with two, a pass empties
+// one of them to <= 63 while the other stays below 64, so both together hold <= 63 + 63 + 64 = 190 (the capacities: 128 and 2 x 256).
+#pragma once
+#include <cstdint>
+
+namespace pt {
+
+// slot of the record pushed by the lane of rank `rank` among the pushing lanes, `count` records waiting before the push
+constexpr uint32_t tq_push_slot(uint32_t count, uint32_t rank) { return count + rank; }
+// slot read by the lane of rank `rank` among the n lanes that take from a queue of `count` records (n <= count, rank < n)
+constexpr uint32_t tq_pop_slot(uint32_t count, uint32_t n, uint32_t rank) { return count - n + rank; }
+
+struct TqTake { uint32_t n1, n2; };      // records a pass takes from queue 1 (every other class) and queue 2 (the class with its own queue)
+
+// Is a pass due?  When a queue is full (pass_min records: a whole wave), or when the work item has no new paths left (`draining`) and
+// anything waits at all.  c2 is 0 in the kernels with one queue.
+constexpr bool tq_pass_due(uint32_t c1, uint32_t c2, bool draining, bool two_queues, uint32_t pass_min) {
+    return (two_queues && c2 >= pass_min) || c1 >= pass_min || (draining && (c1 | c2) != 0u);
+}
+// What the pass takes, n_free lanes being free: ONE class while new paths still arrive — queue 2 first —, and when the work item is
+// draining, whatever waits in either queue shares the pass (the first n2 free lanes take from queue 2, the next n1 from queue 1).
+constexpr TqTake tq_pass_take(uint32_t c1, uint32_t c2, uint32_t n_free, bool draining, bool two_queues, uint32_t pass_min) {
+    const bool full2 = two_queues && c2 >= pass_min, full1 = c1 >= pass_min;
+    const uint32_t n2 = (full2 || (draining && !full1)) ? (n_free < c2 ? n_free : c2) : 0u;
+    const uint32_t n1 = (!full2 || draining) ? (n_free - n2 < c1 ? n_free - n2 : c1) : 0u;
+    return TqTake{n1, n2};
+}
+
+}  // namespace pt
