@@ -312,4 +312,11 @@ const char* mi355pt_version(void);
  * mi355pt_render_accum_tiles_device above).  Declared in its own header, which this one always includes. */
 #include "mi355pt_adaptive.h"
 
+/* ---------------- variance-guided denoiser ---------------- */
+/* EXTENSION, no reference counterpart: a second filter beside the one above, which it leaves as it is — mi355pt_denoise_var_params,
+ * mi355pt_denoise_var_params_default, mi355pt_denoise_var_scratch_bytes, mi355pt_denoise_var_device and mi355pt_denoise_var: an a-trous
+ * filter whose luminance edge stop is scaled by the per-pixel variance that the film and the half film give.  Declared in its own header,
+ * which this one always includes. */
+#include "mi355pt_denoise_var.h"
+
 #endif /* MI355PT_H */

@@ -1,4 +1,4 @@
-// extern "C" boundary of libmi355pt.so (include/mi355pt.h, mi355pt_denoise.h; api_debug.cpp holds mi355pt_debug.h's).  Host C++ only;
+// extern "C" boundary of libmi355pt.so (include/mi355pt.h, mi355pt_denoise.h, mi355pt_denoise_var.h, mi355pt_adaptive.h; api_debug.cpp holds mi355pt_debug.h's).  Host C++ only;
 // the compute lives in pt_kernels.hip, the launch shape in launch_plan.hpp.
 #include <hip/hip_runtime.h>
 
@@ -643,6 +643,68 @@ int mi355pt_denoise(const float* beauty, uint32_t spp_b, const float* albedo, ui
     if (normal) { HIP_TRY(d_n.alloc(n)); HIP_TRY(hipMemcpy(d_n.p, normal, n * sizeof(float), hipMemcpyHostToDevice)); }
     if ((rc = mi355pt_denoise_device(d_b.p, spp_b, albedo ? d_a.p : nullptr, spp_a, normal ? d_n.p : nullptr, spp_n, width, height, dp, d_scratch.p,
                                      scratch_bytes, d_out.p, nullptr))) return rc;
+    HIP_TRY(hipMemcpy(out, d_out.p, n * sizeof(float), hipMemcpyDeviceToHost));      // (synchronises the default stream)
+    return MI355PT_OK;
+}
+
+// ---------------- variance-guided denoiser (include/mi355pt_denoise_var.h) ----------------
+
+void mi355pt_denoise_var_params_default(mi355pt_denoise_var_params* out) {
+    if (!out) return;
+    out->levels = 5; out->sigma_lum = 4.0f; out->sigma_normal = 0.5f; out->sigma_albedo = 0.3f; out->albedo_eps = 0.01f; out->lum_eps = 1e-4f;
+}
+size_t mi355pt_denoise_var_scratch_bytes(uint32_t width, uint32_t height) { return denoise_var_scratch_bytes(width, height); }
+
+// every check of mi355pt_denoise_var_device / mi355pt_denoise_var that does not concern the scratch; host arithmetic only
+static int denoise_var_check(const float* beauty, const float* half, uint32_t spp_b, const uint32_t* tile_spp, const float* albedo, uint32_t spp_a,
+                             const float* normal, uint32_t spp_n, uint32_t width, uint32_t height, const mi355pt_denoise_var_params* dp, const float* out) {
+    if (!beauty || !half || !out || !dp) return fail(MI355PT_E_INVALID, "denoise_var: null beauty, half film, output or params pointer");
+    if (dp->levels < 1 || dp->levels > 8) return fail(MI355PT_E_INVALID, "denoise_var: levels must be 1 .. 8 (mi355pt_denoise_var_params_default fills the struct)");
+    const float pos[5] = {dp->sigma_lum, dp->sigma_normal, dp->sigma_albedo, dp->albedo_eps, dp->lum_eps};
+    for (float v : pos)
+        if (!(std::isfinite(v) && v > 0.0f)) return fail(MI355PT_E_INVALID, "denoise_var: sigma_lum, sigma_normal, sigma_albedo, albedo_eps and lum_eps must be finite and > 0");
+    if (!tile_spp && (spp_b == 0 || (spp_b & 1u) != 0u)) return fail(MI355PT_E_INVALID, "denoise_var: spp_beauty must be even and > 0 (the half film holds the first spp_beauty / 2 samples)");
+    if (tile_spp && spp_b != 0) return fail(MI355PT_E_INVALID, "denoise_var: spp_beauty must be 0 when tile counts are given");
+    if ((albedo && spp_a == 0) || (normal && spp_n == 0)) return fail(MI355PT_E_INVALID, "denoise_var: spp of a given buffer is 0");
+    if (width == 0 || height == 0) return fail(MI355PT_E_INVALID, "denoise_var: zero width or height");
+    if (denoise_grid_blocks(width, height) == 0 || denoise_var_scratch_bytes(width, height) == 0) return fail(MI355PT_E_INVALID, "denoise_var: frame too large");
+    if (out == beauty || out == half || out == albedo || out == normal || (const void*)out == (const void*)tile_spp)
+        return fail(MI355PT_E_INVALID, "denoise_var: the output must not be one of the inputs");
+    return MI355PT_OK;
+}
+
+int mi355pt_denoise_var_device(const float* d_beauty, const float* d_half, uint32_t spp_b, const uint32_t* d_tile_spp, const float* d_albedo, uint32_t spp_a,
+                               const float* d_normal, uint32_t spp_n, uint32_t width, uint32_t height, const mi355pt_denoise_var_params* dp, void* d_scratch,
+                               size_t scratch_bytes, float* d_out, void* hip_stream) {
+    int rc = denoise_var_check(d_beauty, d_half, spp_b, d_tile_spp, d_albedo, spp_a, d_normal, spp_n, width, height, dp, d_out);
+    if (rc) return rc;
+    if (!d_scratch || scratch_bytes < denoise_var_scratch_bytes(width, height)) return fail(MI355PT_E_INVALID, "denoise_var: scratch missing or smaller than mi355pt_denoise_var_scratch_bytes");
+    if (((uintptr_t)d_scratch & 15u) != 0) return fail(MI355PT_E_INVALID, "denoise_var: scratch is not 16-byte aligned");
+    HIP_TRY(launch_denoise_var(d_beauty, d_half, spp_b, d_tile_spp, d_albedo, spp_a, d_normal, spp_n, width, height, dp->levels, dp->sigma_lum, dp->sigma_normal,
+                               dp->sigma_albedo, dp->albedo_eps, dp->lum_eps, d_scratch, d_out, (hipStream_t)hip_stream));
+    return MI355PT_OK;
+}
+
+int mi355pt_denoise_var(const float* beauty, const float* half_film, uint32_t spp_b, const uint32_t* tile_spp, const float* albedo, uint32_t spp_a,
+                        const float* normal, uint32_t spp_n, uint32_t width, uint32_t height, const mi355pt_denoise_var_params* dp, float* out) {
+    int rc = denoise_var_check(beauty, half_film, spp_b, tile_spp, albedo, spp_a, normal, spp_n, width, height, dp, out);
+    if (rc) return rc;
+    const size_t n = (size_t)width * height * 3, scratch_bytes = denoise_var_scratch_bytes(width, height);
+    const size_t n_tiles = (size_t)((width + 7u) / 8u) * ((height + 7u) / 8u);
+    DevBuf<float> d_b, d_h, d_a, d_n, d_out;
+    DevBuf<uint32_t> d_t;
+    DevBuf<unsigned char> d_scratch;
+    HIP_TRY(d_b.alloc(n));
+    HIP_TRY(d_h.alloc(n));
+    HIP_TRY(d_out.alloc(n));
+    HIP_TRY(d_scratch.alloc(scratch_bytes));
+    HIP_TRY(hipMemcpy(d_b.p, beauty, n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_h.p, half_film, n * sizeof(float), hipMemcpyHostToDevice));
+    if (tile_spp) { HIP_TRY(d_t.alloc(n_tiles)); HIP_TRY(hipMemcpy(d_t.p, tile_spp, n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice)); }
+    if (albedo) { HIP_TRY(d_a.alloc(n)); HIP_TRY(hipMemcpy(d_a.p, albedo, n * sizeof(float), hipMemcpyHostToDevice)); }
+    if (normal) { HIP_TRY(d_n.alloc(n)); HIP_TRY(hipMemcpy(d_n.p, normal, n * sizeof(float), hipMemcpyHostToDevice)); }
+    if ((rc = mi355pt_denoise_var_device(d_b.p, d_h.p, spp_b, tile_spp ? d_t.p : nullptr, albedo ? d_a.p : nullptr, spp_a, normal ? d_n.p : nullptr, spp_n, width,
+                                         height, dp, d_scratch.p, scratch_bytes, d_out.p, nullptr))) return rc;
     HIP_TRY(hipMemcpy(out, d_out.p, n * sizeof(float), hipMemcpyDeviceToHost));      // (synchronises the default stream)
     return MI355PT_OK;
 }

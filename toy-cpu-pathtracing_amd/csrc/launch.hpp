@@ -52,6 +52,12 @@ hipError_t launch_adaptive_step(const float* d_film, float* d_half, uint32_t wid
                                 float threshold, float dark_eps, uint32_t level_spp, uint32_t max_spp, void* d_scratch, uint32_t* d_list,
                                 uint32_t* d_count, hipStream_t);
 hipError_t launch_normalize_tiles(const float* d_film, const uint32_t* d_tile_spp, uint32_t width, uint32_t height, float* d_mean, hipStream_t);
+// pt_kernels_denoise_var.hip: the variance-guided a-trous denoiser (include/mi355pt_denoise_var.h); its level launches take the grid of
+// denoise_grid_blocks.  d_tile_spp == nullptr: every pixel has spp_b samples
+size_t denoise_var_scratch_bytes(uint32_t width, uint32_t height);
+hipError_t launch_denoise_var(const float* d_beauty, const float* d_half, uint32_t spp_b, const uint32_t* d_tile_spp, const float* d_albedo, uint32_t spp_a,
+                              const float* d_normal, uint32_t spp_n, uint32_t width, uint32_t height, uint32_t levels, float sigma_lum, float sigma_normal,
+                              float sigma_albedo, float albedo_eps, float lum_eps, void* d_scratch, float* d_out, hipStream_t);
 
 // Resident 64-thread blocks (= waves) of `kernel` on the current device: the persistent grid size of the EXACT instantiation a launch takes
 // (the register count, and so the occupancy, differs between instantiations and between translation units with their own backend flags).

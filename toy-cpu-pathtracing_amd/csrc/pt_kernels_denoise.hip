@@ -21,26 +21,13 @@
 #include <cstdint>
 
 #include "launch.hpp"
+#include "pt_denoise_common.hpp"
 
 namespace pt {
 
 namespace {
 
-constexpr int DN_BLOCK_X = 64, DN_BLOCK_Y = 4;
-
-// the B3-spline taps h = (1/16, 1/4, 3/8, 1/4, 1/16)
-__host__ __device__ constexpr float dn_h5(int k) { return (k == 0 || k == 4) ? 1.0f / 16.0f : ((k == 1 || k == 3) ? 1.0f / 4.0f : 3.0f / 8.0f); }
 __device__ __forceinline__ float dn_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-
-// c = B / spp, non-finite -> 0, max(c, 0) (NaN and -0 give +0); also a = max(A / spp, 0)
-__device__ __forceinline__ float dn_clean(float sum, float spp) {
-    const float c = sum / spp;
-    return (c > 0.0f && c <= FLT_MAX) ? c : 0.0f;
-}
-__device__ __forceinline__ float dn_clip0(float sum, float spp) {
-    const float a = sum / spp;
-    return a > 0.0f ? a : 0.0f;
-}
 
 __global__ __launch_bounds__(256) void denoise_prepass_kernel(const float* __restrict__ beauty, const float* __restrict__ albedo,
                                                               const float* __restrict__ normal, float spp_b, float spp_a, float spp_n,

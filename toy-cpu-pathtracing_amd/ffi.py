@@ -113,6 +113,12 @@ class DenoiseParams(C.Structure):
                 ("albedo_eps", C.c_float)]
 
 
+class DenoiseVarParams(C.Structure):
+    """mi355pt_denoise_var_params (include/mi355pt_denoise_var.h); Product.denoise_var_params_default() fills it — a zeroed one is refused"""
+    _fields_ = [("levels", C.c_uint32), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float),
+                ("albedo_eps", C.c_float), ("lum_eps", C.c_float)]
+
+
 class AdaptiveParams(C.Structure):
     """mi355pt_adaptive_params (include/mi355pt_adaptive.h): threshold has no default, and a zeroed struct is refused"""
     _fields_ = [("threshold", C.c_float), ("dark_eps", C.c_float), ("min_spp", C.c_uint32)]
@@ -150,6 +156,8 @@ ABI_SYMBOLS = [
 ]
 # ... include/mi355pt_denoise.h, the denoiser block mi355pt.h includes (tests/test_denoise.py checks these the same way)
 DENOISE_SYMBOLS = ["denoise_params_default", "denoise_scratch_bytes", "denoise_device", "denoise"]
+# ... include/mi355pt_denoise_var.h, the variance-guided denoiser block mi355pt.h includes (tests/test_denoise_var.py)
+DENOISE_VAR_SYMBOLS = ["denoise_var_params_default", "denoise_var_scratch_bytes", "denoise_var_device", "denoise_var"]
 # ... and include/mi355pt_adaptive.h, the adaptive-sampling block mi355pt.h includes (tests/test_adaptive.py)
 ADAPTIVE_SYMBOLS = ["adaptive_scratch_bytes", "adaptive_step_device", "film_normalize_tiles_device", "render_adaptive_device", "render_adaptive"]
 
@@ -380,6 +388,13 @@ class Product(Backend):
                                                    C.POINTER(DenoiseParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
             lib.mi355pt_denoise.argtypes = [C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float), C.c_uint32,
                                             C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), C.POINTER(C.c_float)]
+        if hasattr(lib, "mi355pt_denoise_var_device"):         # (absent from an older build loaded through MI355PT_LIB)
+            lib.mi355pt_denoise_var_params_default.argtypes = [C.POINTER(DenoiseVarParams)]; lib.mi355pt_denoise_var_params_default.restype = None
+            lib.mi355pt_denoise_var_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]; lib.mi355pt_denoise_var_scratch_bytes.restype = C.c_size_t
+            lib.mi355pt_denoise_var_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                       C.c_uint32, C.POINTER(DenoiseVarParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+            lib.mi355pt_denoise_var.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_uint32,
+                                                C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DenoiseVarParams), C.POINTER(C.c_float)]
         if hasattr(lib, "mi355pt_render_adaptive_device"):     # (absent from an older build loaded through MI355PT_LIB)
             lib.mi355pt_render_accum_tiles_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(C.c_uint32), C.c_uint32,
                                                               C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
@@ -467,6 +482,41 @@ class Product(Backend):
         out = np.zeros(b.shape, dtype=np.float32)
         self.check(self.lib.mi355pt_denoise(_ptr(b, C.c_float), spp_beauty, _ptr(a, C.c_float), spp_albedo, _ptr(n, C.c_float), spp_normal,
                                             b.shape[1], b.shape[0], C.byref(params), _ptr(out, C.c_float)), "denoise")
+        return out
+
+    # ---- the variance-guided denoiser (include/mi355pt_denoise_var.h): the film and the half film give the variance that scales its edge stop ----
+    def denoise_var_params_default(self):
+        p = DenoiseVarParams()
+        self.lib.mi355pt_denoise_var_params_default(C.byref(p))
+        return p
+
+    def denoise_var_scratch_bytes(self, width, height):
+        return int(self.lib.mi355pt_denoise_var_scratch_bytes(width, height))
+
+    def denoise_var_device(self, d_beauty_ptr, d_half_ptr, spp_beauty, d_tile_spp_ptr, d_albedo_ptr, spp_albedo, d_normal_ptr, spp_normal, width, height, params,
+                           d_scratch_ptr, scratch_bytes, d_out_ptr, stream=None):
+        """mi355pt_denoise_var_device on device pointers (films of linear SUMS, W*H*3 f32; tile counts, albedo / normal pointer None or 0 = not given;
+        with tile counts spp_beauty is 0); asynchronous on `stream`.  The output is a linear mean: resolve it with film_resolve_device(.., spp=1, ..)."""
+        self.check(self.lib.mi355pt_denoise_var_device(C.c_void_p(d_beauty_ptr), C.c_void_p(d_half_ptr), spp_beauty, C.c_void_p(d_tile_spp_ptr or 0),
+                                                       C.c_void_p(d_albedo_ptr or 0), spp_albedo, C.c_void_p(d_normal_ptr or 0), spp_normal, width, height,
+                                                       C.byref(params), C.c_void_p(d_scratch_ptr), scratch_bytes, C.c_void_p(d_out_ptr), C.c_void_p(stream or 0)),
+                   "denoise_var_device")
+
+    def denoise_var(self, beauty, half, spp_beauty, tile_spp=None, albedo=None, spp_albedo=0, normal=None, spp_normal=0, params=None):
+        """mi355pt_denoise_var on host arrays (H, W, 3) of linear sums (tile_spp: one uint32 per 8x8 tile, then spp_beauty = 0) -> (H, W, 3) float32
+        linear mean"""
+        b = np.ascontiguousarray(beauty, dtype=np.float32)
+        h = np.ascontiguousarray(half, dtype=np.float32)
+        assert b.ndim == 3 and b.shape[2] == 3
+        a = None if albedo is None else np.ascontiguousarray(albedo, dtype=np.float32)
+        n = None if normal is None else np.ascontiguousarray(normal, dtype=np.float32)
+        assert all(g is None or g.shape == b.shape for g in (h, a, n))
+        t = None if tile_spp is None else np.ascontiguousarray(tile_spp, dtype=np.uint32).reshape(-1)
+        assert t is None or t.size == ((b.shape[0] + 7) // 8) * ((b.shape[1] + 7) // 8)
+        params = params if params is not None else self.denoise_var_params_default()
+        out = np.zeros(b.shape, dtype=np.float32)
+        self.check(self.lib.mi355pt_denoise_var(_ptr(b, C.c_float), _ptr(h, C.c_float), spp_beauty, _ptr(t, C.c_uint32), _ptr(a, C.c_float), spp_albedo,
+                                                _ptr(n, C.c_float), spp_normal, b.shape[1], b.shape[0], C.byref(params), _ptr(out, C.c_float)), "denoise_var")
         return out
 
     def render_accum_device(self, scene, cam, params, s_begin, s_end, d_accum_ptr, stream=None, stats=None):

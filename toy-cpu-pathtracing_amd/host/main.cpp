@@ -6,7 +6,7 @@
 #include <cstdlib>
 #include <string>
 
-#include <hip/hip_runtime_api.h>   // --denoise and --adaptive-threshold: the films of those paths stay on the device (hipMalloc / hipMemcpy / hipFree, no kernels here)
+#include <hip/hip_runtime_api.h>   // --denoise, --denoise-variance and --adaptive-threshold: the films of those paths stay on the device (hipMalloc / hipMemcpy / hipFree, no kernels here)
 
 #include "scenes.hpp"
 
@@ -19,6 +19,8 @@ struct Args {   // main.rs:20-53
     bool albedo_lut = false; int gpus = 1;
     // not in the reference's CLI either: the a-trous denoiser (mi355pt_denoise.h) behind a path renderer, and the spp of its two guide films
     bool denoise = false; uint32_t denoise_guide_spp = 64;
+    // and the variance-guided one (mi355pt_denoise_var.h), which takes the film and a half film instead; 0 = its default sigma_lum
+    bool denoise_variance = false; float denoise_sigma_lum = 0.0f;
     // nor is adaptive sampling (mi355pt_adaptive.h): --spp becomes the maximum.  The threshold has no default (0 = not adaptive).
     // dark_eps 1e-3 is a CHOICE, not a measurement: a thousandth of the radiance of a mid-grey pixel, so that black pixels neither divide
     // by zero nor dominate a tile's estimate
@@ -56,8 +58,39 @@ static double render_denoised(const Scene& scene, const Camera& camera, mi355pt_
     return st.kernel_ms * 1e-3;
 }
 
+// --denoise-variance: the half film H = [0, spp / 2), the film F = H + [spp / 2, spp) — the pair the adaptive driver keeps, here at one
+// count for the whole frame —, the guide films as for --denoise, mi355pt_denoise_var_device, then Sensor::to_rgb on the result as a film
+// with spp 1.  Returns the device seconds of the two beauty launches.
+static mi355pt_denoise_var_params denoise_var_params(float sigma_lum) {
+    mi355pt_denoise_var_params dp;
+    mi355pt_denoise_var_params_default(&dp);
+    if (sigma_lum != 0.0f) dp.sigma_lum = sigma_lum;
+    return dp;
+}
+static double render_denoised_variance(const Scene& scene, const Camera& camera, mi355pt_params p, uint32_t guide_spp, float sigma_lum, std::vector<float>& pixels) {
+    const mi355pt_camera& cam = camera.raw();
+    const uint32_t n_pixels = cam.width * cam.height;
+    const size_t film_bytes = (size_t)n_pixels * 3 * sizeof(float), scratch_bytes = mi355pt_denoise_var_scratch_bytes(cam.width, cam.height);
+    DeviceFilm beauty(film_bytes), half(film_bytes), albedo(film_bytes), normal(film_bytes), out(film_bytes), rgb(film_bytes), scratch(scratch_bytes);
+    mi355pt_stats st0{}, st1{};
+    check(mi355pt_render_accum_device(scene.raw(), &cam, &p, 0, p.spp / 2, half.p, nullptr, &st0), "mi355pt_render_accum_device");
+    if (hipMemcpy(beauty.p, half.p, film_bytes, hipMemcpyDeviceToDevice) != hipSuccess) throw std::runtime_error("mi355pt: copying the half film failed");
+    check(mi355pt_render_accum_device(scene.raw(), &cam, &p, p.spp / 2, p.spp, beauty.p, nullptr, &st1), "mi355pt_render_accum_device");
+    mi355pt_params g = p;
+    g.spp = guide_spp;
+    check(mi355pt_render_aov_accum_device(scene.raw(), &cam, &g, MI355PT_AOV_ALBEDO, scene.d65_lut(), 0, guide_spp, albedo.p, nullptr, nullptr), "mi355pt_render_aov_accum_device");
+    check(mi355pt_render_aov_accum_device(scene.raw(), &cam, &g, MI355PT_AOV_SHADING_NORMAL, scene.d65_lut(), 0, guide_spp, normal.p, nullptr, nullptr), "mi355pt_render_aov_accum_device");
+    const mi355pt_denoise_var_params dp = denoise_var_params(sigma_lum);
+    check(mi355pt_denoise_var_device(beauty.p, half.p, p.spp, nullptr, albedo.p, guide_spp, normal.p, guide_spp, cam.width, cam.height, &dp, scratch.p, scratch_bytes,
+                                     out.p, nullptr), "mi355pt_denoise_var_device");
+    check(mi355pt_film_resolve_device(out.p, n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
+    if (hipMemcpy(pixels.data(), rgb.p, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the frame back failed");
+    return (st0.kernel_ms + st1.kernel_ms) * 1e-3;
+}
+
 // --adaptive-threshold: mi355pt_render_adaptive_device with --spp as the maximum, the per-tile means (a film with spp 1), optionally the
-// denoiser on them, then Sensor::to_rgb.  --spp-map writes the samples per tile as a grey picture, log2(tile_spp / min) / log2(max / min).
+// denoiser on them — or, with --denoise-variance, the driver's film, half film and tile counts straight into that filter, no normalise step
+// before it —, then Sensor::to_rgb.  --spp-map writes the samples per tile as a grey picture, log2(tile_spp / min) / log2(max / min).
 static void render_adaptive(const Scene& scene, const Camera& camera, mi355pt_params p, const Args& a, std::vector<float>& pixels) {
     const mi355pt_camera& cam = camera.raw();
     const uint32_t n_pixels = cam.width * cam.height, tiles_x = (cam.width + 7) / 8, n_tiles = tiles_x * ((cam.height + 7) / 8);
@@ -67,8 +100,20 @@ static void render_adaptive(const Scene& scene, const Camera& camera, mi355pt_pa
     mi355pt_adaptive_result res{};
     check(mi355pt_render_adaptive_device(scene.raw(), &cam, &p, &ap, film.p, half.p, (uint32_t*)tile_spp.p, tile_err.p, (uint32_t*)list.p, scratch.p, scratch_bytes,
                                          nullptr, &res), "mi355pt_render_adaptive_device");
-    check(mi355pt_film_normalize_tiles_device(film.p, (const uint32_t*)tile_spp.p, cam.width, cam.height, half.p, nullptr), "mi355pt_film_normalize_tiles_device");
-    if (a.denoise) {
+    if (a.denoise_variance) {
+        const uint32_t guide_spp = a.denoise_guide_spp;
+        const size_t dn_bytes = mi355pt_denoise_var_scratch_bytes(cam.width, cam.height);
+        DeviceFilm albedo(film_bytes), normal(film_bytes), out(film_bytes), dn_scratch(dn_bytes);
+        mi355pt_params g = p;
+        g.spp = guide_spp;
+        check(mi355pt_render_aov_accum_device(scene.raw(), &cam, &g, MI355PT_AOV_ALBEDO, scene.d65_lut(), 0, guide_spp, albedo.p, nullptr, nullptr), "mi355pt_render_aov_accum_device");
+        check(mi355pt_render_aov_accum_device(scene.raw(), &cam, &g, MI355PT_AOV_SHADING_NORMAL, scene.d65_lut(), 0, guide_spp, normal.p, nullptr, nullptr), "mi355pt_render_aov_accum_device");
+        const mi355pt_denoise_var_params dp = denoise_var_params(a.denoise_sigma_lum);
+        check(mi355pt_denoise_var_device(film.p, half.p, 0, (const uint32_t*)tile_spp.p, albedo.p, guide_spp, normal.p, guide_spp, cam.width, cam.height, &dp,
+                                         dn_scratch.p, dn_bytes, out.p, nullptr), "mi355pt_denoise_var_device");
+        check(mi355pt_film_resolve_device(out.p, n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
+    } else if (a.denoise) {
+        check(mi355pt_film_normalize_tiles_device(film.p, (const uint32_t*)tile_spp.p, cam.width, cam.height, half.p, nullptr), "mi355pt_film_normalize_tiles_device");
         const uint32_t guide_spp = a.denoise_guide_spp;
         const size_t dn_bytes = mi355pt_denoise_scratch_bytes(cam.width, cam.height);
         DeviceFilm albedo(film_bytes), normal(film_bytes), dn_scratch(dn_bytes);
@@ -81,6 +126,7 @@ static void render_adaptive(const Scene& scene, const Camera& camera, mi355pt_pa
         check(mi355pt_denoise_device(half.p, 1, albedo.p, guide_spp, normal.p, guide_spp, cam.width, cam.height, &dp, dn_scratch.p, dn_bytes, film.p, nullptr), "mi355pt_denoise_device");
         check(mi355pt_film_resolve_device(film.p, n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
     } else {
+        check(mi355pt_film_normalize_tiles_device(film.p, (const uint32_t*)tile_spp.p, cam.width, cam.height, half.p, nullptr), "mi355pt_film_normalize_tiles_device");
         check(mi355pt_film_resolve_device(half.p, n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
     }
     if (hipMemcpy(pixels.data(), rgb.p, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the frame back failed");
@@ -108,6 +154,8 @@ static void usage() {
               "       extensions: [--albedo-lut] (clearcoat albedo from its table instead of the 64-sample estimate)  [--gpus N]\n"
               "                   [--renderer shading-normal] (render-space shading normal of every surface: the AOV a denoiser takes)\n"
               "                   [--denoise] (pt|nee|mis: a-trous filter guided by the albedo and shading-normal films)  [--denoise-guide-spp N] (64)\n"
+              "                   [--denoise-variance] (pt|nee|mis, instead of --denoise: a-trous filter whose edge stop follows the variance that the film and a half\n"
+              "                                         film give; --spp even; with --adaptive-threshold it takes the driver's films)  [--denoise-sigma-lum X] (4)\n"
               "                   [--adaptive-threshold X] (pt|nee|mis: samples where the per-tile noise estimate is above X; --spp is the maximum)\n"
               "                   [--adaptive-min-spp N] (16)  [--adaptive-dark-eps E] (1e-3)  [--spp-map FILE] (samples per tile as a grey picture)");
 }
@@ -130,6 +178,8 @@ int main(int argc, char** argv) {
         else if (k == "--albedo-lut") a.albedo_lut = true;
         else if (k == "--gpus") a.gpus = std::stoi(val());
         else if (k == "--denoise") a.denoise = true;
+        else if (k == "--denoise-variance") a.denoise_variance = true;
+        else if (k == "--denoise-sigma-lum") a.denoise_sigma_lum = std::stof(val());
         else if (k == "--denoise-guide-spp") a.denoise_guide_spp = (uint32_t)std::stoul(val());
         else if (k == "--adaptive-threshold") a.adaptive_threshold = std::stof(val());
         else if (k == "--adaptive-min-spp") a.adaptive_min_spp = (uint32_t)std::stoul(val());
@@ -149,6 +199,11 @@ int main(int argc, char** argv) {
     if (a.denoise && aov) { std::fprintf(stderr, "error: --denoise with --renderer %s: the denoiser filters the frame of a path renderer (pt, nee, mis)\n", a.renderer.c_str()); return 2; }
     if (a.denoise && a.gpus > 1) { std::fprintf(stderr, "error: --denoise with --gpus %d: the denoiser runs on one GPU\n", a.gpus); return 2; }
     if (a.denoise && (a.denoise_guide_spp == 0 || a.spp == 0)) { std::fprintf(stderr, "error: --denoise needs --spp and --denoise-guide-spp above 0\n"); return 2; }
+    if (a.denoise_variance && a.denoise) { std::fprintf(stderr, "error: --denoise-variance with --denoise: one filter or the other\n"); return 2; }
+    if (a.denoise_variance && aov) { std::fprintf(stderr, "error: --denoise-variance with --renderer %s: the denoiser filters the frame of a path renderer (pt, nee, mis)\n", a.renderer.c_str()); return 2; }
+    if (a.denoise_variance && a.gpus > 1) { std::fprintf(stderr, "error: --denoise-variance with --gpus %d: the denoiser runs on one GPU\n", a.gpus); return 2; }
+    if (a.denoise_variance && (a.denoise_guide_spp == 0 || a.spp == 0 || (a.spp & 1u) != 0)) { std::fprintf(stderr, "error: --denoise-variance needs an even --spp (the half film holds the first half of the samples) and --denoise-guide-spp above 0\n"); return 2; }
+    if (a.denoise_sigma_lum != 0.0f && (!a.denoise_variance || !(a.denoise_sigma_lum > 0.0f) || !std::isfinite(a.denoise_sigma_lum))) { std::fprintf(stderr, "error: --denoise-sigma-lum needs --denoise-variance and a finite value above 0\n"); return 2; }
     const bool adaptive = a.adaptive_threshold != 0.0f;
     if (!adaptive && !a.spp_map.empty()) { std::fprintf(stderr, "error: --spp-map needs --adaptive-threshold\n"); return 2; }
     if (adaptive && aov) { std::fprintf(stderr, "error: --adaptive-threshold with --renderer %s: adaptive sampling is for the path renderers (pt, nee, mis)\n", a.renderer.c_str()); return 2; }
@@ -203,11 +258,12 @@ int main(int argc, char** argv) {
         const SamplerKind sampler = a.sampler == "sobol" ? SamplerKind::ZSobol : SamplerKind::Random;
         double kernel_s = 0.0;
         if (adaptive) render_adaptive(scene, camera, image.params(sampler, a.albedo_lut), a, image.pixels_mut());
+        else if (a.denoise_variance) kernel_s = render_denoised_variance(scene, camera, image.params(sampler, a.albedo_lut), a.denoise_guide_spp, a.denoise_sigma_lum, image.pixels_mut());
         else kernel_s = a.denoise ? render_denoised(scene, camera, image.params(sampler, a.albedo_lut), a.denoise_guide_spp, image.pixels_mut())
                                     : image.render(sampler, a.albedo_lut);
         double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         std::printf("Finish rendering: %.3f seconds.\n", wall);
-        if (kernel_s > 0.0 && a.denoise) std::printf("(beauty launch alone: device %.3f s, %.1f Msamples/s; the guide films and the filter are in the wall time above)\n", kernel_s, (double)a.width * a.height * a.spp / kernel_s / 1e6);
+        if (kernel_s > 0.0 && (a.denoise || a.denoise_variance)) std::printf("(beauty launch alone: device %.3f s, %.1f Msamples/s; the guide films and the filter are in the wall time above)\n", kernel_s, (double)a.width * a.height * a.spp / kernel_s / 1e6);
         else if (kernel_s > 0.0) std::printf("(device %.3f s, %.1f Msamples/s)\n", kernel_s, (double)a.width * a.height * a.spp / kernel_s / 1e6);
         image.save(a.output);
     } catch (const std::exception& e) {
