@@ -312,6 +312,13 @@ const char* mi355pt_version(void);
  * mi355pt_render_accum_tiles_device above).  Declared in its own header, which this one always includes. */
 #include "mi355pt_adaptive.h"
 
+/* ---------------- G-buffer pass ---------------- */
+/* EXTENSION, no reference counterpart: one primary-ray launch that writes the albedo, shading-normal, hit-position and hit-record films
+ * from the same rays — mi355pt_gbuffer_films, mi355pt_render_gbuffer_accum_device, mi355pt_gbuffer_normalize_device (coverage-normalised
+ * means: position, normal, depth) and mi355pt_render_gbuffer.  Declared in its own header, which this one always includes (ahead of the
+ * variance-guided denoiser's, which stays the last one). */
+#include "mi355pt_gbuffer.h"
+
 /* ---------------- variance-guided denoiser ---------------- */
 /* EXTENSION, no reference counterpart: a second filter beside the one above, which it leaves as it is — mi355pt_denoise_var_params,
  * mi355pt_denoise_var_params_default, mi355pt_denoise_var_scratch_bytes, mi355pt_denoise_var_device and mi355pt_denoise_var: an a-trous

@@ -21,6 +21,7 @@ struct LaunchCtx {
     int device = -1;                  // the device every buffer below lives on (= SceneImpl::device when the context was made)
     int waves[2][2][3] = {{{0}}};     // [instrumented][sampler][strategy]: resident waves of the kernel that combination launches (0: not asked yet)
     int aov_waves[3] = {0, 0, 0};     // [MI355PT_AOV_*]: the same for the AOV kernel of this scene's feature set
+    int gbuffer_waves = 0;            // ... and for the G-buffer kernel (pt_kernels_gbuffer.hip)
     uint64_t* d_hash = nullptr;
     uint32_t hash_seed = 0;
     bool hash_valid = false;

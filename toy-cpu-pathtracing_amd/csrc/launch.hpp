@@ -39,6 +39,13 @@ hipError_t launch_aov(uint32_t kind, const DevScene&, const DevCamera&, const De
                       unsigned* d_counter, DevStats* d_stats, uint32_t feat, int grid, hipStream_t);
 int query_resident_waves_aov(uint32_t kind, uint32_t feat);
 hipError_t launch_aov_resolve(uint32_t kind, const float* d_accum, uint32_t n_values, uint32_t spp, float* d_out, hipStream_t);
+// pt_kernels_gbuffer.hip: the G-buffer pass (include/mi355pt_gbuffer.h): one primary-ray launch, up to four films (nullptr = not wanted).
+// The plan must have block_log2 == 3 and chunks == 1 (api.cpp plan_gbuffer): one pixel per lane, its sums in registers
+struct GbufferFilms { float *albedo, *shading_normal, *position, *hit; };
+hipError_t launch_gbuffer(const DevScene&, const DevCamera&, const DevParams&, uint32_t illuminant_lut, const uint64_t* d_hash, const GbufferFilms&,
+                          unsigned* d_counter, DevStats* d_stats, uint32_t feat, int grid, hipStream_t);
+int query_resident_waves_gbuffer(uint32_t feat);
+hipError_t launch_gbuffer_normalize(const float* d_film, const float* d_hit, uint32_t n_pixels, float* d_out, hipStream_t);
 // pt_kernels_denoise.hip: the a-trous denoiser (include/mi355pt_denoise.h)
 size_t denoise_scratch_bytes(uint32_t width, uint32_t height);
 uint32_t denoise_grid_blocks(uint32_t width, uint32_t height);

@@ -129,6 +129,14 @@ class AdaptiveResult(C.Structure):
     _fields_ = [("passes", C.c_uint32), ("tiles_at_max", C.c_uint32), ("total_samples", C.c_uint64)]
 
 
+class GbufferFilms(C.Structure):
+    """mi355pt_gbuffer_films (include/mi355pt_gbuffer.h): device or host pointers, NULL = not wanted"""
+    _fields_ = [("albedo", C.c_void_p), ("shading_normal", C.c_void_p), ("position", C.c_void_p), ("hit", C.c_void_p)]
+
+
+GBUFFER_FILMS = ("albedo", "shading_normal", "position", "hit")
+
+
 def make_camera(position, direction, up, width, height, fov_deg=45.0):
     return Camera((C.c_float * 3)(*position), (C.c_float * 3)(*direction), (C.c_float * 3)(*up), fov_deg, width, height)
 
@@ -159,6 +167,8 @@ DENOISE_SYMBOLS = ["denoise_params_default", "denoise_scratch_bytes", "denoise_d
 # ... include/mi355pt_denoise_var.h, the variance-guided denoiser block mi355pt.h includes (tests/test_denoise_var.py)
 DENOISE_VAR_SYMBOLS = ["denoise_var_params_default", "denoise_var_scratch_bytes", "denoise_var_device", "denoise_var"]
 # ... and include/mi355pt_adaptive.h, the adaptive-sampling block mi355pt.h includes (tests/test_adaptive.py)
+# ... and include/mi355pt_gbuffer.h, the G-buffer block mi355pt.h includes (tests/test_gbuffer.py)
+GBUFFER_SYMBOLS = ["render_gbuffer_accum_device", "gbuffer_normalize_device", "render_gbuffer"]
 ADAPTIVE_SYMBOLS = ["adaptive_scratch_bytes", "adaptive_step_device", "film_normalize_tiles_device", "render_adaptive_device", "render_adaptive"]
 
 
@@ -406,6 +416,11 @@ class Product(Backend):
                 [C.c_size_t, C.c_void_p, C.POINTER(AdaptiveResult)]
             lib.mi355pt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AdaptiveParams), C.POINTER(C.c_float),
                                                     C.POINTER(C.c_uint32), C.POINTER(AdaptiveResult)]
+        if hasattr(lib, "mi355pt_render_gbuffer"):             # (absent from an older build loaded through MI355PT_LIB)
+            lib.mi355pt_render_gbuffer_accum_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_uint32, C.c_uint32,
+                                                                C.POINTER(GbufferFilms), C.c_void_p, C.POINTER(Stats)]
+            lib.mi355pt_gbuffer_normalize_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+            lib.mi355pt_render_gbuffer.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.POINTER(GbufferFilms), C.POINTER(Stats)]
         if not hasattr(lib, "mi355pt_render_sample_log"):      # an older build loaded through MI355PT_LIB for an A/B timing run
             return
         lib.mi355pt_sample_log_records.argtypes = [C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]
@@ -452,6 +467,26 @@ class Product(Backend):
     def aov_resolve_device(self, kind, d_accum_ptr, n_pixels, spp, d_out_ptr, stream=None):
         self.check(self.lib.mi355pt_aov_resolve_device(kind, C.c_void_p(d_accum_ptr), n_pixels, spp, C.c_void_p(d_out_ptr), C.c_void_p(stream or 0)),
                    "aov_resolve_device")
+
+    # ---- the G-buffer pass (include/mi355pt_gbuffer.h): albedo, shading-normal, position and hit films from one primary-ray launch ----
+    def render_gbuffer_accum_device(self, scene, cam, params, illuminant_lut, s_begin, s_end, films, stream=None, stats=None):
+        """mi355pt_render_gbuffer_accum_device: `films` maps film names (GBUFFER_FILMS) to device pointers; a name left out or None is not wanted"""
+        gf = GbufferFilms(*[C.c_void_p(films.get(k) or None) for k in GBUFFER_FILMS])
+        self.check(self.lib.mi355pt_render_gbuffer_accum_device(scene.h, C.byref(cam), C.byref(params), illuminant_lut, s_begin, s_end, C.byref(gf),
+                                                                C.c_void_p(stream or 0), C.byref(stats) if stats is not None else None),
+                   "render_gbuffer_accum_device")
+
+    def gbuffer_normalize_device(self, d_film_ptr, d_hit_ptr, n_pixels, d_out_ptr, stream=None):
+        self.check(self.lib.mi355pt_gbuffer_normalize_device(C.c_void_p(d_film_ptr), C.c_void_p(d_hit_ptr), n_pixels, C.c_void_p(d_out_ptr),
+                                                             C.c_void_p(stream or 0)), "gbuffer_normalize_device")
+
+    def render_gbuffer(self, scene, cam, params, illuminant_lut=0, films=GBUFFER_FILMS, want_stats=False):
+        """mi355pt_render_gbuffer -> {film name: (H, W, 3) float32 mean} for the names in `films` (albedo: resolved like render_aov's)"""
+        out = {k: np.zeros((cam.height, cam.width, 3), dtype=np.float32) for k in films}
+        gf = GbufferFilms(*[out[k].ctypes.data if k in out else None for k in GBUFFER_FILMS])
+        st = Stats()
+        self.check(self.lib.mi355pt_render_gbuffer(scene.h, C.byref(cam), C.byref(params), illuminant_lut, C.byref(gf), C.byref(st)), "render_gbuffer")
+        return (out, st) if want_stats else out
 
     # ---- the denoiser (include/mi355pt_denoise.h): an a-trous filter over the linear beauty film, guided by the albedo / shading-normal films ----
     def denoise_params_default(self):

@@ -25,6 +25,8 @@ struct Args {   // main.rs:20-53
     // dark_eps 1e-3 is a CHOICE, not a measurement: a thousandth of the radiance of a mid-grey pixel, so that black pixels neither divide
     // by zero nor dominate a tile's estimate
     float adaptive_threshold = 0.0f, adaptive_dark_eps = 1e-3f; uint32_t adaptive_min_spp = 16; std::string spp_map;
+    // nor the G-buffer pass (mi355pt_gbuffer.h): with a denoise flag, the two guide films from ONE launch of it instead of two AOV launches
+    bool fused_guides = false;
 };
 
 // --denoise: the beauty film at --spp, the albedo and shading-normal films at --denoise-guide-spp (converged guides cost a few percent of
@@ -39,17 +41,27 @@ struct DeviceFilm {
     DeviceFilm(const DeviceFilm&) = delete;
     DeviceFilm& operator=(const DeviceFilm&) = delete;
 };
-static double render_denoised(const Scene& scene, const Camera& camera, mi355pt_params p, uint32_t guide_spp, std::vector<float>& pixels) {
+// The two guide films of the denoise paths, guide_spp samples each into zeroed device films: two launches of the AOV kernel, or — `fused`,
+// --fused-guides — one launch of the G-buffer pass, whose two films then come from the same primary rays (the albedo film is the same bits
+// either way; the shading-normal film sees the albedo renderer's sub-pixel positions instead of its own)
+static void render_guides(const Scene& scene, const mi355pt_camera& cam, mi355pt_params g, uint32_t guide_spp, bool fused, float* d_albedo, float* d_normal) {
+    g.spp = guide_spp;
+    if (fused) {
+        const mi355pt_gbuffer_films films{d_albedo, d_normal, nullptr, nullptr};
+        check(mi355pt_render_gbuffer_accum_device(scene.raw(), &cam, &g, scene.d65_lut(), 0, guide_spp, &films, nullptr, nullptr), "mi355pt_render_gbuffer_accum_device");
+        return;
+    }
+    check(mi355pt_render_aov_accum_device(scene.raw(), &cam, &g, MI355PT_AOV_ALBEDO, scene.d65_lut(), 0, guide_spp, d_albedo, nullptr, nullptr), "mi355pt_render_aov_accum_device");
+    check(mi355pt_render_aov_accum_device(scene.raw(), &cam, &g, MI355PT_AOV_SHADING_NORMAL, scene.d65_lut(), 0, guide_spp, d_normal, nullptr, nullptr), "mi355pt_render_aov_accum_device");
+}
+static double render_denoised(const Scene& scene, const Camera& camera, mi355pt_params p, uint32_t guide_spp, bool fused, std::vector<float>& pixels) {
     const mi355pt_camera& cam = camera.raw();
     const uint32_t n_pixels = cam.width * cam.height;
     const size_t film_bytes = (size_t)n_pixels * 3 * sizeof(float), scratch_bytes = mi355pt_denoise_scratch_bytes(cam.width, cam.height);
     DeviceFilm beauty(film_bytes), albedo(film_bytes), normal(film_bytes), out(film_bytes), rgb(film_bytes), scratch(scratch_bytes);
     mi355pt_stats st{};
     check(mi355pt_render_accum_device(scene.raw(), &cam, &p, 0, p.spp, beauty.p, nullptr, &st), "mi355pt_render_accum_device");
-    mi355pt_params g = p;
-    g.spp = guide_spp;
-    check(mi355pt_render_aov_accum_device(scene.raw(), &cam, &g, MI355PT_AOV_ALBEDO, scene.d65_lut(), 0, guide_spp, albedo.p, nullptr, nullptr), "mi355pt_render_aov_accum_device");
-    check(mi355pt_render_aov_accum_device(scene.raw(), &cam, &g, MI355PT_AOV_SHADING_NORMAL, scene.d65_lut(), 0, guide_spp, normal.p, nullptr, nullptr), "mi355pt_render_aov_accum_device");
+    render_guides(scene, cam, p, guide_spp, fused, albedo.p, normal.p);
     mi355pt_denoise_params dp;
     mi355pt_denoise_params_default(&dp);
     check(mi355pt_denoise_device(beauty.p, p.spp, albedo.p, guide_spp, normal.p, guide_spp, cam.width, cam.height, &dp, scratch.p, scratch_bytes, out.p, nullptr), "mi355pt_denoise_device");
@@ -67,7 +79,7 @@ static mi355pt_denoise_var_params denoise_var_params(float sigma_lum) {
     if (sigma_lum != 0.0f) dp.sigma_lum = sigma_lum;
     return dp;
 }
-static double render_denoised_variance(const Scene& scene, const Camera& camera, mi355pt_params p, uint32_t guide_spp, float sigma_lum, std::vector<float>& pixels) {
+static double render_denoised_variance(const Scene& scene, const Camera& camera, mi355pt_params p, uint32_t guide_spp, bool fused, float sigma_lum, std::vector<float>& pixels) {
     const mi355pt_camera& cam = camera.raw();
     const uint32_t n_pixels = cam.width * cam.height;
     const size_t film_bytes = (size_t)n_pixels * 3 * sizeof(float), scratch_bytes = mi355pt_denoise_var_scratch_bytes(cam.width, cam.height);
@@ -76,10 +88,7 @@ static double render_denoised_variance(const Scene& scene, const Camera& camera,
     check(mi355pt_render_accum_device(scene.raw(), &cam, &p, 0, p.spp / 2, half.p, nullptr, &st0), "mi355pt_render_accum_device");
     if (hipMemcpy(beauty.p, half.p, film_bytes, hipMemcpyDeviceToDevice) != hipSuccess) throw std::runtime_error("mi355pt: copying the half film failed");
     check(mi355pt_render_accum_device(scene.raw(), &cam, &p, p.spp / 2, p.spp, beauty.p, nullptr, &st1), "mi355pt_render_accum_device");
-    mi355pt_params g = p;
-    g.spp = guide_spp;
-    check(mi355pt_render_aov_accum_device(scene.raw(), &cam, &g, MI355PT_AOV_ALBEDO, scene.d65_lut(), 0, guide_spp, albedo.p, nullptr, nullptr), "mi355pt_render_aov_accum_device");
-    check(mi355pt_render_aov_accum_device(scene.raw(), &cam, &g, MI355PT_AOV_SHADING_NORMAL, scene.d65_lut(), 0, guide_spp, normal.p, nullptr, nullptr), "mi355pt_render_aov_accum_device");
+    render_guides(scene, cam, p, guide_spp, fused, albedo.p, normal.p);
     const mi355pt_denoise_var_params dp = denoise_var_params(sigma_lum);
     check(mi355pt_denoise_var_device(beauty.p, half.p, p.spp, nullptr, albedo.p, guide_spp, normal.p, guide_spp, cam.width, cam.height, &dp, scratch.p, scratch_bytes,
                                      out.p, nullptr), "mi355pt_denoise_var_device");
@@ -104,10 +113,7 @@ static void render_adaptive(const Scene& scene, const Camera& camera, mi355pt_pa
         const uint32_t guide_spp = a.denoise_guide_spp;
         const size_t dn_bytes = mi355pt_denoise_var_scratch_bytes(cam.width, cam.height);
         DeviceFilm albedo(film_bytes), normal(film_bytes), out(film_bytes), dn_scratch(dn_bytes);
-        mi355pt_params g = p;
-        g.spp = guide_spp;
-        check(mi355pt_render_aov_accum_device(scene.raw(), &cam, &g, MI355PT_AOV_ALBEDO, scene.d65_lut(), 0, guide_spp, albedo.p, nullptr, nullptr), "mi355pt_render_aov_accum_device");
-        check(mi355pt_render_aov_accum_device(scene.raw(), &cam, &g, MI355PT_AOV_SHADING_NORMAL, scene.d65_lut(), 0, guide_spp, normal.p, nullptr, nullptr), "mi355pt_render_aov_accum_device");
+        render_guides(scene, cam, p, guide_spp, a.fused_guides, albedo.p, normal.p);
         const mi355pt_denoise_var_params dp = denoise_var_params(a.denoise_sigma_lum);
         check(mi355pt_denoise_var_device(film.p, half.p, 0, (const uint32_t*)tile_spp.p, albedo.p, guide_spp, normal.p, guide_spp, cam.width, cam.height, &dp,
                                          dn_scratch.p, dn_bytes, out.p, nullptr), "mi355pt_denoise_var_device");
@@ -117,10 +123,7 @@ static void render_adaptive(const Scene& scene, const Camera& camera, mi355pt_pa
         const uint32_t guide_spp = a.denoise_guide_spp;
         const size_t dn_bytes = mi355pt_denoise_scratch_bytes(cam.width, cam.height);
         DeviceFilm albedo(film_bytes), normal(film_bytes), dn_scratch(dn_bytes);
-        mi355pt_params g = p;
-        g.spp = guide_spp;
-        check(mi355pt_render_aov_accum_device(scene.raw(), &cam, &g, MI355PT_AOV_ALBEDO, scene.d65_lut(), 0, guide_spp, albedo.p, nullptr, nullptr), "mi355pt_render_aov_accum_device");
-        check(mi355pt_render_aov_accum_device(scene.raw(), &cam, &g, MI355PT_AOV_SHADING_NORMAL, scene.d65_lut(), 0, guide_spp, normal.p, nullptr, nullptr), "mi355pt_render_aov_accum_device");
+        render_guides(scene, cam, p, guide_spp, a.fused_guides, albedo.p, normal.p);
         mi355pt_denoise_params dp;
         mi355pt_denoise_params_default(&dp);
         check(mi355pt_denoise_device(half.p, 1, albedo.p, guide_spp, normal.p, guide_spp, cam.width, cam.height, &dp, dn_scratch.p, dn_bytes, film.p, nullptr), "mi355pt_denoise_device");
@@ -148,6 +151,23 @@ static void render_adaptive(const Scene& scene, const Camera& camera, mi355pt_pa
     }
 }
 
+// --renderer position | depth: the G-buffer pass's position and hit films at --spp, coverage-normalised on the device
+// (mi355pt_gbuffer_normalize_device): the mean render-space hit position over the samples that hit, or the mean distance along the unit ray
+// replicated to RGB; 0 where no sample hit.  Float output: `pixels` goes to a PFM as it is.  Returns the device seconds of the launch.
+static double render_gbuffer_float(const Scene& scene, const Camera& camera, mi355pt_params p, bool depth, std::vector<float>& pixels) {
+    const mi355pt_camera& cam = camera.raw();
+    const uint32_t n_pixels = cam.width * cam.height;
+    const size_t film_bytes = (size_t)n_pixels * 3 * sizeof(float);
+    DeviceFilm position(depth ? sizeof(float) : film_bytes), hit(film_bytes), out(film_bytes);
+    const mi355pt_gbuffer_films films{nullptr, nullptr, depth ? nullptr : position.p, hit.p};
+    mi355pt_stats st{};
+    check(mi355pt_render_gbuffer_accum_device(scene.raw(), &cam, &p, scene.d65_lut(), 0, p.spp, &films, nullptr, &st), "mi355pt_render_gbuffer_accum_device");
+    check(mi355pt_gbuffer_normalize_device(depth ? hit.p : position.p, hit.p, n_pixels, out.p, nullptr), "mi355pt_gbuffer_normalize_device");
+    if (hipMemcpy(pixels.data(), out.p, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the frame back failed");
+    if (depth) for (uint32_t i = 0; i < n_pixels; ++i) pixels[3 * (size_t)i + 1] = pixels[3 * (size_t)i + 2] = pixels[3 * (size_t)i];
+    return st.kernel_ms * 1e-3;
+}
+
 static void usage() {
     std::puts("Usage: mi355pt [--scene N] [-s|--spp N] [--seed N] [--filter box] [--sampler random|sobol]\n"
               "               [--renderer normal|albedo|pt|nee|mis] [--width N] [--height N] [-d|--max-depth N] [-o|--output FILE]\n"
@@ -157,7 +177,10 @@ static void usage() {
               "                   [--denoise-variance] (pt|nee|mis, instead of --denoise: a-trous filter whose edge stop follows the variance that the film and a half\n"
               "                                         film give; --spp even; with --adaptive-threshold it takes the driver's films)  [--denoise-sigma-lum X] (4)\n"
               "                   [--adaptive-threshold X] (pt|nee|mis: samples where the per-tile noise estimate is above X; --spp is the maximum)\n"
-              "                   [--adaptive-min-spp N] (16)  [--adaptive-dark-eps E] (1e-3)  [--spp-map FILE] (samples per tile as a grey picture)");
+              "                   [--adaptive-min-spp N] (16)  [--adaptive-dark-eps E] (1e-3)  [--spp-map FILE] (samples per tile as a grey picture)\n"
+              "                   [--renderer position|depth] (the G-buffer pass: mean render-space hit position / mean distance over the samples that hit,\n"
+              "                                                0 where none did; float output, -o must end in .pfm)\n"
+              "                   [--fused-guides] (with --denoise or --denoise-variance: both guide films from one G-buffer launch, the same primary rays)");
 }
 
 int main(int argc, char** argv) {
@@ -185,16 +208,23 @@ int main(int argc, char** argv) {
         else if (k == "--adaptive-min-spp") a.adaptive_min_spp = (uint32_t)std::stoul(val());
         else if (k == "--adaptive-dark-eps") a.adaptive_dark_eps = std::stof(val());
         else if (k == "--spp-map") a.spp_map = val();
+        else if (k == "--fused-guides") a.fused_guides = true;
         else if (k == "-h" || k == "--help") { usage(); return 0; }
         else { std::fprintf(stderr, "error: unexpected argument '%s'\n", k.c_str()); usage(); return 2; }
     }
     if (a.filter != "box") { std::fprintf(stderr, "error: invalid value '%s' for '--filter' (main.rs:33-37 offers only box)\n", a.filter.c_str()); return 2; }
     if (a.sampler != "random" && a.sampler != "sobol") { std::fprintf(stderr, "error: invalid value '%s' for '--sampler'\n", a.sampler.c_str()); return 2; }
-    const bool aov = a.renderer == "normal" || a.renderer == "albedo" || a.renderer == "shading-normal";
+    const bool gbuf = a.renderer == "position" || a.renderer == "depth";
+    const bool aov = gbuf || a.renderer == "normal" || a.renderer == "albedo" || a.renderer == "shading-normal";   // (the primary-ray renderers)
     if (!aov && a.renderer != "pt" && a.renderer != "nee" && a.renderer != "mis") {
-        std::fprintf(stderr, "error: invalid value '%s' for '--renderer' (main.rs:38-40: normal, albedo, pt, nee, mis; extension: shading-normal)\n", a.renderer.c_str());
+        std::fprintf(stderr, "error: invalid value '%s' for '--renderer' (main.rs:38-40: normal, albedo, pt, nee, mis; extensions: shading-normal, position, depth)\n", a.renderer.c_str());
         return 2;
     }
+    if (gbuf && (a.output.size() < 4 || a.output.compare(a.output.size() - 4, 4, ".pfm") != 0)) {
+        std::fprintf(stderr, "error: --renderer %s writes float values: -o must end in .pfm (got '%s')\n", a.renderer.c_str(), a.output.c_str());
+        return 2;
+    }
+    if (a.fused_guides && !a.denoise && !a.denoise_variance) { std::fprintf(stderr, "error: --fused-guides needs --denoise or --denoise-variance: it renders their guide films\n"); return 2; }
     if (aov && a.gpus > 1) { std::fprintf(stderr, "error: --gpus %d with --renderer %s: the AOV renderers run on one GPU\n", a.gpus, a.renderer.c_str()); return 2; }
     if (a.denoise && aov) { std::fprintf(stderr, "error: --denoise with --renderer %s: the denoiser filters the frame of a path renderer (pt, nee, mis)\n", a.renderer.c_str()); return 2; }
     if (a.denoise && a.gpus > 1) { std::fprintf(stderr, "error: --denoise with --gpus %d: the denoiser runs on one GPU\n", a.gpus); return 2; }
@@ -251,21 +281,22 @@ int main(int argc, char** argv) {
         else if (a.renderer == "mis") r = SrgbRendererMis(args, 1.0f, a.max_depth);
         else if (a.renderer == "normal") r = NormalRenderer(args);                      // main.rs:155-170
         else if (a.renderer == "albedo") r = AlbedoRenderer(args);                      // main.rs:171-186
-        else r = ShadingNormalRenderer(args);
+        else r = ShadingNormalRenderer(args);                                           // (position / depth: its params; the G-buffer pass renders)
         RendererImage image(a.width, a.height, r);
         std::puts("Start rendering...");                                                // main.rs:166-172
         t0 = std::chrono::steady_clock::now();
         const SamplerKind sampler = a.sampler == "sobol" ? SamplerKind::ZSobol : SamplerKind::Random;
         double kernel_s = 0.0;
-        if (adaptive) render_adaptive(scene, camera, image.params(sampler, a.albedo_lut), a, image.pixels_mut());
-        else if (a.denoise_variance) kernel_s = render_denoised_variance(scene, camera, image.params(sampler, a.albedo_lut), a.denoise_guide_spp, a.denoise_sigma_lum, image.pixels_mut());
-        else kernel_s = a.denoise ? render_denoised(scene, camera, image.params(sampler, a.albedo_lut), a.denoise_guide_spp, image.pixels_mut())
+        if (gbuf) kernel_s = render_gbuffer_float(scene, camera, image.params(sampler, a.albedo_lut), a.renderer == "depth", image.pixels_mut());
+        else if (adaptive) render_adaptive(scene, camera, image.params(sampler, a.albedo_lut), a, image.pixels_mut());
+        else if (a.denoise_variance) kernel_s = render_denoised_variance(scene, camera, image.params(sampler, a.albedo_lut), a.denoise_guide_spp, a.fused_guides, a.denoise_sigma_lum, image.pixels_mut());
+        else kernel_s = a.denoise ? render_denoised(scene, camera, image.params(sampler, a.albedo_lut), a.denoise_guide_spp, a.fused_guides, image.pixels_mut())
                                     : image.render(sampler, a.albedo_lut);
         double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         std::printf("Finish rendering: %.3f seconds.\n", wall);
         if (kernel_s > 0.0 && (a.denoise || a.denoise_variance)) std::printf("(beauty launch alone: device %.3f s, %.1f Msamples/s; the guide films and the filter are in the wall time above)\n", kernel_s, (double)a.width * a.height * a.spp / kernel_s / 1e6);
         else if (kernel_s > 0.0) std::printf("(device %.3f s, %.1f Msamples/s)\n", kernel_s, (double)a.width * a.height * a.spp / kernel_s / 1e6);
-        image.save(a.output);
+        if (gbuf) write_pfm(a.output, image.pixels().data(), a.width, a.height); else image.save(a.output);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "mi355pt: %s\n", e.what());
         return 1;

@@ -290,6 +290,15 @@ inline std::vector<float> load_pfm(const std::string& path, uint32_t* w, uint32_
     for (uint32_t y = 0; y < *h; ++y) std::memcpy(&out[(size_t)y * *w * 3], &raw[(size_t)(*h - 1 - y) * *w * 3], (size_t)*w * 3 * sizeof(float));
     return out;
 }
+// the other way: top-to-bottom h*w*3 floats -> a little-endian colour PFM (scale -1), rows bottom to top; every value keeps its bits
+// (the float output of the CLI's position and depth renderers)
+inline void write_pfm(const std::string& path, const float* rgb, uint32_t w, uint32_t h) {
+    std::ofstream f(path, std::ios::binary);
+    if (!f) throw std::runtime_error("cannot write " + path);
+    f << "PF\n" << w << " " << h << "\n-1.0\n";
+    for (uint32_t y = h; y-- > 0;) f.write((const char*)&rgb[(size_t)y * w * 3], (std::streamsize)((size_t)w * 3 * sizeof(float)));
+    if (!f) throw std::runtime_error(path + ": write failed");
+}
 // float RGB environment maps as the reference reads them: OpenEXR through image::open(..).to_rgb32f() (environment_light.rs:30-41).
 // Own reader for the scanline subset HDR skies ship in: single part, NO / ZIPS / ZIP compression (the zlib inflate above + OpenEXR's
 // byte predictor and de-interleave), HALF or FLOAT channels R, G, B (other channels such as A are skipped), either line order.
