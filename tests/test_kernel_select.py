@@ -3,11 +3,13 @@ every input it can get, with a restatement of the rules as the plain launcher, t
 them out before they shared one lookup, and the single list of compiled feature sets against its two classes."""
 import itertools
 import os
-import subprocess
+import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_matrix import compile_selector  # noqa: E402
+
 TEX, DIEL, CC, MLIGHT, ROUGH, METAL, DELTA, ENV, EMTEX = (1 << i for i in range(9))
 STD, ALL = 255, 511
 GENERIC, MIS_SOBOL, NEE_SOBOL, PT = 0, 1, 2, 3
@@ -33,18 +35,7 @@ def former_key(tiles, stats, feat, sampler, strategy):
 
 @pytest.fixture(scope="module")
 def selector(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("kernel_select") / "kernel_select_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "toy-cpu-pathtracing_amd", "csrc"), "-o", exe,
-                    os.path.join(ROOT, "tests", "kernel_select_check.cpp")], check=True)
-    out = {"k": {}}
-    for line in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines():
-        tag, *vals = line.split()
-        vals = list(map(int, vals))
-        if tag == "k":
-            out["k"][tuple(vals[:5])] = tuple(vals[5:])
-        else:
-            out[tag] = vals
-    return out
+    return compile_selector(tmp_path_factory.mktemp("kernel_select"))
 
 
 def test_feature_sets_are_one_list_in_two_classes(selector):
