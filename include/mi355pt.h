@@ -319,6 +319,14 @@ const char* mi355pt_version(void);
  * variance-guided denoiser's, which stays the last one). */
 #include "mi355pt_gbuffer.h"
 
+/* ---------------- temporal reprojection ---------------- */
+/* EXTENSION, no reference counterpart: the consumer of the position and hit films — mi355pt_temporal_view, mi355pt_temporal_params,
+ * mi355pt_temporal_frame, mi355pt_temporal_params_default, mi355pt_temporal_view_from_cameras, mi355pt_temporal_accumulate_device and
+ * mi355pt_temporal_accumulate: the previous frame's accumulated film pair, gathered where each pixel's hit position lands in the previous
+ * camera, blended with the current frame.  Declared in its own header, which this one always includes (ahead of the variance-guided
+ * denoiser's, which takes the accumulated pair as it is). */
+#include "mi355pt_temporal.h"
+
 /* ---------------- variance-guided denoiser ---------------- */
 /* EXTENSION, no reference counterpart: a second filter beside the one above, which it leaves as it is — mi355pt_denoise_var_params,
  * mi355pt_denoise_var_params_default, mi355pt_denoise_var_scratch_bytes, mi355pt_denoise_var_device and mi355pt_denoise_var: an a-trous

@@ -1,0 +1,150 @@
+// The mi355pt_temporal.h surface of libmi355pt.so: the view of a camera pair (host arithmetic), the argument checks and the two entry
+// points of the temporal reprojection.  Host C++ only, like api.cpp; the kernel is pt_kernels_temporal.hip.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <string>
+
+#include "api_internal.hpp"
+
+using namespace pt;
+
+namespace {
+
+bool normalize3(const float v[3], double out[3]) {
+    const double x = v[0], y = v[1], z = v[2], l = std::sqrt(x * x + y * y + z * z);
+    if (!(std::isfinite(l) && l > 0.0)) return false;
+    out[0] = x / l; out[1] = y / l; out[2] = z / l;
+    return true;
+}
+
+// every check of mi355pt_temporal_accumulate_device / mi355pt_temporal_accumulate; host arithmetic only
+int temporal_check(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev, const mi355pt_temporal_view* view, uint32_t width,
+                   uint32_t height, const mi355pt_temporal_params* tp, const float* out_film, const float* out_half, const float* out_length) {
+    if (!cur || !tp || !out_film || !out_length) return fail(MI355PT_E_INVALID, "temporal: null current frame, params, output film or output length pointer");
+    if ((prev == nullptr) != (view == nullptr)) return fail(MI355PT_E_INVALID, "temporal: the previous frame and the view must both be given or both be NULL");
+    if (!cur->film || !cur->position || !cur->shading_normal || !cur->hit)
+        return fail(MI355PT_E_INVALID, "temporal: the current frame needs its film, position, shading_normal and hit films");
+    if (prev && (!prev->film || !prev->length || !prev->position || !prev->shading_normal || !prev->hit))
+        return fail(MI355PT_E_INVALID, "temporal: the previous frame needs its film, length, position, shading_normal and hit films");
+    const bool half = cur->half != nullptr;
+    if ((out_half != nullptr) != half || (prev && (prev->half != nullptr) != half))
+        return fail(MI355PT_E_INVALID, "temporal: the half films of the current frame, the previous frame and the output must all be given or all be NULL");
+    if (spp == 0 || (half && (spp & 1u) != 0u)) return fail(MI355PT_E_INVALID, "temporal: spp must be > 0, and even with a half film (it holds the first spp / 2 samples)");
+    if (width == 0 || height == 0) return fail(MI355PT_E_INVALID, "temporal: zero width or height");
+    if (width > (1u << 24) || height > (1u << 24) || denoise_grid_blocks(width, height) == 0) return fail(MI355PT_E_INVALID, "temporal: frame too large");
+    const float pos[3] = {tp->pos_tol, tp->min_weight, tp->max_history};
+    for (float v : pos)
+        if (!(std::isfinite(v) && v > 0.0f))
+            return fail(MI355PT_E_INVALID, "temporal: pos_tol, min_weight and max_history must be finite and > 0 (mi355pt_temporal_params_default fills the struct)");
+    if (tp->max_history < 1.0f) return fail(MI355PT_E_INVALID, "temporal: max_history must be >= 1");
+    if (!(tp->normal_cos >= -1.0f && tp->normal_cos <= 1.0f)) return fail(MI355PT_E_INVALID, "temporal: normal_cos must be in [-1, 1]");
+    const float* in[11] = {cur->film, cur->half, cur->position, cur->shading_normal, cur->hit, prev ? prev->film : nullptr, prev ? prev->half : nullptr,
+                           prev ? prev->length : nullptr, prev ? prev->position : nullptr, prev ? prev->shading_normal : nullptr, prev ? prev->hit : nullptr};
+    const float* out[3] = {out_film, out_half, out_length};
+    for (int i = 0; i < 3; ++i) {
+        if (!out[i]) continue;
+        for (const float* q : in)
+            if (q == out[i]) return fail(MI355PT_E_INVALID, "temporal: an output must not be one of the inputs");
+        for (int j = i + 1; j < 3; ++j)
+            if (out[j] == out[i]) return fail(MI355PT_E_INVALID, "temporal: two outputs are the same buffer");
+    }
+    return MI355PT_OK;
+}
+
+TemporalFrameDev frame_dev(const mi355pt_temporal_frame& f) {
+    TemporalFrameDev d;
+    d.film = f.film; d.half = f.half; d.length = f.length; d.position = f.position; d.shading_normal = f.shading_normal; d.hit = f.hit;
+    return d;
+}
+
+}  // namespace
+
+extern "C" {
+
+void mi355pt_temporal_params_default(mi355pt_temporal_params* out) {
+    if (!out) return;
+    out->pos_tol = 0.01f; out->normal_cos = 0.9f; out->min_weight = 0.01f; out->max_history = 32.0f;
+}
+
+int mi355pt_temporal_view_from_cameras(const mi355pt_camera* cur, const mi355pt_camera* prev, mi355pt_temporal_view* out) {
+    if (!cur || !prev || !out) return fail(MI355PT_E_INVALID, "temporal view: null argument");
+    if (cur->width == 0 || cur->height == 0 || cur->width != prev->width || cur->height != prev->height)
+        return fail(MI355PT_E_INVALID, "temporal view: the two cameras must have the same non-zero width and height");
+    if (!(cur->fov_deg == prev->fov_deg)) return fail(MI355PT_E_INVALID, "temporal view: the two cameras must have the same fov_deg");
+    double f[3], up[3];
+    if (!normalize3(prev->direction, f) || !normalize3(prev->up, up)) return fail(MI355PT_E_INVALID, "temporal view: zero direction or up");
+    // look_to_rh(direction, up): s = normalize(f x up), u = s x f; the rows of world -> camera are s, u, -f
+    const double c[3] = {f[1] * up[2] - f[2] * up[1], f[2] * up[0] - f[0] * up[2], f[0] * up[1] - f[1] * up[0]};
+    const double cl = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+    if (!(std::isfinite(cl) && cl > 1e-12)) return fail(MI355PT_E_INVALID, "temporal view: direction is parallel to up");
+    const double s[3] = {c[0] / cl, c[1] / cl, c[2] / cl};
+    const double u[3] = {s[1] * f[2] - s[2] * f[1], s[2] * f[0] - s[0] * f[2], s[0] * f[1] - s[1] * f[0]};
+    const double w = (double)cur->width, h = (double)cur->height;
+    const double scale = std::tan((double)prev->fov_deg * (3.14159265358979323846 / 180.0) / 2.0);
+    if (!(std::isfinite(scale) && scale > 0.0)) return fail(MI355PT_E_INVALID, "temporal view: fov_deg must be in (0, 180)");
+    for (int i = 0; i < 3; ++i) {
+        out->delta[i] = (float)((double)cur->position[i] - (double)prev->position[i]);
+        out->rows[i] = (float)s[i]; out->rows[3 + i] = (float)u[i]; out->rows[6 + i] = (float)-f[i];
+    }
+    out->sx = (float)((w / 2.0) / ((w / h) * scale));
+    out->sy = (float)((h / 2.0) / scale);
+    out->cx = (float)(w / 2.0);
+    out->cy = (float)(h / 2.0);
+    return MI355PT_OK;
+}
+
+int mi355pt_temporal_accumulate_device(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev, const mi355pt_temporal_view* view,
+                                       uint32_t width, uint32_t height, const mi355pt_temporal_params* tp, float* d_out_film, float* d_out_half,
+                                       float* d_out_length, void* hip_stream) {
+    int rc = temporal_check(cur, spp, prev, view, width, height, tp, d_out_film, d_out_half, d_out_length);
+    if (rc) return rc;
+    TemporalArgs a{};
+    a.width = width; a.height = height;
+    a.spp = (float)spp; a.half_spp = (float)(spp >> 1);
+    a.wf = (float)width; a.hf = (float)height;
+    if (view) {
+        for (int i = 0; i < 3; ++i) a.delta[i] = view->delta[i];
+        for (int i = 0; i < 9; ++i) a.rows[i] = view->rows[i];
+        a.sx = view->sx; a.sy = view->sy; a.cx = view->cx; a.cy = view->cy;
+    }
+    a.pos_tol = tp->pos_tol; a.normal_cos = tp->normal_cos; a.min_weight = tp->min_weight; a.max_history = tp->max_history;
+    const TemporalFrameDev dc = frame_dev(*cur), dp = prev ? frame_dev(*prev) : TemporalFrameDev{};
+    HIP_TRY(launch_temporal_accumulate(dc, prev ? &dp : nullptr, a, d_out_film, d_out_half, d_out_length, (hipStream_t)hip_stream));
+    return MI355PT_OK;
+}
+
+int mi355pt_temporal_accumulate(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev, const mi355pt_temporal_view* view,
+                                uint32_t width, uint32_t height, const mi355pt_temporal_params* tp, float* out_film, float* out_half, float* out_length) {
+    int rc = temporal_check(cur, spp, prev, view, width, height, tp, out_film, out_half, out_length);
+    if (rc) return rc;
+    const size_t np = (size_t)width * height, n = np * 3;
+    // the films of the two frames in the order of mi355pt_temporal_frame (length: W x H; the current frame's is ignored)
+    DevBuf<float> d_in[2][6], d_film, d_half, d_len;
+    mi355pt_temporal_frame dev[2] = {};
+    const mi355pt_temporal_frame* host[2] = {cur, prev};
+    for (int k = 0; k < 2; ++k) {
+        if (!host[k]) continue;
+        const float* src[6] = {host[k]->film, host[k]->half, k == 0 ? nullptr : host[k]->length, host[k]->position, host[k]->shading_normal, host[k]->hit};
+        const float* dst[6] = {};
+        for (int i = 0; i < 6; ++i) {
+            if (!src[i]) continue;
+            const size_t count = i == 2 ? np : n;
+            HIP_TRY(d_in[k][i].alloc(count));
+            HIP_TRY(hipMemcpy(d_in[k][i].p, src[i], count * sizeof(float), hipMemcpyHostToDevice));
+            dst[i] = d_in[k][i].p;
+        }
+        dev[k].film = dst[0]; dev[k].half = dst[1]; dev[k].length = dst[2]; dev[k].position = dst[3]; dev[k].shading_normal = dst[4]; dev[k].hit = dst[5];
+    }
+    HIP_TRY(d_film.alloc(n));
+    HIP_TRY(d_len.alloc(np));
+    if (out_half) HIP_TRY(d_half.alloc(n));
+    if ((rc = mi355pt_temporal_accumulate_device(&dev[0], spp, prev ? &dev[1] : nullptr, view, width, height, tp, d_film.p, out_half ? d_half.p : nullptr,
+                                                 d_len.p, nullptr))) return rc;
+    HIP_TRY(hipMemcpy(out_film, d_film.p, n * sizeof(float), hipMemcpyDeviceToHost));      // (synchronises the default stream)
+    if (out_half) HIP_TRY(hipMemcpy(out_half, d_half.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_length, d_len.p, np * sizeof(float), hipMemcpyDeviceToHost));
+    return MI355PT_OK;
+}
+
+}  // extern "C"

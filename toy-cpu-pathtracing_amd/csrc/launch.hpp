@@ -65,6 +65,19 @@ size_t denoise_var_scratch_bytes(uint32_t width, uint32_t height);
 hipError_t launch_denoise_var(const float* d_beauty, const float* d_half, uint32_t spp_b, const uint32_t* d_tile_spp, const float* d_albedo, uint32_t spp_a,
                               const float* d_normal, uint32_t spp_n, uint32_t width, uint32_t height, uint32_t levels, float sigma_lum, float sigma_normal,
                               float sigma_albedo, float albedo_eps, float lum_eps, void* d_scratch, float* d_out, hipStream_t);
+// pt_kernels_temporal.hip: the temporal reprojection (include/mi355pt_temporal.h): one launch on the grid of denoise_grid_blocks.
+// A frame's films as the kernel takes them (half == nullptr: no half film; length is read of the previous frame only); prev == nullptr:
+// the first frame.  The launcher fills TemporalArgs::blocks_x
+struct TemporalFrameDev { const float *film = nullptr, *half = nullptr, *length = nullptr, *position = nullptr, *shading_normal = nullptr, *hit = nullptr; };
+struct TemporalArgs {
+    uint32_t width, height, blocks_x;
+    float spp, half_spp;                    // (float)spp, (float)(spp / 2)
+    float wf, hf;                           // (float)width, (float)height
+    float delta[3], rows[9], sx, sy, cx, cy;
+    float pos_tol, normal_cos, min_weight, max_history;
+};
+hipError_t launch_temporal_accumulate(const TemporalFrameDev& cur, const TemporalFrameDev* prev, TemporalArgs args, float* d_out_film, float* d_out_half,
+                                      float* d_out_length, hipStream_t);
 
 // Resident 64-thread blocks (= waves) of `kernel` on the current device: the persistent grid size of the EXACT instantiation a launch takes
 // (the register count, and so the occupancy, differs between instantiations and between translation units with their own backend flags).

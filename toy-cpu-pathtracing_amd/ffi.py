@@ -137,6 +137,25 @@ class GbufferFilms(C.Structure):
 GBUFFER_FILMS = ("albedo", "shading_normal", "position", "hit")
 
 
+class TemporalView(C.Structure):
+    """mi355pt_temporal_view (include/mi355pt_temporal.h): how a render-space point of the current frame lands in the previous frame's image"""
+    _fields_ = [("delta", C.c_float * 3), ("rows", C.c_float * 9), ("sx", C.c_float), ("sy", C.c_float), ("cx", C.c_float), ("cy", C.c_float)]
+
+
+class TemporalParams(C.Structure):
+    """mi355pt_temporal_params; Product.temporal_params_default() fills it — a zeroed one is refused"""
+    _fields_ = [("pos_tol", C.c_float), ("normal_cos", C.c_float), ("min_weight", C.c_float), ("max_history", C.c_float)]
+
+
+class TemporalFrame(C.Structure):
+    """mi355pt_temporal_frame: device or host pointers; half may be NULL, length is read of the previous frame only"""
+    _fields_ = [("film", C.c_void_p), ("half", C.c_void_p), ("length", C.c_void_p), ("position", C.c_void_p), ("shading_normal", C.c_void_p),
+                ("hit", C.c_void_p)]
+
+
+TEMPORAL_FILMS = ("film", "half", "length", "position", "shading_normal", "hit")
+
+
 def make_camera(position, direction, up, width, height, fov_deg=45.0):
     return Camera((C.c_float * 3)(*position), (C.c_float * 3)(*direction), (C.c_float * 3)(*up), fov_deg, width, height)
 
@@ -169,6 +188,8 @@ DENOISE_VAR_SYMBOLS = ["denoise_var_params_default", "denoise_var_scratch_bytes"
 # ... and include/mi355pt_adaptive.h, the adaptive-sampling block mi355pt.h includes (tests/test_adaptive.py)
 # ... and include/mi355pt_gbuffer.h, the G-buffer block mi355pt.h includes (tests/test_gbuffer.py)
 GBUFFER_SYMBOLS = ["render_gbuffer_accum_device", "gbuffer_normalize_device", "render_gbuffer"]
+# ... and include/mi355pt_temporal.h, the temporal-reprojection block mi355pt.h includes (tests/test_temporal.py)
+TEMPORAL_SYMBOLS = ["temporal_params_default", "temporal_view_from_cameras", "temporal_accumulate_device", "temporal_accumulate"]
 ADAPTIVE_SYMBOLS = ["adaptive_scratch_bytes", "adaptive_step_device", "film_normalize_tiles_device", "render_adaptive_device", "render_adaptive"]
 
 
@@ -421,6 +442,13 @@ class Product(Backend):
                                                                 C.POINTER(GbufferFilms), C.c_void_p, C.POINTER(Stats)]
             lib.mi355pt_gbuffer_normalize_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
             lib.mi355pt_render_gbuffer.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.POINTER(GbufferFilms), C.POINTER(Stats)]
+        if hasattr(lib, "mi355pt_temporal_accumulate_device"):  # (absent from an older build loaded through MI355PT_LIB)
+            lib.mi355pt_temporal_params_default.argtypes = [C.POINTER(TemporalParams)]; lib.mi355pt_temporal_params_default.restype = None
+            lib.mi355pt_temporal_view_from_cameras.argtypes = [C.POINTER(Camera), C.POINTER(Camera), C.POINTER(TemporalView)]
+            lib.mi355pt_temporal_accumulate_device.argtypes = [C.POINTER(TemporalFrame), C.c_uint32, C.POINTER(TemporalFrame), C.POINTER(TemporalView), C.c_uint32,
+                                                               C.c_uint32, C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.mi355pt_temporal_accumulate.argtypes = [C.POINTER(TemporalFrame), C.c_uint32, C.POINTER(TemporalFrame), C.POINTER(TemporalView), C.c_uint32,
+                                                        C.c_uint32, C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p]
         if not hasattr(lib, "mi355pt_render_sample_log"):      # an older build loaded through MI355PT_LIB for an A/B timing run
             return
         lib.mi355pt_sample_log_records.argtypes = [C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]
@@ -553,6 +581,45 @@ class Product(Backend):
         self.check(self.lib.mi355pt_denoise_var(_ptr(b, C.c_float), _ptr(h, C.c_float), spp_beauty, _ptr(t, C.c_uint32), _ptr(a, C.c_float), spp_albedo,
                                                 _ptr(n, C.c_float), spp_normal, b.shape[1], b.shape[0], C.byref(params), _ptr(out, C.c_float)), "denoise_var")
         return out
+
+    # ---- the temporal reprojection (include/mi355pt_temporal.h): the previous frame's accumulated films gathered through the hit position ----
+    def temporal_params_default(self):
+        p = TemporalParams()
+        self.lib.mi355pt_temporal_params_default(C.byref(p))
+        return p
+
+    def temporal_view_from_cameras(self, cur, prev):
+        """mi355pt_temporal_view_from_cameras (host only) -> TemporalView"""
+        v = TemporalView()
+        self.check(self.lib.mi355pt_temporal_view_from_cameras(C.byref(cur), C.byref(prev), C.byref(v)), "temporal_view_from_cameras")
+        return v
+
+    def temporal_accumulate_device(self, cur, spp, prev, view, width, height, params, d_out_film_ptr, d_out_half_ptr, d_out_length_ptr, stream=None):
+        """mi355pt_temporal_accumulate_device: `cur` / `prev` map film names (TEMPORAL_FILMS) to device pointers (a name left out or None is
+        NULL); prev and view None = the first frame; d_out_half_ptr None or 0 without a half film"""
+        fc = TemporalFrame(*[C.c_void_p(cur.get(k) or None) for k in TEMPORAL_FILMS])
+        fp = TemporalFrame(*[C.c_void_p(prev.get(k) or None) for k in TEMPORAL_FILMS]) if prev is not None else None
+        self.check(self.lib.mi355pt_temporal_accumulate_device(C.byref(fc), spp, C.byref(fp) if fp is not None else None,
+                                                               C.byref(view) if view is not None else None, width, height, C.byref(params),
+                                                               C.c_void_p(d_out_film_ptr), C.c_void_p(d_out_half_ptr or 0), C.c_void_p(d_out_length_ptr),
+                                                               C.c_void_p(stream or 0)), "temporal_accumulate_device")
+
+    def temporal_accumulate(self, cur, spp, prev=None, view=None, params=None):
+        """mi355pt_temporal_accumulate on host arrays: `cur` / `prev` map film names to (H, W, 3) float32 arrays ((H, W) for length)
+        -> (out_film, out_half or None, out_length)"""
+        def host(frame):
+            keep = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in frame.items() if v is not None}
+            return keep, TemporalFrame(*[keep[k].ctypes.data if k in keep else None for k in TEMPORAL_FILMS])
+        kc, fc = host(cur)
+        kp, fp = host(prev) if prev is not None else (None, None)
+        h, w = kc["film"].shape[:2]
+        params = params if params is not None else self.temporal_params_default()
+        out_film, out_len = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32)
+        out_half = np.zeros((h, w, 3), np.float32) if "half" in kc else None
+        self.check(self.lib.mi355pt_temporal_accumulate(C.byref(fc), spp, C.byref(fp) if fp is not None else None,
+                                                        C.byref(view) if view is not None else None, w, h, C.byref(params), out_film.ctypes.data,
+                                                        out_half.ctypes.data if out_half is not None else None, out_len.ctypes.data), "temporal_accumulate")
+        return out_film, out_half, out_len
 
     def render_accum_device(self, scene, cam, params, s_begin, s_end, d_accum_ptr, stream=None, stats=None):
         self.check(self.lib.mi355pt_render_accum_device(scene.h, C.byref(cam), C.byref(params), s_begin, s_end, C.c_void_p(d_accum_ptr),

@@ -4,9 +4,10 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <stdexcept>
 #include <string>
 
-#include <hip/hip_runtime_api.h>   // --denoise, --denoise-variance and --adaptive-threshold: the films of those paths stay on the device (hipMalloc / hipMemcpy / hipFree, no kernels here)
+#include <hip/hip_runtime_api.h>   // --denoise, --denoise-variance, --adaptive-threshold and --temporal-frames: the films of those paths stay on the device (hipMalloc / hipMemcpy / hipFree, no kernels here)
 
 #include "scenes.hpp"
 
@@ -27,6 +28,8 @@ struct Args {   // main.rs:20-53
     float adaptive_threshold = 0.0f, adaptive_dark_eps = 1e-3f; uint32_t adaptive_min_spp = 16; std::string spp_map;
     // nor the G-buffer pass (mi355pt_gbuffer.h): with a denoise flag, the two guide films from ONE launch of it instead of two AOV launches
     bool fused_guides = false;
+    // nor temporal accumulation (mi355pt_temporal.h): N frames, frame k with seed + k from position + k * step, each reprojected into the next
+    bool temporal = false; uint32_t temporal_frames = 0; bool camera_step_given = false; float camera_step[3] = {0.0f, 0.0f, 0.0f};
 };
 
 // --denoise: the beauty film at --spp, the albedo and shading-normal films at --denoise-guide-spp (converged guides cost a few percent of
@@ -168,6 +171,77 @@ static double render_gbuffer_float(const Scene& scene, const Camera& camera, mi3
     return st.kernel_ms * 1e-3;
 }
 
+// --temporal-frames N [--camera-step dx,dy,dz]: N frames of --spp samples, frame k with seed + k and the camera at position + k * step (the
+// scene is built again when the position changes: mi355pt_scene_build bakes it in).  Per frame one G-buffer launch at --denoise-guide-spp
+// (shading normal, position, hit — and albedo when --denoise-variance follows), the beauty film (and the half film with --denoise-variance),
+// then mi355pt_temporal_accumulate_device against the previous frame's accumulated films.  After the last frame optionally the
+// variance-guided filter on the accumulated pair (spp 2), then Sensor::to_rgb.  Returns the device seconds of the beauty launches.
+static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params p, const Args& a, std::vector<float>& pixels) {
+    const mi355pt_camera base = camera.raw();
+    const uint32_t n_pixels = base.width * base.height, guide_spp = a.denoise_guide_spp;
+    const size_t film_bytes = (size_t)n_pixels * 3 * sizeof(float), len_bytes = (size_t)n_pixels * sizeof(float);
+    const bool half = a.denoise_variance, moving = a.camera_step[0] != 0.0f || a.camera_step[1] != 0.0f || a.camera_step[2] != 0.0f;
+    const size_t opt = half ? film_bytes : sizeof(float);
+    // two sets that alternate: the frame's G-buffer films and its accumulated pair with the length film
+    DeviceFilm normal0(film_bytes), normal1(film_bytes), position0(film_bytes), position1(film_bytes), hit0(film_bytes), hit1(film_bytes);
+    DeviceFilm acc0(film_bytes), acc1(film_bytes), acch0(opt), acch1(opt), len0(len_bytes), len1(len_bytes);
+    DeviceFilm beauty(film_bytes), bhalf(opt), albedo(opt), rgb(film_bytes);
+    float *normal[2] = {normal0.p, normal1.p}, *position[2] = {position0.p, position1.p}, *hit[2] = {hit0.p, hit1.p};
+    float *acc[2] = {acc0.p, acc1.p}, *acch[2] = {acch0.p, acch1.p}, *len[2] = {len0.p, len1.p};
+    mi355pt_temporal_params tp;
+    mi355pt_temporal_params_default(&tp);
+    mi355pt_camera cam = base, cam_prev = base;
+    double kernel_ms = 0.0;
+    for (uint32_t k = 0; k < a.temporal_frames; ++k) {
+        const int c = (int)(k & 1u), q = c ^ 1;
+        cam_prev = cam;
+        for (int i = 0; i < 3; ++i) cam.position[i] = base.position[i] + (float)k * a.camera_step[i];
+        if (k > 0 && moving) {
+            Camera moved(base.fov_deg, base.width, base.height);
+            moved.set_look_to({cam.position[0], cam.position[1], cam.position[2]}, {cam.direction[0], cam.direction[1], cam.direction[2]}, {cam.up[0], cam.up[1], cam.up[2]});
+            scene.build(moved);
+        }
+        p.seed = a.seed + k;
+        bool ok = hipMemset(normal[c], 0, film_bytes) == hipSuccess && hipMemset(position[c], 0, film_bytes) == hipSuccess && hipMemset(hit[c], 0, film_bytes) == hipSuccess &&
+                  hipMemset(beauty.p, 0, film_bytes) == hipSuccess;
+        if (half) ok = ok && hipMemset(bhalf.p, 0, film_bytes) == hipSuccess && hipMemset(albedo.p, 0, film_bytes) == hipSuccess;
+        if (!ok) throw std::runtime_error("mi355pt: clearing the frame's films failed");
+        mi355pt_params g = p;
+        g.spp = guide_spp;
+        const mi355pt_gbuffer_films films{half ? albedo.p : nullptr, normal[c], position[c], hit[c]};
+        check(mi355pt_render_gbuffer_accum_device(scene.raw(), &cam, &g, scene.d65_lut(), 0, guide_spp, &films, nullptr, nullptr), "mi355pt_render_gbuffer_accum_device");
+        mi355pt_stats st0{}, st1{};
+        if (half) {
+            check(mi355pt_render_accum_device(scene.raw(), &cam, &p, 0, p.spp / 2, bhalf.p, nullptr, &st0), "mi355pt_render_accum_device");
+            if (hipMemcpy(beauty.p, bhalf.p, film_bytes, hipMemcpyDeviceToDevice) != hipSuccess) throw std::runtime_error("mi355pt: copying the half film failed");
+            check(mi355pt_render_accum_device(scene.raw(), &cam, &p, p.spp / 2, p.spp, beauty.p, nullptr, &st1), "mi355pt_render_accum_device");
+        } else {
+            check(mi355pt_render_accum_device(scene.raw(), &cam, &p, 0, p.spp, beauty.p, nullptr, &st0), "mi355pt_render_accum_device");
+        }
+        kernel_ms += st0.kernel_ms + st1.kernel_ms;
+        const mi355pt_temporal_frame cur{beauty.p, half ? bhalf.p : nullptr, nullptr, position[c], normal[c], hit[c]};
+        const mi355pt_temporal_frame prev{acc[q], half ? acch[q] : nullptr, len[q], position[q], normal[q], hit[q]};
+        mi355pt_temporal_view view{};
+        if (k > 0) check(mi355pt_temporal_view_from_cameras(&cam, &cam_prev, &view), "mi355pt_temporal_view_from_cameras");
+        check(mi355pt_temporal_accumulate_device(&cur, p.spp, k > 0 ? &prev : nullptr, k > 0 ? &view : nullptr, base.width, base.height, &tp, acc[c],
+                                                 half ? acch[c] : nullptr, len[c], nullptr), "mi355pt_temporal_accumulate_device");
+    }
+    const int last = (int)((a.temporal_frames - 1) & 1u);
+    if (half) {
+        const size_t scratch_bytes = mi355pt_denoise_var_scratch_bytes(base.width, base.height);
+        DeviceFilm out(film_bytes), scratch(scratch_bytes);
+        const mi355pt_denoise_var_params dp = denoise_var_params(a.denoise_sigma_lum);
+        check(mi355pt_denoise_var_device(acc[last], acch[last], 2, nullptr, albedo.p, guide_spp, normal[last], guide_spp, base.width, base.height, &dp, scratch.p,
+                                         scratch_bytes, out.p, nullptr), "mi355pt_denoise_var_device");
+        check(mi355pt_film_resolve_device(out.p, n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
+        if (hipMemcpy(pixels.data(), rgb.p, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the frame back failed");
+    } else {
+        check(mi355pt_film_resolve_device(acc[last], n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
+        if (hipMemcpy(pixels.data(), rgb.p, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the frame back failed");
+    }
+    return kernel_ms * 1e-3;
+}
+
 static void usage() {
     std::puts("Usage: mi355pt [--scene N] [-s|--spp N] [--seed N] [--filter box] [--sampler random|sobol]\n"
               "               [--renderer normal|albedo|pt|nee|mis] [--width N] [--height N] [-d|--max-depth N] [-o|--output FILE]\n"
@@ -180,7 +254,10 @@ static void usage() {
               "                   [--adaptive-min-spp N] (16)  [--adaptive-dark-eps E] (1e-3)  [--spp-map FILE] (samples per tile as a grey picture)\n"
               "                   [--renderer position|depth] (the G-buffer pass: mean render-space hit position / mean distance over the samples that hit,\n"
               "                                                0 where none did; float output, -o must end in .pfm)\n"
-              "                   [--fused-guides] (with --denoise or --denoise-variance: both guide films from one G-buffer launch, the same primary rays)");
+              "                   [--fused-guides] (with --denoise or --denoise-variance: both guide films from one G-buffer launch, the same primary rays)\n"
+              "                   [--temporal-frames N] (pt|nee|mis: N frames of --spp samples, frame k with seed + k, each reprojected into the next through its\n"
+              "                                          G-buffer at --denoise-guide-spp and accumulated; writes the last; --denoise-variance filters the accumulated pair)\n"
+              "                   [--camera-step dx,dy,dz] (with --temporal-frames: frame k renders from position + k * step)");
 }
 
 int main(int argc, char** argv) {
@@ -209,6 +286,17 @@ int main(int argc, char** argv) {
         else if (k == "--adaptive-dark-eps") a.adaptive_dark_eps = std::stof(val());
         else if (k == "--spp-map") a.spp_map = val();
         else if (k == "--fused-guides") a.fused_guides = true;
+        else if (k == "--temporal-frames") { a.temporal = true; a.temporal_frames = (uint32_t)std::stoul(val()); }
+        else if (k == "--camera-step") {
+            const std::string v = val();
+            char tail = 0;
+            a.camera_step_given = true;
+            if (std::sscanf(v.c_str(), "%f,%f,%f%c", &a.camera_step[0], &a.camera_step[1], &a.camera_step[2], &tail) != 3 || !std::isfinite(a.camera_step[0]) ||
+                !std::isfinite(a.camera_step[1]) || !std::isfinite(a.camera_step[2])) {
+                std::fprintf(stderr, "error: invalid value '%s' for '--camera-step': three finite numbers dx,dy,dz\n", v.c_str());
+                return 2;
+            }
+        }
         else if (k == "-h" || k == "--help") { usage(); return 0; }
         else { std::fprintf(stderr, "error: unexpected argument '%s'\n", k.c_str()); usage(); return 2; }
     }
@@ -220,6 +308,13 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "error: invalid value '%s' for '--renderer' (main.rs:38-40: normal, albedo, pt, nee, mis; extensions: shading-normal, position, depth)\n", a.renderer.c_str());
         return 2;
     }
+    if (a.camera_step_given && !a.temporal) { std::fprintf(stderr, "error: --camera-step needs --temporal-frames: it moves the camera between the frames\n"); return 2; }
+    if (a.temporal && a.temporal_frames == 0) { std::fprintf(stderr, "error: --temporal-frames must be above 0\n"); return 2; }
+    if (a.temporal && aov) { std::fprintf(stderr, "error: --temporal-frames with --renderer %s: temporal accumulation is for the path renderers (pt, nee, mis)\n", a.renderer.c_str()); return 2; }
+    if (a.temporal && a.gpus > 1) { std::fprintf(stderr, "error: --temporal-frames with --gpus %d: temporal accumulation runs on one GPU\n", a.gpus); return 2; }
+    if (a.temporal && a.denoise) { std::fprintf(stderr, "error: --temporal-frames with --denoise: the accumulated pair goes to --denoise-variance\n"); return 2; }
+    if (a.temporal && a.adaptive_threshold != 0.0f) { std::fprintf(stderr, "error: --temporal-frames with --adaptive-threshold: temporal accumulation takes one sample count per frame\n"); return 2; }
+    if (a.temporal && (a.spp == 0 || a.denoise_guide_spp == 0)) { std::fprintf(stderr, "error: --temporal-frames needs --spp and --denoise-guide-spp above 0\n"); return 2; }
     if (gbuf && (a.output.size() < 4 || a.output.compare(a.output.size() - 4, 4, ".pfm") != 0)) {
         std::fprintf(stderr, "error: --renderer %s writes float values: -o must end in .pfm (got '%s')\n", a.renderer.c_str(), a.output.c_str());
         return 2;
@@ -288,13 +383,15 @@ int main(int argc, char** argv) {
         const SamplerKind sampler = a.sampler == "sobol" ? SamplerKind::ZSobol : SamplerKind::Random;
         double kernel_s = 0.0;
         if (gbuf) kernel_s = render_gbuffer_float(scene, camera, image.params(sampler, a.albedo_lut), a.renderer == "depth", image.pixels_mut());
+        else if (a.temporal) kernel_s = render_temporal(scene, camera, image.params(sampler, a.albedo_lut), a, image.pixels_mut());
         else if (adaptive) render_adaptive(scene, camera, image.params(sampler, a.albedo_lut), a, image.pixels_mut());
         else if (a.denoise_variance) kernel_s = render_denoised_variance(scene, camera, image.params(sampler, a.albedo_lut), a.denoise_guide_spp, a.fused_guides, a.denoise_sigma_lum, image.pixels_mut());
         else kernel_s = a.denoise ? render_denoised(scene, camera, image.params(sampler, a.albedo_lut), a.denoise_guide_spp, a.fused_guides, image.pixels_mut())
                                     : image.render(sampler, a.albedo_lut);
         double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         std::printf("Finish rendering: %.3f seconds.\n", wall);
-        if (kernel_s > 0.0 && (a.denoise || a.denoise_variance)) std::printf("(beauty launch alone: device %.3f s, %.1f Msamples/s; the guide films and the filter are in the wall time above)\n", kernel_s, (double)a.width * a.height * a.spp / kernel_s / 1e6);
+        if (kernel_s > 0.0 && a.temporal) std::printf("(beauty launches of %u frames: device %.3f s; the G-buffer, the accumulation and the scene builds are in the wall time above)\n", a.temporal_frames, kernel_s);
+        else if (kernel_s > 0.0 && (a.denoise || a.denoise_variance)) std::printf("(beauty launch alone: device %.3f s, %.1f Msamples/s; the guide films and the filter are in the wall time above)\n", kernel_s, (double)a.width * a.height * a.spp / kernel_s / 1e6);
         else if (kernel_s > 0.0) std::printf("(device %.3f s, %.1f Msamples/s)\n", kernel_s, (double)a.width * a.height * a.spp / kernel_s / 1e6);
         if (gbuf) write_pfm(a.output, image.pixels().data(), a.width, a.height); else image.save(a.output);
     } catch (const std::exception& e) {
