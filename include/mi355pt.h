@@ -326,6 +326,11 @@ const char* mi355pt_version(void);
  * camera, blended with the current frame.  Declared in its own header, which this one always includes (ahead of the variance-guided
  * denoiser's, which takes the accumulated pair as it is). */
 #include "mi355pt_temporal.h"
+/* ... and its rectified form — mi355pt_temporal_rectify_params, mi355pt_temporal_rectify_params_default,
+ * mi355pt_temporal_rectify_scratch_bytes, mi355pt_temporal_accumulate_rectified_device and mi355pt_temporal_accumulate_rectified: the
+ * gathered history is first scaled so that its local mean agrees with the current frame's, which lets the accumulation follow a change of
+ * illumination.  Declared in its own header, which this one always includes. */
+#include "mi355pt_temporal_rectify.h"
 
 /* ---------------- variance-guided denoiser ---------------- */
 /* EXTENSION, no reference counterpart: a second filter beside the one above, which it leaves as it is — mi355pt_denoise_var_params,

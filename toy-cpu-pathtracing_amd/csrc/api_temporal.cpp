@@ -1,8 +1,10 @@
 // The mi355pt_temporal.h surface of libmi355pt.so: the view of a camera pair (host arithmetic), the argument checks and the two entry
-// points of the temporal reprojection.  Host C++ only, like api.cpp; the kernel is pt_kernels_temporal.hip.
+// points of the temporal reprojection — and the mi355pt_temporal_rectify.h surface, which adds its own checks to the same ones and two entry
+// points of the same shape.  Host C++ only, like api.cpp; the kernels are pt_kernels_temporal.hip and pt_kernels_temporal_rectify.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdint>
 #include <string>
 
 #include "api_internal.hpp"
@@ -58,6 +60,86 @@ TemporalFrameDev frame_dev(const mi355pt_temporal_frame& f) {
     return d;
 }
 
+TemporalArgs temporal_args(uint32_t spp, const mi355pt_temporal_view* view, uint32_t width, uint32_t height, const mi355pt_temporal_params* tp) {
+    TemporalArgs a{};
+    a.width = width; a.height = height;
+    a.spp = (float)spp; a.half_spp = (float)(spp >> 1);
+    a.wf = (float)width; a.hf = (float)height;
+    if (view) {
+        for (int i = 0; i < 3; ++i) a.delta[i] = view->delta[i];
+        for (int i = 0; i < 9; ++i) a.rows[i] = view->rows[i];
+        a.sx = view->sx; a.sy = view->sy; a.cx = view->cx; a.cy = view->cy;
+    }
+    a.pos_tol = tp->pos_tol; a.normal_cos = tp->normal_cos; a.min_weight = tp->min_weight; a.max_history = tp->max_history;
+    return a;
+}
+
+// what mi355pt_temporal_rectify.h adds to temporal_check: the rectification's own parameters ...
+int rectify_params_check(const mi355pt_temporal_rectify_params* rp) {
+    if (!rp) return fail(MI355PT_E_INVALID, "temporal rectify: null rectify_params pointer");
+    if (rp->radius < 1 || rp->radius > 3) return fail(MI355PT_E_INVALID, "temporal rectify: radius must be 1, 2 or 3 (mi355pt_temporal_rectify_params_default fills the struct)");
+    if (!(std::isfinite(rp->gamma) && rp->gamma > 0.0f)) return fail(MI355PT_E_INVALID, "temporal rectify: gamma must be finite and > 0");
+    return MI355PT_OK;
+}
+// ... and the device entry point's scratch
+int rectify_scratch_check(const mi355pt_temporal_frame* cur, const mi355pt_temporal_frame* prev, uint32_t width, uint32_t height, const void* scratch,
+                          size_t scratch_bytes, const float* out_film, const float* out_half, const float* out_length) {
+    if (!scratch) return fail(MI355PT_E_INVALID, "temporal rectify: null scratch pointer");
+    if (((uintptr_t)scratch & 15u) != 0) return fail(MI355PT_E_INVALID, "temporal rectify: the scratch must be 16-byte aligned");
+    const size_t need = mi355pt_temporal_rectify_scratch_bytes(width, height);
+    if (need == 0 || scratch_bytes < need) return fail(MI355PT_E_INVALID, "temporal rectify: scratch smaller than mi355pt_temporal_rectify_scratch_bytes(width, height)");
+    const void* other[15] = {cur->film, cur->half, cur->length, cur->position, cur->shading_normal, cur->hit, prev ? prev->film : nullptr,
+                             prev ? prev->half : nullptr, prev ? prev->length : nullptr, prev ? prev->position : nullptr,
+                             prev ? prev->shading_normal : nullptr, prev ? prev->hit : nullptr, out_film, out_half, out_length};
+    for (const void* q : other)
+        if (q == scratch) return fail(MI355PT_E_INVALID, "temporal rectify: the scratch must not be one of the inputs or outputs");
+    return MI355PT_OK;
+}
+
+// the two host-buffer entry points: device copies of the films, the device entry point (rectified when rp is given, with a scratch of its
+// own) on the default stream, the outputs copied back.  Every argument has been checked.
+int temporal_accumulate_host(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev, const mi355pt_temporal_view* view,
+                             uint32_t width, uint32_t height, const mi355pt_temporal_params* tp, const mi355pt_temporal_rectify_params* rp, float* out_film,
+                             float* out_half, float* out_length) {
+    int rc = MI355PT_OK;
+    const size_t np = (size_t)width * height, n = np * 3;
+    // the films of the two frames in the order of mi355pt_temporal_frame (length: W x H; the current frame's is ignored)
+    DevBuf<float> d_in[2][6], d_film, d_half, d_len;
+    DevBuf<unsigned char> d_scratch;
+    mi355pt_temporal_frame dev[2] = {};
+    const mi355pt_temporal_frame* host[2] = {cur, prev};
+    for (int k = 0; k < 2; ++k) {
+        if (!host[k]) continue;
+        const float* src[6] = {host[k]->film, host[k]->half, k == 0 ? nullptr : host[k]->length, host[k]->position, host[k]->shading_normal, host[k]->hit};
+        const float* dst[6] = {};
+        for (int i = 0; i < 6; ++i) {
+            if (!src[i]) continue;
+            const size_t count = i == 2 ? np : n;
+            HIP_TRY(d_in[k][i].alloc(count));
+            HIP_TRY(hipMemcpy(d_in[k][i].p, src[i], count * sizeof(float), hipMemcpyHostToDevice));
+            dst[i] = d_in[k][i].p;
+        }
+        dev[k].film = dst[0]; dev[k].half = dst[1]; dev[k].length = dst[2]; dev[k].position = dst[3]; dev[k].shading_normal = dst[4]; dev[k].hit = dst[5];
+    }
+    HIP_TRY(d_film.alloc(n));
+    HIP_TRY(d_len.alloc(np));
+    if (out_half) HIP_TRY(d_half.alloc(n));
+    if (rp) {
+        const size_t scratch_bytes = mi355pt_temporal_rectify_scratch_bytes(width, height);
+        HIP_TRY(d_scratch.alloc(scratch_bytes));
+        rc = mi355pt_temporal_accumulate_rectified_device(&dev[0], spp, prev ? &dev[1] : nullptr, view, width, height, tp, rp, d_scratch.p, scratch_bytes, d_film.p,
+                                                          out_half ? d_half.p : nullptr, d_len.p, nullptr);
+    } else {
+        rc = mi355pt_temporal_accumulate_device(&dev[0], spp, prev ? &dev[1] : nullptr, view, width, height, tp, d_film.p, out_half ? d_half.p : nullptr, d_len.p,
+                                                nullptr);
+    }
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(out_film, d_film.p, n * sizeof(float), hipMemcpyDeviceToHost));      // (synchronises the default stream)
+    if (out_half) HIP_TRY(hipMemcpy(out_half, d_half.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_length, d_len.p, np * sizeof(float), hipMemcpyDeviceToHost));
+    return MI355PT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -99,16 +181,7 @@ int mi355pt_temporal_accumulate_device(const mi355pt_temporal_frame* cur, uint32
                                        float* d_out_length, void* hip_stream) {
     int rc = temporal_check(cur, spp, prev, view, width, height, tp, d_out_film, d_out_half, d_out_length);
     if (rc) return rc;
-    TemporalArgs a{};
-    a.width = width; a.height = height;
-    a.spp = (float)spp; a.half_spp = (float)(spp >> 1);
-    a.wf = (float)width; a.hf = (float)height;
-    if (view) {
-        for (int i = 0; i < 3; ++i) a.delta[i] = view->delta[i];
-        for (int i = 0; i < 9; ++i) a.rows[i] = view->rows[i];
-        a.sx = view->sx; a.sy = view->sy; a.cx = view->cx; a.cy = view->cy;
-    }
-    a.pos_tol = tp->pos_tol; a.normal_cos = tp->normal_cos; a.min_weight = tp->min_weight; a.max_history = tp->max_history;
+    const TemporalArgs a = temporal_args(spp, view, width, height, tp);
     const TemporalFrameDev dc = frame_dev(*cur), dp = prev ? frame_dev(*prev) : TemporalFrameDev{};
     HIP_TRY(launch_temporal_accumulate(dc, prev ? &dp : nullptr, a, d_out_film, d_out_half, d_out_length, (hipStream_t)hip_stream));
     return MI355PT_OK;
@@ -118,33 +191,47 @@ int mi355pt_temporal_accumulate(const mi355pt_temporal_frame* cur, uint32_t spp,
                                 uint32_t width, uint32_t height, const mi355pt_temporal_params* tp, float* out_film, float* out_half, float* out_length) {
     int rc = temporal_check(cur, spp, prev, view, width, height, tp, out_film, out_half, out_length);
     if (rc) return rc;
-    const size_t np = (size_t)width * height, n = np * 3;
-    // the films of the two frames in the order of mi355pt_temporal_frame (length: W x H; the current frame's is ignored)
-    DevBuf<float> d_in[2][6], d_film, d_half, d_len;
-    mi355pt_temporal_frame dev[2] = {};
-    const mi355pt_temporal_frame* host[2] = {cur, prev};
-    for (int k = 0; k < 2; ++k) {
-        if (!host[k]) continue;
-        const float* src[6] = {host[k]->film, host[k]->half, k == 0 ? nullptr : host[k]->length, host[k]->position, host[k]->shading_normal, host[k]->hit};
-        const float* dst[6] = {};
-        for (int i = 0; i < 6; ++i) {
-            if (!src[i]) continue;
-            const size_t count = i == 2 ? np : n;
-            HIP_TRY(d_in[k][i].alloc(count));
-            HIP_TRY(hipMemcpy(d_in[k][i].p, src[i], count * sizeof(float), hipMemcpyHostToDevice));
-            dst[i] = d_in[k][i].p;
-        }
-        dev[k].film = dst[0]; dev[k].half = dst[1]; dev[k].length = dst[2]; dev[k].position = dst[3]; dev[k].shading_normal = dst[4]; dev[k].hit = dst[5];
+    return temporal_accumulate_host(cur, spp, prev, view, width, height, tp, nullptr, out_film, out_half, out_length);
+}
+
+/* ---- mi355pt_temporal_rectify.h ---- */
+void mi355pt_temporal_rectify_params_default(mi355pt_temporal_rectify_params* out) {
+    if (!out) return;
+    out->radius = 2; out->gamma = 2.0f;
+}
+
+size_t mi355pt_temporal_rectify_scratch_bytes(uint32_t width, uint32_t height) {
+    const size_t np = (size_t)width * (size_t)height;
+    if (width != 0 && np / width != height) return 0;
+    if (np > SIZE_MAX / TEMPORAL_RECTIFY_RECORD_BYTES) return 0;
+    return np * TEMPORAL_RECTIFY_RECORD_BYTES;
+}
+
+int mi355pt_temporal_accumulate_rectified_device(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev,
+                                                 const mi355pt_temporal_view* view, uint32_t width, uint32_t height, const mi355pt_temporal_params* tp,
+                                                 const mi355pt_temporal_rectify_params* rp, void* d_scratch, size_t scratch_bytes, float* d_out_film,
+                                                 float* d_out_half, float* d_out_length, void* hip_stream) {
+    int rc = temporal_check(cur, spp, prev, view, width, height, tp, d_out_film, d_out_half, d_out_length);
+    if (rc) return rc;
+    if ((rc = rectify_params_check(rp))) return rc;
+    if ((rc = rectify_scratch_check(cur, prev, width, height, d_scratch, scratch_bytes, d_out_film, d_out_half, d_out_length))) return rc;
+    const TemporalArgs a = temporal_args(spp, view, width, height, tp);
+    const TemporalFrameDev dc = frame_dev(*cur);
+    if (!prev) {      // the first frame: nothing to rectify, the scratch stays as it is
+        HIP_TRY(launch_temporal_accumulate(dc, nullptr, a, d_out_film, d_out_half, d_out_length, (hipStream_t)hip_stream));
+        return MI355PT_OK;
     }
-    HIP_TRY(d_film.alloc(n));
-    HIP_TRY(d_len.alloc(np));
-    if (out_half) HIP_TRY(d_half.alloc(n));
-    if ((rc = mi355pt_temporal_accumulate_device(&dev[0], spp, prev ? &dev[1] : nullptr, view, width, height, tp, d_film.p, out_half ? d_half.p : nullptr,
-                                                 d_len.p, nullptr))) return rc;
-    HIP_TRY(hipMemcpy(out_film, d_film.p, n * sizeof(float), hipMemcpyDeviceToHost));      // (synchronises the default stream)
-    if (out_half) HIP_TRY(hipMemcpy(out_half, d_half.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_length, d_len.p, np * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(launch_temporal_rectify(dc, frame_dev(*prev), a, rp->radius, rp->gamma, d_scratch, d_out_film, d_out_half, d_out_length, (hipStream_t)hip_stream));
     return MI355PT_OK;
+}
+
+int mi355pt_temporal_accumulate_rectified(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev, const mi355pt_temporal_view* view,
+                                          uint32_t width, uint32_t height, const mi355pt_temporal_params* tp, const mi355pt_temporal_rectify_params* rp,
+                                          float* out_film, float* out_half, float* out_length) {
+    int rc = temporal_check(cur, spp, prev, view, width, height, tp, out_film, out_half, out_length);
+    if (rc) return rc;
+    if ((rc = rectify_params_check(rp))) return rc;
+    return temporal_accumulate_host(cur, spp, prev, view, width, height, tp, rp, out_film, out_half, out_length);
 }
 
 }  // extern "C"

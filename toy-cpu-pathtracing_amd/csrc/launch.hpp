@@ -78,6 +78,12 @@ struct TemporalArgs {
 };
 hipError_t launch_temporal_accumulate(const TemporalFrameDev& cur, const TemporalFrameDev* prev, TemporalArgs args, float* d_out_film, float* d_out_half,
                                       float* d_out_length, hipStream_t);
+// pt_kernels_temporal_rectify.hip: the rectified accumulation (include/mi355pt_temporal_rectify.h) of a frame WITH a previous frame: two
+// launches on the same grid, the gather into d_scratch (TEMPORAL_RECTIFY_RECORD_BYTES per pixel, 16-byte aligned) and the rectifying blend.
+// radius is 1 .. 3.  The launcher fills TemporalArgs::blocks_x
+constexpr size_t TEMPORAL_RECTIFY_RECORD_BYTES = 32;
+hipError_t launch_temporal_rectify(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, uint32_t radius, float gamma, void* d_scratch,
+                                   float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
 
 // Resident 64-thread blocks (= waves) of `kernel` on the current device: the persistent grid size of the EXACT instantiation a launch takes
 // (the register count, and so the occupancy, differs between instantiations and between translation units with their own backend flags).

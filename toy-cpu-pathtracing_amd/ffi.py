@@ -156,6 +156,12 @@ class TemporalFrame(C.Structure):
 TEMPORAL_FILMS = ("film", "half", "length", "position", "shading_normal", "hit")
 
 
+class TemporalRectifyParams(C.Structure):
+    """mi355pt_temporal_rectify_params (include/mi355pt_temporal_rectify.h); Product.temporal_rectify_params_default() fills it — a zeroed
+    one is refused"""
+    _fields_ = [("radius", C.c_uint32), ("gamma", C.c_float)]
+
+
 def make_camera(position, direction, up, width, height, fov_deg=45.0):
     return Camera((C.c_float * 3)(*position), (C.c_float * 3)(*direction), (C.c_float * 3)(*up), fov_deg, width, height)
 
@@ -190,6 +196,9 @@ DENOISE_VAR_SYMBOLS = ["denoise_var_params_default", "denoise_var_scratch_bytes"
 GBUFFER_SYMBOLS = ["render_gbuffer_accum_device", "gbuffer_normalize_device", "render_gbuffer"]
 # ... and include/mi355pt_temporal.h, the temporal-reprojection block mi355pt.h includes (tests/test_temporal.py)
 TEMPORAL_SYMBOLS = ["temporal_params_default", "temporal_view_from_cameras", "temporal_accumulate_device", "temporal_accumulate"]
+# ... and include/mi355pt_temporal_rectify.h, its rectified form (tests/test_temporal_rectify.py)
+TEMPORAL_RECTIFY_SYMBOLS = ["temporal_rectify_params_default", "temporal_rectify_scratch_bytes", "temporal_accumulate_rectified_device",
+                            "temporal_accumulate_rectified"]
 ADAPTIVE_SYMBOLS = ["adaptive_scratch_bytes", "adaptive_step_device", "film_normalize_tiles_device", "render_adaptive_device", "render_adaptive"]
 
 
@@ -449,6 +458,15 @@ class Product(Backend):
                                                                C.c_uint32, C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             lib.mi355pt_temporal_accumulate.argtypes = [C.POINTER(TemporalFrame), C.c_uint32, C.POINTER(TemporalFrame), C.POINTER(TemporalView), C.c_uint32,
                                                         C.c_uint32, C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "mi355pt_temporal_accumulate_rectified_device"):  # (absent from an older build loaded through MI355PT_LIB)
+            lib.mi355pt_temporal_rectify_params_default.argtypes = [C.POINTER(TemporalRectifyParams)]; lib.mi355pt_temporal_rectify_params_default.restype = None
+            lib.mi355pt_temporal_rectify_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]; lib.mi355pt_temporal_rectify_scratch_bytes.restype = C.c_size_t
+            lib.mi355pt_temporal_accumulate_rectified_device.argtypes = [C.POINTER(TemporalFrame), C.c_uint32, C.POINTER(TemporalFrame), C.POINTER(TemporalView),
+                                                                         C.c_uint32, C.c_uint32, C.POINTER(TemporalParams), C.POINTER(TemporalRectifyParams),
+                                                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.mi355pt_temporal_accumulate_rectified.argtypes = [C.POINTER(TemporalFrame), C.c_uint32, C.POINTER(TemporalFrame), C.POINTER(TemporalView), C.c_uint32,
+                                                                  C.c_uint32, C.POINTER(TemporalParams), C.POINTER(TemporalRectifyParams), C.c_void_p, C.c_void_p,
+                                                                  C.c_void_p]
         if not hasattr(lib, "mi355pt_render_sample_log"):      # an older build loaded through MI355PT_LIB for an A/B timing run
             return
         lib.mi355pt_sample_log_records.argtypes = [C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]
@@ -619,6 +637,45 @@ class Product(Backend):
         self.check(self.lib.mi355pt_temporal_accumulate(C.byref(fc), spp, C.byref(fp) if fp is not None else None,
                                                         C.byref(view) if view is not None else None, w, h, C.byref(params), out_film.ctypes.data,
                                                         out_half.ctypes.data if out_half is not None else None, out_len.ctypes.data), "temporal_accumulate")
+        return out_film, out_half, out_len
+
+    # ---- its rectified form (include/mi355pt_temporal_rectify.h): the gathered history is scaled to the current frame's local mean first ----
+    def temporal_rectify_params_default(self):
+        p = TemporalRectifyParams()
+        self.lib.mi355pt_temporal_rectify_params_default(C.byref(p))
+        return p
+
+    def temporal_rectify_scratch_bytes(self, width, height):
+        return int(self.lib.mi355pt_temporal_rectify_scratch_bytes(width, height))
+
+    def temporal_accumulate_rectified_device(self, cur, spp, prev, view, width, height, params, rectify_params, d_scratch_ptr, scratch_bytes, d_out_film_ptr,
+                                             d_out_half_ptr, d_out_length_ptr, stream=None):
+        """mi355pt_temporal_accumulate_rectified_device: the arguments of temporal_accumulate_device, the rectification's parameters and a
+        device scratch of temporal_rectify_scratch_bytes(width, height) bytes"""
+        fc = TemporalFrame(*[C.c_void_p(cur.get(k) or None) for k in TEMPORAL_FILMS])
+        fp = TemporalFrame(*[C.c_void_p(prev.get(k) or None) for k in TEMPORAL_FILMS]) if prev is not None else None
+        self.check(self.lib.mi355pt_temporal_accumulate_rectified_device(C.byref(fc), spp, C.byref(fp) if fp is not None else None,
+                                                                         C.byref(view) if view is not None else None, width, height, C.byref(params),
+                                                                         C.byref(rectify_params), C.c_void_p(d_scratch_ptr), scratch_bytes,
+                                                                         C.c_void_p(d_out_film_ptr), C.c_void_p(d_out_half_ptr or 0), C.c_void_p(d_out_length_ptr),
+                                                                         C.c_void_p(stream or 0)), "temporal_accumulate_rectified_device")
+
+    def temporal_accumulate_rectified(self, cur, spp, prev=None, view=None, params=None, rectify_params=None):
+        """mi355pt_temporal_accumulate_rectified on host arrays, as temporal_accumulate -> (out_film, out_half or None, out_length)"""
+        def host(frame):
+            keep = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in frame.items() if v is not None}
+            return keep, TemporalFrame(*[keep[k].ctypes.data if k in keep else None for k in TEMPORAL_FILMS])
+        kc, fc = host(cur)
+        kp, fp = host(prev) if prev is not None else (None, None)
+        h, w = kc["film"].shape[:2]
+        params = params if params is not None else self.temporal_params_default()
+        rectify_params = rectify_params if rectify_params is not None else self.temporal_rectify_params_default()
+        out_film, out_len = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32)
+        out_half = np.zeros((h, w, 3), np.float32) if "half" in kc else None
+        self.check(self.lib.mi355pt_temporal_accumulate_rectified(C.byref(fc), spp, C.byref(fp) if fp is not None else None,
+                                                                  C.byref(view) if view is not None else None, w, h, C.byref(params), C.byref(rectify_params),
+                                                                  out_film.ctypes.data, out_half.ctypes.data if out_half is not None else None,
+                                                                  out_len.ctypes.data), "temporal_accumulate_rectified")
         return out_film, out_half, out_len
 
     def render_accum_device(self, scene, cam, params, s_begin, s_end, d_accum_ptr, stream=None, stats=None):

@@ -30,6 +30,9 @@ struct Args {   // main.rs:20-53
     bool fused_guides = false;
     // nor temporal accumulation (mi355pt_temporal.h): N frames, frame k with seed + k from position + k * step, each reprojected into the next
     bool temporal = false; uint32_t temporal_frames = 0; bool camera_step_given = false; float camera_step[3] = {0.0f, 0.0f, 0.0f};
+    // and its rectified form (mi355pt_temporal_rectify.h): the history is first scaled to the current frame's local mean; radius and gamma not given = its defaults
+    bool temporal_rectify = false, temporal_rectify_radius_given = false, temporal_rectify_gamma_given = false;
+    uint32_t temporal_rectify_radius = 0; float temporal_rectify_gamma = 0.0f;
 };
 
 // --denoise: the beauty film at --spp, the albedo and shading-normal films at --denoise-guide-spp (converged guides cost a few percent of
@@ -174,7 +177,8 @@ static double render_gbuffer_float(const Scene& scene, const Camera& camera, mi3
 // --temporal-frames N [--camera-step dx,dy,dz]: N frames of --spp samples, frame k with seed + k and the camera at position + k * step (the
 // scene is built again when the position changes: mi355pt_scene_build bakes it in).  Per frame one G-buffer launch at --denoise-guide-spp
 // (shading normal, position, hit — and albedo when --denoise-variance follows), the beauty film (and the half film with --denoise-variance),
-// then mi355pt_temporal_accumulate_device against the previous frame's accumulated films.  After the last frame optionally the
+// then mi355pt_temporal_accumulate_device (with --temporal-rectify: mi355pt_temporal_accumulate_rectified_device, radius and gamma from
+// --temporal-rectify-radius / --temporal-rectify-gamma or the defaults) against the previous frame's accumulated films.  After the last frame optionally the
 // variance-guided filter on the accumulated pair (spp 2), then Sensor::to_rgb.  Returns the device seconds of the beauty launches.
 static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params p, const Args& a, std::vector<float>& pixels) {
     const mi355pt_camera base = camera.raw();
@@ -190,6 +194,12 @@ static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params
     float *acc[2] = {acc0.p, acc1.p}, *acch[2] = {acch0.p, acch1.p}, *len[2] = {len0.p, len1.p};
     mi355pt_temporal_params tp;
     mi355pt_temporal_params_default(&tp);
+    mi355pt_temporal_rectify_params rp;
+    mi355pt_temporal_rectify_params_default(&rp);
+    if (a.temporal_rectify_radius_given) rp.radius = a.temporal_rectify_radius;
+    if (a.temporal_rectify_gamma_given) rp.gamma = a.temporal_rectify_gamma;
+    const size_t rectify_bytes = a.temporal_rectify ? mi355pt_temporal_rectify_scratch_bytes(base.width, base.height) : sizeof(float);
+    DeviceFilm rectify_scratch(rectify_bytes);
     mi355pt_camera cam = base, cam_prev = base;
     double kernel_ms = 0.0;
     for (uint32_t k = 0; k < a.temporal_frames; ++k) {
@@ -223,8 +233,13 @@ static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params
         const mi355pt_temporal_frame prev{acc[q], half ? acch[q] : nullptr, len[q], position[q], normal[q], hit[q]};
         mi355pt_temporal_view view{};
         if (k > 0) check(mi355pt_temporal_view_from_cameras(&cam, &cam_prev, &view), "mi355pt_temporal_view_from_cameras");
-        check(mi355pt_temporal_accumulate_device(&cur, p.spp, k > 0 ? &prev : nullptr, k > 0 ? &view : nullptr, base.width, base.height, &tp, acc[c],
-                                                 half ? acch[c] : nullptr, len[c], nullptr), "mi355pt_temporal_accumulate_device");
+        if (a.temporal_rectify)
+            check(mi355pt_temporal_accumulate_rectified_device(&cur, p.spp, k > 0 ? &prev : nullptr, k > 0 ? &view : nullptr, base.width, base.height, &tp, &rp,
+                                                               rectify_scratch.p, rectify_bytes, acc[c], half ? acch[c] : nullptr, len[c], nullptr),
+                  "mi355pt_temporal_accumulate_rectified_device");
+        else
+            check(mi355pt_temporal_accumulate_device(&cur, p.spp, k > 0 ? &prev : nullptr, k > 0 ? &view : nullptr, base.width, base.height, &tp, acc[c],
+                                                     half ? acch[c] : nullptr, len[c], nullptr), "mi355pt_temporal_accumulate_device");
     }
     const int last = (int)((a.temporal_frames - 1) & 1u);
     if (half) {
@@ -257,7 +272,10 @@ static void usage() {
               "                   [--fused-guides] (with --denoise or --denoise-variance: both guide films from one G-buffer launch, the same primary rays)\n"
               "                   [--temporal-frames N] (pt|nee|mis: N frames of --spp samples, frame k with seed + k, each reprojected into the next through its\n"
               "                                          G-buffer at --denoise-guide-spp and accumulated; writes the last; --denoise-variance filters the accumulated pair)\n"
-              "                   [--camera-step dx,dy,dz] (with --temporal-frames: frame k renders from position + k * step)");
+              "                   [--camera-step dx,dy,dz] (with --temporal-frames: frame k renders from position + k * step)\n"
+              "                   [--temporal-rectify] (with --temporal-frames: the gathered history is first scaled so that its local mean agrees with the\n"
+              "                                         current frame's: the accumulation follows a change of illumination)\n"
+              "                   [--temporal-rectify-radius R] (2; 1 .. 3: the window is (2R + 1)^2 pixels)  [--temporal-rectify-gamma G] (2; > 0: standard errors allowed)");
 }
 
 int main(int argc, char** argv) {
@@ -287,6 +305,9 @@ int main(int argc, char** argv) {
         else if (k == "--spp-map") a.spp_map = val();
         else if (k == "--fused-guides") a.fused_guides = true;
         else if (k == "--temporal-frames") { a.temporal = true; a.temporal_frames = (uint32_t)std::stoul(val()); }
+        else if (k == "--temporal-rectify") a.temporal_rectify = true;
+        else if (k == "--temporal-rectify-radius") { a.temporal_rectify_radius_given = true; a.temporal_rectify_radius = (uint32_t)std::stoul(val()); }
+        else if (k == "--temporal-rectify-gamma") { a.temporal_rectify_gamma_given = true; a.temporal_rectify_gamma = std::stof(val()); }
         else if (k == "--camera-step") {
             const std::string v = val();
             char tail = 0;
@@ -315,6 +336,22 @@ int main(int argc, char** argv) {
     if (a.temporal && a.denoise) { std::fprintf(stderr, "error: --temporal-frames with --denoise: the accumulated pair goes to --denoise-variance\n"); return 2; }
     if (a.temporal && a.adaptive_threshold != 0.0f) { std::fprintf(stderr, "error: --temporal-frames with --adaptive-threshold: temporal accumulation takes one sample count per frame\n"); return 2; }
     if (a.temporal && (a.spp == 0 || a.denoise_guide_spp == 0)) { std::fprintf(stderr, "error: --temporal-frames needs --spp and --denoise-guide-spp above 0\n"); return 2; }
+    if ((a.temporal_rectify || a.temporal_rectify_radius_given || a.temporal_rectify_gamma_given) && !a.temporal) {
+        std::fprintf(stderr, "error: --temporal-rectify, --temporal-rectify-radius and --temporal-rectify-gamma need --temporal-frames: they rectify its history\n");
+        return 2;
+    }
+    if ((a.temporal_rectify_radius_given || a.temporal_rectify_gamma_given) && !a.temporal_rectify) {
+        std::fprintf(stderr, "error: --temporal-rectify-radius and --temporal-rectify-gamma need --temporal-rectify\n");
+        return 2;
+    }
+    if (a.temporal_rectify_radius_given && (a.temporal_rectify_radius < 1 || a.temporal_rectify_radius > 3)) {
+        std::fprintf(stderr, "error: --temporal-rectify-radius must be 1, 2 or 3\n");
+        return 2;
+    }
+    if (a.temporal_rectify_gamma_given && !(std::isfinite(a.temporal_rectify_gamma) && a.temporal_rectify_gamma > 0.0f)) {
+        std::fprintf(stderr, "error: --temporal-rectify-gamma must be finite and above 0\n");
+        return 2;
+    }
     if (gbuf && (a.output.size() < 4 || a.output.compare(a.output.size() - 4, 4, ".pfm") != 0)) {
         std::fprintf(stderr, "error: --renderer %s writes float values: -o must end in .pfm (got '%s')\n", a.renderer.c_str(), a.output.c_str());
         return 2;
