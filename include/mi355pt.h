@@ -332,6 +332,13 @@ const char* mi355pt_version(void);
  * illumination.  Declared in its own header, which this one always includes. */
 #include "mi355pt_temporal_rectify.h"
 
+/* ---------------- guided half-resolution rendering ---------------- */
+/* EXTENSION, no reference counterpart: a film traced at W/2 x H/2 rebuilt at W x H — mi355pt_upsample_params, mi355pt_upsample_guides,
+ * mi355pt_upsample_params_default, mi355pt_upsample_low_camera, mi355pt_upsample_device and mi355pt_upsample: a joint-bilateral upsample
+ * whose taps are tested against the full-resolution G-buffer (plane distance, shading normal, emitter share).  Its output pair goes to the
+ * temporal accumulation, the variance-guided denoiser and the resolve as it is.  Declared in its own header, which this one always includes. */
+#include "mi355pt_upsample.h"
+
 /* ---------------- variance-guided denoiser ---------------- */
 /* EXTENSION, no reference counterpart: a second filter beside the one above, which it leaves as it is — mi355pt_denoise_var_params,
  * mi355pt_denoise_var_params_default, mi355pt_denoise_var_scratch_bytes, mi355pt_denoise_var_device and mi355pt_denoise_var: an a-trous

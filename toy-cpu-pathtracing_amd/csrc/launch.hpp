@@ -84,6 +84,18 @@ hipError_t launch_temporal_accumulate(const TemporalFrameDev& cur, const Tempora
 constexpr size_t TEMPORAL_RECTIFY_RECORD_BYTES = 32;
 hipError_t launch_temporal_rectify(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, uint32_t radius, float gamma, void* d_scratch,
                                    float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
+// pt_kernels_upsample.hip: the guided half-resolution upsample (include/mi355pt_upsample.h): one launch on the grid of denoise_grid_blocks
+// over the FULL frame.  The G-buffer sums of one resolution as the kernel takes them (albedo == nullptr: not given, then on both sides);
+// low_half == nullptr: no half film (then out_half is not written).  The launcher fills UpsampleArgs::blocks_x
+struct UpsampleGuidesDev { const float *albedo = nullptr, *shading_normal = nullptr, *position = nullptr, *hit = nullptr; };
+struct UpsampleArgs {
+    uint32_t width, height, blocks_x;      // the FULL frame, both even; the low frame is width / 2 x height / 2
+    float spp, half_spp;                   // (float)spp, (float)(spp / 2)
+    float spp_albedo_low, spp_albedo_full;
+    float pos_tol, normal_cos, emitter_tol, min_weight, albedo_eps;
+};
+hipError_t launch_upsample(const float* d_low_film, const float* d_low_half, const UpsampleGuidesDev& low, const UpsampleGuidesDev& full, UpsampleArgs args,
+                           float* d_out_film, float* d_out_half, hipStream_t);
 
 // Resident 64-thread blocks (= waves) of `kernel` on the current device: the persistent grid size of the EXACT instantiation a launch takes
 // (the register count, and so the occupancy, differs between instantiations and between translation units with their own backend flags).

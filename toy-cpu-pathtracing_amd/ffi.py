@@ -162,6 +162,19 @@ class TemporalRectifyParams(C.Structure):
     _fields_ = [("radius", C.c_uint32), ("gamma", C.c_float)]
 
 
+class UpsampleParams(C.Structure):
+    """mi355pt_upsample_params (include/mi355pt_upsample.h); Product.upsample_params_default() fills it — a zeroed one is refused"""
+    _fields_ = [("pos_tol", C.c_float), ("normal_cos", C.c_float), ("emitter_tol", C.c_float), ("min_weight", C.c_float), ("albedo_eps", C.c_float)]
+
+
+class UpsampleGuides(C.Structure):
+    """mi355pt_upsample_guides: the raw G-buffer sums of one resolution, device or host pointers; albedo may be NULL (then on both sides)"""
+    _fields_ = [("albedo", C.c_void_p), ("shading_normal", C.c_void_p), ("position", C.c_void_p), ("hit", C.c_void_p)]
+
+
+UPSAMPLE_GUIDES = ("albedo", "shading_normal", "position", "hit")
+
+
 def make_camera(position, direction, up, width, height, fov_deg=45.0):
     return Camera((C.c_float * 3)(*position), (C.c_float * 3)(*direction), (C.c_float * 3)(*up), fov_deg, width, height)
 
@@ -199,6 +212,8 @@ TEMPORAL_SYMBOLS = ["temporal_params_default", "temporal_view_from_cameras", "te
 # ... and include/mi355pt_temporal_rectify.h, its rectified form (tests/test_temporal_rectify.py)
 TEMPORAL_RECTIFY_SYMBOLS = ["temporal_rectify_params_default", "temporal_rectify_scratch_bytes", "temporal_accumulate_rectified_device",
                             "temporal_accumulate_rectified"]
+# ... and include/mi355pt_upsample.h, the guided half-resolution block (tests/test_upsample.py)
+UPSAMPLE_SYMBOLS = ["upsample_params_default", "upsample_low_camera", "upsample_device", "upsample"]
 ADAPTIVE_SYMBOLS = ["adaptive_scratch_bytes", "adaptive_step_device", "film_normalize_tiles_device", "render_adaptive_device", "render_adaptive"]
 
 
@@ -467,7 +482,14 @@ class Product(Backend):
             lib.mi355pt_temporal_accumulate_rectified.argtypes = [C.POINTER(TemporalFrame), C.c_uint32, C.POINTER(TemporalFrame), C.POINTER(TemporalView), C.c_uint32,
                                                                   C.c_uint32, C.POINTER(TemporalParams), C.POINTER(TemporalRectifyParams), C.c_void_p, C.c_void_p,
                                                                   C.c_void_p]
-        if not hasattr(lib, "mi355pt_render_sample_log"):      # an older build loaded through MI355PT_LIB for an A/B timing run
+        if hasattr(lib, "mi355pt_upsample_device"):  # (absent from an older build loaded through MI355PT_LIB)
+            lib.mi355pt_upsample_params_default.argtypes = [C.POINTER(UpsampleParams)]; lib.mi355pt_upsample_params_default.restype = None
+            lib.mi355pt_upsample_low_camera.argtypes = [C.POINTER(Camera), C.POINTER(Camera)]
+            lib.mi355pt_upsample_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(UpsampleGuides), C.c_uint32, C.POINTER(UpsampleGuides), C.c_uint32,
+                                                    C.c_uint32, C.c_uint32, C.POINTER(UpsampleParams), C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.mi355pt_upsample.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(UpsampleGuides), C.c_uint32, C.POINTER(UpsampleGuides), C.c_uint32,
+                                             C.c_uint32, C.c_uint32, C.POINTER(UpsampleParams), C.c_void_p, C.c_void_p]
+        if not hasattr(lib, "mi355pt_render_sample_log"):     # an older build loaded through MI355PT_LIB for an A/B timing run
             return
         lib.mi355pt_sample_log_records.argtypes = [C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]
         lib.mi355pt_render_sample_log.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_uint32] + \
@@ -677,6 +699,48 @@ class Product(Backend):
                                                                   out_film.ctypes.data, out_half.ctypes.data if out_half is not None else None,
                                                                   out_len.ctypes.data), "temporal_accumulate_rectified")
         return out_film, out_half, out_len
+
+    # ---- guided half-resolution rendering (include/mi355pt_upsample.h): a film traced at W/2 x H/2 rebuilt at W x H through both G-buffers ----
+    def upsample_params_default(self):
+        p = UpsampleParams()
+        self.lib.mi355pt_upsample_params_default(C.byref(p))
+        return p
+
+    def upsample_low_camera(self, full):
+        """mi355pt_upsample_low_camera (host only) -> Camera of width / 2 x height / 2"""
+        low = Camera()
+        self.check(self.lib.mi355pt_upsample_low_camera(C.byref(full), C.byref(low)), "upsample_low_camera")
+        return low
+
+    def upsample_device(self, d_low_film_ptr, d_low_half_ptr, spp, low_guides, spp_albedo_low, full_guides, spp_albedo_full, width, height, params,
+                        d_out_film_ptr, d_out_half_ptr, stream=None):
+        """mi355pt_upsample_device: low_guides / full_guides map guide names (UPSAMPLE_GUIDES) to device pointers (a name left out or None is
+        NULL); width and height are the FULL size; d_low_half_ptr and d_out_half_ptr None or 0 without a half film"""
+        gl = UpsampleGuides(*[C.c_void_p(low_guides.get(k) or None) for k in UPSAMPLE_GUIDES])
+        gf = UpsampleGuides(*[C.c_void_p(full_guides.get(k) or None) for k in UPSAMPLE_GUIDES])
+        self.check(self.lib.mi355pt_upsample_device(C.c_void_p(d_low_film_ptr), C.c_void_p(d_low_half_ptr or 0), spp, C.byref(gl), spp_albedo_low, C.byref(gf),
+                                                    spp_albedo_full, width, height, C.byref(params), C.c_void_p(d_out_film_ptr), C.c_void_p(d_out_half_ptr or 0),
+                                                    C.c_void_p(stream or 0)), "upsample_device")
+
+    def upsample(self, low_film, low_half, spp, low_guides, spp_albedo_low, full_guides, spp_albedo_full, params=None):
+        """mi355pt_upsample on host arrays: low_film / low_half (h, w, 3) float32 sums (low_half may be None), the guides map names to
+        (h, w, 3) / (H, W, 3) arrays -> (out_film, out_half or None), (H, W, 3)"""
+        def host(g):
+            keep = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in g.items() if v is not None and k in UPSAMPLE_GUIDES}
+            return keep, UpsampleGuides(*[keep[k].ctypes.data if k in keep else None for k in UPSAMPLE_GUIDES])
+        kl, gl = host(low_guides)
+        kf, gf = host(full_guides)
+        b = np.ascontiguousarray(low_film, dtype=np.float32)
+        hf = None if low_half is None else np.ascontiguousarray(low_half, dtype=np.float32)
+        h, w = kf["hit"].shape[:2]
+        assert b.shape == (h // 2, w // 2, 3) and kl["hit"].shape == b.shape
+        params = params if params is not None else self.upsample_params_default()
+        out_film = np.zeros((h, w, 3), np.float32)
+        out_half = np.zeros((h, w, 3), np.float32) if hf is not None else None
+        self.check(self.lib.mi355pt_upsample(b.ctypes.data, hf.ctypes.data if hf is not None else None, spp, C.byref(gl), spp_albedo_low, C.byref(gf),
+                                             spp_albedo_full, w, h, C.byref(params), out_film.ctypes.data,
+                                             out_half.ctypes.data if out_half is not None else None), "upsample")
+        return out_film, out_half
 
     def render_accum_device(self, scene, cam, params, s_begin, s_end, d_accum_ptr, stream=None, stats=None):
         self.check(self.lib.mi355pt_render_accum_device(scene.h, C.byref(cam), C.byref(params), s_begin, s_end, C.c_void_p(d_accum_ptr),

@@ -7,7 +7,7 @@
 #include <stdexcept>
 #include <string>
 
-#include <hip/hip_runtime_api.h>   // --denoise, --denoise-variance, --adaptive-threshold and --temporal-frames: the films of those paths stay on the device (hipMalloc / hipMemcpy / hipFree, no kernels here)
+#include <hip/hip_runtime_api.h>   // --denoise, --denoise-variance, --adaptive-threshold, --temporal-frames and --half-res: the films of those paths stay on the device (hipMalloc / hipMemcpy / hipFree, no kernels here)
 
 #include "scenes.hpp"
 
@@ -33,6 +33,9 @@ struct Args {   // main.rs:20-53
     // and its rectified form (mi355pt_temporal_rectify.h): the history is first scaled to the current frame's local mean; radius and gamma not given = its defaults
     bool temporal_rectify = false, temporal_rectify_radius_given = false, temporal_rectify_gamma_given = false;
     uint32_t temporal_rectify_radius = 0; float temporal_rectify_gamma = 0.0f;
+    // nor guided half-resolution rendering (mi355pt_upsample.h): the paths traced at width / 2 x height / 2, the frame rebuilt through both G-buffers;
+    // albedo demodulation is off by default (profiles/upsample_quality.json: it does not win on both measured scenes)
+    bool half_res = false, half_res_albedo = false;
 };
 
 // --denoise: the beauty film at --spp, the albedo and shading-normal films at --denoise-guide-spp (converged guides cost a few percent of
@@ -257,6 +260,108 @@ static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params
     return kernel_ms * 1e-3;
 }
 
+// --half-res [--half-res-albedo]: the paths are traced at width / 2 x height / 2 and the frame is rebuilt at width x height
+// (mi355pt_upsample.h).  Per frame: the camera of the low frame from mi355pt_upsample_low_camera, rendered on the SAME built scene (a build
+// fixes the position only); the low and the full G-buffer at --denoise-guide-spp (shading normal, position, hit — the low albedo with
+// --half-res-albedo, the full albedo with it or when --denoise-variance follows); the low beauty film (and the low half film with
+// --denoise-variance); mi355pt_upsample_device.  With --temporal-frames N the upsampled pair is the current frame (spp 2, or 1 without a half
+// film) of the accumulation of render_temporal, frame k with seed + k from position + k * step.  Then optionally the variance-guided filter on
+// the pair (spp 2) with the full guides, then Sensor::to_rgb.  Returns the device seconds of the (low) beauty launches.
+static double render_half_res(Scene& scene, const Camera& camera, mi355pt_params p, const Args& a, std::vector<float>& pixels) {
+    const mi355pt_camera base = camera.raw();
+    const uint32_t n_pixels = base.width * base.height, n_low = (base.width / 2) * (base.height / 2), guide_spp = a.denoise_guide_spp;
+    const size_t film_bytes = (size_t)n_pixels * 3 * sizeof(float), low_bytes = (size_t)n_low * 3 * sizeof(float), len_bytes = (size_t)n_pixels * sizeof(float);
+    const bool half = a.denoise_variance, demod = a.half_res_albedo, full_albedo = demod || half;
+    const bool moving = a.camera_step[0] != 0.0f || a.camera_step[1] != 0.0f || a.camera_step[2] != 0.0f;
+    const uint32_t frames = a.temporal ? a.temporal_frames : 1u, up_spp = half ? 2u : 1u;
+    const size_t opt = half ? film_bytes : sizeof(float), topt = a.temporal ? film_bytes : sizeof(float), thopt = a.temporal && half ? film_bytes : sizeof(float);
+    // the full G-buffer in two sets that alternate (the temporal accumulation reads the previous frame's), the low one, the low films, the upsampled pair
+    DeviceFilm normal0(film_bytes), normal1(topt), position0(film_bytes), position1(topt), hit0(film_bytes), hit1(topt), albedo(full_albedo ? film_bytes : sizeof(float));
+    DeviceFilm lnormal(low_bytes), lposition(low_bytes), lhit(low_bytes), lalbedo(demod ? low_bytes : sizeof(float)), lbeauty(low_bytes), lhalf(half ? low_bytes : sizeof(float));
+    DeviceFilm up(film_bytes), uph(opt), rgb(film_bytes);
+    DeviceFilm acc0(topt), acc1(topt), acch0(thopt), acch1(thopt), len0(a.temporal ? len_bytes : sizeof(float)), len1(a.temporal ? len_bytes : sizeof(float));
+    float *normal[2] = {normal0.p, a.temporal ? normal1.p : normal0.p}, *position[2] = {position0.p, a.temporal ? position1.p : position0.p};
+    float *hit[2] = {hit0.p, a.temporal ? hit1.p : hit0.p}, *acc[2] = {acc0.p, acc1.p}, *acch[2] = {acch0.p, acch1.p}, *len[2] = {len0.p, len1.p};
+    mi355pt_upsample_params up_params;
+    mi355pt_upsample_params_default(&up_params);
+    mi355pt_temporal_params tp;
+    mi355pt_temporal_params_default(&tp);
+    mi355pt_temporal_rectify_params rp;
+    mi355pt_temporal_rectify_params_default(&rp);
+    if (a.temporal_rectify_radius_given) rp.radius = a.temporal_rectify_radius;
+    if (a.temporal_rectify_gamma_given) rp.gamma = a.temporal_rectify_gamma;
+    const size_t rectify_bytes = a.temporal_rectify ? mi355pt_temporal_rectify_scratch_bytes(base.width, base.height) : sizeof(float);
+    DeviceFilm rectify_scratch(rectify_bytes);
+    mi355pt_camera cam = base, cam_prev = base, low_cam{};
+    double kernel_ms = 0.0;
+    int c = 0;
+    for (uint32_t k = 0; k < frames; ++k) {
+        c = (int)(k & 1u);
+        const int q = c ^ 1;
+        cam_prev = cam;
+        for (int i = 0; i < 3; ++i) cam.position[i] = base.position[i] + (float)k * a.camera_step[i];
+        if (k > 0 && moving) {
+            Camera moved(base.fov_deg, base.width, base.height);
+            moved.set_look_to({cam.position[0], cam.position[1], cam.position[2]}, {cam.direction[0], cam.direction[1], cam.direction[2]}, {cam.up[0], cam.up[1], cam.up[2]});
+            scene.build(moved);
+        }
+        check(mi355pt_upsample_low_camera(&cam, &low_cam), "mi355pt_upsample_low_camera");
+        p.seed = a.seed + k;
+        bool ok = hipMemset(normal[c], 0, film_bytes) == hipSuccess && hipMemset(position[c], 0, film_bytes) == hipSuccess && hipMemset(hit[c], 0, film_bytes) == hipSuccess &&
+                  hipMemset(lnormal.p, 0, low_bytes) == hipSuccess && hipMemset(lposition.p, 0, low_bytes) == hipSuccess && hipMemset(lhit.p, 0, low_bytes) == hipSuccess &&
+                  hipMemset(lbeauty.p, 0, low_bytes) == hipSuccess;
+        if (full_albedo) ok = ok && hipMemset(albedo.p, 0, film_bytes) == hipSuccess;
+        if (demod) ok = ok && hipMemset(lalbedo.p, 0, low_bytes) == hipSuccess;
+        if (half) ok = ok && hipMemset(lhalf.p, 0, low_bytes) == hipSuccess;
+        if (!ok) throw std::runtime_error("mi355pt: clearing the frame's films failed");
+        mi355pt_params g = p;
+        g.spp = guide_spp;
+        const mi355pt_gbuffer_films full_films{full_albedo ? albedo.p : nullptr, normal[c], position[c], hit[c]};
+        const mi355pt_gbuffer_films low_films{demod ? lalbedo.p : nullptr, lnormal.p, lposition.p, lhit.p};
+        check(mi355pt_render_gbuffer_accum_device(scene.raw(), &cam, &g, scene.d65_lut(), 0, guide_spp, &full_films, nullptr, nullptr), "mi355pt_render_gbuffer_accum_device");
+        check(mi355pt_render_gbuffer_accum_device(scene.raw(), &low_cam, &g, scene.d65_lut(), 0, guide_spp, &low_films, nullptr, nullptr), "mi355pt_render_gbuffer_accum_device");
+        mi355pt_stats st0{}, st1{};
+        if (half) {
+            check(mi355pt_render_accum_device(scene.raw(), &low_cam, &p, 0, p.spp / 2, lhalf.p, nullptr, &st0), "mi355pt_render_accum_device");
+            if (hipMemcpy(lbeauty.p, lhalf.p, low_bytes, hipMemcpyDeviceToDevice) != hipSuccess) throw std::runtime_error("mi355pt: copying the half film failed");
+            check(mi355pt_render_accum_device(scene.raw(), &low_cam, &p, p.spp / 2, p.spp, lbeauty.p, nullptr, &st1), "mi355pt_render_accum_device");
+        } else {
+            check(mi355pt_render_accum_device(scene.raw(), &low_cam, &p, 0, p.spp, lbeauty.p, nullptr, &st0), "mi355pt_render_accum_device");
+        }
+        kernel_ms += st0.kernel_ms + st1.kernel_ms;
+        const mi355pt_upsample_guides lg{demod ? lalbedo.p : nullptr, lnormal.p, lposition.p, lhit.p};
+        const mi355pt_upsample_guides fg{demod ? albedo.p : nullptr, normal[c], position[c], hit[c]};
+        check(mi355pt_upsample_device(lbeauty.p, half ? lhalf.p : nullptr, p.spp, &lg, guide_spp, &fg, guide_spp, base.width, base.height, &up_params, up.p,
+                                      half ? uph.p : nullptr, nullptr), "mi355pt_upsample_device");
+        if (!a.temporal) continue;
+        const mi355pt_temporal_frame cur{up.p, half ? uph.p : nullptr, nullptr, position[c], normal[c], hit[c]};
+        const mi355pt_temporal_frame prev{acc[q], half ? acch[q] : nullptr, len[q], position[q], normal[q], hit[q]};
+        mi355pt_temporal_view view{};
+        if (k > 0) check(mi355pt_temporal_view_from_cameras(&cam, &cam_prev, &view), "mi355pt_temporal_view_from_cameras");
+        if (a.temporal_rectify)
+            check(mi355pt_temporal_accumulate_rectified_device(&cur, up_spp, k > 0 ? &prev : nullptr, k > 0 ? &view : nullptr, base.width, base.height, &tp, &rp,
+                                                               rectify_scratch.p, rectify_bytes, acc[c], half ? acch[c] : nullptr, len[c], nullptr),
+                  "mi355pt_temporal_accumulate_rectified_device");
+        else
+            check(mi355pt_temporal_accumulate_device(&cur, up_spp, k > 0 ? &prev : nullptr, k > 0 ? &view : nullptr, base.width, base.height, &tp, acc[c],
+                                                     half ? acch[c] : nullptr, len[c], nullptr), "mi355pt_temporal_accumulate_device");
+    }
+    const float* film = a.temporal ? acc[c] : up.p;           // the pair that leaves the loop: spp 2 with a half film; a mean without (the accumulation's, the upsample's)
+    const float* film_half = a.temporal ? acch[c] : uph.p;
+    if (half) {
+        const size_t scratch_bytes = mi355pt_denoise_var_scratch_bytes(base.width, base.height);
+        DeviceFilm out(film_bytes), scratch(scratch_bytes);
+        const mi355pt_denoise_var_params dp = denoise_var_params(a.denoise_sigma_lum);
+        check(mi355pt_denoise_var_device(film, film_half, 2, nullptr, albedo.p, guide_spp, normal[c], guide_spp, base.width, base.height, &dp, scratch.p, scratch_bytes,
+                                         out.p, nullptr), "mi355pt_denoise_var_device");
+        check(mi355pt_film_resolve_device(out.p, n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
+    } else {
+        check(mi355pt_film_resolve_device(film, n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
+    }
+    if (hipMemcpy(pixels.data(), rgb.p, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the frame back failed");
+    return kernel_ms * 1e-3;
+}
+
 static void usage() {
     std::puts("Usage: mi355pt [--scene N] [-s|--spp N] [--seed N] [--filter box] [--sampler random|sobol]\n"
               "               [--renderer normal|albedo|pt|nee|mis] [--width N] [--height N] [-d|--max-depth N] [-o|--output FILE]\n"
@@ -275,7 +380,10 @@ static void usage() {
               "                   [--camera-step dx,dy,dz] (with --temporal-frames: frame k renders from position + k * step)\n"
               "                   [--temporal-rectify] (with --temporal-frames: the gathered history is first scaled so that its local mean agrees with the\n"
               "                                         current frame's: the accumulation follows a change of illumination)\n"
-              "                   [--temporal-rectify-radius R] (2; 1 .. 3: the window is (2R + 1)^2 pixels)  [--temporal-rectify-gamma G] (2; > 0: standard errors allowed)");
+              "                   [--temporal-rectify-radius R] (2; 1 .. 3: the window is (2R + 1)^2 pixels)  [--temporal-rectify-gamma G] (2; > 0: standard errors allowed)\n"
+              "                   [--half-res] (pt|nee|mis, even --width and --height: the paths are traced at half the width and height and the frame is rebuilt at\n"
+              "                                 full size through the G-buffers of both sizes at --denoise-guide-spp; with --denoise-variance and --temporal-frames)\n"
+              "                   [--half-res-albedo] (with --half-res: the low film is divided by the low albedo and multiplied by the full one)");
 }
 
 int main(int argc, char** argv) {
@@ -308,6 +416,8 @@ int main(int argc, char** argv) {
         else if (k == "--temporal-rectify") a.temporal_rectify = true;
         else if (k == "--temporal-rectify-radius") { a.temporal_rectify_radius_given = true; a.temporal_rectify_radius = (uint32_t)std::stoul(val()); }
         else if (k == "--temporal-rectify-gamma") { a.temporal_rectify_gamma_given = true; a.temporal_rectify_gamma = std::stof(val()); }
+        else if (k == "--half-res") a.half_res = true;
+        else if (k == "--half-res-albedo") a.half_res_albedo = true;
         else if (k == "--camera-step") {
             const std::string v = val();
             char tail = 0;
@@ -329,6 +439,13 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "error: invalid value '%s' for '--renderer' (main.rs:38-40: normal, albedo, pt, nee, mis; extensions: shading-normal, position, depth)\n", a.renderer.c_str());
         return 2;
     }
+    if (a.half_res_albedo && !a.half_res) { std::fprintf(stderr, "error: --half-res-albedo needs --half-res: it demodulates the film that --half-res upsamples\n"); return 2; }
+    if (a.half_res && aov) { std::fprintf(stderr, "error: --half-res with --renderer %s: half-resolution rendering is for the path renderers (pt, nee, mis)\n", a.renderer.c_str()); return 2; }
+    if (a.half_res && (a.width == 0 || a.height == 0 || (a.width & 1u) != 0 || (a.height & 1u) != 0)) { std::fprintf(stderr, "error: --half-res needs an even --width and --height above 0 (got %u x %u)\n", a.width, a.height); return 2; }
+    if (a.half_res && a.gpus > 1) { std::fprintf(stderr, "error: --half-res with --gpus %d: half-resolution rendering runs on one GPU\n", a.gpus); return 2; }
+    if (a.half_res && a.denoise) { std::fprintf(stderr, "error: --half-res with --denoise: the upsampled pair goes to --denoise-variance\n"); return 2; }
+    if (a.half_res && a.adaptive_threshold != 0.0f) { std::fprintf(stderr, "error: --half-res with --adaptive-threshold: half-resolution rendering takes one sample count per frame\n"); return 2; }
+    if (a.half_res && (a.spp == 0 || a.denoise_guide_spp == 0)) { std::fprintf(stderr, "error: --half-res needs --spp and --denoise-guide-spp above 0\n"); return 2; }
     if (a.camera_step_given && !a.temporal) { std::fprintf(stderr, "error: --camera-step needs --temporal-frames: it moves the camera between the frames\n"); return 2; }
     if (a.temporal && a.temporal_frames == 0) { std::fprintf(stderr, "error: --temporal-frames must be above 0\n"); return 2; }
     if (a.temporal && aov) { std::fprintf(stderr, "error: --temporal-frames with --renderer %s: temporal accumulation is for the path renderers (pt, nee, mis)\n", a.renderer.c_str()); return 2; }
@@ -420,6 +537,7 @@ int main(int argc, char** argv) {
         const SamplerKind sampler = a.sampler == "sobol" ? SamplerKind::ZSobol : SamplerKind::Random;
         double kernel_s = 0.0;
         if (gbuf) kernel_s = render_gbuffer_float(scene, camera, image.params(sampler, a.albedo_lut), a.renderer == "depth", image.pixels_mut());
+        else if (a.half_res) kernel_s = render_half_res(scene, camera, image.params(sampler, a.albedo_lut), a, image.pixels_mut());
         else if (a.temporal) kernel_s = render_temporal(scene, camera, image.params(sampler, a.albedo_lut), a, image.pixels_mut());
         else if (adaptive) render_adaptive(scene, camera, image.params(sampler, a.albedo_lut), a, image.pixels_mut());
         else if (a.denoise_variance) kernel_s = render_denoised_variance(scene, camera, image.params(sampler, a.albedo_lut), a.denoise_guide_spp, a.fused_guides, a.denoise_sigma_lum, image.pixels_mut());
@@ -427,7 +545,8 @@ int main(int argc, char** argv) {
                                     : image.render(sampler, a.albedo_lut);
         double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         std::printf("Finish rendering: %.3f seconds.\n", wall);
-        if (kernel_s > 0.0 && a.temporal) std::printf("(beauty launches of %u frames: device %.3f s; the G-buffer, the accumulation and the scene builds are in the wall time above)\n", a.temporal_frames, kernel_s);
+        if (kernel_s > 0.0 && a.half_res) std::printf("(beauty launches at %u x %u: device %.3f s; the two G-buffers, the upsample and what follows it are in the wall time above)\n", a.width / 2, a.height / 2, kernel_s);
+        else if (kernel_s > 0.0 && a.temporal) std::printf("(beauty launches of %u frames: device %.3f s; the G-buffer, the accumulation and the scene builds are in the wall time above)\n", a.temporal_frames, kernel_s);
         else if (kernel_s > 0.0 && (a.denoise || a.denoise_variance)) std::printf("(beauty launch alone: device %.3f s, %.1f Msamples/s; the guide films and the filter are in the wall time above)\n", kernel_s, (double)a.width * a.height * a.spp / kernel_s / 1e6);
         else if (kernel_s > 0.0) std::printf("(device %.3f s, %.1f Msamples/s)\n", kernel_s, (double)a.width * a.height * a.spp / kernel_s / 1e6);
         if (gbuf) write_pfm(a.output, image.pixels().data(), a.width, a.height); else image.save(a.output);
