@@ -31,6 +31,16 @@ int mi355pt_scene_debug_set_lowering(mi355pt_scene* s, int mode);
 int mi355pt_scene_debug_lowering_digest(const mi355pt_scene* s, const mi355pt_camera* cam, char* names_buf, size_t names_len,
                                         uint64_t* digests, uint32_t* n);
 
+/* The camera-ray candidate lists of the production kernels (csrc/camera_candidates.hpp), computed on the host: lowers the scene for `cam`
+ * like mi355pt_scene_debug_lowering_digest (no device, the scene left as it is) and runs the header's walk over the lowered 4-wide tree
+ * for each of n_rects pixel rectangles (rects: x0, y0, x1, y1 per rectangle, inclusive; the kernels' rectangle is a work item's pixel
+ * block).  Rectangle r: out_counts[r] leaf-order triangle indices in out_indices[r * cap ...] (NULL ok), out_overflow[r] != 0 when more than
+ * `cap` triangles qualify and the list is incomplete (cap 1 .. 4096; the kernels' is 16).  out_tris (NULL ok): the lowered triangles in leaf
+ * order, 9 floats each, RENDER space; *n_tris (NULL ok) holds its capacity in triangles on entry and the triangle count on return.
+ * Nothing on the render path calls this: tests/test_camera_candidates*.py and tools/camera_list_stats.py do. */
+int mi355pt_scene_debug_camera_candidates(const mi355pt_scene* s, const mi355pt_camera* cam, const uint32_t* rects, uint32_t n_rects, uint32_t cap,
+                                          uint32_t* out_counts, uint8_t* out_overflow, uint32_t* out_indices, float* out_tris, uint32_t* n_tris);
+
 /* ---------------- probes (parity tests; same device code as the render path) ---------------- */
 /* The built acceleration structure as the device holds it (no reference counterpart; the reference's is scene/src/bvh.rs:300-343):
  * node records of 64 B {bx[4] = lo0.x lo1.x hi0.x hi1.x, by[4], bz[4], int32 child[2] (>= 0 node index, < 0 leaf:

@@ -157,8 +157,12 @@ static int launch_range(const mi355pt_scene* s, const mi355pt_camera* cam, const
     if ((rc = grow_device_buffer(&lc->d_defer, &lc->defer_bytes, aov ? (size_t)0 : query_defer_bytes_per_wave(key) * (size_t)plan.grid, stream))) return rc;
     if (aov) HIP_TRY(launch_aov((uint32_t)aov_kind, s->impl.dev, dc, dp, illuminant_lut, lc->d_hash, d_accum, d_counter, stats ? d_stats : nullptr,
                                 s->impl.features, plan.grid, stream));
-    else HIP_TRY(launch_pt(key, s->impl.dev, dc, dp, plan.n_tiles,
-                           lc->d_hash, d_accum, lc->d_partial, d_counter, d_list ? nullptr : d_stats, plan.grid, stream, pout, lc->d_defer));
+    else {
+        DevScene dev = s->impl.dev;
+        dev.cam_lists = use_camera_lists(key, dp.block_log2, camera_lists_enabled()) ? 1u : 0u;
+        HIP_TRY(launch_pt(key, dev, dc, dp, plan.n_tiles,
+                          lc->d_hash, d_accum, lc->d_partial, d_counter, d_list ? nullptr : d_stats, plan.grid, stream, pout, lc->d_defer));
+    }
     if (stats) {
         HIP_TRY(hipEventRecord(e1, stream));
         HIP_TRY(hipEventSynchronize(e1));

@@ -9,6 +9,7 @@
 
 #include "../../include/mi355pt_debug.h"
 #include "api_internal.hpp"
+#include "camera_candidates.hpp"
 #include "scene_lower.hpp"
 
 using namespace pt;
@@ -46,6 +47,42 @@ int mi355pt_scene_debug_lowering_digest(const mi355pt_scene* s, const mi355pt_ca
     if (cap < dig.size() || names_len < text.size() + 1) return fail(MI355PT_E_INVALID, "digest or name buffer too small");
     std::memcpy(digests, dig.data(), dig.size() * sizeof(uint64_t));
     std::memcpy(names_buf, text.c_str(), text.size() + 1);
+    return MI355PT_OK;
+}
+
+int mi355pt_scene_debug_camera_candidates(const mi355pt_scene* s, const mi355pt_camera* cam, const uint32_t* rects, uint32_t n_rects, uint32_t cap,
+                                          uint32_t* out_counts, uint8_t* out_overflow, uint32_t* out_indices, float* out_tris, uint32_t* n_tris) {
+    if (!s || !cam || (n_rects && (!rects || !out_counts || !out_overflow))) return fail(MI355PT_E_INVALID, "null argument");
+    if (cap < 1u || cap > 4096u) return fail(MI355PT_E_INVALID, "cap must be 1 .. 4096");
+    if (PT_NODE_Q16) return fail(MI355PT_E_INVALID, "the candidate walk reads the float 4-wide tree");
+    // the lowering of mi355pt_scene_debug_lowering_digest: host builder, nothing uploaded
+    std::string err;
+    int rc;
+    LoweredGeometry geo; BvhOut bvh; LoweredScene ls; LowerReport rep;
+    if ((rc = lower_geometry(s->impl, cam, &geo, &err))) return fail(rc, err);
+    build_bvh(geo.build_tris, &bvh);
+    if (bvh.max_depth >= STACK_DEPTH) return fail(MI355PT_E_INVALID, "BVH deeper than the traversal stack");
+    float cmf[470 * 4];
+    cie_cmf4(cmf);
+    if ((rc = lower_scene(s->impl, std::move(geo), std::move(bvh), cmf, &ls, &rep, &err)) || (rc = lower_tree4(&ls, &rep, &err))) return fail(rc, err);
+    const uint32_t n = (uint32_t)ls.tris_render.size();
+    if (out_tris) {
+        if (!n_tris || *n_tris < n) return fail(MI355PT_E_INVALID, "triangle buffer too small");
+        for (uint32_t i = 0; i < n; ++i) std::memcpy(out_tris + 9 * (size_t)i, &ls.tris_render[i], 9 * sizeof(float));    // p0, p1, p2: the record's first 36 bytes
+    }
+    if (n_tris) *n_tris = n;
+#if !PT_NODE_Q16
+    const DevCamera dc = make_camera(cam);
+    const DevTri* tris = ls.dev.tris_are_local ? ls.tris_local.data() : ls.tris_render.data();      // DevScene::tris (scene.cpp upload)
+    uint32_t stack[CAM_WALK_STACK];
+    std::vector<uint32_t> list(cap);
+    for (uint32_t r = 0; r < n_rects; ++r) {
+        const uint32_t* q = rects + 4 * (size_t)r;
+        const CamWalk w = cam_walk(ls.nodes4.data(), ls.dev.root4, tris, ls.dev.tri_shift, cam_pyramid(dc, q[0], q[1], q[2], q[3]), list.data(), cap, stack);
+        out_counts[r] = w.count; out_overflow[r] = w.overflow ? 1 : 0;
+        if (out_indices) std::memcpy(out_indices + (size_t)r * cap, list.data(), sizeof(uint32_t) * w.count);
+    }
+#endif
     return MI355PT_OK;
 }
 

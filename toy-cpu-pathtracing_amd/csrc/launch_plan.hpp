@@ -218,4 +218,14 @@ inline KernelKey select_kernel(bool tiles, bool stats, uint32_t feat, uint32_t s
     return KernelKey{tiles, false, mode, pick_features(feat)};
 }
 
+// ---- camera-ray candidate lists (camera_candidates.hpp, pt_kernel_body.inc) ----
+// Does the launch take its camera-ray hits from per-work-item triangle lists (DevScene::cam_lists)?  Only the production kernels with the
+// tail queue have the code (pt_kernel.hpp tail_queue_of: the instrumented kernels, the plain path tracer and the two-traversal clearcoat
+// kernels walk the tree for every ray as before).  Every block size builds lists: measured, the 8x8 items of a 64-index launch gain 2.2 %
+// with them (95 % of scene 3's 8x8 blocks stay within the cap) and lose 0.5 % without (profiles/camera_list_ab.json); block_log2 is the
+// place to exclude a shape should one lose.  `enabled`: camera_lists_enabled().
+inline bool use_camera_lists(const KernelKey& key, uint32_t block_log2, bool enabled) { return enabled && !key.stats && block_log2 <= 3u; }
+// the host-side switch, read per launch: MI355PT_NO_CAMERA_LISTS=1 (any value but "0") turns the lists off; default on
+inline bool camera_lists_enabled() { const char* e = getenv("MI355PT_NO_CAMERA_LISTS"); return !(e && e[0] != '\0' && !(e[0] == '0' && e[1] == '\0')); }
+
 }  // namespace pt

@@ -237,7 +237,9 @@ struct DevScene {
     uint32_t n_nodes, n_tris, n_lights, n_materials;
     int32_t root;                 // root link (node index, or leaf if the scene has <= MAX_LEAF_TRIS tris)
     int32_t root4;                // root of nodes4
-    uint32_t n_nodes4, pad1;
+    uint32_t n_nodes4;
+    uint32_t cam_lists;           // 1: the production kernels take camera-ray hits from per-work-item candidate lists (camera_candidates.hpp).  0 in the
+                                  // lowered scene; the launcher sets it in its own copy, per launch (launch_plan.hpp use_camera_lists)
     const DevEnv* envs;           // every infinite light of the scene (Scene sums them all: scene.rs:185-231)
     uint32_t n_envs, pad_env;
 };

@@ -11,8 +11,19 @@
 #include "pt_device.hpp"
 #include "pt_path.hpp"
 #include "tail_queue_plan.hpp"
+// (a wave-uniform value the compiler cannot see as one — it came through LDS — goes back to a scalar register)
+#define PT_CAM_UNIFORM(v) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(v)))
+#include "camera_candidates.hpp"
 
 namespace pt {
+
+// CAMERA RAYS FROM A LIST (camera_candidates.hpp): the kernels with the tail queue find, once per work item, the triangles a camera ray of
+// the item's pixel block can hit (a walk of the 4-wide tree against the block's pyramid of directions, by the whole wave in lockstep) and
+// keep up to CAM_LIST_CAP indices in LDS.  A fresh camera ray then takes its hit from that list — the ring flush's own triangle test on each
+// candidate, the atomicMin merge's own key, winner_hit — and stays out of the cooperative traversal; an iteration that holds only fresh
+// camera rays skips the traversal.  A list that overflows, DevScene::cam_lists == 0 (launch_plan.hpp use_camera_lists), and every other
+// kernel: the traversal for every ray, as before.  cam_n == CAM_LIST_NONE says so.
+constexpr uint32_t CAM_LIST_NONE = 0xffffffffu;
 
 #ifndef PT_MIN_WAVES_CC
 #define PT_MIN_WAVES_CC 3

@@ -25,6 +25,8 @@
     const ClosestLds closest_lds{s_ring, s_best, s_pair};
     __shared__ uint32_t s_infl[2];
     const PairLds pair_lds{s_ring, s_best, s_occl, s_pair, s_infl};
+    constexpr bool CAMLIST = !STATS && tail_queue<FEAT, MODE>();          // camera rays from the work item's candidate list (pt_kernel.hpp)
+    __shared__ uint32_t s_cand[CAMLIST ? CAM_LIST_CAP : 1u];
     DevParams prm = prm_in;
     if constexpr (MODE == MODE_MIS_SOBOL) { prm.strategy = 2u; prm.sampler = 1u; }
     if constexpr (MODE == MODE_NEE_SOBOL) { prm.strategy = 1u; prm.sampler = 1u; }
@@ -91,6 +93,16 @@
             }
             sctx.hi_lds = s_hi; sctx.p6_lds = s_p6;
         }
+        // the item's camera-ray candidates: every lane walks the tree against the block's pyramid with the same arguments (the links pending
+        // in s_ring: no traversal is in flight between items), so the wave runs the walk uniformly and all lanes store the same list
+        uint32_t cam_n = CAM_LIST_NONE;                            // wave-uniform: candidates in s_cand, or none (no list: overflow, switched off)
+        if constexpr (CAMLIST) {
+            if (sc.cam_lists != 0u) {
+                const uint32_t x0 = PT_CAM_UNIFORM(job0.px), y0 = PT_CAM_UNIFORM(job0.py);
+                const CamWalk cw = cam_walk(sc.nodes4, sc.root4, sc.tris, sc.tri_shift, cam_pyramid(cam, x0, y0, x0 + blk_mask, y0 + blk_mask), s_cand, CAM_LIST_CAP, s_ring);
+                cam_n = PT_CAM_UNIFORM(cw.overflow ? CAM_LIST_NONE : cw.count);
+            }
+        }
         // The work item's paths form a pool of (pixel, sample) pairs, sample-major.  A lane whose path ended takes the next pair,
         // whichever pixel of the tile it belongs to: no lane idles while another still has samples of "its" pixel to do.  The
         // tile's film lives in LDS (ds_add_f32); the hand-out order is a function of the wave's own deterministic schedule.
@@ -154,9 +166,38 @@
                 // ONE traversal for this iteration's closest-hit rays and the light connections the previous shading left pending
                 bool occluded = false;
                 if (STATS && sh.on) st.w[6]++;
-                PT_PRIO_TRAV_ENTER;
-                trace_pair_coop<STATS>(sc, P.ro, P.rd, active && !dying && !popped, sh.o, sh.d, sh.t, sh.on, stack, lane, pair_lds, hit, got, occluded, st, &carry, susp, &susp);
-                PT_PRIO_TRAV_EXIT;
+                // a fresh camera ray of an item with a candidate list takes its hit from the list (below) and stays out of the traversal;
+                // an iteration with no other ray — most of the iterations that start new paths — has no traversal at all
+                bool cam_ray = false;
+                if constexpr (CAMLIST) cam_ray = cam_n != CAM_LIST_NONE && active && !dying && P.from_camera && P.depth == 0u;
+                if (!CAMLIST || __ballot((active && !dying && !popped && !cam_ray) || sh.on) != 0ull) {
+                    PT_PRIO_TRAV_ENTER;
+                    trace_pair_coop<STATS>(sc, P.ro, P.rd, active && !dying && !popped && !cam_ray, sh.o, sh.d, sh.t, sh.on, stack, lane, pair_lds, hit, got, occluded, st, &carry, susp, &susp);
+                    PT_PRIO_TRAV_EXIT;
+                }
+                if constexpr (CAMLIST) {
+                    if (__ballot(cam_ray) != 0ull) {
+                        // what the traversal computes for such a ray: the ring flush's test (same function, same inputs, the limit the first
+                        // flush sees) on every triangle the ray can hit, the minimum of the merge's key (t bits << 32 | triangle), winner_hit.
+                        // The candidate is wave-uniform: its vertices come through uniform-address loads
+                        const RaySetup rs = setup_ray(P.rd);
+                        const f3 o2 = tri_origin(sc, P.ro);
+                        unsigned long long key = (0x7f7fffffull << 32) | 0xffffffffull;                 // (FLT_MAX, no triangle)
+                        for (uint32_t i = 0u; i < cam_n; ++i) {
+                            const uint32_t tri = PT_CAM_UNIFORM(s_cand[i]);
+                            const TriVerts tv = load_tri(sc.tris, tri);
+                            float t, b0, b1, b2;
+                            if (intersect_triangle<false>(o2, P.rd, rs.kx, rs.ky, rs.kz, rs.sx, rs.sy, rs.sz, 3.402823466e+38f, tv, t, b0, b1, b2)) {
+                                const unsigned long long k = ((unsigned long long)__float_as_uint(t) << 32) | (unsigned long long)tri;
+                                key = k < key ? k : key;
+                            }
+                        }
+                        if (cam_ray) {
+                            got = (uint32_t)key != 0xffffffffu;
+                            if (got) winner_hit(sc, P.ro, P.rd, rs, (uint32_t)key, hit);
+                        }
+                    }
+                }
                 if (sh.on && !occluded) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) P.L[i] = P.L[i] + sh.c[i];

@@ -190,7 +190,7 @@ def _ptr(a, ty):
 
 
 # every symbol include/mi355pt.h declares (tests/test_abi.py checks the built library exports all of them) ...
-DEBUG_SYMBOLS = ["debug_unlock", "scene_debug_set_lowering", "scene_debug_lowering_digest", "scene_export_bvh", "probe_bvh_collapse", "probe_bvh_collapse_nodes", "probe_sobol", "probe_sincos", "probe_intersect", "probe_occluded",
+DEBUG_SYMBOLS = ["debug_unlock", "scene_debug_set_lowering", "scene_debug_lowering_digest", "scene_debug_camera_candidates", "scene_export_bvh", "probe_bvh_collapse", "probe_bvh_collapse_nodes", "probe_sobol", "probe_sincos", "probe_intersect", "probe_occluded",
                  "sample_log_records", "render_sample_log", "probe_radiance"]     # ... and include/mi355pt_debug.h
 ABI_SYMBOLS = [
     "scene_create", "scene_destroy", "scene_set_rgb2spec", "scene_add_lut470", "scene_add_tex_rgb8", "scene_add_mesh",
@@ -383,6 +383,25 @@ class SceneHandle:
         *names, info = text.value.decode().split("\n")
         assert len(names) == n.value
         return {nm: f"{dig[i]:016x}" for i, nm in enumerate(names)}, info
+
+    def debug_camera_candidates(self, cam, rects, cap=16, want_tris=False):
+        """mi355pt_scene_debug_camera_candidates (host only, product only): the candidate lists of csrc/camera_candidates.hpp for the pixel
+        rectangles `rects` (n x 4: x0, y0, x1, y1, inclusive) -> counts (n,), overflow (n,) bool, indices (n, cap) uint32 (row r: counts[r]
+        valid entries) and, on request, the lowered triangles in leaf order as (m, 3, 3) float32 render-space vertices"""
+        fn = self.b.fn("scene_debug_camera_candidates")
+        fn.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8),
+                       C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
+        r = np.ascontiguousarray(rects, dtype=np.uint32).reshape(-1, 4)
+        n = r.shape[0]
+        counts = np.zeros(n, np.uint32); over = np.zeros(n, np.uint8); idx = np.zeros((n, cap), np.uint32)
+        nt = C.c_uint32(0)
+        tris = None
+        if want_tris:
+            self.b.check(fn(self.h, C.byref(cam), None, 0, cap, None, None, None, None, C.byref(nt)), "scene_debug_camera_candidates")
+            tris = np.zeros((nt.value, 3, 3), np.float32)
+        self.b.check(fn(self.h, C.byref(cam), _ptr(r, C.c_uint32), n, cap, _ptr(counts, C.c_uint32), _ptr(over, C.c_uint8), _ptr(idx, C.c_uint32),
+                        _ptr(tris, C.c_float), C.byref(nt)), "scene_debug_camera_candidates")
+        return (counts, over.astype(bool), idx, tris) if want_tris else (counts, over.astype(bool), idx)
 
     def build(self, cam):
         self.b.check(self.b.fn("scene_build")(self.h, C.byref(cam)), "scene_build")
