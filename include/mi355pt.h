@@ -339,6 +339,14 @@ const char* mi355pt_version(void);
  * temporal accumulation, the variance-guided denoiser and the resolve as it is.  Declared in its own header, which this one always includes. */
 #include "mi355pt_upsample.h"
 
+/* ---------------- display stage ---------------- */
+/* EXTENSION, no reference counterpart: from a finished linear film to the picture — mi355pt_display_params, mi355pt_display_params_default,
+ * mi355pt_display_scratch_bytes, mi355pt_display_meter_device and mi355pt_display_meter (a trimmed pseudo-log luminance histogram whose mean
+ * bin gives an exposure, blended with the previous frame's), mi355pt_display_device and mi355pt_display (exposure, one of five rational tone
+ * curves, linear or sRGB encoding).  mi355pt_film_resolve_device above stays as it is.  Declared in its own header, which this one always
+ * includes. */
+#include "mi355pt_display.h"
+
 /* ---------------- variance-guided denoiser ---------------- */
 /* EXTENSION, no reference counterpart: a second filter beside the one above, which it leaves as it is — mi355pt_denoise_var_params,
  * mi355pt_denoise_var_params_default, mi355pt_denoise_var_scratch_bytes, mi355pt_denoise_var_device and mi355pt_denoise_var: an a-trous

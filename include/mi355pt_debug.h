@@ -68,6 +68,11 @@ int mi355pt_probe_sobol(uint32_t width, uint32_t height, uint32_t spp, uint32_t 
  * e.g. scene/src/material/bsdf/dielectric.rs:77-112 via common.rs) for the n floats with bit patterns first_bits + i * stride, compared on
  * the host with sinf / cosf of THIS machine's libm: out_counts[3] = {compared, sin results that differ in any bit, cos results}. */
 int mi355pt_probe_sincos(uint32_t first_bits, uint32_t stride, uint32_t n, uint64_t* out_counts /* 3 */);
+/* The two launches of mi355pt_display_meter_device (include/mi355pt_display.h) on the default stream with a HIP event between them: out_ms[2] =
+ * {the block histograms, the one-block finish} in milliseconds.  No previous record, no histogram output; the same argument checks;
+ * synchronises.  For tools/display_rate.py: the public entry point gives no place to put an event. */
+int mi355pt_probe_display_meter_ms(const float* d_film, uint32_t width, uint32_t height, uint32_t spp, const mi355pt_display_params* params, void* d_scratch,
+                                   size_t scratch_bytes, uint32_t* d_record, float* out_ms /* 2 */);
 /* Scene::intersect for n rays (render space).  out_t < 0 means miss.  scene.rs:80-90 */
 int mi355pt_probe_intersect(const mi355pt_scene* s, const float* origins, const float* dirs, uint32_t n, float* out_t,
                             uint32_t* out_instance, uint32_t* out_triangle, float* out_normal /* n*3 geometric, NULL ok */);

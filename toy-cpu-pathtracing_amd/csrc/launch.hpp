@@ -96,6 +96,30 @@ struct UpsampleArgs {
 };
 hipError_t launch_upsample(const float* d_low_film, const float* d_low_half, const UpsampleGuidesDev& low, const UpsampleGuidesDev& full, UpsampleArgs args,
                            float* d_out_film, float* d_out_half, hipStream_t);
+// pt_kernels_display.hip: the display stage (include/mi355pt_display.h).  The meter: two launches, the block histograms of display_plan.hpp's
+// plan into d_scratch (rows x 258 words, every word that is read is written first) and the one-block finish, which reads d_prev_record
+// (nullptr: none; may be d_record) before it writes d_record (8 words) and, when given, d_hist (258 words).  The display: one launch, one
+// thread per pixel; d_record == nullptr: E is args.exposure.  white2 and hable_white are the host's f32 white * white and h(white)
+struct DisplayMeterArgs {
+    uint32_t width, height;
+    float spp;                              // (float)spp
+    uint32_t base;                          // (log2_lum_min + 127) << 3
+    uint32_t trim_low, trim_high;
+    float key, e_min, e_max, adapt;
+};
+struct DisplayArgs {
+    uint32_t width, height;
+    float spp;
+    uint32_t tone, encode;
+    float exposure, white2, hable_white;
+};
+hipError_t launch_display_meter(const float* d_film, const DisplayMeterArgs& args, const uint32_t* d_prev_record, uint32_t* d_scratch, uint32_t* d_record,
+                                uint32_t* d_hist, hipStream_t);
+// ... and its two launches one by one (mi355pt_probe_display_meter_ms times them apart)
+hipError_t launch_display_hist(const float* d_film, const DisplayMeterArgs& args, uint32_t* d_scratch, hipStream_t);
+hipError_t launch_display_finish(const uint32_t* d_scratch, const DisplayMeterArgs& args, const uint32_t* d_prev_record, uint32_t* d_record, uint32_t* d_hist, hipStream_t);
+hipError_t launch_display(const float* d_film, const DisplayArgs& args, const uint32_t* d_record, float* d_out, hipStream_t);
+float display_hable(float x);      // h(x) of the header on the host, the same single-rounded steps as the kernel
 
 // Resident 64-thread blocks (= waves) of `kernel` on the current device: the persistent grid size of the EXACT instantiation a launch takes
 // (the register count, and so the occupancy, differs between instantiations and between translation units with their own backend flags).

@@ -175,6 +175,17 @@ class UpsampleGuides(C.Structure):
 UPSAMPLE_GUIDES = ("albedo", "shading_normal", "position", "hit")
 
 
+class DisplayParams(C.Structure):
+    """mi355pt_display_params (include/mi355pt_display.h); Product.display_params_default() fills it — a zeroed one is refused"""
+    _fields_ = [("tone", C.c_uint32), ("encode", C.c_uint32), ("exposure", C.c_float), ("white", C.c_float), ("log2_lum_min", C.c_int32),
+                ("trim_low", C.c_uint32), ("trim_high", C.c_uint32), ("key", C.c_float), ("e_min", C.c_float), ("e_max", C.c_float), ("adapt", C.c_float)]
+
+
+TONE = {"none": 0, "reinhard": 1, "reinhard-ext": 2, "aces": 3, "hable": 4}      # MI355PT_TONE_*
+ENCODE = {"linear": 0, "srgb": 1}                                                # MI355PT_ENCODE_*
+DISPLAY_RECORD_WORDS, DISPLAY_HIST_WORDS = 8, 258
+
+
 def make_camera(position, direction, up, width, height, fov_deg=45.0):
     return Camera((C.c_float * 3)(*position), (C.c_float * 3)(*direction), (C.c_float * 3)(*up), fov_deg, width, height)
 
@@ -191,7 +202,7 @@ def _ptr(a, ty):
 
 # every symbol include/mi355pt.h declares (tests/test_abi.py checks the built library exports all of them) ...
 DEBUG_SYMBOLS = ["debug_unlock", "scene_debug_set_lowering", "scene_debug_lowering_digest", "scene_debug_camera_candidates", "scene_export_bvh", "probe_bvh_collapse", "probe_bvh_collapse_nodes", "probe_sobol", "probe_sincos", "probe_intersect", "probe_occluded",
-                 "sample_log_records", "render_sample_log", "probe_radiance"]     # ... and include/mi355pt_debug.h
+                 "sample_log_records", "render_sample_log", "probe_radiance", "probe_display_meter_ms"]     # ... and include/mi355pt_debug.h
 ABI_SYMBOLS = [
     "scene_create", "scene_destroy", "scene_set_rgb2spec", "scene_add_lut470", "scene_add_tex_rgb8", "scene_add_mesh",
     "scene_add_material", "scene_add_instance", "scene_add_delta_light", "scene_add_environment_light", "scene_set_bvh_builder", "scene_build", "render", "render_accum_device", "film_resolve_device",
@@ -214,6 +225,8 @@ TEMPORAL_RECTIFY_SYMBOLS = ["temporal_rectify_params_default", "temporal_rectify
                             "temporal_accumulate_rectified"]
 # ... and include/mi355pt_upsample.h, the guided half-resolution block (tests/test_upsample.py)
 UPSAMPLE_SYMBOLS = ["upsample_params_default", "upsample_low_camera", "upsample_device", "upsample"]
+# ... and include/mi355pt_display.h, the display block (tests/test_display.py)
+DISPLAY_SYMBOLS = ["display_params_default", "display_scratch_bytes", "display_meter_device", "display_device", "display_meter", "display"]
 ADAPTIVE_SYMBOLS = ["adaptive_scratch_bytes", "adaptive_step_device", "film_normalize_tiles_device", "render_adaptive_device", "render_adaptive"]
 
 
@@ -508,6 +521,14 @@ class Product(Backend):
                                                     C.c_uint32, C.c_uint32, C.POINTER(UpsampleParams), C.c_void_p, C.c_void_p, C.c_void_p]
             lib.mi355pt_upsample.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(UpsampleGuides), C.c_uint32, C.POINTER(UpsampleGuides), C.c_uint32,
                                              C.c_uint32, C.c_uint32, C.POINTER(UpsampleParams), C.c_void_p, C.c_void_p]
+        if hasattr(lib, "mi355pt_display_device"):  # (absent from an older build loaded through MI355PT_LIB)
+            lib.mi355pt_display_params_default.argtypes = [C.POINTER(DisplayParams)]; lib.mi355pt_display_params_default.restype = None
+            lib.mi355pt_display_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]; lib.mi355pt_display_scratch_bytes.restype = C.c_size_t
+            lib.mi355pt_display_meter_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DisplayParams), C.c_void_p, C.c_void_p, C.c_size_t,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.mi355pt_display_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DisplayParams), C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.mi355pt_display_meter.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DisplayParams), C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.mi355pt_display.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DisplayParams), C.c_void_p, C.c_void_p]
         if not hasattr(lib, "mi355pt_render_sample_log"):     # an older build loaded through MI355PT_LIB for an A/B timing run
             return
         lib.mi355pt_sample_log_records.argtypes = [C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]
@@ -760,6 +781,57 @@ class Product(Backend):
                                              spp_albedo_full, w, h, C.byref(params), out_film.ctypes.data,
                                              out_half.ctypes.data if out_half is not None else None), "upsample")
         return out_film, out_half
+
+    # ---- the display stage (include/mi355pt_display.h): histogram auto-exposure, tone curves, encoding ----
+    def display_params_default(self):
+        p = DisplayParams()
+        self.lib.mi355pt_display_params_default(C.byref(p))
+        return p
+
+    def display_scratch_bytes(self, width, height):
+        return int(self.lib.mi355pt_display_scratch_bytes(width, height))
+
+    def display_meter_device(self, d_film_ptr, width, height, spp, params, d_prev_record_ptr, d_scratch_ptr, scratch_bytes, d_record_ptr, d_hist_ptr=None, stream=None):
+        """mi355pt_display_meter_device: d_prev_record_ptr None or 0 = no previous record (it may equal d_record_ptr); d_hist_ptr None = not wanted"""
+        self.check(self.lib.mi355pt_display_meter_device(C.c_void_p(d_film_ptr), width, height, spp, C.byref(params), C.c_void_p(d_prev_record_ptr or 0),
+                                                         C.c_void_p(d_scratch_ptr), scratch_bytes, C.c_void_p(d_record_ptr), C.c_void_p(d_hist_ptr or 0),
+                                                         C.c_void_p(stream or 0)), "display_meter_device")
+
+    def display_device(self, d_film_ptr, width, height, spp, params, d_record_ptr, d_out_ptr, stream=None):
+        """mi355pt_display_device: d_record_ptr None or 0 = the constant params.exposure"""
+        self.check(self.lib.mi355pt_display_device(C.c_void_p(d_film_ptr), width, height, spp, C.byref(params), C.c_void_p(d_record_ptr or 0), C.c_void_p(d_out_ptr),
+                                                   C.c_void_p(stream or 0)), "display_device")
+
+    def probe_display_meter_ms(self, d_film_ptr, width, height, spp, params, d_scratch_ptr, scratch_bytes, d_record_ptr):
+        """mi355pt_probe_display_meter_ms (include/mi355pt_debug.h) -> (ms of the block histograms, ms of the finish)"""
+        out = (C.c_float * 2)()
+        self.lib.mi355pt_probe_display_meter_ms.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DisplayParams), C.c_void_p, C.c_size_t, C.c_void_p,
+                                                            C.POINTER(C.c_float)]
+        self.check(self.lib.mi355pt_probe_display_meter_ms(C.c_void_p(d_film_ptr), width, height, spp, C.byref(params), C.c_void_p(d_scratch_ptr), scratch_bytes,
+                                                           C.c_void_p(d_record_ptr), out), "probe_display_meter_ms")
+        return float(out[0]), float(out[1])
+
+    def display_meter(self, film, spp, params=None, prev_record=None, want_hist=True):
+        """mi355pt_display_meter on a host (H, W, 3) float32 film of sums -> (record: 8 uint32, hist: 258 uint32 or None)"""
+        f = np.ascontiguousarray(film, dtype=np.float32)
+        h, w = f.shape[:2]
+        params = params if params is not None else self.display_params_default()
+        prev = None if prev_record is None else np.ascontiguousarray(prev_record, dtype=np.uint32)
+        record = np.zeros(DISPLAY_RECORD_WORDS, np.uint32)
+        hist = np.zeros(DISPLAY_HIST_WORDS, np.uint32) if want_hist else None
+        self.check(self.lib.mi355pt_display_meter(f.ctypes.data, w, h, spp, C.byref(params), prev.ctypes.data if prev is not None else None, record.ctypes.data,
+                                                  hist.ctypes.data if hist is not None else None), "display_meter")
+        return record, hist
+
+    def display(self, film, spp, params=None, record=None):
+        """mi355pt_display on a host (H, W, 3) float32 film of sums -> (H, W, 3) float32; record None = the constant params.exposure"""
+        f = np.ascontiguousarray(film, dtype=np.float32)
+        h, w = f.shape[:2]
+        params = params if params is not None else self.display_params_default()
+        rec = None if record is None else np.ascontiguousarray(record, dtype=np.uint32)
+        out = np.zeros((h, w, 3), np.float32)
+        self.check(self.lib.mi355pt_display(f.ctypes.data, w, h, spp, C.byref(params), rec.ctypes.data if rec is not None else None, out.ctypes.data), "display")
+        return out
 
     def render_accum_device(self, scene, cam, params, s_begin, s_end, d_accum_ptr, stream=None, stats=None):
         self.check(self.lib.mi355pt_render_accum_device(scene.h, C.byref(cam), C.byref(params), s_begin, s_end, C.c_void_p(d_accum_ptr),

@@ -4,10 +4,11 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 
-#include <hip/hip_runtime_api.h>   // --denoise, --denoise-variance, --adaptive-threshold, --temporal-frames and --half-res: the films of those paths stay on the device (hipMalloc / hipMemcpy / hipFree, no kernels here)
+#include <hip/hip_runtime_api.h>   // --denoise, --denoise-variance, --adaptive-threshold, --temporal-frames, --half-res, --tone-map and --auto-exposure: the films of those paths stay on the device (hipMalloc / hipMemcpy / hipFree, no kernels here)
 
 #include "scenes.hpp"
 
@@ -36,6 +37,11 @@ struct Args {   // main.rs:20-53
     // nor guided half-resolution rendering (mi355pt_upsample.h): the paths traced at width / 2 x height / 2, the frame rebuilt through both G-buffers;
     // albedo demodulation is off by default (profiles/upsample_quality.json: it does not win on both measured scenes)
     bool half_res = false, half_res_albedo = false;
+    // nor the display stage (mi355pt_display.h): a tone curve other than the reference's Reinhard, and an exposure metered from the frame's
+    // histogram instead of the constant 1 (--temporal-frames: every frame metered with the previous frame's record).  Not given = the defaults
+    std::string tone_map; bool white_given = false; float white = 0.0f;
+    bool auto_exposure = false, exposure_key_given = false, exposure_adapt_given = false, exposure_trim_given = false;
+    float exposure_key = 0.0f, exposure_adapt = 0.0f; uint32_t exposure_trim[2] = {0, 0};
 };
 
 // --denoise: the beauty film at --spp, the albedo and shading-normal films at --denoise-guide-spp (converged guides cost a few percent of
@@ -50,6 +56,58 @@ struct DeviceFilm {
     DeviceFilm(const DeviceFilm&) = delete;
     DeviceFilm& operator=(const DeviceFilm&) = delete;
 };
+// The last step of every device path below.  Without --tone-map and --auto-exposure it IS mi355pt_film_resolve_device, the call this file
+// made before the display stage existed.  With either, mi355pt_display_device: the chosen curve, sRGB, and — with --auto-exposure — the
+// exposure of a record that mi355pt_display_meter_device wrote: the loops of --temporal-frames meter every frame's accumulated film with
+// the previous frame's record (meter()), every other path meters the film it hands to resolve() there, with no previous record.
+struct DisplayStage {
+    bool on = false, auto_exposure = false, have_record = false;
+    mi355pt_display_params dp{};
+    uint32_t* record = nullptr;
+    void* scratch = nullptr;
+    size_t scratch_bytes = 0;
+    void release() { (void)hipFree(record); (void)hipFree(scratch); record = nullptr; scratch = nullptr; scratch_bytes = 0; }      // (called in main: no HIP call from a static destructor)
+    void meter(const float* film, uint32_t width, uint32_t height, uint32_t spp) {
+        if (!on || !auto_exposure) return;
+        const size_t need = mi355pt_display_scratch_bytes(width, height);
+        if (!record && hipMalloc((void**)&record, MI355PT_DISPLAY_RECORD_WORDS * sizeof(uint32_t)) != hipSuccess) throw std::runtime_error("mi355pt: device allocation failed");
+        if (need > scratch_bytes) {
+            (void)hipFree(scratch); scratch = nullptr; scratch_bytes = 0;
+            if (hipMalloc(&scratch, need) != hipSuccess) throw std::runtime_error("mi355pt: device allocation failed");
+            scratch_bytes = need;
+        }
+        check(mi355pt_display_meter_device(film, width, height, spp, &dp, have_record ? record : nullptr, scratch, scratch_bytes, record, nullptr, nullptr),
+              "mi355pt_display_meter_device");
+        have_record = true;
+    }
+    void resolve(const float* film, uint32_t width, uint32_t height, uint32_t spp, float* rgb) {
+        if (!on) { check(mi355pt_film_resolve_device(film, width * height, spp, rgb, nullptr), "mi355pt_film_resolve_device"); return; }
+        if (auto_exposure && !have_record) meter(film, width, height, spp);
+        check(mi355pt_display_device(film, width, height, spp, &dp, auto_exposure ? record : nullptr, rgb, nullptr), "mi355pt_display_device");
+        if (auto_exposure) {
+            uint32_t r[MI355PT_DISPLAY_RECORD_WORDS];
+            float e[3];
+            if (hipMemcpy(r, record, sizeof r, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the exposure record back failed");
+            std::memcpy(e, r, sizeof e);
+            std::printf("(auto-exposure: E %.6g, target %.6g, mean luminance %.6g; %u pixels metered, %u below and %u above the range)\n", e[0], e[1], e[2], r[3], r[4], r[5]);
+        }
+    }
+};
+static DisplayStage display_stage;      // configured once in main, before any render path runs
+
+// --tone-map / --auto-exposure on a plain path render (no filter, no accumulation): the film at --spp on the device, then the display stage.
+// Returns the device seconds of the beauty launch.
+static double render_displayed(const Scene& scene, const Camera& camera, mi355pt_params p, std::vector<float>& pixels) {
+    const mi355pt_camera& cam = camera.raw();
+    const size_t film_bytes = (size_t)cam.width * cam.height * 3 * sizeof(float);
+    DeviceFilm film(film_bytes), rgb(film_bytes);
+    mi355pt_stats st{};
+    check(mi355pt_render_accum_device(scene.raw(), &cam, &p, 0, p.spp, film.p, nullptr, &st), "mi355pt_render_accum_device");
+    display_stage.resolve(film.p, cam.width, cam.height, p.spp, rgb.p);
+    if (hipMemcpy(pixels.data(), rgb.p, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the frame back failed");
+    return st.kernel_ms * 1e-3;
+}
+
 // The two guide films of the denoise paths, guide_spp samples each into zeroed device films: two launches of the AOV kernel, or — `fused`,
 // --fused-guides — one launch of the G-buffer pass, whose two films then come from the same primary rays (the albedo film is the same bits
 // either way; the shading-normal film sees the albedo renderer's sub-pixel positions instead of its own)
@@ -74,7 +132,7 @@ static double render_denoised(const Scene& scene, const Camera& camera, mi355pt_
     mi355pt_denoise_params dp;
     mi355pt_denoise_params_default(&dp);
     check(mi355pt_denoise_device(beauty.p, p.spp, albedo.p, guide_spp, normal.p, guide_spp, cam.width, cam.height, &dp, scratch.p, scratch_bytes, out.p, nullptr), "mi355pt_denoise_device");
-    check(mi355pt_film_resolve_device(out.p, n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
+    display_stage.resolve(out.p, cam.width, cam.height, 1, rgb.p);
     if (hipMemcpy(pixels.data(), rgb.p, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the frame back failed");
     return st.kernel_ms * 1e-3;
 }
@@ -101,7 +159,7 @@ static double render_denoised_variance(const Scene& scene, const Camera& camera,
     const mi355pt_denoise_var_params dp = denoise_var_params(sigma_lum);
     check(mi355pt_denoise_var_device(beauty.p, half.p, p.spp, nullptr, albedo.p, guide_spp, normal.p, guide_spp, cam.width, cam.height, &dp, scratch.p, scratch_bytes,
                                      out.p, nullptr), "mi355pt_denoise_var_device");
-    check(mi355pt_film_resolve_device(out.p, n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
+    display_stage.resolve(out.p, cam.width, cam.height, 1, rgb.p);
     if (hipMemcpy(pixels.data(), rgb.p, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the frame back failed");
     return (st0.kernel_ms + st1.kernel_ms) * 1e-3;
 }
@@ -126,7 +184,7 @@ static void render_adaptive(const Scene& scene, const Camera& camera, mi355pt_pa
         const mi355pt_denoise_var_params dp = denoise_var_params(a.denoise_sigma_lum);
         check(mi355pt_denoise_var_device(film.p, half.p, 0, (const uint32_t*)tile_spp.p, albedo.p, guide_spp, normal.p, guide_spp, cam.width, cam.height, &dp,
                                          dn_scratch.p, dn_bytes, out.p, nullptr), "mi355pt_denoise_var_device");
-        check(mi355pt_film_resolve_device(out.p, n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
+        display_stage.resolve(out.p, cam.width, cam.height, 1, rgb.p);
     } else if (a.denoise) {
         check(mi355pt_film_normalize_tiles_device(film.p, (const uint32_t*)tile_spp.p, cam.width, cam.height, half.p, nullptr), "mi355pt_film_normalize_tiles_device");
         const uint32_t guide_spp = a.denoise_guide_spp;
@@ -136,10 +194,10 @@ static void render_adaptive(const Scene& scene, const Camera& camera, mi355pt_pa
         mi355pt_denoise_params dp;
         mi355pt_denoise_params_default(&dp);
         check(mi355pt_denoise_device(half.p, 1, albedo.p, guide_spp, normal.p, guide_spp, cam.width, cam.height, &dp, dn_scratch.p, dn_bytes, film.p, nullptr), "mi355pt_denoise_device");
-        check(mi355pt_film_resolve_device(film.p, n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
+        display_stage.resolve(film.p, cam.width, cam.height, 1, rgb.p);
     } else {
         check(mi355pt_film_normalize_tiles_device(film.p, (const uint32_t*)tile_spp.p, cam.width, cam.height, half.p, nullptr), "mi355pt_film_normalize_tiles_device");
-        check(mi355pt_film_resolve_device(half.p, n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
+        display_stage.resolve(half.p, cam.width, cam.height, 1, rgb.p);
     }
     if (hipMemcpy(pixels.data(), rgb.p, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the frame back failed");
     std::printf("(adaptive: %u passes, mean %.1f spp of at most %u, %u of %u tiles at the maximum)\n", res.passes, (double)res.total_samples / n_pixels, p.spp,
@@ -243,6 +301,7 @@ static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params
         else
             check(mi355pt_temporal_accumulate_device(&cur, p.spp, k > 0 ? &prev : nullptr, k > 0 ? &view : nullptr, base.width, base.height, &tp, acc[c],
                                                      half ? acch[c] : nullptr, len[c], nullptr), "mi355pt_temporal_accumulate_device");
+        display_stage.meter(acc[c], base.width, base.height, half ? 2u : 1u);      // --auto-exposure: every frame, with the previous frame's record
     }
     const int last = (int)((a.temporal_frames - 1) & 1u);
     if (half) {
@@ -251,10 +310,10 @@ static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params
         const mi355pt_denoise_var_params dp = denoise_var_params(a.denoise_sigma_lum);
         check(mi355pt_denoise_var_device(acc[last], acch[last], 2, nullptr, albedo.p, guide_spp, normal[last], guide_spp, base.width, base.height, &dp, scratch.p,
                                          scratch_bytes, out.p, nullptr), "mi355pt_denoise_var_device");
-        check(mi355pt_film_resolve_device(out.p, n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
+        display_stage.resolve(out.p, base.width, base.height, 1, rgb.p);
         if (hipMemcpy(pixels.data(), rgb.p, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the frame back failed");
     } else {
-        check(mi355pt_film_resolve_device(acc[last], n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
+        display_stage.resolve(acc[last], base.width, base.height, 1, rgb.p);
         if (hipMemcpy(pixels.data(), rgb.p, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the frame back failed");
     }
     return kernel_ms * 1e-3;
@@ -345,6 +404,7 @@ static double render_half_res(Scene& scene, const Camera& camera, mi355pt_params
         else
             check(mi355pt_temporal_accumulate_device(&cur, up_spp, k > 0 ? &prev : nullptr, k > 0 ? &view : nullptr, base.width, base.height, &tp, acc[c],
                                                      half ? acch[c] : nullptr, len[c], nullptr), "mi355pt_temporal_accumulate_device");
+        display_stage.meter(acc[c], base.width, base.height, up_spp);      // --auto-exposure: every frame, with the previous frame's record
     }
     const float* film = a.temporal ? acc[c] : up.p;           // the pair that leaves the loop: spp 2 with a half film; a mean without (the accumulation's, the upsample's)
     const float* film_half = a.temporal ? acch[c] : uph.p;
@@ -354,9 +414,9 @@ static double render_half_res(Scene& scene, const Camera& camera, mi355pt_params
         const mi355pt_denoise_var_params dp = denoise_var_params(a.denoise_sigma_lum);
         check(mi355pt_denoise_var_device(film, film_half, 2, nullptr, albedo.p, guide_spp, normal[c], guide_spp, base.width, base.height, &dp, scratch.p, scratch_bytes,
                                          out.p, nullptr), "mi355pt_denoise_var_device");
-        check(mi355pt_film_resolve_device(out.p, n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
+        display_stage.resolve(out.p, base.width, base.height, 1, rgb.p);
     } else {
-        check(mi355pt_film_resolve_device(film, n_pixels, 1, rgb.p, nullptr), "mi355pt_film_resolve_device");
+        display_stage.resolve(film, base.width, base.height, 1, rgb.p);
     }
     if (hipMemcpy(pixels.data(), rgb.p, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the frame back failed");
     return kernel_ms * 1e-3;
@@ -383,7 +443,13 @@ static void usage() {
               "                   [--temporal-rectify-radius R] (2; 1 .. 3: the window is (2R + 1)^2 pixels)  [--temporal-rectify-gamma G] (2; > 0: standard errors allowed)\n"
               "                   [--half-res] (pt|nee|mis, even --width and --height: the paths are traced at half the width and height and the frame is rebuilt at\n"
               "                                 full size through the G-buffers of both sizes at --denoise-guide-spp; with --denoise-variance and --temporal-frames)\n"
-              "                   [--half-res-albedo] (with --half-res: the low film is divided by the low albedo and multiplied by the full one)");
+              "                   [--half-res-albedo] (with --half-res: the low film is divided by the low albedo and multiplied by the full one)\n"
+              "                   [--tone-map none|reinhard|reinhard-ext|aces|hable] (pt|nee|mis: the display stage's curve instead of the resolve's Reinhard)\n"
+              "                   [--white W] (11.2; with --tone-map reinhard-ext|hable: the luminance / value that maps to 1)\n"
+              "                   [--auto-exposure] (pt|nee|mis: the exposure from the frame's trimmed luminance histogram; with --temporal-frames every\n"
+              "                                      frame is metered and blended with the previous frame's exposure)\n"
+              "                   [--exposure-key K] (0.18: the value the mean luminance is mapped to)  [--exposure-adapt A] (1; 0 .. 1: the share of the way\n"
+              "                                      to the new exposure taken per frame)  [--exposure-trim LO,HI] (102,51: 1/1024ths of the pixels left out)");
 }
 
 int main(int argc, char** argv) {
@@ -418,6 +484,20 @@ int main(int argc, char** argv) {
         else if (k == "--temporal-rectify-gamma") { a.temporal_rectify_gamma_given = true; a.temporal_rectify_gamma = std::stof(val()); }
         else if (k == "--half-res") a.half_res = true;
         else if (k == "--half-res-albedo") a.half_res_albedo = true;
+        else if (k == "--tone-map") a.tone_map = val();
+        else if (k == "--white") { a.white_given = true; a.white = std::stof(val()); }
+        else if (k == "--auto-exposure") a.auto_exposure = true;
+        else if (k == "--exposure-key") { a.exposure_key_given = true; a.exposure_key = std::stof(val()); }
+        else if (k == "--exposure-adapt") { a.exposure_adapt_given = true; a.exposure_adapt = std::stof(val()); }
+        else if (k == "--exposure-trim") {
+            const std::string v = val();
+            char tail = 0;
+            a.exposure_trim_given = true;
+            if (std::sscanf(v.c_str(), "%u,%u%c", &a.exposure_trim[0], &a.exposure_trim[1], &tail) != 2 || (uint64_t)a.exposure_trim[0] + a.exposure_trim[1] >= 1024u) {
+                std::fprintf(stderr, "error: invalid value '%s' for '--exposure-trim': two counts of 1/1024ths LO,HI whose sum is below 1024\n", v.c_str());
+                return 2;
+            }
+        }
         else if (k == "--camera-step") {
             const std::string v = val();
             char tail = 0;
@@ -439,6 +519,34 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "error: invalid value '%s' for '--renderer' (main.rs:38-40: normal, albedo, pt, nee, mis; extensions: shading-normal, position, depth)\n", a.renderer.c_str());
         return 2;
     }
+    // the display stage: refused here, before anything is loaded; mi355pt_display_device checks the struct again
+    const bool display_on = !a.tone_map.empty() || a.auto_exposure;
+    mi355pt_display_params_default(&display_stage.dp);
+    if (!a.tone_map.empty()) {
+        const char* names[5] = {"none", "reinhard", "reinhard-ext", "aces", "hable"};
+        uint32_t t = 5;
+        for (uint32_t i = 0; i < 5; ++i) if (a.tone_map == names[i]) t = i;
+        if (t == 5) { std::fprintf(stderr, "error: invalid value '%s' for '--tone-map' (none, reinhard, reinhard-ext, aces, hable)\n", a.tone_map.c_str()); return 2; }
+        display_stage.dp.tone = t;
+    }
+    if (display_on && (a.renderer != "pt" && a.renderer != "nee" && a.renderer != "mis")) {
+        std::fprintf(stderr, "error: %s with --renderer %s: the display stage takes the film of a path renderer (pt, nee, mis)\n", a.auto_exposure ? "--auto-exposure" : "--tone-map", a.renderer.c_str());
+        return 2;
+    }
+    if (display_on && a.gpus > 1) { std::fprintf(stderr, "error: %s with --gpus %d: the display stage runs on one GPU\n", a.auto_exposure ? "--auto-exposure" : "--tone-map", a.gpus); return 2; }
+    if (a.white_given && display_stage.dp.tone != MI355PT_TONE_REINHARD_EXT && display_stage.dp.tone != MI355PT_TONE_HABLE) { std::fprintf(stderr, "error: --white needs --tone-map reinhard-ext or hable: the other curves have no white point\n"); return 2; }
+    if (a.white_given && !(std::isfinite(a.white) && a.white >= 0x1p-16f && a.white <= 0x1p16f)) { std::fprintf(stderr, "error: --white must be in [2^-16, 2^16]\n"); return 2; }
+    if ((a.exposure_key_given || a.exposure_adapt_given || a.exposure_trim_given) && !a.auto_exposure) {
+        std::fprintf(stderr, "error: --exposure-key, --exposure-adapt and --exposure-trim need --auto-exposure: they are the meter's parameters\n");
+        return 2;
+    }
+    if (a.exposure_key_given && !(std::isfinite(a.exposure_key) && a.exposure_key > 0.0f)) { std::fprintf(stderr, "error: --exposure-key must be finite and above 0\n"); return 2; }
+    if (a.exposure_adapt_given && !(a.exposure_adapt >= 0.0f && a.exposure_adapt <= 1.0f)) { std::fprintf(stderr, "error: --exposure-adapt must be in [0, 1]\n"); return 2; }
+    display_stage.on = display_on; display_stage.auto_exposure = a.auto_exposure;
+    if (a.white_given) display_stage.dp.white = a.white;
+    if (a.exposure_key_given) display_stage.dp.key = a.exposure_key;
+    if (a.exposure_adapt_given) display_stage.dp.adapt = a.exposure_adapt;
+    if (a.exposure_trim_given) { display_stage.dp.trim_low = a.exposure_trim[0]; display_stage.dp.trim_high = a.exposure_trim[1]; }
     if (a.half_res_albedo && !a.half_res) { std::fprintf(stderr, "error: --half-res-albedo needs --half-res: it demodulates the film that --half-res upsamples\n"); return 2; }
     if (a.half_res && aov) { std::fprintf(stderr, "error: --half-res with --renderer %s: half-resolution rendering is for the path renderers (pt, nee, mis)\n", a.renderer.c_str()); return 2; }
     if (a.half_res && (a.width == 0 || a.height == 0 || (a.width & 1u) != 0 || (a.height & 1u) != 0)) { std::fprintf(stderr, "error: --half-res needs an even --width and --height above 0 (got %u x %u)\n", a.width, a.height); return 2; }
@@ -542,13 +650,14 @@ int main(int argc, char** argv) {
         else if (adaptive) render_adaptive(scene, camera, image.params(sampler, a.albedo_lut), a, image.pixels_mut());
         else if (a.denoise_variance) kernel_s = render_denoised_variance(scene, camera, image.params(sampler, a.albedo_lut), a.denoise_guide_spp, a.fused_guides, a.denoise_sigma_lum, image.pixels_mut());
         else kernel_s = a.denoise ? render_denoised(scene, camera, image.params(sampler, a.albedo_lut), a.denoise_guide_spp, a.fused_guides, image.pixels_mut())
-                                    : image.render(sampler, a.albedo_lut);
+                                    : (display_stage.on ? render_displayed(scene, camera, image.params(sampler, a.albedo_lut), image.pixels_mut()) : image.render(sampler, a.albedo_lut));
         double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         std::printf("Finish rendering: %.3f seconds.\n", wall);
         if (kernel_s > 0.0 && a.half_res) std::printf("(beauty launches at %u x %u: device %.3f s; the two G-buffers, the upsample and what follows it are in the wall time above)\n", a.width / 2, a.height / 2, kernel_s);
         else if (kernel_s > 0.0 && a.temporal) std::printf("(beauty launches of %u frames: device %.3f s; the G-buffer, the accumulation and the scene builds are in the wall time above)\n", a.temporal_frames, kernel_s);
         else if (kernel_s > 0.0 && (a.denoise || a.denoise_variance)) std::printf("(beauty launch alone: device %.3f s, %.1f Msamples/s; the guide films and the filter are in the wall time above)\n", kernel_s, (double)a.width * a.height * a.spp / kernel_s / 1e6);
         else if (kernel_s > 0.0) std::printf("(device %.3f s, %.1f Msamples/s)\n", kernel_s, (double)a.width * a.height * a.spp / kernel_s / 1e6);
+        display_stage.release();
         if (gbuf) write_pfm(a.output, image.pixels().data(), a.width, a.height); else image.save(a.output);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "mi355pt: %s\n", e.what());
