@@ -64,16 +64,13 @@ def test_sobol_stratification(oracle):
     assert len(set(zip(u.tolist(), v.tolist()))) == 16
 
 
-@pytest.fixture(scope="module")
-def small_scene(oracle, pkg):
+@pytest.mark.parametrize("scene_id", [0, 3, 7, 8, 10, 12, 17, 19, 21])
+def test_fast_mode_equals_faithful_mode(oracle, pkg, scene_id):
+    """The t_max-shrinking traversal used for golden generation returns exactly the faithful traversal's hits: the same ray probe and the
+    48 x 36 film at 4 spp under all three strategies, on scenes with a textured, a glass, a clearcoat and a scaled / rotated hero, an
+    environment light and delta lights (on adversarial geometry: tests/test_geometry_stress.py)."""
     sc = oracle.new_scene()
-    cam = pkg.scenes.load_scene(sc, 3, 48, 36, tex_size=128)
-    return sc, cam
-
-
-def test_fast_mode_equals_faithful_mode(oracle, pkg, small_scene):
-    """The t_max-shrinking traversal used for golden generation returns exactly the faithful traversal's hits."""
-    sc, cam = small_scene
+    cam = pkg.scenes.load_scene(sc, scene_id, 48, 36, tex_size=128)
     rng = np.random.default_rng(3)
     n = 4000
     o = np.tile(np.array([[0.0, 0.0, 0.0]], np.float32), (n, 1))
@@ -86,12 +83,13 @@ def test_fast_mode_equals_faithful_mode(oracle, pkg, small_scene):
     b = sc.probe_intersect(o, d)
     for x, y in zip(a, b):
         assert np.array_equal(x, y)
-    prm = pkg.make_params(4, "mis", "sobol")
-    oracle.set_faithful(sc, True)
-    acc_a, _ = oracle.render_accum(sc, cam, prm, threads=8)
-    oracle.set_faithful(sc, False)
-    acc_b, _ = oracle.render_accum(sc, cam, prm, threads=8)
-    assert np.array_equal(acc_a, acc_b)
+    for strategy in ("pt", "nee", "mis"):
+        prm = pkg.make_params(4, strategy, "sobol")
+        oracle.set_faithful(sc, True)
+        acc_a, _ = oracle.render_accum(sc, cam, prm, threads=8)
+        oracle.set_faithful(sc, False)
+        acc_b, _ = oracle.render_accum(sc, cam, prm, threads=8)
+        assert np.array_equal(acc_a, acc_b), strategy
 
 
 def test_pt_nee_mis_consistency(oracle, pkg):
