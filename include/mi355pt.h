@@ -347,6 +347,14 @@ const char* mi355pt_version(void);
  * includes. */
 #include "mi355pt_display.h"
 
+/* ---------------- robust film ---------------- */
+/* EXTENSION, no reference counterpart: firefly rejection by an adaptive median of means — mi355pt_robust_params, mi355pt_robust_params_default,
+ * mi355pt_robust_combine_device and mi355pt_robust_combine (K bucket films of consecutive sample ranges combined per pixel by a trimmed mean
+ * whose trim comes from the Gini coefficient of the bucket means), mi355pt_render_buckets_device (the K films, over
+ * mi355pt_render_accum_device above) and mi355pt_render_robust (the seam's shape).  mi355pt_render above stays as it is.  Declared in its own
+ * header, which this one always includes (ahead of the variance-guided denoiser's, which stays the last one). */
+#include "mi355pt_robust.h"
+
 /* ---------------- variance-guided denoiser ---------------- */
 /* EXTENSION, no reference counterpart: a second filter beside the one above, which it leaves as it is — mi355pt_denoise_var_params,
  * mi355pt_denoise_var_params_default, mi355pt_denoise_var_scratch_bytes, mi355pt_denoise_var_device and mi355pt_denoise_var: an a-trous

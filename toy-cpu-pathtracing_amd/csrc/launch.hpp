@@ -120,6 +120,17 @@ hipError_t launch_display_hist(const float* d_film, const DisplayMeterArgs& args
 hipError_t launch_display_finish(const uint32_t* d_scratch, const DisplayMeterArgs& args, const uint32_t* d_prev_record, uint32_t* d_record, uint32_t* d_hist, hipStream_t);
 hipError_t launch_display(const float* d_film, const DisplayArgs& args, const uint32_t* d_record, float* d_out, hipStream_t);
 float display_hable(float x);      // h(x) of the header on the host, the same single-rounded steps as the kernel
+// pt_kernels_robust.hip: the robust film (include/mi355pt_robust.h): one launch, one thread per pixel, over n_buckets in {4, 8, 16, 32} films
+// of args.pixels x 3 floats at d_buckets.  d_out_half == nullptr: single output (one set of n_buckets); otherwise pair output (two sets of
+// n_buckets / 2).  d_out_trim == nullptr: not wanted.  The frame has fewer than 2^32 pixels
+struct RobustArgs {
+    uint64_t pixels;
+    float spp;                              // (float)spp_bucket
+    float inv_spp;                          // 1 / spp where spp_bucket is a power of two (exact), 0 otherwise: the kernel divides
+    uint32_t mode;                          // MI355PT_ROBUST_*
+    float gini_scale;
+};
+hipError_t launch_robust_combine(const float* d_buckets, uint32_t n_buckets, const RobustArgs& args, float* d_out, float* d_out_half, uint8_t* d_out_trim, hipStream_t);
 
 // Resident 64-thread blocks (= waves) of `kernel` on the current device: the persistent grid size of the EXACT instantiation a launch takes
 // (the register count, and so the occupancy, differs between instantiations and between translation units with their own backend flags).

@@ -186,6 +186,14 @@ ENCODE = {"linear": 0, "srgb": 1}                                               
 DISPLAY_RECORD_WORDS, DISPLAY_HIST_WORDS = 8, 258
 
 
+class RobustParams(C.Structure):
+    """mi355pt_robust_params (include/mi355pt_robust.h); Product.robust_params_default() gives GMON with scale 1, a zeroed one is MEAN"""
+    _fields_ = [("mode", C.c_uint32), ("gini_scale", C.c_float)]
+
+
+ROBUST_MODE = {"mean": 0, "mom": 1, "gmon": 2}                                   # MI355PT_ROBUST_*
+
+
 def make_camera(position, direction, up, width, height, fov_deg=45.0):
     return Camera((C.c_float * 3)(*position), (C.c_float * 3)(*direction), (C.c_float * 3)(*up), fov_deg, width, height)
 
@@ -227,6 +235,8 @@ TEMPORAL_RECTIFY_SYMBOLS = ["temporal_rectify_params_default", "temporal_rectify
 UPSAMPLE_SYMBOLS = ["upsample_params_default", "upsample_low_camera", "upsample_device", "upsample"]
 # ... and include/mi355pt_display.h, the display block (tests/test_display.py)
 DISPLAY_SYMBOLS = ["display_params_default", "display_scratch_bytes", "display_meter_device", "display_device", "display_meter", "display"]
+# ... and include/mi355pt_robust.h, the robust-film block (tests/test_robust.py)
+ROBUST_SYMBOLS = ["robust_params_default", "robust_combine_device", "robust_combine", "render_buckets_device", "render_robust"]
 ADAPTIVE_SYMBOLS = ["adaptive_scratch_bytes", "adaptive_step_device", "film_normalize_tiles_device", "render_adaptive_device", "render_adaptive"]
 
 
@@ -529,6 +539,13 @@ class Product(Backend):
             lib.mi355pt_display_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DisplayParams), C.c_void_p, C.c_void_p, C.c_void_p]
             lib.mi355pt_display_meter.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DisplayParams), C.c_void_p, C.c_void_p, C.c_void_p]
             lib.mi355pt_display.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DisplayParams), C.c_void_p, C.c_void_p]
+        if hasattr(lib, "mi355pt_robust_combine_device"):  # (absent from an older build loaded through MI355PT_LIB)
+            lib.mi355pt_robust_params_default.argtypes = [C.POINTER(RobustParams)]; lib.mi355pt_robust_params_default.restype = None
+            lib.mi355pt_robust_combine_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RobustParams), C.c_void_p, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p]
+            lib.mi355pt_robust_combine.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RobustParams), C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.mi355pt_render_buckets_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+            lib.mi355pt_render_robust.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.POINTER(RobustParams), C.c_void_p]
         if not hasattr(lib, "mi355pt_render_sample_log"):     # an older build loaded through MI355PT_LIB for an A/B timing run
             return
         lib.mi355pt_sample_log_records.argtypes = [C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]
@@ -831,6 +848,44 @@ class Product(Backend):
         rec = None if record is None else np.ascontiguousarray(record, dtype=np.uint32)
         out = np.zeros((h, w, 3), np.float32)
         self.check(self.lib.mi355pt_display(f.ctypes.data, w, h, spp, C.byref(params), rec.ctypes.data if rec is not None else None, out.ctypes.data), "display")
+        return out
+
+    # ---- the robust film (include/mi355pt_robust.h): K bucket films, a per-pixel trimmed mean chosen by their Gini coefficient ----
+    def robust_params_default(self):
+        p = RobustParams()
+        self.lib.mi355pt_robust_params_default(C.byref(p))
+        return p
+
+    def robust_params(self, mode="gmon", gini_scale=1.0):
+        return RobustParams(ROBUST_MODE[mode], gini_scale)
+
+    def robust_combine_device(self, d_buckets_ptr, n_buckets, spp_bucket, width, height, params, d_out_ptr, d_out_half_ptr=None, d_out_trim_ptr=None, stream=None):
+        """mi355pt_robust_combine_device: d_out_half_ptr None or 0 = single output; d_out_trim_ptr None or 0 = not wanted"""
+        self.check(self.lib.mi355pt_robust_combine_device(C.c_void_p(d_buckets_ptr), n_buckets, spp_bucket, width, height, C.byref(params), C.c_void_p(d_out_ptr),
+                                                          C.c_void_p(d_out_half_ptr or 0), C.c_void_p(d_out_trim_ptr or 0), C.c_void_p(stream or 0)),
+                   "robust_combine_device")
+
+    def robust_combine(self, buckets, spp_bucket, params=None, pair=False, want_trim=True):
+        """mi355pt_robust_combine on a host (K, H, W, 3) float32 stack of sums -> (out, out_half or None, trim (H, W, 2) uint8 or None)"""
+        b = np.ascontiguousarray(buckets, dtype=np.float32)
+        k, h, w = b.shape[:3]
+        params = params if params is not None else self.robust_params_default()
+        out = np.zeros((h, w, 3), np.float32)
+        half = np.zeros((h, w, 3), np.float32) if pair else None
+        trim = np.zeros((h, w, 2), np.uint8) if want_trim else None
+        self.check(self.lib.mi355pt_robust_combine(b.ctypes.data, k, spp_bucket, w, h, C.byref(params), out.ctypes.data, half.ctypes.data if pair else None,
+                                                   trim.ctypes.data if want_trim else None), "robust_combine")
+        return out, half, trim
+
+    def render_buckets_device(self, scene, cam, params, n_buckets, d_buckets_ptr, stream=None, stats=None):
+        self.check(self.lib.mi355pt_render_buckets_device(scene.h, C.byref(cam), C.byref(params), n_buckets, C.c_void_p(d_buckets_ptr), C.c_void_p(stream or 0),
+                                                          C.byref(stats) if stats is not None else None), "render_buckets_device")
+
+    def render_robust(self, scene, cam, params, n_buckets, robust_params=None):
+        """mi355pt_render_robust -> (H, W, 3) float32, tone-mapped and sRGB-encoded like render()"""
+        rp = robust_params if robust_params is not None else self.robust_params_default()
+        out = np.zeros((cam.height, cam.width, 3), np.float32)
+        self.check(self.lib.mi355pt_render_robust(scene.h, C.byref(cam), C.byref(params), n_buckets, C.byref(rp), out.ctypes.data), "render_robust")
         return out
 
     def render_accum_device(self, scene, cam, params, s_begin, s_end, d_accum_ptr, stream=None, stats=None):

@@ -8,7 +8,7 @@
 #include <stdexcept>
 #include <string>
 
-#include <hip/hip_runtime_api.h>   // --denoise, --denoise-variance, --adaptive-threshold, --temporal-frames, --half-res, --tone-map and --auto-exposure: the films of those paths stay on the device (hipMalloc / hipMemcpy / hipFree, no kernels here)
+#include <hip/hip_runtime_api.h>   // --denoise, --denoise-variance, --adaptive-threshold, --temporal-frames, --half-res, --tone-map, --auto-exposure and --robust-buckets: the films of those paths stay on the device (hipMalloc / hipMemcpy / hipFree, no kernels here)
 
 #include "scenes.hpp"
 
@@ -42,6 +42,9 @@ struct Args {   // main.rs:20-53
     std::string tone_map; bool white_given = false; float white = 0.0f;
     bool auto_exposure = false, exposure_key_given = false, exposure_adapt_given = false, exposure_trim_given = false;
     float exposure_key = 0.0f, exposure_adapt = 0.0f; uint32_t exposure_trim[2] = {0, 0};
+    // nor the robust film (mi355pt_robust.h): --spp rendered as K buckets of --spp / K consecutive samples, combined per pixel by a trimmed
+    // mean of the bucket means (0 = off).  Mode and scale not given = mi355pt_robust_params_default: GMON, 1
+    uint32_t robust_buckets = 0; bool robust_given = false; std::string robust_mode; bool robust_scale_given = false; float robust_scale = 0.0f;
 };
 
 // --denoise: the beauty film at --spp, the albedo and shading-normal films at --denoise-guide-spp (converged guides cost a few percent of
@@ -105,6 +108,53 @@ static double render_displayed(const Scene& scene, const Camera& camera, mi355pt
     check(mi355pt_render_accum_device(scene.raw(), &cam, &p, 0, p.spp, film.p, nullptr, &st), "mi355pt_render_accum_device");
     display_stage.resolve(film.p, cam.width, cam.height, p.spp, rgb.p);
     if (hipMemcpy(pixels.data(), rgb.p, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the frame back failed");
+    return st.kernel_ms * 1e-3;
+}
+
+static void render_guides(const Scene& scene, const mi355pt_camera& cam, mi355pt_params g, uint32_t guide_spp, bool fused, float* d_albedo, float* d_normal);
+static mi355pt_denoise_var_params denoise_var_params(float sigma_lum);
+
+// --robust-buckets K: the frame as K bucket films (mi355pt_render_buckets_device), then mi355pt_robust_combine_device.  Plain: the single
+// output, a film with spp 1, to the display stage or the resolve.  --denoise: the single output as the beauty film with spp 1.
+// --denoise-variance: the pair output as (beauty, half) with spp 2.  Prints the share of pixels trimmed and the mean trim count.  Returns
+// the device seconds of the K bucket launches.
+static double render_robust(const Scene& scene, const Camera& camera, mi355pt_params p, const Args& a, const mi355pt_robust_params& rp, std::vector<float>& pixels) {
+    const mi355pt_camera& cam = camera.raw();
+    const uint32_t n_pixels = cam.width * cam.height, K = a.robust_buckets, guide_spp = a.denoise_guide_spp;
+    const size_t film_bytes = (size_t)n_pixels * 3 * sizeof(float), trim_bytes = (size_t)n_pixels * 2;
+    const bool pair = a.denoise_variance;
+    DeviceFilm buckets(film_bytes * K), theta(film_bytes), half(pair ? film_bytes : 4), trim(trim_bytes), rgb(film_bytes);
+    mi355pt_stats st{};
+    check(mi355pt_render_buckets_device(scene.raw(), &cam, &p, K, buckets.p, nullptr, &st), "mi355pt_render_buckets_device");
+    check(mi355pt_robust_combine_device(buckets.p, K, p.spp / K, cam.width, cam.height, &rp, theta.p, pair ? half.p : nullptr, (uint8_t*)trim.p, nullptr),
+          "mi355pt_robust_combine_device");
+    if (a.denoise || a.denoise_variance) {
+        const size_t scratch_bytes = pair ? mi355pt_denoise_var_scratch_bytes(cam.width, cam.height) : mi355pt_denoise_scratch_bytes(cam.width, cam.height);
+        DeviceFilm albedo(film_bytes), normal(film_bytes), out(film_bytes), scratch(scratch_bytes);
+        render_guides(scene, cam, p, guide_spp, a.fused_guides, albedo.p, normal.p);
+        if (pair) {
+            const mi355pt_denoise_var_params dp = denoise_var_params(a.denoise_sigma_lum);
+            check(mi355pt_denoise_var_device(theta.p, half.p, 2, nullptr, albedo.p, guide_spp, normal.p, guide_spp, cam.width, cam.height, &dp, scratch.p, scratch_bytes,
+                                             out.p, nullptr), "mi355pt_denoise_var_device");
+        } else {
+            mi355pt_denoise_params dp;
+            mi355pt_denoise_params_default(&dp);
+            check(mi355pt_denoise_device(theta.p, 1, albedo.p, guide_spp, normal.p, guide_spp, cam.width, cam.height, &dp, scratch.p, scratch_bytes, out.p, nullptr), "mi355pt_denoise_device");
+        }
+        display_stage.resolve(out.p, cam.width, cam.height, 1, rgb.p);
+    } else {
+        display_stage.resolve(theta.p, cam.width, cam.height, 1, rgb.p);
+    }
+    if (hipMemcpy(pixels.data(), rgb.p, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the frame back failed");
+    std::vector<uint8_t> t(trim_bytes);
+    if (hipMemcpy(t.data(), trim.p, trim_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the trim counts back failed");
+    uint64_t trimmed = 0, total = 0;
+    for (uint32_t i = 0; i < n_pixels; ++i) {
+        const uint32_t ti = pair ? (uint32_t)t[2 * i] + t[2 * i + 1] : t[2 * i];
+        trimmed += ti != 0; total += ti;
+    }
+    std::printf("(robust film: %u buckets of %u spp%s; %.2f %% of the pixels trimmed, mean trim count %.3f of at most %u)\n", K, p.spp / K,
+                pair ? ", even and odd sets" : "", 100.0 * (double)trimmed / n_pixels, (double)total / n_pixels / (pair ? 2.0 : 1.0), (pair ? K / 2 : K) / 2 - 1);
     return st.kernel_ms * 1e-3;
 }
 
@@ -449,7 +499,12 @@ static void usage() {
               "                   [--auto-exposure] (pt|nee|mis: the exposure from the frame's trimmed luminance histogram; with --temporal-frames every\n"
               "                                      frame is metered and blended with the previous frame's exposure)\n"
               "                   [--exposure-key K] (0.18: the value the mean luminance is mapped to)  [--exposure-adapt A] (1; 0 .. 1: the share of the way\n"
-              "                                      to the new exposure taken per frame)  [--exposure-trim LO,HI] (102,51: 1/1024ths of the pixels left out)");
+              "                                      to the new exposure taken per frame)  [--exposure-trim LO,HI] (102,51: 1/1024ths of the pixels left out)\n"
+              "                   [--robust-buckets K] (pt|nee|mis, K = 4|8|16|32 dividing --spp: the frame as K buckets of consecutive samples, combined per\n"
+              "                                         pixel by a trimmed mean of the bucket means: firefly rejection; with --denoise, --denoise-variance,\n"
+              "                                         --fused-guides, --tone-map and --auto-exposure)\n"
+              "                   [--robust-mode gmon|mom|mean] (gmon: the trim follows the Gini coefficient of the bucket means; mom: the median of means;\n"
+              "                                         mean: no trim)  [--robust-scale X] (1; >= 0: the factor on the Gini term)");
 }
 
 int main(int argc, char** argv) {
@@ -498,6 +553,9 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        else if (k == "--robust-buckets") { a.robust_given = true; a.robust_buckets = (uint32_t)std::stoul(val()); }
+        else if (k == "--robust-mode") a.robust_mode = val();
+        else if (k == "--robust-scale") { a.robust_scale_given = true; a.robust_scale = std::stof(val()); }
         else if (k == "--camera-step") {
             const std::string v = val();
             char tail = 0;
@@ -547,6 +605,29 @@ int main(int argc, char** argv) {
     if (a.exposure_key_given) display_stage.dp.key = a.exposure_key;
     if (a.exposure_adapt_given) display_stage.dp.adapt = a.exposure_adapt;
     if (a.exposure_trim_given) { display_stage.dp.trim_low = a.exposure_trim[0]; display_stage.dp.trim_high = a.exposure_trim[1]; }
+    // the robust film: refused here, before anything is loaded; mi355pt_robust_combine_device checks the struct again
+    mi355pt_robust_params robust_params;
+    mi355pt_robust_params_default(&robust_params);
+    if ((!a.robust_mode.empty() || a.robust_scale_given) && !a.robust_given) { std::fprintf(stderr, "error: --robust-mode and --robust-scale need --robust-buckets: they are the combination's parameters\n"); return 2; }
+    if (a.robust_given) {
+        const uint32_t K = a.robust_buckets;
+        if (K != 4 && K != 8 && K != 16 && K != 32) { std::fprintf(stderr, "error: invalid value '%u' for '--robust-buckets' (4, 8, 16 or 32)\n", K); return 2; }
+        if (aov) { std::fprintf(stderr, "error: --robust-buckets with --renderer %s: the robust film is for the path renderers (pt, nee, mis)\n", a.renderer.c_str()); return 2; }
+        if (a.gpus > 1) { std::fprintf(stderr, "error: --robust-buckets with --gpus %d: the robust film runs on one GPU\n", a.gpus); return 2; }
+        if (a.adaptive_threshold != 0.0f) { std::fprintf(stderr, "error: --robust-buckets with --adaptive-threshold: the buckets take one sample count per frame\n"); return 2; }
+        if (a.half_res) { std::fprintf(stderr, "error: --robust-buckets with --half-res: the buckets are rendered at full size\n"); return 2; }
+        if (a.temporal) { std::fprintf(stderr, "error: --robust-buckets with --temporal-frames: the robust film is one frame\n"); return 2; }
+        if (a.spp == 0 || a.spp % K != 0) { std::fprintf(stderr, "error: --robust-buckets %u needs --spp to be a multiple of it above 0 (got --spp %u)\n", K, a.spp); return 2; }
+        if (!a.robust_mode.empty()) {
+            const char* names[3] = {"mean", "mom", "gmon"};      // MI355PT_ROBUST_*
+            uint32_t m = 3;
+            for (uint32_t i = 0; i < 3; ++i) if (a.robust_mode == names[i]) m = i;
+            if (m == 3) { std::fprintf(stderr, "error: invalid value '%s' for '--robust-mode' (gmon, mom, mean)\n", a.robust_mode.c_str()); return 2; }
+            robust_params.mode = m;
+        }
+        if (a.robust_scale_given && !(std::isfinite(a.robust_scale) && a.robust_scale >= 0.0f)) { std::fprintf(stderr, "error: --robust-scale must be finite and not below 0\n"); return 2; }
+        if (a.robust_scale_given) robust_params.gini_scale = a.robust_scale;
+    }
     if (a.half_res_albedo && !a.half_res) { std::fprintf(stderr, "error: --half-res-albedo needs --half-res: it demodulates the film that --half-res upsamples\n"); return 2; }
     if (a.half_res && aov) { std::fprintf(stderr, "error: --half-res with --renderer %s: half-resolution rendering is for the path renderers (pt, nee, mis)\n", a.renderer.c_str()); return 2; }
     if (a.half_res && (a.width == 0 || a.height == 0 || (a.width & 1u) != 0 || (a.height & 1u) != 0)) { std::fprintf(stderr, "error: --half-res needs an even --width and --height above 0 (got %u x %u)\n", a.width, a.height); return 2; }
@@ -648,6 +729,7 @@ int main(int argc, char** argv) {
         else if (a.half_res) kernel_s = render_half_res(scene, camera, image.params(sampler, a.albedo_lut), a, image.pixels_mut());
         else if (a.temporal) kernel_s = render_temporal(scene, camera, image.params(sampler, a.albedo_lut), a, image.pixels_mut());
         else if (adaptive) render_adaptive(scene, camera, image.params(sampler, a.albedo_lut), a, image.pixels_mut());
+        else if (a.robust_given) kernel_s = render_robust(scene, camera, image.params(sampler, a.albedo_lut), a, robust_params, image.pixels_mut());
         else if (a.denoise_variance) kernel_s = render_denoised_variance(scene, camera, image.params(sampler, a.albedo_lut), a.denoise_guide_spp, a.fused_guides, a.denoise_sigma_lum, image.pixels_mut());
         else kernel_s = a.denoise ? render_denoised(scene, camera, image.params(sampler, a.albedo_lut), a.denoise_guide_spp, a.fused_guides, image.pixels_mut())
                                     : (display_stage.on ? render_displayed(scene, camera, image.params(sampler, a.albedo_lut), image.pixels_mut()) : image.render(sampler, a.albedo_lut));
@@ -655,6 +737,7 @@ int main(int argc, char** argv) {
         std::printf("Finish rendering: %.3f seconds.\n", wall);
         if (kernel_s > 0.0 && a.half_res) std::printf("(beauty launches at %u x %u: device %.3f s; the two G-buffers, the upsample and what follows it are in the wall time above)\n", a.width / 2, a.height / 2, kernel_s);
         else if (kernel_s > 0.0 && a.temporal) std::printf("(beauty launches of %u frames: device %.3f s; the G-buffer, the accumulation and the scene builds are in the wall time above)\n", a.temporal_frames, kernel_s);
+        else if (kernel_s > 0.0 && a.robust_given) std::printf("(bucket launches: device %.3f s, %.1f Msamples/s; the combination and what follows it are in the wall time above)\n", kernel_s, (double)a.width * a.height * a.spp / kernel_s / 1e6);
         else if (kernel_s > 0.0 && (a.denoise || a.denoise_variance)) std::printf("(beauty launch alone: device %.3f s, %.1f Msamples/s; the guide films and the filter are in the wall time above)\n", kernel_s, (double)a.width * a.height * a.spp / kernel_s / 1e6);
         else if (kernel_s > 0.0) std::printf("(device %.3f s, %.1f Msamples/s)\n", kernel_s, (double)a.width * a.height * a.spp / kernel_s / 1e6);
         display_stage.release();
