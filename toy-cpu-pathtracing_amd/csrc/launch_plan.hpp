@@ -228,4 +228,11 @@ inline bool use_camera_lists(const KernelKey& key, uint32_t block_log2, bool ena
 // the host-side switch, read per launch: MI355PT_NO_CAMERA_LISTS=1 (any value but "0") turns the lists off; default on
 inline bool camera_lists_enabled() { const char* e = getenv("MI355PT_NO_CAMERA_LISTS"); return !(e && e[0] != '\0' && !(e[0] == '0' && e[1] == '\0')); }
 
+// ---- tail-queue staging (tail_queue_plan.hpp, pt_kernel_body.inc) ----
+// Do the kernels with one tail queue keep the records a pass takes in the same iteration in LDS (DevScene::queue_stage)?  The kernels
+// without the code (two queues, the instrumented ones, the plain path tracer) ignore the flag.  `enabled`: queue_staging_enabled().
+inline bool use_queue_staging(const KernelKey& key, bool enabled) { return enabled && !key.stats; }
+// the host-side switch, read per launch: MI355PT_NO_QUEUE_STAGING=1 (any value but "0") sends every record through the global stack; default on
+inline bool queue_staging_enabled() { const char* e = getenv("MI355PT_NO_QUEUE_STAGING"); return !(e && e[0] != '\0' && !(e[0] == '0' && e[1] == '\0')); }
+
 }  // namespace pt

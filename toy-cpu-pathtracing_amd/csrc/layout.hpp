@@ -241,7 +241,9 @@ struct DevScene {
     uint32_t cam_lists;           // 1: the production kernels take camera-ray hits from per-work-item candidate lists (camera_candidates.hpp).  0 in the
                                   // lowered scene; the launcher sets it in its own copy, per launch (launch_plan.hpp use_camera_lists)
     const DevEnv* envs;           // every infinite light of the scene (Scene sums them all: scene.rs:185-231)
-    uint32_t n_envs, pad_env;
+    uint32_t n_envs;
+    uint32_t queue_stage;         // 1: the kernels with one tail queue hand a pass its fresh records through LDS (tail_queue_plan.hpp).  0 in the lowered
+                                  // scene; set per launch like cam_lists (launch_plan.hpp use_queue_staging)
 };
 
 struct DevCamera {

@@ -147,6 +147,18 @@ template <uint32_t FEAT, uint32_t MODE> constexpr uint32_t defer_classes() { ret
 // stack goes cold until the work item drains.  The order of the pops is still a function of the wave's own state, so frames stay
 // bit-identical from run to run; a pixel's samples reach the LDS film tile in another order than with the rings, so the film's float sums
 // differ from that build's in the last bits (per-sample values do not: tests/test_tail_queue_order_gpu.py).
+// STAGING (the kernels with ONE queue; tail_queue_plan.hpp tq_stage_*, tests/test_tail_queue_stage.py): when the push of an iteration
+// makes a pass due, that pass — in the same iteration, every lane being free — pops the newest min(64, count) records, and those include
+// all of the <= 64 just pushed.  Such records need no memory: the front writes them to LDS, into the traversal stack (s_stack: used only
+// inside trace_*, holding nothing between two traversals; 64 records x 80 B = 5 KB of its 6 KB, so no new LDS), in the global stack's
+// own field-major layout over 64 slots, and the pass reads them back from there.  Logically they still lie on top of the stack: the pass
+// hands each free lane the slot tq_pop_slot names, a slot at or above the pre-push count comes from LDS, one below it from the global
+// stack, and the count ends where it would — the record -> lane mapping, the order in which a pixel's samples reach the film tile and so
+// the film are bit for bit those of the all-global path (tests/test_tail_queue_stage_gpu.py).  In C2's cadence (three pushes of ~43 after
+// a pass, one of ~62 camera paths, a pass at 64) three pushes in four are followed by a pass: 148 of 191 records never leave the CU.  A
+// push without a pass goes to the global stack as before.  The two-queue kernels do not stage: their class-2-first rule lets a pass leave
+// fresh records of the other class behind.  MI355PT_NO_QUEUE_STAGING=1 (launch_plan.hpp, DevScene::queue_stage) sends every record through
+// the global stack again: the A/B control (profiles/queue_stage_ab.json).
 #ifndef PT_TAILQ
 #define PT_TAILQ 1
 #endif

@@ -3,7 +3,7 @@
 // progression; lane_job_tiles: an explicit list).  Included, not called: even a helper called from pt_kernel changes the schedule of every
 // tuned kernel, and those are measured as they are (tools/asm_identity.sh compares the device assembly with a revision's).
 // Expects the kernel's parameters (sc, cam, prm_in, dim_hash_tab, accum, partial, work_counter, stats, pout, defer_buf) and STATS, FEAT, MODE.
-    __shared__ uint32_t s_stack[STACK_DEPTH * 64];
+    __shared__ __attribute__((aligned(16))) uint32_t s_stack[STACK_DEPTH * 64];    // (16 B: between two traversals it stages tail-queue records as float4, below)
 #ifndef PT_FILM_PIX
 #define PT_FILM_PIX 64
 #endif
@@ -134,6 +134,14 @@
         // entries per stack: with one queue at most 127 paths ever wait (a pass starts at 64, an iteration adds at most 64 and every lane is
         // free after the front), with two at most 191 in both together — the smaller stack keeps the records closer to the L2
         constexpr uint32_t QR = (TQ_CLASSES != 0u) ? QUEUE_RING : PT_TAILQ_RING1;
+        // STAGING (one queue only; tail_queue_plan.hpp): when a pass follows the front in the same iteration, the records the front pushes
+        // are all among the ones that pass pops, so they go through LDS instead of the global stack — through s_stack, which only the
+        // traversals use and which holds nothing between two of them (cam_walk keeps its links in s_ring; the carry-over that resumed a
+        // traversal from its stack is dead).  Same layout as in memory, field-major over 64 slots: float4 k of slot s at dword (k * 64 + s) * 4.
+        // The two-queue kernels cannot: their class-2-first rule lets a pass leave fresh records of the other class behind.
+        constexpr bool STAGE = TAILQ && TQ_CLASSES == 0u;
+        static_assert(STACK_DEPTH * 64 >= (int)(TQ_STAGE_SLOTS * TQ_F4 * 4u) && TQ_STAGE_SLOTS == 64u, "a pass's worth of staged tail-queue records fits the traversal stack's LDS");
+        float4* const s_stage = (float4*)s_stack;
         while (true) {
             unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, ts4 = 0, tsa = 0, tsb = 0;
             uint32_t bsdf_classes = 0u;
@@ -223,18 +231,22 @@
             // Layout: FIELD-major inside a stack (float4 k of entry e at stack base + k * capacity + e): the entries of one push / pop are
             // consecutive, so each of the five store / load instructions of a wave covers 64 x 16 B = eight whole 128-byte lines instead of a
             // sixth of 64 different ones (+1 ... 2 % over the record-major layout; 128 entries where one queue suffices +0.2 ... 0.8 %)
-            auto tq_store = [&](uint32_t e, const Path& Q, const Hit& h, uint32_t pix) {
-                float4* r = q_base + (size_t)(e >> 8) * (TQ_F4 * QUEUE_RING) + (e & (QR - 1u));
+            // (tq_put / tq_get: the record at r, field k at r[k * stride] — in a global stack, or staged in LDS)
+            auto tq_put = [&](float4* r, uint32_t stride, const Path& Q, const Hit& h, uint32_t pix) {
                 const uint32_t fl = (Q.wl.term ? 1u : 0u) | ((Q.depth & 1023u) << 1) | ((pix & 63u) << 11) | (Q.smp.dimension << 17);   // (max_depth <= 1000, api.cpp check_args: dimension <= 3 + 8 * 1000 < 2^15)
-                r[0u * QR] = make_float4(__uint_as_float(Q.smp.morton), __uint_as_float(fl), Q.wl.lam0, __uint_as_float(h.tri));
-                r[1u * QR] = make_float4(Q.T[0], Q.T[1], Q.T[2], Q.T[3]);
-                r[2u * QR] = make_float4(Q.L[0], Q.L[1], Q.L[2], Q.L[3]);
-                r[3u * QR] = make_float4(Q.rd.x, Q.rd.y, Q.rd.z, h.b0);
-                r[4u * QR] = make_float4(h.b1, h.b2, __uint_as_float(Q.smp.rkey_lo), __uint_as_float(Q.smp.rkey_hi));
+                r[0u * stride] = make_float4(__uint_as_float(Q.smp.morton), __uint_as_float(fl), Q.wl.lam0, __uint_as_float(h.tri));
+                r[1u * stride] = make_float4(Q.T[0], Q.T[1], Q.T[2], Q.T[3]);
+                r[2u * stride] = make_float4(Q.L[0], Q.L[1], Q.L[2], Q.L[3]);
+                r[3u * stride] = make_float4(Q.rd.x, Q.rd.y, Q.rd.z, h.b0);
+                r[4u * stride] = make_float4(h.b1, h.b2, __uint_as_float(Q.smp.rkey_lo), __uint_as_float(Q.smp.rkey_hi));
             };
-            auto tq_load = [&](uint32_t e, Path& Q, Hit& h, uint32_t& pix) {
-                const float4* r = q_base + (size_t)(e >> 8) * (TQ_F4 * QUEUE_RING) + (e & (QR - 1u));
-                const float4 a = r[0u * QR], b = r[1u * QR], c = r[2u * QR], d = r[3u * QR], e4 = r[4u * QR];
+            auto tq_store = [&](uint32_t e, const Path& Q, const Hit& h, uint32_t pix) {
+                tq_put(q_base + (size_t)(e >> 8) * (TQ_F4 * QUEUE_RING) + (e & (QR - 1u)), QR, Q, h, pix);
+            };
+            struct TqRec { float4 a, b, c, d, e4; };
+            auto tq_get = [&](const float4* r, uint32_t stride) { return TqRec{r[0u * stride], r[1u * stride], r[2u * stride], r[3u * stride], r[4u * stride]}; };
+            auto tq_unpack = [&](const TqRec& rec, Path& Q, Hit& h, uint32_t& pix) {
+                const float4 a = rec.a, b = rec.b, c = rec.c, d = rec.d, e4 = rec.e4;
                 const uint32_t fl = __float_as_uint(a.y);
                 Q.smp.morton = __float_as_uint(a.x); Q.smp.dimension = fl >> 17; Q.smp.rkey_lo = __float_as_uint(e4.z); Q.smp.rkey_hi = __float_as_uint(e4.w);
                 Q.wl.lam0 = a.z; Q.wl.term = (fl & 1u) != 0u; Q.depth = (fl >> 1) & 1023u; pix = (fl >> 11) & 63u;
@@ -245,6 +257,9 @@
 #pragma unroll
                 for (int i = 0; i < 4; ++i) Q.pf[i] = 0.0f;
                 Q.p_pdf = 0.0f; Q.prev_pos = mk3(0.0f, 0.0f, 0.0f);
+            };
+            auto tq_load = [&](uint32_t e, Path& Q, Hit& h, uint32_t& pix) {
+                tq_unpack(tq_get(q_base + (size_t)(e >> 8) * (TQ_F4 * QUEUE_RING) + (e & (QR - 1u)), QR), Q, h, pix);
             };
             // the deferral queue's record (the instrumented kernels): the whole path, the hit and the pixel, record-major, 8 float4 = 128 B
             auto dq_store = [&](uint32_t e, const Path& Q, const Hit& h, uint32_t pix) {
@@ -297,11 +312,23 @@
                 const bool go_on = front && !end_path;
                 const bool cls2 = TQ_CLASSES != 0u && ((TQ_CLASSES >> (hit.mclass & 31u)) & 1u) != 0u;
                 const unsigned long long m_on1 = __ballot(go_on && !cls2), m_on2 = TQ_CLASSES != 0u ? __ballot(go_on && cls2) : 0ull;
+                // one queue: a pass is due after this push?  Then it takes every record of the push, and they wait in LDS (wave-uniform;
+                // sc.queue_stage == 0, launch_plan.hpp use_queue_staging: everything through the global stack)
+                // (`if constexpr`: not a statement of this may reach the two-queue kernels, whose schedule is measured as it is)
+                uint32_t n_on1 = 0u;
+                bool stage = false;
+                if constexpr (STAGE) {
+                    n_on1 = (uint32_t)__popcll(m_on1);
+                    stage = sc.queue_stage != 0u && tq_stage_pushes(q_count, n_on1, pool_next >= pool_size, (uint32_t)PT_TAILQ_MIN);
+                }
                 if ((m_on1 | m_on2) != 0ull) {
                     if (go_on) {
-                        // (on top of the stack: consecutive ranks, consecutive entries)
-                        const uint32_t e = cls2 ? QUEUE_RING + tq_push_slot(q2_count, rank_below(m_on2)) : tq_push_slot(q_count, rank_below(m_on1));
-                        tq_store(e, P, hit, my_pix);
+                        if (STAGE && stage) tq_put(s_stage + tq_stage_push_index(rank_below(m_on1)), TQ_STAGE_SLOTS, P, hit, my_pix);
+                        else {
+                            // (on top of the stack: consecutive ranks, consecutive entries)
+                            const uint32_t e = cls2 ? QUEUE_RING + tq_push_slot(q2_count, rank_below(m_on2)) : tq_push_slot(q_count, rank_below(m_on1));
+                            tq_store(e, P, hit, my_pix);
+                        }
                         active = false;
                     }
                     q_count += (uint32_t)__popcll(m_on1); q2_count += (uint32_t)__popcll(m_on2);
@@ -324,6 +351,9 @@
                     const bool take2 = !active && r < n2, take1 = !active && !take2 && r - n2 < n1;
                     const bool take = take1 || take2;
                     const uint32_t e = take2 ? QUEUE_RING + tq_pop_slot(q2_count, n2, r) : tq_pop_slot(q_count, n1, r - n2);
+                    // (one queue: the same slot, and where it is — the records staged above lie on top of the q_count - n_on1 older ones)
+                    TqStagePop sp{0u, false, 0u};
+                    if constexpr (STAGE) sp = tq_stage_pop(stage ? q_count - n_on1 : q_count, stage ? n_on1 : 0u, n1, r - n2);
                     q2_count -= n2; q_count -= n1;
                     bool ep = false;
                     if constexpr ((FEAT & FEAT_CC) != 0u) {
@@ -343,8 +373,14 @@
                     } else if (take) {
                         // (ONE divergent region for the back of the head and the tail: ShadeCtx must not cross a re-convergence point in the
                         // kernels that run 4 waves per SIMD — the split form of this block cost them 12 %)
+                        // (the older records from the global stack, the staged ones from LDS: written global side first, but the compiler
+                        // orders the two sides of the branch itself and puts the five LDS reads first — one LDS round trip per mixed pass)
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                        tq_load(e, P, hit, my_pix);
+                        static_assert(STAGE, "the kernels without the clearcoat code have one queue");
+                        TqRec rec;
+                        if (!sp.staged) rec = tq_get(q_base + sp.slot, QR);
+                        else rec = tq_get(s_stage + sp.index, TQ_STAGE_SLOTS);
+                        tq_unpack(rec, P, hit, my_pix);
                         active = true;
                         ShadeCtx C;
                         C.cont = false; C.need_cc = false; C.cc_fc = 0.0f;

@@ -36,4 +36,28 @@ constexpr TqTake tq_pass_take(uint32_t c1, uint32_t c2, uint32_t n_free, bool dr
     return TqTake{n1, n2};
 }
 
+// ---- staging (the kernels with ONE queue) ----
+// When a pass follows the front in the same iteration it takes the newest min(64, count) records, and those include every record the front
+// has just pushed (<= 64, every lane being free after the front).  Such records never need the global stack: the front writes them to LDS
+// instead (the traversal stack, idle between two traversals), rank r of the pushing lanes at LDS index r, and the pass reads them from
+// there.  Logically they still sit in slots [count, count + n_push) of the stack: the pass hands out the slots tq_pop_slot names, a slot at
+// or above the pre-push count comes from LDS, one below it from the global stack, and the count ends where it ends without staging.
+constexpr uint32_t TQ_STAGE_SLOTS = 64u;          // records the LDS area holds: one push
+
+// Does this iteration stage its pushes?  `count`: records waiting before the push; n_push: lanes that push (<= 64).  Exactly when a pass is
+// due after the push — that pass takes all of them.
+constexpr bool tq_stage_pushes(uint32_t count, uint32_t n_push, bool draining, uint32_t pass_min) {
+    return n_push != 0u && tq_pass_due(count + n_push, 0u, draining, false, pass_min);
+}
+// LDS index of the record staged by the lane of rank `rank` among the pushing lanes
+constexpr uint32_t tq_stage_push_index(uint32_t rank) { return rank; }
+
+struct TqStagePop { uint32_t slot; bool staged; uint32_t index; };    // the logical stack slot; in LDS?; if so, at which index
+// What the lane of rank `rank` among the n_take lanes of the pass pops, the iteration having staged n_push records on top of `count` waiting
+// ones (n_push = 0: nothing staged, every slot is in the global stack)
+constexpr TqStagePop tq_stage_pop(uint32_t count, uint32_t n_push, uint32_t n_take, uint32_t rank) {
+    const uint32_t slot = tq_pop_slot(count + n_push, n_take, rank);
+    return TqStagePop{slot, slot >= count, slot >= count ? slot - count : 0u};
+}
+
 }  // namespace pt
