@@ -355,6 +355,14 @@ const char* mi355pt_version(void);
  * header, which this one always includes (ahead of the variance-guided denoiser's, which stays the last one). */
 #include "mi355pt_robust.h"
 
+/* ---------------- camera moves on a built scene ---------------- */
+/* EXTENSION, no reference counterpart: mi355pt_move_result and mi355pt_scene_move_camera — a camera translation applied to the built scene
+ * on the device: the render-space vertices re-based, the boxes of both trees refit bottom-up, the instance matrices, lights and emissive
+ * triangles recomputed; the topology of the tree, and every array that does not depend on the camera, stay.  Byte-equal to the host
+ * lowering for the new camera over the same tree; falls back to mi355pt_scene_build where that cannot hold.  Declared in its own header,
+ * which this one always includes (ahead of the variance-guided denoiser's, which stays the last one). */
+#include "mi355pt_rebase.h"
+
 /* ---------------- variance-guided denoiser ---------------- */
 /* EXTENSION, no reference counterpart: a second filter beside the one above, which it leaves as it is — mi355pt_denoise_var_params,
  * mi355pt_denoise_var_params_default, mi355pt_denoise_var_scratch_bytes, mi355pt_denoise_var_device and mi355pt_denoise_var: an a-trous

@@ -41,6 +41,25 @@ int mi355pt_scene_debug_lowering_digest(const mi355pt_scene* s, const mi355pt_ca
 int mi355pt_scene_debug_camera_candidates(const mi355pt_scene* s, const mi355pt_camera* cam, const uint32_t* rects, uint32_t n_rects, uint32_t cap,
                                           uint32_t* out_counts, uint8_t* out_overflow, uint32_t* out_indices, float* out_tris, uint32_t* n_tris);
 
+/* mi355pt_scene_move_camera (include/mi355pt_rebase.h) on the host: the digests, in mi355pt_scene_debug_lowering_digest's format and order, of
+ * the scene lowered for `cam_new` with the topology PINNED to the tree of `cam_built` — stage A for cam_new; the BVH2 of cam_built (its links
+ * and leaf order) with every box recomputed from the new triangles; stage B; then cam_built's 4-wide collapse with its boxes copied from that
+ * BVH2 and padded.  The tree of cam_built is the host builder's, except that a scene whose tree WAS built at cam_built's position by the GPU
+ * builder — wherever mi355pt_scene_move_camera has taken it since — pins to that tree (the build keeps it on the host).  No device, the scene left as it is.  *out_reason (NULL ok): the MI355PT_MOVE_* reason
+ * a move from cam_built to cam_new would report; for the two reasons that rebuild, the digests are those of a fresh lowering for cam_new.
+ * With cam_new = cam_built the digests are mi355pt_scene_debug_lowering_digest's: the refit and the pad reproduce the builders' boxes. */
+int mi355pt_scene_debug_move_digest(const mi355pt_scene* s, const mi355pt_camera* cam_built, const mi355pt_camera* cam_new, char* names_buf,
+                                    size_t names_len, uint64_t* digests, uint32_t* n, uint32_t* out_reason);
+/* The tree of that pinned lowering in mi355pt_scene_export_bvh's layout and calling convention (NULL buffers for the counts), host only; and
+ * out_pad_radii (2 floats, NULL ok): the largest coordinate magnitude the pad of the 4-wide tree is scaled by, {as the move computes it from
+ * the BVH2 root record's two child boxes, as the lowering's own loop over the unpadded 4-wide boxes computes it}. */
+int mi355pt_scene_debug_move_export(const mi355pt_scene* s, const mi355pt_camera* cam_built, const mi355pt_camera* cam_new, void* out_nodes,
+                                    uint32_t* n_nodes, void* out_tris, uint32_t* n_tris, int32_t* root, float* out_pad_radii);
+/* The same digests of what the DEVICE holds: reads back every array of a built scene and hashes it the same way, in upload order, with the
+ * scalars' digest last; pointers inside hashed records count as null.  The text after the names is mi355pt_scene_info's without its *_ms
+ * fields.  Needs the scene's device current. */
+int mi355pt_scene_debug_device_digest(const mi355pt_scene* s, char* names_buf, size_t names_len, uint64_t* digests, uint32_t* n);
+
 /* ---------------- probes (parity tests; same device code as the render path) ---------------- */
 /* The built acceleration structure as the device holds it (no reference counterpart; the reference's is scene/src/bvh.rs:300-343):
  * node records of 64 B {bx[4] = lo0.x lo1.x hi0.x hi1.x, by[4], bz[4], int32 child[2] (>= 0 node index, < 0 leaf:

@@ -131,6 +131,15 @@ struct RobustArgs {
     float gini_scale;
 };
 hipError_t launch_robust_combine(const float* d_buckets, uint32_t n_buckets, const RobustArgs& args, float* d_out, float* d_out_half, uint8_t* d_out_trim, hipStream_t);
+// pt_kernels_rebase.hip: a camera move on a built scene (include/mi355pt_rebase.h, scene_rebase.cpp).  launch_rebase_tris: the render-space
+// positions of all n_tris leaf-order triangles from the local records and the instance matrices; count_degenerate adds the number of
+// triangles whose cross product is exactly zero to *d_degenerate_count (which the caller has cleared).  launch_refit_bvh2_height: the boxes of
+// the `count` (node, side) entries from d_entries[first] on — ONE height group of rebase_plan.hpp's plan; the caller launches the groups
+// lowest first on one stream.  launch_refit_nodes4: every used slot of the 4-wide tree from its source in the refit BVH2, padded
+hipError_t launch_rebase_tris(const DevTriLocal* d_local, const DevInstance* d_instances, DevTri* d_render, uint32_t n_tris, bool count_degenerate,
+                              uint32_t* d_degenerate_count, hipStream_t);
+hipError_t launch_refit_bvh2_height(DevNode* d_nodes, const DevTri* d_tris_render, const uint32_t* d_entries, uint32_t first, uint32_t count, hipStream_t);
+hipError_t launch_refit_nodes4(DevNode4* d_nodes4, const DevNode* d_nodes, const uint32_t* d_slot_src, uint32_t n_slots, int32_t root, hipStream_t);
 
 // Resident 64-thread blocks (= waves) of `kernel` on the current device: the persistent grid size of the EXACT instantiation a launch takes
 // (the register count, and so the occupancy, differs between instantiations and between translation units with their own backend flags).

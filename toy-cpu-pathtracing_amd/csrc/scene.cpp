@@ -37,6 +37,7 @@ SceneImpl::~SceneImpl() { release(); }
 void SceneImpl::release() {
     for (void* p : allocs) (void)hipFree(p);
     allocs.clear();
+    rebase = RebaseState{};
     built = false;
 }
 
@@ -106,6 +107,18 @@ int SceneImpl::build(const mi355pt_camera* cam, const float* cmf4 /*470*4*/, std
     }
     if (bvh.max_depth >= STACK_DEPTH) { *err = "BVH deeper than the traversal stack"; return MI355PT_E_INVALID; }
 
+    RebaseState rb;                                 // what a later camera move needs of the build's intermediate results
+    rb.gpu_built = gpu_built;
+    std::memcpy(rb.tree_cam_pos, cam->position, sizeof(rb.tree_cam_pos));
+    if (gpu_built) { rb.gpu_nodes = bvh.nodes; rb.gpu_order = bvh.order; rb.gpu_depth = bvh.max_depth; rb.gpu_root = bvh.root; }
+    if (!geo.tris_are_local) {
+        size_t k = 0;
+        for (size_t t = 0; t < geo.tris.size(); ++t) {
+            if (k < geo.kept.size() && geo.kept[k] == t) { ++k; continue; }
+            rb.left_out.push_back(geo.shade[t].instance); rb.left_out.push_back(geo.shade[t].local_tri);
+        }
+    }
+
     LoweredScene ls;
     LowerReport rep;
     if ((rc = lower_scene(*this, std::move(geo), std::move(bvh), cmf4, &ls, &rep, err))) return rc;
@@ -114,6 +127,8 @@ int SceneImpl::build(const mi355pt_camera* cam, const float* cmf4 /*470*4*/, std
     ms[2] = ms_since(tc);
 
     if ((rc = upload(ls, err))) return rc;
+    rebase = std::move(rb);
+    if ((rc = prepare_rebase(ls, rep, err))) return rc;
     features = ls.features;
     info = lowering_info(ls, rep, gpu_built, ms);
     built = true;

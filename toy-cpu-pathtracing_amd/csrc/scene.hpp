@@ -40,6 +40,31 @@ bool build_bvh_gpu(const std::vector<BuildTri>& tris, BvhOut* out, double* devic
 constexpr size_t BVH_GPU_AUTO_TRIS = 1u << 17;   // "auto": scenes from 131 072 triangles on are built on the GPU
 
 struct LoweredScene;   // scene_lower.hpp
+struct LowerReport;
+
+struct MeshBounds { float lo[3], hi[3]; };   // a mesh's local AABB (scene_lower.cpp mesh_local_bounds)
+// What mi355pt_scene_move_camera (scene_rebase.cpp) keeps beside the lowered scene, made by SceneImpl::build.  Not part of LoweredScene: what
+// the upload takes and the digests hash stays what it was.
+struct RebaseState {
+    bool ready = false;                       // false: a move builds again (MI355PT_MOVE_UNSUPPORTED_BUILD)
+    bool gpu_built = false;
+    std::vector<uint32_t> height_offset;      // rebase_plan.hpp RebasePlan::height_offset
+    uint32_t n_slots = 0;                     // 4 * n_nodes4
+    uint32_t* d_entries = nullptr;            // RebasePlan::entries, RebasePlan::slot_src and the degenerate counter, on the device
+    uint32_t* d_slot_src = nullptr;           // (all three in SceneImpl::allocs)
+    uint32_t* d_count = nullptr;
+    std::vector<uint8_t> identity;            // DevInstance::identity of the build, per instance
+    bool tris_are_local = false;
+    std::vector<uint32_t> left_out;           // (instance, mesh triangle) pairs the build found degenerate in render space and left out of the tree
+    std::vector<MeshBounds> bounds;           // per mesh
+    std::vector<DevLight> lights;             // the build's records: an area light's and a light triangle's cdf do not depend on the camera
+    std::vector<DevLightTri> light_tris;
+    std::vector<DevNode> gpu_nodes;           // a GPU-built tree as it came back (the host builder's can be built again): what
+    std::vector<uint32_t> gpu_order;          // mi355pt_scene_debug_move_digest pins the topology to, without a device
+    int gpu_depth = 0; int32_t gpu_root = 0;
+    float tree_cam_pos[3] = {0, 0, 0};        // the camera position the tree was BUILT for (build_cam_pos follows the moves)
+    size_t n_degenerate = 0; int bvh_depth = 0, stack_need = 0; std::string collapse_method;   // the build's LowerReport (mi355pt_scene_debug_device_digest)
+};
 
 struct SceneImpl {
     // ---- description ----
@@ -63,6 +88,7 @@ struct SceneImpl {
     std::vector<void*> allocs;
     uint32_t features = FEAT_ALL;   // FEAT_* bits the scene's materials need (kernel specialisation)
     std::string info;             // mi355pt_scene_info
+    RebaseState rebase;
 
     ~SceneImpl();
     void release();
@@ -72,6 +98,7 @@ struct SceneImpl {
     // release(), the device query, lower_geometry, the tree build (host or GPU), lower_scene + lower_tree4, upload, the info string
     int build(const mi355pt_camera* cam, const float* cmf4 /*470*4*/, std::string* err);
     int upload(const LoweredScene& ls, std::string* err);   // the one place that allocates device memory and copies to it
+    int prepare_rebase(const LoweredScene& ls, const LowerReport& rep, std::string* err);   // scene_rebase.cpp: the side tables of a built scene, after upload()
 };
 
 // mi355pt_coat_albedo_table (scene_lower.cpp): E(cos theta_o) of the clearcoat's directional-albedo estimator, 64 entries

@@ -128,9 +128,11 @@ void lower_delta_light(const HostDeltaLight& hl, const float* w2r, LoweredGeomet
 }
 
 // primitive bounds = the mesh's local AABB carried through local_to_render (primitive/impls/triangle_mesh.rs:62-70), joined to the scene's
-void grow_scene_bounds(const HostMesh& mesh, const float* l2r, float sb_lo[3], float sb_hi[3]) {
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+void mesh_aabb(const HostMesh& mesh, float lo[3], float hi[3]) {
+    for (int a = 0; a < 3; ++a) { lo[a] = INFINITY; hi[a] = -INFINITY; }
     for (uint32_t v = 0; v < mesh.n_vert; ++v) for (int a = 0; a < 3; ++a) { lo[a] = std::fmin(lo[a], mesh.pos[3 * v + a]); hi[a] = std::fmax(hi[a], mesh.pos[3 * v + a]); }
+}
+void grow_scene_bounds(const float lo[3], const float hi[3], const float* l2r, float sb_lo[3], float sb_hi[3]) {
     for (int k = 0; k < 8; ++k) {
         V3 q = xform_point(l2r, V3{(k & 1) ? hi[0] : lo[0], (k & 2) ? hi[1] : lo[1], (k & 4) ? hi[2] : lo[2]});
         sb_lo[0] = std::fmin(sb_lo[0], q.x); sb_lo[1] = std::fmin(sb_lo[1], q.y); sb_lo[2] = std::fmin(sb_lo[2], q.z);
@@ -382,10 +384,7 @@ inline bool slot_used(const DevNode4& n, int c) { return n.lox[c] <= n.hix[c] &&
 #if PT_NODE_FMA
 // pad the boxes the fma slab test sees (layout.hpp PT_NODE_FMA); unused slots stay as they are
 void pad_nodes4(std::vector<DevNode4>* nodes4) {
-    float r = 0.0f;
-    for (const DevNode4& n : *nodes4) for (int c = 0; c < 4; ++c) if (slot_used(n, c))
-        for (float v : {n.lox[c], n.loy[c], n.loz[c], n.hix[c], n.hiy[c], n.hiz[c]}) r = std::max(r, std::fabs(v));
-    const float pad = r * NODE4_PAD_REL;
+    const float pad = nodes4_pad_radius(*nodes4) * NODE4_PAD_REL;
     for (DevNode4& n : *nodes4) for (int c = 0; c < 4; ++c) if (slot_used(n, c)) {
         n.lox[c] -= pad; n.loy[c] -= pad; n.loz[c] -= pad; n.hix[c] += pad; n.hiy[c] += pad; n.hiz[c] += pad;
     }
@@ -440,6 +439,14 @@ inline uint64_t fnv1a64(const void* data, size_t n) {
 }
 
 }  // namespace
+
+// the largest coordinate magnitude over the used slots: what pad_nodes4 scales its pad by
+float nodes4_pad_radius(const std::vector<DevNode4>& nodes4) {
+    float r = 0.0f;
+    for (const DevNode4& n : nodes4) for (int c = 0; c < 4; ++c) if (n.lox[c] <= n.hix[c] && n.lox[c] < FLT_MAX)
+        for (float v : {n.lox[c], n.loy[c], n.loz[c], n.hix[c], n.hiy[c], n.hiz[c]}) r = std::max(r, std::fabs(v));
+    return r;
+}
 
 // ---------------- spectra and tables of the description (SceneImpl's const helpers) ----------------
 
@@ -571,7 +578,7 @@ int lower_geometry(const SceneImpl& scene, const mi355pt_camera* cam, LoweredGeo
         const HostMesh& mesh = scene.meshes[inst.geom];
         float l2r[16];
         mat4_mul(w2r, inst.l2w, l2r);                                          // triangle_mesh.rs:38-40
-        grow_scene_bounds(mesh, l2r, sb_lo, sb_hi);
+        { float lo[3], hi[3]; mesh_aabb(mesh, lo, hi); grow_scene_bounds(lo, hi, l2r, sb_lo, sb_hi); }
         DevInstance& di = g->instances[ii];
         if (!lower_transform(l2r, scene.lowering, &di)) { *err = "singular instance transform"; return MI355PT_E_INVALID; }
         // do all instances share ONE pure translation?  (DevScene::tris_are_local)
@@ -597,6 +604,68 @@ int lower_geometry(const SceneImpl& scene, const mi355pt_camera* cam, LoweredGeo
     if (g->build_tris.empty()) { *err = "scene has no triangles"; return MI355PT_E_INVALID; }
     if (g->build_tris.size() > ((size_t)MAX_LEAF_TRIS << MAX_BUILD_DEPTH)) { *err = "too many triangles"; return MI355PT_E_INVALID; }   // 16.7 M: depth bound of the traversal stack
     return MI355PT_OK;
+}
+
+// ---------------- a camera translation on a built scene (scene_rebase.cpp) ----------------
+
+void mesh_local_bounds(const SceneImpl& scene, std::vector<MeshBounds>* out) {
+    out->resize(scene.meshes.size());
+    for (size_t i = 0; i < scene.meshes.size(); ++i) mesh_aabb(scene.meshes[i], (*out)[i].lo, (*out)[i].hi);
+}
+
+// lower_geometry's loop without its per-triangle work: the same functions in the same order on the same inputs
+int lower_camera_records(const SceneImpl& scene, const mi355pt_camera* cam, const std::vector<MeshBounds>& bounds, const std::vector<DevLight>& built_lights,
+                         const std::vector<DevLightTri>& built_light_tris, CameraRecords* out, std::string* err) {
+    const float w2r[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, -cam->position[0], -cam->position[1], -cam->position[2], 1};
+    LoweredGeometry g;                                                         // the light list and the slots lower_delta_light fills
+    g.env_light_index.assign(scene.envs.size(), 0u);
+    g.env_l2r.resize(scene.envs.size());
+    *out = CameraRecords{};
+    out->instances.resize(scene.instances.size());
+    out->light_tris = built_light_tris;                                        // cdf and pad stay; vertices and normal follow the camera
+    bool all_shared = true, have_shared = false;
+    float sb_lo[3] = {INFINITY, INFINITY, INFINITY}, sb_hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    const std::vector<HostDeltaLight>& delta = scene.delta_lights;
+    size_t next_delta = 0, lt = 0;
+    for (size_t ii = 0; ii < scene.instances.size(); ++ii) {
+        while (next_delta < delta.size() && delta[next_delta].after_instances <= ii) lower_delta_light(delta[next_delta++], w2r, &g);
+        const HostInstance& inst = scene.instances[ii];
+        const HostMesh& mesh = scene.meshes[inst.geom];
+        float l2r[16];
+        mat4_mul(w2r, inst.l2w, l2r);
+        grow_scene_bounds(bounds[inst.geom].lo, bounds[inst.geom].hi, l2r, sb_lo, sb_hi);
+        DevInstance& di = out->instances[ii];
+        if (!lower_transform(l2r, scene.lowering, &di)) { *err = "singular instance transform"; return MI355PT_E_INVALID; }
+        if (!di.identity) all_shared = false;
+        else if (!have_shared) { have_shared = true; std::memcpy(out->shared_iw, di.inv + 9, 12); std::memcpy(out->shared_mw, di.m + 9, 12); }
+        else if (std::memcmp(out->shared_iw, di.inv + 9, 12) != 0 || std::memcmp(out->shared_mw, di.m + 9, 12) != 0) all_shared = false;
+        if (scene.materials[inst.mat].type != MT_EMISSIVE) continue;
+        // an area light's record holds world-space areas only (area_light_tables): it is the built one
+        if (g.lights.size() >= built_lights.size() || lt + mesh.n_tri > out->light_tris.size()) { *err = "internal error: light list changed since the build"; return MI355PT_E_INVALID; }
+        g.lights.push_back(built_lights[g.lights.size()]);
+        for (uint32_t t = 0; t < mesh.n_tri; ++t, ++lt) {
+            V3 p[3];
+            for (int k = 0; k < 3; ++k) p[k] = xform_point(l2r, vertex(mesh, mesh.idx[3 * t + k]));
+            DevLightTri& r = out->light_tris[lt];
+            set_vertices(r, p[0], p[1], p[2]);
+            const V3 n = normalize(normalize(cross(p[1] - p[0], p[2] - p[0])));
+            r.n[0] = n.x; r.n[1] = n.y; r.n[2] = n.z;
+        }
+    }
+    while (next_delta < delta.size()) lower_delta_light(delta[next_delta++], w2r, &g);
+    if (g.lights.size() != built_lights.size() || lt != out->light_tris.size()) { *err = "internal error: light list changed since the build"; return MI355PT_E_INVALID; }
+    set_directional_areas(sb_lo, sb_hi, &g.lights);
+    out->lights = std::move(g.lights);
+    out->tris_are_local = all_shared && have_shared && scene.lowering < 1;
+    return MI355PT_OK;
+}
+
+bool render_triangle_degenerate(const SceneImpl& scene, const DevInstance& di, uint32_t instance, uint32_t tri) {
+    const HostMesh& mesh = scene.meshes[scene.instances[instance].geom];
+    const float l2r[16] = {di.m[0], di.m[1], di.m[2], 0, di.m[3], di.m[4], di.m[5], 0, di.m[6], di.m[7], di.m[8], 0, di.m[9], di.m[10], di.m[11], 1};
+    V3 p[3];
+    for (int k = 0; k < 3; ++k) p[k] = xform_point(l2r, vertex(mesh, mesh.idx[3 * tri + k]));
+    return degenerate(p[0], p[1], p[2]);
 }
 
 int lower_scene(const SceneImpl& scene, LoweredGeometry&& g, BvhOut&& bvh, const float* cmf4, LoweredScene* ls, LowerReport* rep, std::string* err) {

@@ -72,6 +72,24 @@ int lower_geometry(const SceneImpl& scene, const mi355pt_camera* cam, LoweredGeo
 // Stage B.  Consumes the geometry and the tree (their arrays move into *out); cmf4: [470][4].
 int lower_scene(const SceneImpl& scene, LoweredGeometry&& geo, BvhOut&& bvh, const float* cmf4, LoweredScene* out, LowerReport* rep, std::string* err);
 int lower_tree4(LoweredScene* ls, LowerReport* rep, std::string* err);   // ls->nodes -> ls->nodes4 (+ root4, n_nodes4, the Q16 grid)
+float nodes4_pad_radius(const std::vector<DevNode4>& nodes4);   // r of the pad lower_tree4 applies (PT_NODE_FMA): largest |coordinate| over the used slots, BEFORE the pad
+
+// What a camera TRANSLATION changes besides the triangles' positions and the boxes of the two trees (mi355pt_scene_move_camera,
+// scene_rebase.cpp): lower_geometry's own functions on the instance matrices, the delta lights, the scene bounds (from the meshes' local
+// boxes, which the caller caches: mesh_local_bounds) and the emissive triangles.  `built_lights` / `built_light_tris`: the records of the
+// build — an area light's record and a light triangle's cdf hold world-space areas and stay.
+void mesh_local_bounds(const SceneImpl& scene, std::vector<MeshBounds>* out);
+struct CameraRecords {
+    std::vector<DevInstance> instances;
+    std::vector<DevLight> lights;
+    std::vector<DevLightTri> light_tris;
+    bool tris_are_local = false;
+    float shared_iw[3] = {0, 0, 0}, shared_mw[3] = {0, 0, 0};
+};
+int lower_camera_records(const SceneImpl& scene, const mi355pt_camera* cam, const std::vector<MeshBounds>& bounds, const std::vector<DevLight>& built_lights,
+                         const std::vector<DevLightTri>& built_light_tris, CameraRecords* out, std::string* err);
+// degenerate() on the render-space vertices of triangle `tri` of instance `instance`, whose lowered record is `di`
+bool render_triangle_degenerate(const SceneImpl& scene, const DevInstance& di, uint32_t instance, uint32_t tri);
 
 // scene_info's text; ms = {bvh_ms, bvh_device_ms, collapse_ms} or null to leave the three timings out (what the digests are recorded with)
 std::string lowering_info(const LoweredScene& ls, const LowerReport& rep, bool gpu_builder, const double* ms);

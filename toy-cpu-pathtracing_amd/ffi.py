@@ -194,6 +194,18 @@ class RobustParams(C.Structure):
 ROBUST_MODE = {"mean": 0, "mom": 1, "gmon": 2}                                   # MI355PT_ROBUST_*
 
 
+class MoveResult(C.Structure):
+    """mi355pt_move_result (include/mi355pt_rebase.h)"""
+    _fields_ = [("rebuilt", C.c_uint32), ("reason", C.c_uint32), ("launches", C.c_uint32), ("host_ms", C.c_double), ("device_ms", C.c_double)]
+
+    def as_dict(self):
+        return {"rebuilt": int(self.rebuilt), "reason": MOVE_REASON[self.reason], "launches": int(self.launches), "host_ms": float(self.host_ms),
+                "device_ms": float(self.device_ms)}
+
+
+MOVE_REASON = ["rebased", "same_position", "degenerate_set_changed", "instance_class_changed", "unsupported_build"]   # MI355PT_MOVE_*
+
+
 def make_camera(position, direction, up, width, height, fov_deg=45.0):
     return Camera((C.c_float * 3)(*position), (C.c_float * 3)(*direction), (C.c_float * 3)(*up), fov_deg, width, height)
 
@@ -209,7 +221,7 @@ def _ptr(a, ty):
 
 
 # every symbol include/mi355pt.h declares (tests/test_abi.py checks the built library exports all of them) ...
-DEBUG_SYMBOLS = ["debug_unlock", "scene_debug_set_lowering", "scene_debug_lowering_digest", "scene_debug_camera_candidates", "scene_export_bvh", "probe_bvh_collapse", "probe_bvh_collapse_nodes", "probe_sobol", "probe_sincos", "probe_intersect", "probe_occluded",
+DEBUG_SYMBOLS = ["debug_unlock", "scene_debug_set_lowering", "scene_debug_lowering_digest", "scene_debug_camera_candidates", "scene_debug_move_digest", "scene_debug_move_export", "scene_debug_device_digest", "scene_export_bvh", "probe_bvh_collapse", "probe_bvh_collapse_nodes", "probe_sobol", "probe_sincos", "probe_intersect", "probe_occluded",
                  "sample_log_records", "render_sample_log", "probe_radiance", "probe_display_meter_ms"]     # ... and include/mi355pt_debug.h
 ABI_SYMBOLS = [
     "scene_create", "scene_destroy", "scene_set_rgb2spec", "scene_add_lut470", "scene_add_tex_rgb8", "scene_add_mesh",
@@ -237,6 +249,8 @@ UPSAMPLE_SYMBOLS = ["upsample_params_default", "upsample_low_camera", "upsample_
 DISPLAY_SYMBOLS = ["display_params_default", "display_scratch_bytes", "display_meter_device", "display_device", "display_meter", "display"]
 # ... and include/mi355pt_robust.h, the robust-film block (tests/test_robust.py)
 ROBUST_SYMBOLS = ["robust_params_default", "robust_combine_device", "robust_combine", "render_buckets_device", "render_robust"]
+# ... and include/mi355pt_rebase.h, the camera-move block (tests/test_rebase.py)
+REBASE_SYMBOLS = ["scene_move_camera"]
 ADAPTIVE_SYMBOLS = ["adaptive_scratch_bytes", "adaptive_step_device", "film_normalize_tiles_device", "render_adaptive_device", "render_adaptive"]
 
 
@@ -428,6 +442,51 @@ class SceneHandle:
 
     def build(self, cam):
         self.b.check(self.b.fn("scene_build")(self.h, C.byref(cam)), "scene_build")
+
+    def move_camera(self, cam):
+        """mi355pt_scene_move_camera (include/mi355pt_rebase.h, product only): the built scene re-based to cam's position on the device ->
+        {"rebuilt", "reason" (a MOVE_REASON name), "launches", "host_ms", "device_ms"}"""
+        fn = self.b.fn("scene_move_camera")
+        fn.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(MoveResult)]
+        res = MoveResult()
+        self.b.check(fn(self.h, C.byref(cam), C.byref(res)), "scene_move_camera")
+        return res.as_dict()
+
+    def _digests(self, call, what):
+        text = C.create_string_buffer(4096); dig = (C.c_uint64 * 128)(); n = C.c_uint32(128)
+        self.b.check(call(text, 4096, dig, C.byref(n)), what)
+        *names, info = text.value.decode().split("\n")
+        assert len(names) == n.value
+        return {nm: f"{dig[i]:016x}" for i, nm in enumerate(names)}, info
+
+    def debug_move_digest(self, cam_built, cam_new):
+        """mi355pt_scene_debug_move_digest (host only, product only): debug_lowering_digest's pair for the scene lowered for cam_new over the
+        tree of cam_built, and the MOVE_REASON name a move from cam_built to cam_new would report"""
+        fn = self.b.fn("scene_debug_move_digest")
+        fn.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Camera), C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        reason = C.c_uint32(0)
+        got, info = self._digests(lambda *a: fn(self.h, C.byref(cam_built), C.byref(cam_new), *a, C.byref(reason)), "scene_debug_move_digest")
+        return got, info, MOVE_REASON[reason.value]
+
+    def debug_move_export(self, cam_built, cam_new):
+        """mi355pt_scene_debug_move_export (host only, product only): the tree of debug_move_digest's lowering as Product.export_bvh gives a
+        built one — nodes (n, 16) uint32, triangle records (m, 12) uint32, root — and the pad's two radii (from the root record, by the
+        lowering's own loop)"""
+        fn = self.b.fn("scene_debug_move_export")
+        fn.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Camera), C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint32),
+                       C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+        nn, nt, root = C.c_uint32(0), C.c_uint32(0), C.c_int32(0)
+        self.b.check(fn(self.h, C.byref(cam_built), C.byref(cam_new), None, C.byref(nn), None, C.byref(nt), None, None), "scene_debug_move_export")
+        nodes = np.zeros((nn.value, 16), np.uint32); tris = np.zeros((nt.value, 12), np.uint32); radii = (C.c_float * 2)()
+        self.b.check(fn(self.h, C.byref(cam_built), C.byref(cam_new), nodes.ctypes.data_as(C.c_void_p), C.byref(nn), tris.ctypes.data_as(C.c_void_p),
+                        C.byref(nt), C.byref(root), radii), "scene_debug_move_export")
+        return nodes, tris, int(root.value), (np.float32(radii[0]), np.float32(radii[1]))
+
+    def debug_device_digest(self):
+        """mi355pt_scene_debug_device_digest (product only): the same pair hashed from what the device holds"""
+        fn = self.b.fn("scene_debug_device_digest")
+        fn.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+        return self._digests(lambda *a: fn(self.h, *a), "scene_debug_device_digest")
 
     # ---- probes ----
     def probe_intersect(self, origins, dirs):

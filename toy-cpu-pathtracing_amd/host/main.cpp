@@ -31,6 +31,7 @@ struct Args {   // main.rs:20-53
     bool fused_guides = false;
     // nor temporal accumulation (mi355pt_temporal.h): N frames, frame k with seed + k from position + k * step, each reprojected into the next
     bool temporal = false; uint32_t temporal_frames = 0; bool camera_step_given = false; float camera_step[3] = {0.0f, 0.0f, 0.0f};
+    bool camera_move_given = false; std::string camera_move = "rebuild";   // --camera-move rebuild|rebase: how the frames of --temporal-frames follow --camera-step
     // and its rectified form (mi355pt_temporal_rectify.h): the history is first scaled to the current frame's local mean; radius and gamma not given = its defaults
     bool temporal_rectify = false, temporal_rectify_radius_given = false, temporal_rectify_gamma_given = false;
     uint32_t temporal_rectify_radius = 0; float temporal_rectify_gamma = 0.0f;
@@ -285,8 +286,16 @@ static double render_gbuffer_float(const Scene& scene, const Camera& camera, mi3
     return st.kernel_ms * 1e-3;
 }
 
+// --camera-move: the scene of the --temporal-frames loops at the next frame's camera position.  rebuild (the default): mi355pt_scene_build
+// again.  rebase: mi355pt_scene_move_camera — the built scene re-based and refit on the device — and one line per frame on stderr
+static void follow_camera(Scene& scene, const Camera& moved, const Args& a, uint32_t frame) {
+    if (a.camera_move != "rebase") { scene.build(moved); return; }
+    const mi355pt_move_result r = scene.move_camera(moved);
+    std::fprintf(stderr, "camera move, frame %u: rebuilt=%u host_ms=%.3f device_ms=%.3f\n", frame, r.rebuilt, r.host_ms, r.device_ms);
+}
+
 // --temporal-frames N [--camera-step dx,dy,dz]: N frames of --spp samples, frame k with seed + k and the camera at position + k * step (the
-// scene is built again when the position changes: mi355pt_scene_build bakes it in).  Per frame one G-buffer launch at --denoise-guide-spp
+// scene follows as --camera-move says: built again, mi355pt_scene_build bakes the position in, or re-based on the device).  Per frame one G-buffer launch at --denoise-guide-spp
 // (shading normal, position, hit — and albedo when --denoise-variance follows), the beauty film (and the half film with --denoise-variance),
 // then mi355pt_temporal_accumulate_device (with --temporal-rectify: mi355pt_temporal_accumulate_rectified_device, radius and gamma from
 // --temporal-rectify-radius / --temporal-rectify-gamma or the defaults) against the previous frame's accumulated films.  After the last frame optionally the
@@ -320,7 +329,7 @@ static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params
         if (k > 0 && moving) {
             Camera moved(base.fov_deg, base.width, base.height);
             moved.set_look_to({cam.position[0], cam.position[1], cam.position[2]}, {cam.direction[0], cam.direction[1], cam.direction[2]}, {cam.up[0], cam.up[1], cam.up[2]});
-            scene.build(moved);
+            follow_camera(scene, moved, a, k);
         }
         p.seed = a.seed + k;
         bool ok = hipMemset(normal[c], 0, film_bytes) == hipSuccess && hipMemset(position[c], 0, film_bytes) == hipSuccess && hipMemset(hit[c], 0, film_bytes) == hipSuccess &&
@@ -412,7 +421,7 @@ static double render_half_res(Scene& scene, const Camera& camera, mi355pt_params
         if (k > 0 && moving) {
             Camera moved(base.fov_deg, base.width, base.height);
             moved.set_look_to({cam.position[0], cam.position[1], cam.position[2]}, {cam.direction[0], cam.direction[1], cam.direction[2]}, {cam.up[0], cam.up[1], cam.up[2]});
-            scene.build(moved);
+            follow_camera(scene, moved, a, k);
         }
         check(mi355pt_upsample_low_camera(&cam, &low_cam), "mi355pt_upsample_low_camera");
         p.seed = a.seed + k;
@@ -488,6 +497,8 @@ static void usage() {
               "                   [--temporal-frames N] (pt|nee|mis: N frames of --spp samples, frame k with seed + k, each reprojected into the next through its\n"
               "                                          G-buffer at --denoise-guide-spp and accumulated; writes the last; --denoise-variance filters the accumulated pair)\n"
               "                   [--camera-step dx,dy,dz] (with --temporal-frames: frame k renders from position + k * step)\n"
+              "                   [--camera-move rebuild|rebase] (with --temporal-frames: between frames the scene is built again (the default) or the built\n"
+              "                                 scene follows the camera on the device, mi355pt_scene_move_camera; one line per frame on stderr)\n"
               "                   [--temporal-rectify] (with --temporal-frames: the gathered history is first scaled so that its local mean agrees with the\n"
               "                                         current frame's: the accumulation follows a change of illumination)\n"
               "                   [--temporal-rectify-radius R] (2; 1 .. 3: the window is (2R + 1)^2 pixels)  [--temporal-rectify-gamma G] (2; > 0: standard errors allowed)\n"
@@ -566,6 +577,7 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        else if (k == "--camera-move") { a.camera_move_given = true; a.camera_move = val(); }
         else if (k == "-h" || k == "--help") { usage(); return 0; }
         else { std::fprintf(stderr, "error: unexpected argument '%s'\n", k.c_str()); usage(); return 2; }
     }
@@ -636,6 +648,8 @@ int main(int argc, char** argv) {
     if (a.half_res && a.adaptive_threshold != 0.0f) { std::fprintf(stderr, "error: --half-res with --adaptive-threshold: half-resolution rendering takes one sample count per frame\n"); return 2; }
     if (a.half_res && (a.spp == 0 || a.denoise_guide_spp == 0)) { std::fprintf(stderr, "error: --half-res needs --spp and --denoise-guide-spp above 0\n"); return 2; }
     if (a.camera_step_given && !a.temporal) { std::fprintf(stderr, "error: --camera-step needs --temporal-frames: it moves the camera between the frames\n"); return 2; }
+    if (a.camera_move != "rebuild" && a.camera_move != "rebase") { std::fprintf(stderr, "error: invalid value '%s' for '--camera-move' (rebuild or rebase)\n", a.camera_move.c_str()); return 2; }
+    if (a.camera_move_given && !a.temporal) { std::fprintf(stderr, "error: --camera-move needs --temporal-frames: it says how the scene follows the camera between the frames\n"); return 2; }
     if (a.temporal && a.temporal_frames == 0) { std::fprintf(stderr, "error: --temporal-frames must be above 0\n"); return 2; }
     if (a.temporal && aov) { std::fprintf(stderr, "error: --temporal-frames with --renderer %s: temporal accumulation is for the path renderers (pt, nee, mis)\n", a.renderer.c_str()); return 2; }
     if (a.temporal && a.gpus > 1) { std::fprintf(stderr, "error: --temporal-frames with --gpus %d: temporal accumulation runs on one GPU\n", a.gpus); return 2; }

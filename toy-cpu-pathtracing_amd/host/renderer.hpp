@@ -697,6 +697,13 @@ public:
         d65_lut_ = lower_spectrum(presets::cie_illum_d6500()).id;
         check(mi355pt_scene_build(s_, &cam.raw()), "mi355pt_scene_build");
     }
+    // EXTENSION (include/mi355pt_rebase.h): the built scene follows a camera TRANSLATION on the device — vertices re-based, both trees
+    // refit — instead of being built again; falls back to the full build where that would not give a fresh lowering's records
+    mi355pt_move_result move_camera(const Camera& cam) {
+        mi355pt_move_result r{};
+        check(mi355pt_scene_move_camera(s_, &cam.raw(), &r), "mi355pt_scene_move_camera");
+        return r;
+    }
     // Scene::build over the first `n_devices` GPUs of the node (mi355pt_scene_build_multi): RendererImage::render then shards the frame
     void build_multi(const Camera& cam, int n_devices) {
         std::vector<int> ids((size_t)n_devices);
