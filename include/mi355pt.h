@@ -363,6 +363,15 @@ const char* mi355pt_version(void);
  * which this one always includes (ahead of the variance-guided denoiser's, which stays the last one). */
 #include "mi355pt_rebase.h"
 
+/* ---------------- instance moves on a built scene ---------------- */
+/* EXTENSION, no reference counterpart: mi355pt_scene_set_instance_dynamic, mi355pt_instance_move_params, mi355pt_instance_move_result and
+ * mi355pt_scene_move_instances — new local_to_world matrices for instances of the built scene, applied on the device: positions
+ * re-transformed, the moved instances' shading normals and light pdfs refreshed, both trees refit, moved area lights' tables recomputed, and
+ * the SAH cost of the refit tree reported so that the caller knows when to build again.  Refit only; the temporal accumulation assumes a
+ * static world and has no object motion vectors.  Declared in its own header, which this one always includes (ahead of the
+ * variance-guided denoiser's, which stays the last one). */
+#include "mi355pt_instances.h"
+
 /* ---------------- variance-guided denoiser ---------------- */
 /* EXTENSION, no reference counterpart: a second filter beside the one above, which it leaves as it is — mi355pt_denoise_var_params,
  * mi355pt_denoise_var_params_default, mi355pt_denoise_var_scratch_bytes, mi355pt_denoise_var_device and mi355pt_denoise_var: an a-trous

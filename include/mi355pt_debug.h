@@ -60,6 +60,28 @@ int mi355pt_scene_debug_move_export(const mi355pt_scene* s, const mi355pt_camera
  * fields.  Needs the scene's device current. */
 int mi355pt_scene_debug_device_digest(const mi355pt_scene* s, char* names_buf, size_t names_len, uint64_t* digests, uint32_t* n);
 
+/* mi355pt_scene_move_instances (include/mi355pt_instances.h) on the host: the digests, in mi355pt_scene_debug_lowering_digest's format and
+ * order, of the host lowering of the BUILT scene's CURRENT description (the matrices the moves left) for `cam`, over the topology the built
+ * scene holds — the build keeps both trees on the host, whichever builder made them — with every box refit from the new triangles by the
+ * functions the kernels call.  No device, the scene left as it is.  At unchanged transforms and the built camera the digests are
+ * mi355pt_scene_debug_lowering_digest's under the host builder.  MI355PT_E_NOT_BUILT for an unbuilt scene; MI355PT_E_INVALID when the
+ * description no longer lowers over that tree (another degenerate set, another instance class): only a rebuild serves it. */
+int mi355pt_scene_debug_pinned_digest(const mi355pt_scene* s, const mi355pt_camera* cam, char* names_buf, size_t names_len, uint64_t* digests, uint32_t* n);
+/* The BVH2 of that pinned lowering in mi355pt_scene_export_bvh's layout and calling convention (NULL buffers for the counts), host only, and
+ * (n_entries NULL: not wanted) the refit plan's (node << 1 | side) entries in the order the SAH cost sums their terms. */
+int mi355pt_scene_debug_pinned_export(const mi355pt_scene* s, const mi355pt_camera* cam, void* out_nodes, uint32_t* n_nodes, void* out_tris, uint32_t* n_tris,
+                                      int32_t* root, uint32_t* out_entries, uint32_t* n_entries);
+/* The two calls above without a device: mi355pt_scene_debug_pin_host_tree lowers an UNBUILT scene for `cam` with the host builder and keeps
+ * what a build keeps on the host (both trees, the instance classes, the left-out triangles, the light records) — no device array exists and
+ * the scene stays unbuilt for every other call; mi355pt_scene_debug_set_instance_transform then replaces a local_to_world matrix (column-major
+ * 4x4) of the description of such a scene, as mi355pt_scene_move_instances does on a built one, without any check of the matrix.  Both
+ * refuse a built scene with MI355PT_E_INVALID. */
+int mi355pt_scene_debug_pin_host_tree(mi355pt_scene* s, const mi355pt_camera* cam);
+int mi355pt_scene_debug_set_instance_transform(mi355pt_scene* s, uint32_t instance, const float* local_to_world);
+/* The host form of the SAH cost mi355pt_scene_move_instances reports (csrc/instance_move_plan.hpp sah_cost_host): node records as
+ * mi355pt_scene_export_bvh gives them, the entries of mi355pt_scene_debug_pinned_export.  No device. */
+int mi355pt_debug_sah_cost(const void* nodes, uint32_t n_nodes, int32_t root, const uint32_t* entries, uint32_t n_entries, float* out_cost);
+
 /* ---------------- probes (parity tests; same device code as the render path) ---------------- */
 /* The built acceleration structure as the device holds it (no reference counterpart; the reference's is scene/src/bvh.rs:300-343):
  * node records of 64 B {bx[4] = lo0.x lo1.x hi0.x hi1.x, by[4], bz[4], int32 child[2] (>= 0 node index, < 0 leaf:

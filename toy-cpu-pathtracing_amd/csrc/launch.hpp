@@ -140,6 +140,16 @@ hipError_t launch_rebase_tris(const DevTriLocal* d_local, const DevInstance* d_i
                               uint32_t* d_degenerate_count, hipStream_t);
 hipError_t launch_refit_bvh2_height(DevNode* d_nodes, const DevTri* d_tris_render, const uint32_t* d_entries, uint32_t first, uint32_t count, hipStream_t);
 hipError_t launch_refit_nodes4(DevNode4* d_nodes4, const DevNode* d_nodes, const uint32_t* d_slot_src, uint32_t n_slots, int32_t root, hipStream_t);
+// pt_kernels_instances.hip: an instance move on a built scene (include/mi355pt_instances.h, scene_instances.cpp).  launch_shade_refresh: ng
+// and light_pdf_area of the leaf-order shading records whose instance has its bit set in d_moved_bits ((n_instances + 31) / 32 words);
+// d_light_pdf: light_pdf_area per light triangle, indexed DevLight::first_tri + local_tri.  launch_sah_cost: TWO launches, the block sums of
+// the terms of all n_entries plan entries and the one-block finish; d_scratch holds sah_scratch_floats(n_entries) floats and receives
+// {cost, sum of the terms, half area of the root} in its first three
+hipError_t launch_shade_refresh(DevTriShade* d_shade, const DevTriLocal* d_local, const DevInstance* d_instances, const uint32_t* d_moved_bits, const DevLight* d_lights,
+                                const float* d_light_pdf, uint32_t n_tris, uint32_t n_instances, uint32_t n_lights, uint32_t n_light_pdf, hipStream_t);
+size_t sah_scratch_floats(uint32_t n_entries);
+hipError_t launch_sah_cost(const DevNode* d_nodes, int32_t root, const uint32_t* d_entries, uint32_t n_entries, float* d_scratch, hipStream_t);
+constexpr uint32_t SAH_COST_LAUNCHES = 2;
 
 // Resident 64-thread blocks (= waves) of `kernel` on the current device: the persistent grid size of the EXACT instantiation a launch takes
 // (the register count, and so the occupancy, differs between instantiations and between translation units with their own backend flags).

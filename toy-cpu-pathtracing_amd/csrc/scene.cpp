@@ -107,17 +107,8 @@ int SceneImpl::build(const mi355pt_camera* cam, const float* cmf4 /*470*4*/, std
     }
     if (bvh.max_depth >= STACK_DEPTH) { *err = "BVH deeper than the traversal stack"; return MI355PT_E_INVALID; }
 
-    RebaseState rb;                                 // what a later camera move needs of the build's intermediate results
-    rb.gpu_built = gpu_built;
-    std::memcpy(rb.tree_cam_pos, cam->position, sizeof(rb.tree_cam_pos));
-    if (gpu_built) { rb.gpu_nodes = bvh.nodes; rb.gpu_order = bvh.order; rb.gpu_depth = bvh.max_depth; rb.gpu_root = bvh.root; }
-    if (!geo.tris_are_local) {
-        size_t k = 0;
-        for (size_t t = 0; t < geo.tris.size(); ++t) {
-            if (k < geo.kept.size() && geo.kept[k] == t) { ++k; continue; }
-            rb.left_out.push_back(geo.shade[t].instance); rb.left_out.push_back(geo.shade[t].local_tri);
-        }
-    }
+    RebaseState rb;                                 // what a later move (of the camera, of instances) needs of the build's intermediate results
+    keep_topology(geo, bvh, cam, gpu_built, &rb);
 
     LoweredScene ls;
     LowerReport rep;

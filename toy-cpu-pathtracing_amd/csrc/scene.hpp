@@ -16,7 +16,7 @@ struct HostMesh {
     std::vector<uint32_t> idx;
     uint32_t n_vert = 0, n_tri = 0;
 };
-struct HostInstance { uint32_t geom, mat; float l2w[16]; };
+struct HostInstance { uint32_t geom, mat; float l2w[16]; uint32_t dynamic = 0; };   // dynamic: mi355pt_scene_set_instance_dynamic (include/mi355pt_instances.h)
 struct HostDeltaLight { mi355pt_light_desc d; uint32_t material; uint32_t after_instances; uint32_t env_index = 0; };   // hidden emissive material holds the spectrum
 
 struct BuildTri { float lo[3], hi[3], c[3]; };
@@ -47,6 +47,7 @@ struct MeshBounds { float lo[3], hi[3]; };   // a mesh's local AABB (scene_lower
 // the upload takes and the digests hash stays what it was.
 struct RebaseState {
     bool ready = false;                       // false: a move builds again (MI355PT_MOVE_UNSUPPORTED_BUILD)
+    bool pinned = false;                      // the host side tables below are there (a build, or mi355pt_scene_debug_pin_host_tree without a device)
     bool gpu_built = false;
     std::vector<uint32_t> height_offset;      // rebase_plan.hpp RebasePlan::height_offset
     uint32_t n_slots = 0;                     // 4 * n_nodes4
@@ -59,9 +60,19 @@ struct RebaseState {
     std::vector<MeshBounds> bounds;           // per mesh
     std::vector<DevLight> lights;             // the build's records: an area light's and a light triangle's cdf do not depend on the camera
     std::vector<DevLightTri> light_tris;
-    std::vector<DevNode> gpu_nodes;           // a GPU-built tree as it came back (the host builder's can be built again): what
-    std::vector<uint32_t> gpu_order;          // mi355pt_scene_debug_move_digest pins the topology to, without a device
-    int gpu_depth = 0; int32_t gpu_root = 0;
+    std::vector<DevNode> tree_nodes;          // the built tree as its builder returned it, either builder's (after an instance move the host
+    std::vector<uint32_t> tree_order;         // builder would no longer reproduce it from the description): what the pinned lowerings
+    int tree_depth = 0; int32_t tree_root = 0;   // (mi355pt_scene_debug_move_digest for a GPU-built tree, mi355pt_scene_debug_pinned_digest) pin the topology to
+    std::vector<DevNode4> tree_nodes4;        // ... and its 4-wide collapse (links and used slots; the boxes follow a refit)
+    int32_t tree_root4 = 0;
+    std::vector<uint32_t> kept;               // build index -> triangle of the build, when it left triangles out (else the identity, not stored)
+    // mi355pt_scene_move_instances (scene_instances.cpp): allocated / computed by the first move after a build (all in SceneImpl::allocs)
+    uint32_t n_entries = 0;                   // RebasePlan::entries.size()
+    float* d_sah = nullptr;                   // launch_sah_cost's scratch
+    uint32_t* d_moved_bits = nullptr;         // one bit per instance
+    float* d_light_pdf = nullptr;             // light_pdf_area per light triangle
+    bool sah_built_valid = false;
+    float sah_built = 0.0f;
     float tree_cam_pos[3] = {0, 0, 0};        // the camera position the tree was BUILT for (build_cam_pos follows the moves)
     size_t n_degenerate = 0; int bvh_depth = 0, stack_need = 0; std::string collapse_method;   // the build's LowerReport (mi355pt_scene_debug_device_digest)
 };
@@ -98,7 +109,8 @@ struct SceneImpl {
     // release(), the device query, lower_geometry, the tree build (host or GPU), lower_scene + lower_tree4, upload, the info string
     int build(const mi355pt_camera* cam, const float* cmf4 /*470*4*/, std::string* err);
     int upload(const LoweredScene& ls, std::string* err);   // the one place that allocates device memory and copies to it
-    int prepare_rebase(const LoweredScene& ls, const LowerReport& rep, std::string* err);   // scene_rebase.cpp: the side tables of a built scene, after upload()
+    // scene_rebase.cpp: the side tables of a built scene, after upload(); on_device = false: the host tables only (rebase.pinned, not .ready)
+    int prepare_rebase(const LoweredScene& ls, const LowerReport& rep, std::string* err, bool on_device = true);
 };
 
 // mi355pt_coat_albedo_table (scene_lower.cpp): E(cos theta_o) of the clearcoat's directional-albedo estimator, 64 entries

@@ -8,6 +8,8 @@
 #include <cstdio>
 #include <cstring>
 
+#include "instance_move_plan.hpp"
+
 namespace pt {
 
 namespace {
@@ -141,7 +143,7 @@ void grow_scene_bounds(const float lo[3], const float hi[3], const float* l2r, f
 }
 
 // The instance's two matrices and whether both are a pure translation
-bool lower_transform(const float* l2r, int lowering, DevInstance* di) {
+bool lower_transform(const float* l2r, int lowering, bool dynamic, DevInstance* di) {
     double a[9], inv3[9];
     if (mat3_inverse(l2r, a, inv3) == 0.0) return false;
     float inv[16];
@@ -153,6 +155,7 @@ bool lower_transform(const float* l2r, int lowering, DevInstance* di) {
     di->identity = 1u;
     for (int k = 0; k < 9; ++k) { const float e = (k % 4 == 0) ? 1.0f : 0.0f; if (!(di->m[k] == e) || !(di->inv[k] == e)) di->identity = 0u; }
     if (lowering >= 2) di->identity = 0u;                                 // (mi355pt_scene_debug_set_lowering: every instance through the general matrix path)
+    if (dynamic) di->identity = 0u;                                       // (mi355pt_scene_set_instance_dynamic: this one through it, whatever it is moved to)
     di->pad[0] = di->pad[1] = di->pad[2] = 0;
     return true;
 }
@@ -211,11 +214,9 @@ void lower_triangles(const SceneImpl& scene, uint32_t ii, const float* l2r, cons
         DevTriShade sh{};
         {   // the hit's geometric normal is a function of the triangle alone: ray.rs:167-174 in LOCAL space, then Transform * Normal
             // (samples.rs:135, transform.rs:45-51: transpose(inverse) * n, renormalised) - computed here once with the arithmetic of the
-            // device code it replaces (xf_normal, pt_device.hpp; a translation leaves normalize(n))
-            V3 n = normalize(normalize(cross(pl[1] - pl[0], pl[2] - pl[0])));
-            if (!di.identity)
-                n = V3{(di.inv[0] * n.x + di.inv[1] * n.y) + di.inv[2] * n.z, (di.inv[3] * n.x + di.inv[4] * n.y) + di.inv[5] * n.z, (di.inv[6] * n.x + di.inv[7] * n.y) + di.inv[8] * n.z};
-            n = normalize(n);
+            // device code it replaces (xf_normal, pt_device.hpp; a translation leaves normalize(n)).  instance_move_plan.hpp holds the
+            // expression: an instance move recomputes it on the device (shade_refresh_kernel)
+            const IV3 n = shade_normal(IV3{pl[0].x, pl[0].y, pl[0].z}, IV3{pl[1].x, pl[1].y, pl[1].z}, IV3{pl[2].x, pl[2].y, pl[2].z}, di.inv, di.identity != 0u);
             sh.ng[0] = n.x; sh.ng[1] = n.y; sh.ng[2] = n.z; sh.pad_ng = 0;
         }
         const float* n0 = &mesh.nrm[3 * vi[0]]; const float* n1 = &mesh.nrm[3 * vi[1]]; const float* n2 = &mesh.nrm[3 * vi[2]];
@@ -233,8 +234,7 @@ void lower_triangles(const SceneImpl& scene, uint32_t ii, const float* l2r, cons
         sh.light_pdf_area = 0.0f;
         if (areas) {
             sh.flags |= 2u;
-            float probability = t == 0 ? areas->cdf[0] : areas->cdf[t] - areas->cdf[t - 1];
-            sh.light_pdf_area = 1.0f / areas->area[t] * probability;                       // :334-353
+            sh.light_pdf_area = light_pdf_area_of(areas->area, areas->cdf, t);            // :334-353
             DevLightTri lt{};
             set_vertices(lt, p[0], p[1], p[2]);                                  // sample_radiance transforms the ORIGINAL vertex order with local_to_render (:200-206)
             lt.cdf = areas->cdf[t];
@@ -580,7 +580,7 @@ int lower_geometry(const SceneImpl& scene, const mi355pt_camera* cam, LoweredGeo
         mat4_mul(w2r, inst.l2w, l2r);                                          // triangle_mesh.rs:38-40
         { float lo[3], hi[3]; mesh_aabb(mesh, lo, hi); grow_scene_bounds(lo, hi, l2r, sb_lo, sb_hi); }
         DevInstance& di = g->instances[ii];
-        if (!lower_transform(l2r, scene.lowering, &di)) { *err = "singular instance transform"; return MI355PT_E_INVALID; }
+        if (!lower_transform(l2r, scene.lowering, inst.dynamic != 0u, &di)) { *err = "singular instance transform"; return MI355PT_E_INVALID; }
         // do all instances share ONE pure translation?  (DevScene::tris_are_local)
         if (!di.identity) all_shared = false;
         else if (!have_shared) { have_shared = true; std::memcpy(g->shared_iw, di.inv + 9, 12); std::memcpy(g->shared_mw, di.m + 9, 12); }
@@ -615,7 +615,8 @@ void mesh_local_bounds(const SceneImpl& scene, std::vector<MeshBounds>* out) {
 
 // lower_geometry's loop without its per-triangle work: the same functions in the same order on the same inputs
 int lower_camera_records(const SceneImpl& scene, const mi355pt_camera* cam, const std::vector<MeshBounds>& bounds, const std::vector<DevLight>& built_lights,
-                         const std::vector<DevLightTri>& built_light_tris, CameraRecords* out, std::string* err) {
+                         const std::vector<DevLightTri>& built_light_tris, CameraRecords* out, std::string* err, const uint8_t* moved,
+                         std::vector<float>* light_pdf) {
     const float w2r[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, -cam->position[0], -cam->position[1], -cam->position[2], 1};
     LoweredGeometry g;                                                         // the light list and the slots lower_delta_light fills
     g.env_light_index.assign(scene.envs.size(), 0u);
@@ -627,6 +628,7 @@ int lower_camera_records(const SceneImpl& scene, const mi355pt_camera* cam, cons
     float sb_lo[3] = {INFINITY, INFINITY, INFINITY}, sb_hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     const std::vector<HostDeltaLight>& delta = scene.delta_lights;
     size_t next_delta = 0, lt = 0;
+    if (light_pdf) light_pdf->assign(built_light_tris.size(), 0.0f);
     for (size_t ii = 0; ii < scene.instances.size(); ++ii) {
         while (next_delta < delta.size() && delta[next_delta].after_instances <= ii) lower_delta_light(delta[next_delta++], w2r, &g);
         const HostInstance& inst = scene.instances[ii];
@@ -635,14 +637,22 @@ int lower_camera_records(const SceneImpl& scene, const mi355pt_camera* cam, cons
         mat4_mul(w2r, inst.l2w, l2r);
         grow_scene_bounds(bounds[inst.geom].lo, bounds[inst.geom].hi, l2r, sb_lo, sb_hi);
         DevInstance& di = out->instances[ii];
-        if (!lower_transform(l2r, scene.lowering, &di)) { *err = "singular instance transform"; return MI355PT_E_INVALID; }
+        if (!lower_transform(l2r, scene.lowering, inst.dynamic != 0u, &di)) { *err = "singular instance transform"; return MI355PT_E_INVALID; }
         if (!di.identity) all_shared = false;
         else if (!have_shared) { have_shared = true; std::memcpy(out->shared_iw, di.inv + 9, 12); std::memcpy(out->shared_mw, di.m + 9, 12); }
         else if (std::memcmp(out->shared_iw, di.inv + 9, 12) != 0 || std::memcmp(out->shared_mw, di.m + 9, 12) != 0) all_shared = false;
         if (scene.materials[inst.mat].type != MT_EMISSIVE) continue;
-        // an area light's record holds world-space areas only (area_light_tables): it is the built one
+        // an area light's record holds world-space areas only (area_light_tables): it is the built one, unless the instance moved
         if (g.lights.size() >= built_lights.size() || lt + mesh.n_tri > out->light_tris.size()) { *err = "internal error: light list changed since the build"; return MI355PT_E_INVALID; }
         g.lights.push_back(built_lights[g.lights.size()]);
+        if (moved && moved[ii]) {
+            const AreaTables areas = area_light_tables(mesh, inst.l2w);
+            g.lights.back().area_sum = areas.sum;
+            for (uint32_t t = 0; t < mesh.n_tri; ++t) {
+                out->light_tris[lt + t].cdf = areas.cdf[t];
+                if (light_pdf) (*light_pdf)[lt + t] = light_pdf_area_of(areas.area, areas.cdf, t);
+            }
+        }
         for (uint32_t t = 0; t < mesh.n_tri; ++t, ++lt) {
             V3 p[3];
             for (int k = 0; k < 3; ++k) p[k] = xform_point(l2r, vertex(mesh, mesh.idx[3 * t + k]));
@@ -656,11 +666,34 @@ int lower_camera_records(const SceneImpl& scene, const mi355pt_camera* cam, cons
     if (g.lights.size() != built_lights.size() || lt != out->light_tris.size()) { *err = "internal error: light list changed since the build"; return MI355PT_E_INVALID; }
     set_directional_areas(sb_lo, sb_hi, &g.lights);
     out->lights = std::move(g.lights);
-    out->tris_are_local = all_shared && have_shared && scene.lowering < 1;
+    out->tris_are_local = all_shared && have_shared && scene.lowering < 1;   // (a dynamic instance is never `shared`: its identity is 0)
     return MI355PT_OK;
 }
 
-bool render_triangle_degenerate(const SceneImpl& scene, const DevInstance& di, uint32_t instance, uint32_t tri) {
+void keep_topology(const LoweredGeometry& geo, const BvhOut& bvh, const mi355pt_camera* cam, bool gpu_built, RebaseState* rb) {
+    rb->gpu_built = gpu_built;
+    std::memcpy(rb->tree_cam_pos, cam->position, sizeof(rb->tree_cam_pos));
+    rb->tree_nodes = bvh.nodes; rb->tree_order = bvh.order; rb->tree_depth = bvh.max_depth; rb->tree_root = bvh.root;
+    if (geo.n_degenerate) rb->kept = geo.kept;
+    if (!geo.tris_are_local) {
+        size_t k = 0;
+        for (size_t t = 0; t < geo.tris.size(); ++t) {
+            if (k < geo.kept.size() && geo.kept[k] == t) { ++k; continue; }
+            rb->left_out.push_back(geo.shade[t].instance); rb->left_out.push_back(geo.shade[t].local_tri);
+        }
+    }
+}
+
+bool instance_transform_ok(const SceneImpl& scene, const mi355pt_camera* cam, const float* l2w) {
+    for (int k = 0; k < 16; ++k) if (!std::isfinite(l2w[k])) return false;
+    const float w2r[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, -cam->position[0], -cam->position[1], -cam->position[2], 1};
+    float l2r[16];
+    mat4_mul(w2r, l2w, l2r);
+    DevInstance di;
+    return lower_transform(l2r, scene.lowering, false, &di);
+}
+
+bool render_triangle_degenerate(const SceneImpl& scene,const DevInstance& di, uint32_t instance, uint32_t tri) {
     const HostMesh& mesh = scene.meshes[scene.instances[instance].geom];
     const float l2r[16] = {di.m[0], di.m[1], di.m[2], 0, di.m[3], di.m[4], di.m[5], 0, di.m[6], di.m[7], di.m[8], 0, di.m[9], di.m[10], di.m[11], 1};
     V3 p[3];

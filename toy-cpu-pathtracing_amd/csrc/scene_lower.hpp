@@ -87,7 +87,17 @@ struct CameraRecords {
     float shared_iw[3] = {0, 0, 0}, shared_mw[3] = {0, 0, 0};
 };
 int lower_camera_records(const SceneImpl& scene, const mi355pt_camera* cam, const std::vector<MeshBounds>& bounds, const std::vector<DevLight>& built_lights,
-                         const std::vector<DevLightTri>& built_light_tris, CameraRecords* out, std::string* err);
+                         const std::vector<DevLightTri>& built_light_tris, CameraRecords* out, std::string* err, const uint8_t* moved = nullptr,
+                         std::vector<float>* light_pdf = nullptr);
+// ... and what NEW local_to_world matrices change besides (mi355pt_scene_move_instances, scene_instances.cpp): `moved` (per instance, NULL =
+// none) marks the instances whose matrix differs from the one `built_lights` / `built_light_tris` were made for.  A moved emissive instance
+// gets its world-space area tables again (area_light_tables on the description's matrix): DevLight::area_sum, every DevLightTri::cdf, and in
+// *light_pdf (NULL ok; one float per light triangle, indexed DevLight::first_tri + triangle, 0 for unmoved lights) DevTriShade::light_pdf_area.
+// `lowering`'s test of a matrix (finite, not singular; the whole instance record) on its own: false = mi355pt_scene_build would refuse it
+bool instance_transform_ok(const SceneImpl& scene, const mi355pt_camera* cam, const float* l2w);
+// What a later move keeps of stage A and the tree build (RebaseState, scene.hpp): the tree as its builder returned it, the camera position it
+// was built for, the triangles it leaves out
+void keep_topology(const LoweredGeometry& geo, const BvhOut& bvh, const mi355pt_camera* cam, bool gpu_built, RebaseState* rb);
 // degenerate() on the render-space vertices of triangle `tri` of instance `instance`, whose lowered record is `di`
 bool render_triangle_degenerate(const SceneImpl& scene, const DevInstance& di, uint32_t instance, uint32_t tri);
 

@@ -10,6 +10,7 @@
 
 #include "../../include/mi355pt_debug.h"
 #include "api_internal.hpp"
+#include "instance_move_plan.hpp"
 #include "rebase_plan.hpp"
 #include "scene_lower.hpp"
 
@@ -64,8 +65,8 @@ int pinned_lowering(const mi355pt_scene* s, const mi355pt_camera* cam_built, con
     LoweredGeometry geo_b; BvhOut bvh_b; LoweredScene ls_b; LowerReport rep_b;
     if ((rc = lower_geometry(impl, cam_built, &geo_b, &err))) return fail(rc, err);
     const bool gpu_tree = impl.built && impl.rebase.gpu_built && std::memcmp(cam_built->position, impl.rebase.tree_cam_pos, sizeof(float) * 3) == 0 &&
-                          impl.rebase.gpu_order.size() == geo_b.build_tris.size();
-    if (gpu_tree) { bvh_b.nodes = impl.rebase.gpu_nodes; bvh_b.order = impl.rebase.gpu_order; bvh_b.root = impl.rebase.gpu_root; bvh_b.max_depth = impl.rebase.gpu_depth; }
+                          impl.rebase.tree_order.size() == geo_b.build_tris.size();
+    if (gpu_tree) { bvh_b.nodes = impl.rebase.tree_nodes; bvh_b.order = impl.rebase.tree_order; bvh_b.root = impl.rebase.tree_root; bvh_b.max_depth = impl.rebase.tree_depth; }
     else build_bvh(geo_b.build_tris, &bvh_b);
     if (bvh_b.max_depth >= STACK_DEPTH) return fail(MI355PT_E_INVALID, "BVH deeper than the traversal stack");
     const BvhOut topology = bvh_b;
@@ -117,27 +118,64 @@ int pinned_lowering(const mi355pt_scene* s, const mi355pt_camera* cam_built, con
 #endif
 }
 
+// mi355pt_scene_debug_pinned_digest's lowering: the CURRENT description for `cam` over the topology the built scene holds (the build keeps
+// both trees on the host), every box refit from the new triangles
+int pinned_current(const mi355pt_scene* s, const mi355pt_camera* cam, LoweredScene* ls, LowerReport* rep) {
+#if PT_NODE_Q16
+    return fail(MI355PT_E_INVALID, "a build with quantised 4-wide nodes does not re-base");
+#else
+    const SceneImpl& impl = s->impl;
+    const RebaseState& rb = impl.rebase;
+    if (!impl.built && !rb.pinned) return fail(MI355PT_E_NOT_BUILT, "scene not built");
+    if (!rb.pinned) return fail(MI355PT_E_INVALID, "the built tree has no refit plan");
+    std::string err;
+    int rc;
+    float cmf[470 * 4];
+    cie_cmf4(cmf);
+    LoweredGeometry geo;
+    if ((rc = lower_geometry(impl, cam, &geo, &err))) return fail(rc, err);
+    bool same = geo.kept.size() == rb.tree_order.size() && geo.n_degenerate == rb.n_degenerate && geo.tris_are_local == rb.tris_are_local &&
+                geo.instances.size() == rb.identity.size();
+    if (same && geo.n_degenerate) same = geo.kept == rb.kept;
+    for (size_t i = 0; same && i < rb.identity.size(); ++i) same = (geo.instances[i].identity != 0) == (rb.identity[i] != 0);
+    if (!same) return fail(MI355PT_E_INVALID, "the description no longer lowers over the built tree (degenerate set or instance class changed)");
+    RebasePlan plan;
+    if (!make_rebase_plan(rb.tree_nodes, rb.tree_root, rb.tree_nodes4, rb.tree_root4, rb.tree_order.size(), &plan)) return fail(MI355PT_E_INVALID, "internal error: no refit plan for the built tree");
+    BvhOut pinned;
+    pinned.nodes = rb.tree_nodes; pinned.order = rb.tree_order; pinned.root = rb.tree_root; pinned.max_depth = rb.tree_depth;
+    if ((rc = lower_scene(impl, std::move(geo), std::move(pinned), cmf, ls, rep, &err))) return fail(rc, err);
+    ls->nodes4 = rb.tree_nodes4;
+    ls->dev.root4 = rb.tree_root4; ls->dev.n_nodes4 = (uint32_t)rb.tree_nodes4.size();
+    rep->stack_need = rb.stack_need; rep->collapse_method = rb.collapse_method.c_str();
+    refit_host(plan, ls->dev.root, ls->tris_render.data(), &ls->nodes, &ls->nodes4);
+    return MI355PT_OK;
+#endif
+}
+
 }  // namespace
 
-int SceneImpl::prepare_rebase(const LoweredScene& ls, const LowerReport& rep, std::string* err) {
+int SceneImpl::prepare_rebase(const LoweredScene& ls, const LowerReport& rep, std::string* err, bool on_device) {
     RebaseState& rb = rebase;
-    rb.ready = false;
+    rb.ready = false; rb.pinned = false;
     rb.n_degenerate = rep.n_degenerate; rb.bvh_depth = rep.bvh_depth; rb.stack_need = rep.stack_need; rb.collapse_method = rep.collapse_method;
 #if !PT_NODE_Q16
     RebasePlan plan;
     if (!make_rebase_plan(ls.nodes, ls.dev.root, ls.nodes4, ls.dev.root4, ls.tris_render.size(), &plan)) return MI355PT_OK;   // (a tree the plan does not cover: a move builds again)
     int rc;
-    if ((rc = upload_words(this, plan.entries, &rb.d_entries, err)) || (rc = upload_words(this, plan.slot_src, &rb.d_slot_src, err)) ||
-        (rc = upload_words(this, std::vector<uint32_t>(4, 0u), &rb.d_count, err))) return rc;
+    if (on_device && ((rc = upload_words(this, plan.entries, &rb.d_entries, err)) || (rc = upload_words(this, plan.slot_src, &rb.d_slot_src, err)) ||
+                      (rc = upload_words(this, std::vector<uint32_t>(4, 0u), &rb.d_count, err)))) return rc;
     rb.height_offset = plan.height_offset;
     rb.n_slots = (uint32_t)plan.slot_src.size();
+    rb.n_entries = (uint32_t)plan.entries.size();
+    rb.tree_nodes4 = ls.nodes4; rb.tree_root4 = ls.dev.root4;
     rb.identity.resize(ls.instances.size());
     for (size_t i = 0; i < ls.instances.size(); ++i) rb.identity[i] = (uint8_t)ls.instances[i].identity;
     rb.tris_are_local = ls.dev.tris_are_local != 0;
     mesh_local_bounds(*this, &rb.bounds);
     rb.lights = ls.lights;
     rb.light_tris = ls.light_tris;
-    rb.ready = true;
+    rb.pinned = true;
+    rb.ready = on_device;
 #endif
     return MI355PT_OK;
 }
@@ -227,6 +265,71 @@ int mi355pt_scene_debug_move_export(const mi355pt_scene* s, const mi355pt_camera
     if (out_tris) { if (*n_tris < ls.tris_render.size()) return fail(MI355PT_E_INVALID, "triangle buffer too small"); std::memcpy(out_tris, ls.tris_render.data(), ls.tris_render.size() * sizeof(DevTri)); }
     *n_nodes = (uint32_t)ls.nodes.size(); *n_tris = (uint32_t)ls.tris_render.size();
     if (root) *root = ls.dev.root;
+    return MI355PT_OK;
+}
+
+int mi355pt_scene_debug_pinned_digest(const mi355pt_scene* s, const mi355pt_camera* cam, char* names_buf, size_t names_len, uint64_t* digests, uint32_t* n) {
+    if (!s || !cam || !names_buf || !digests || !n) return fail(MI355PT_E_INVALID, "null argument");
+    LoweredScene ls; LowerReport rep;
+    if (int rc = pinned_current(s, cam, &ls, &rep)) return rc;
+    return digests_out(ls, rep, s->impl.rebase.gpu_built, names_buf, names_len, digests, n);
+}
+
+int mi355pt_scene_debug_pinned_export(const mi355pt_scene* s, const mi355pt_camera* cam, void* out_nodes, uint32_t* n_nodes, void* out_tris, uint32_t* n_tris,
+                                      int32_t* root, uint32_t* out_entries, uint32_t* n_entries) {
+    if (!s || !cam || !n_nodes || !n_tris) return fail(MI355PT_E_INVALID, "null argument");
+    LoweredScene ls; LowerReport rep;
+    if (int rc = pinned_current(s, cam, &ls, &rep)) return rc;
+    if (out_nodes) { if (*n_nodes < ls.nodes.size()) return fail(MI355PT_E_INVALID, "node buffer too small"); std::memcpy(out_nodes, ls.nodes.data(), ls.nodes.size() * sizeof(DevNode)); }
+    if (out_tris) { if (*n_tris < ls.tris_render.size()) return fail(MI355PT_E_INVALID, "triangle buffer too small"); std::memcpy(out_tris, ls.tris_render.data(), ls.tris_render.size() * sizeof(DevTri)); }
+    *n_nodes = (uint32_t)ls.nodes.size(); *n_tris = (uint32_t)ls.tris_render.size();
+    if (root) *root = ls.dev.root;
+#if !PT_NODE_Q16
+    if (n_entries) {
+        RebasePlan plan;
+        if (!make_rebase_plan(ls.nodes, ls.dev.root, ls.nodes4, ls.dev.root4, ls.tris_render.size(), &plan)) return fail(MI355PT_E_INVALID, "internal error: no refit plan");
+        if (out_entries) { if (*n_entries < plan.entries.size()) return fail(MI355PT_E_INVALID, "entry buffer too small"); std::memcpy(out_entries, plan.entries.data(), plan.entries.size() * sizeof(uint32_t)); }
+        *n_entries = (uint32_t)plan.entries.size();
+    }
+#endif
+    return MI355PT_OK;
+}
+
+int mi355pt_scene_debug_pin_host_tree(mi355pt_scene* s, const mi355pt_camera* cam) {
+    if (!s || !cam) return fail(MI355PT_E_INVALID, "null argument");
+    SceneImpl& impl = s->impl;
+    if (impl.built || !s->parts.empty()) return fail(MI355PT_E_INVALID, "mi355pt_scene_debug_pin_host_tree is for a scene that is not built");
+    impl.rebase = RebaseState{};
+    std::string err;
+    int rc;
+    float cmf[470 * 4];
+    cie_cmf4(cmf);
+    LoweredGeometry geo; BvhOut bvh; LoweredScene ls; LowerReport rep;
+    if ((rc = lower_geometry(impl, cam, &geo, &err))) return fail(rc, err);
+    build_bvh(geo.build_tris, &bvh);
+    if (bvh.max_depth >= STACK_DEPTH) return fail(MI355PT_E_INVALID, "BVH deeper than the traversal stack");
+    keep_topology(geo, bvh, cam, false, &impl.rebase);
+    if ((rc = lower_scene(impl, std::move(geo), std::move(bvh), cmf, &ls, &rep, &err)) || (rc = lower_tree4(&ls, &rep, &err)) ||
+        (rc = impl.prepare_rebase(ls, rep, &err, false))) return fail(rc, err);
+    if (!impl.rebase.pinned) return fail(MI355PT_E_INVALID, "the tree has no refit plan");
+    std::memcpy(impl.build_cam_pos, cam->position, sizeof(impl.build_cam_pos));
+    return MI355PT_OK;
+}
+
+int mi355pt_scene_debug_set_instance_transform(mi355pt_scene* s, uint32_t instance, const float* local_to_world) {
+    if (!s || !local_to_world) return fail(MI355PT_E_INVALID, "null argument");
+    if (s->impl.built || !s->parts.empty()) return fail(MI355PT_E_INVALID, "a built scene moves with mi355pt_scene_move_instances");
+    if (instance >= s->impl.instances.size()) return fail(MI355PT_E_INVALID, "bad instance id");
+    std::memcpy(s->impl.instances[instance].l2w, local_to_world, sizeof(float) * 16);
+    return MI355PT_OK;
+}
+
+int mi355pt_debug_sah_cost(const void* nodes, uint32_t n_nodes, int32_t root, const uint32_t* entries, uint32_t n_entries, float* out_cost) {
+    if ((!nodes && n_nodes) || (!entries && n_entries) || !out_cost) return fail(MI355PT_E_INVALID, "null argument");
+    for (uint32_t k = 0; k < n_entries; ++k) if ((entries[k] >> 1) >= n_nodes) return fail(MI355PT_E_INVALID, "entry names a node out of range");
+    if (root >= 0 && (uint32_t)root >= n_nodes) return fail(MI355PT_E_INVALID, "root out of range");
+    const DevNode* p = (const DevNode*)nodes;
+    *out_cost = sah_cost_host(std::vector<DevNode>(p, p + n_nodes), root, std::vector<uint32_t>(entries, entries + n_entries));
     return MI355PT_OK;
 }
 

@@ -206,6 +206,26 @@ class MoveResult(C.Structure):
 MOVE_REASON = ["rebased", "same_position", "degenerate_set_changed", "instance_class_changed", "unsupported_build"]   # MI355PT_MOVE_*
 
 
+# mi355pt_instance_move_result.reason: MOVE_REASON plus the two of include/mi355pt_instances.h
+INSTANCE_MOVE_REASON = MOVE_REASON + ["same_transforms", "sah_degraded"]
+
+
+class InstanceMoveParams(C.Structure):
+    """mi355pt_instance_move_params (include/mi355pt_instances.h)"""
+    _fields_ = [("rebuild_above", C.c_float)]
+
+
+class InstanceMoveResult(C.Structure):
+    """mi355pt_instance_move_result (include/mi355pt_instances.h)"""
+    _fields_ = [("rebuilt", C.c_uint32), ("reason", C.c_uint32), ("launches", C.c_uint32), ("sah_built", C.c_float), ("sah_after", C.c_float),
+                ("host_ms", C.c_double), ("device_ms", C.c_double)]
+
+    def as_dict(self):
+        return {"rebuilt": int(self.rebuilt), "reason": INSTANCE_MOVE_REASON[self.reason], "launches": int(self.launches),
+                "sah_built": np.float32(self.sah_built), "sah_after": np.float32(self.sah_after), "host_ms": float(self.host_ms),
+                "device_ms": float(self.device_ms)}
+
+
 def make_camera(position, direction, up, width, height, fov_deg=45.0):
     return Camera((C.c_float * 3)(*position), (C.c_float * 3)(*direction), (C.c_float * 3)(*up), fov_deg, width, height)
 
@@ -221,7 +241,7 @@ def _ptr(a, ty):
 
 
 # every symbol include/mi355pt.h declares (tests/test_abi.py checks the built library exports all of them) ...
-DEBUG_SYMBOLS = ["debug_unlock", "scene_debug_set_lowering", "scene_debug_lowering_digest", "scene_debug_camera_candidates", "scene_debug_move_digest", "scene_debug_move_export", "scene_debug_device_digest", "scene_export_bvh", "probe_bvh_collapse", "probe_bvh_collapse_nodes", "probe_sobol", "probe_sincos", "probe_intersect", "probe_occluded",
+DEBUG_SYMBOLS = ["debug_unlock", "scene_debug_set_lowering", "scene_debug_lowering_digest", "scene_debug_camera_candidates", "scene_debug_move_digest", "scene_debug_move_export", "scene_debug_device_digest", "scene_debug_pinned_digest", "scene_debug_pinned_export", "scene_debug_pin_host_tree", "scene_debug_set_instance_transform", "debug_sah_cost", "scene_export_bvh", "probe_bvh_collapse", "probe_bvh_collapse_nodes", "probe_sobol", "probe_sincos", "probe_intersect", "probe_occluded",
                  "sample_log_records", "render_sample_log", "probe_radiance", "probe_display_meter_ms"]     # ... and include/mi355pt_debug.h
 ABI_SYMBOLS = [
     "scene_create", "scene_destroy", "scene_set_rgb2spec", "scene_add_lut470", "scene_add_tex_rgb8", "scene_add_mesh",
@@ -251,6 +271,8 @@ DISPLAY_SYMBOLS = ["display_params_default", "display_scratch_bytes", "display_m
 ROBUST_SYMBOLS = ["robust_params_default", "robust_combine_device", "robust_combine", "render_buckets_device", "render_robust"]
 # ... and include/mi355pt_rebase.h, the camera-move block (tests/test_rebase.py)
 REBASE_SYMBOLS = ["scene_move_camera"]
+# ... and include/mi355pt_instances.h, the instance-move block (tests/test_instance_move.py)
+INSTANCES_SYMBOLS = ["scene_set_instance_dynamic", "scene_move_instances"]
 ADAPTIVE_SYMBOLS = ["adaptive_scratch_bytes", "adaptive_step_device", "film_normalize_tiles_device", "render_adaptive_device", "render_adaptive"]
 
 
@@ -327,6 +349,7 @@ class SceneHandle:
         backend.check(backend.fn("scene_create")(C.byref(self.h)), "scene_create")
         self.keep = []
         self.material_descs = []       # by material id (delta / environment lights add hidden materials on the library side, after these)
+        self.instances = []            # by instance id: (geometry, material, local_to_world as a row-major 4 x 4 float32 array) as described
 
     def close(self):
         if self.h:
@@ -382,6 +405,7 @@ class SceneHandle:
         m = np.eye(4, dtype=np.float32) if local_to_world is None else np.asarray(local_to_world, dtype=np.float32)
         cols = np.ascontiguousarray(m.T.reshape(-1))   # column-major
         self.b.check(self.b.fn("scene_add_instance")(self.h, geom, mat, _ptr(cols, C.c_float)), "scene_add_instance")
+        self.instances.append((geom, mat, m.copy()))
 
     def add_delta_light(self, kind, intensity, spectrum, local_to_world=None, angle_inner=0.0, angle_outer=0.0):
         m = np.eye(4, dtype=np.float32) if local_to_world is None else np.asarray(local_to_world, dtype=np.float32)
@@ -451,6 +475,61 @@ class SceneHandle:
         res = MoveResult()
         self.b.check(fn(self.h, C.byref(cam), C.byref(res)), "scene_move_camera")
         return res.as_dict()
+
+    def set_instance_dynamic(self, instance, dynamic=True):
+        """mi355pt_scene_set_instance_dynamic (include/mi355pt_instances.h, product only): before the build, mark an instance that will move"""
+        fn = self.b.fn("scene_set_instance_dynamic")
+        fn.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        self.b.check(fn(self.h, instance, 1 if dynamic else 0), "scene_set_instance_dynamic")
+
+    def move_instances(self, cam, ids, local_to_world, rebuild_above=0.0):
+        """mi355pt_scene_move_instances (include/mi355pt_instances.h, product only): new local_to_world matrices (row-major 4 x 4 each, as
+        add_instance takes them) for the instances `ids` (strictly ascending) of the built scene, applied on the device ->
+        {"rebuilt", "reason" (an INSTANCE_MOVE_REASON name), "launches", "sah_built", "sah_after", "host_ms", "device_ms"}"""
+        fn = self.b.fn("scene_move_instances")
+        fn.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_uint32, C.POINTER(InstanceMoveParams),
+                       C.POINTER(InstanceMoveResult)]
+        idv = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        m = np.asarray(local_to_world, dtype=np.float32).reshape(-1, 4, 4)
+        assert m.shape[0] == idv.size
+        cols = np.ascontiguousarray(m.transpose(0, 2, 1).reshape(-1))          # column-major
+        prm = InstanceMoveParams(rebuild_above)
+        res = InstanceMoveResult()
+        self.b.check(fn(self.h, C.byref(cam), _ptr(idv, C.c_uint32), _ptr(cols, C.c_float), idv.size, C.byref(prm), C.byref(res)), "scene_move_instances")
+        return res.as_dict()
+
+    def debug_pin_host_tree(self, cam):
+        """mi355pt_scene_debug_pin_host_tree (host only, product only): what a build keeps on the host, for an unbuilt scene"""
+        fn = self.b.fn("scene_debug_pin_host_tree")
+        fn.argtypes = [C.c_void_p, C.POINTER(Camera)]
+        self.b.check(fn(self.h, C.byref(cam)), "scene_debug_pin_host_tree")
+
+    def debug_set_instance_transform(self, instance, local_to_world):
+        """mi355pt_scene_debug_set_instance_transform (host only, product only): a new matrix (row-major 4 x 4) in the description of an unbuilt scene"""
+        fn = self.b.fn("scene_debug_set_instance_transform")
+        fn.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
+        cols = np.ascontiguousarray(np.asarray(local_to_world, dtype=np.float32).T.reshape(-1))
+        self.b.check(fn(self.h, instance, _ptr(cols, C.c_float)), "scene_debug_set_instance_transform")
+
+    def debug_pinned_digest(self, cam):
+        """mi355pt_scene_debug_pinned_digest (host only, product only): debug_lowering_digest's pair for the built scene's CURRENT description
+        over the topology the built scene holds"""
+        fn = self.b.fn("scene_debug_pinned_digest")
+        fn.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+        return self._digests(lambda *a: fn(self.h, C.byref(cam), *a), "scene_debug_pinned_digest")
+
+    def debug_pinned_export(self, cam):
+        """mi355pt_scene_debug_pinned_export (host only, product only): the BVH2 of debug_pinned_digest's lowering as Product.export_bvh
+        gives a built one — nodes (n, 16) uint32, triangle records (m, 12) uint32, root — and the refit plan's entries (uint32)"""
+        fn = self.b.fn("scene_debug_pinned_export")
+        fn.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int32),
+                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        nn, nt, ne, root = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_int32(0)
+        self.b.check(fn(self.h, C.byref(cam), None, C.byref(nn), None, C.byref(nt), None, None, C.byref(ne)), "scene_debug_pinned_export")
+        nodes = np.zeros((nn.value, 16), np.uint32); tris = np.zeros((nt.value, 12), np.uint32); entries = np.zeros(ne.value, np.uint32)
+        self.b.check(fn(self.h, C.byref(cam), nodes.ctypes.data_as(C.c_void_p), C.byref(nn), tris.ctypes.data_as(C.c_void_p), C.byref(nt), C.byref(root),
+                        _ptr(entries, C.c_uint32), C.byref(ne)), "scene_debug_pinned_export")
+        return nodes, tris, int(root.value), entries
 
     def _digests(self, call, what):
         text = C.create_string_buffer(4096); dig = (C.c_uint64 * 128)(); n = C.c_uint32(128)
@@ -1017,6 +1096,16 @@ class Product(Backend):
         nodes = np.zeros((nn.value, 16), np.uint32); tris = np.zeros((nt.value, 12), np.uint32)
         self.check(fn(scene.h, nodes.ctypes.data, C.byref(nn), tris.ctypes.data, C.byref(nt), C.byref(root)), "scene_export_bvh")
         return nodes, tris, root.value
+
+    def debug_sah_cost(self, nodes, root, entries):
+        """mi355pt_debug_sah_cost (host only): the SAH cost of an exported BVH2 over the refit plan's entries, in the fixed order of
+        csrc/instance_move_plan.hpp -> numpy float32"""
+        fn = self.lib.mi355pt_debug_sah_cost
+        fn.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_float)]
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint32).reshape(-1, 16); entries = np.ascontiguousarray(entries, dtype=np.uint32).reshape(-1)
+        out = C.c_float(0.0)
+        self.check(fn(nodes.ctypes.data_as(C.c_void_p), nodes.shape[0], root, _ptr(entries, C.c_uint32), entries.size, C.byref(out)), "debug_sah_cost")
+        return np.float32(out.value)
 
     def probe_bvh_collapse(self, tri_pos, rays_od):
         """mi355pt_probe_bvh_collapse (host-only) -> (info dict, rays whose leaf sets differ between the BVH2 and the collapsed BVH4)"""

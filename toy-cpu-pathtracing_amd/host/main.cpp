@@ -46,7 +46,25 @@ struct Args {   // main.rs:20-53
     // nor the robust film (mi355pt_robust.h): --spp rendered as K buckets of --spp / K consecutive samples, combined per pixel by a trimmed
     // mean of the bucket means (0 = off).  Mode and scale not given = mi355pt_robust_params_default: GMON, 1
     uint32_t robust_buckets = 0; bool robust_given = false; std::string robust_mode; bool robust_scale_given = false; float robust_scale = 0.0f;
+    // nor moving instances of the built scene (mi355pt_instances.h): --instance-transform ID:tx,ty,tz[:ry_deg[:sx,sy,sz]], repeatable — the
+    // scene is built as described with those instances marked dynamic, then each takes T . R_y . S . local_to_world on the device before the
+    // frame.  --instance-rebuild-above 0 (the library's default): never build again because of the tree's SAH cost
+    struct InstanceTransform { uint32_t id; float t[3]; float ry_deg; float s[3]; };
+    std::vector<InstanceTransform> instance_transforms; bool instance_rebuild_given = false; float instance_rebuild_above = 0.0f;
 };
+
+// T . R_y . S . local_to_world (column-major): T R S composed in double and rounded to float, the product in double and rounded to float
+void instance_transform_matrix(const Args::InstanceTransform& it, const float* l2w, float* out) {
+    const double a = (double)it.ry_deg * (3.14159265358979323846 / 180.0), c = std::cos(a), s = std::sin(a);
+    const double rot[3][3] = {{c, 0.0, s}, {0.0, 1.0, 0.0}, {-s, 0.0, c}};
+    float x[4][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 1}};                    // row-major
+    for (int r = 0; r < 3; ++r) { for (int k = 0; k < 3; ++k) x[r][k] = (float)(rot[r][k] * (double)it.s[k]); x[r][3] = it.t[r]; }
+    for (int col = 0; col < 4; ++col) for (int r = 0; r < 4; ++r) {
+        double v = 0.0;
+        for (int k = 0; k < 4; ++k) v += (double)x[r][k] * (double)l2w[4 * col + k];
+        out[4 * col + r] = (float)v;
+    }
+}
 
 // --denoise: the beauty film at --spp, the albedo and shading-normal films at --denoise-guide-spp (converged guides cost a few percent of
 // the frame; guides as noisy as the frame hurt), mi355pt_denoise_device, then Sensor::to_rgb on the result as a film with spp 1.
@@ -515,7 +533,13 @@ static void usage() {
               "                                         pixel by a trimmed mean of the bucket means: firefly rejection; with --denoise, --denoise-variance,\n"
               "                                         --fused-guides, --tone-map and --auto-exposure)\n"
               "                   [--robust-mode gmon|mom|mean] (gmon: the trim follows the Gini coefficient of the bucket means; mom: the median of means;\n"
-              "                                         mean: no trim)  [--robust-scale X] (1; >= 0: the factor on the Gini term)");
+              "                                         mean: no trim)  [--robust-scale X] (1; >= 0: the factor on the Gini term)\n"
+              "                   [--instance-transform ID:tx,ty,tz[:ry_deg[:sx,sy,sz]]] (repeatable; pt|nee|mis|normal|albedo|position|depth: the scene is\n"
+              "                                         built as described with instance ID marked dynamic, then its local_to_world becomes\n"
+              "                                         T . R_y . S . local_to_world on the device, mi355pt_scene_move_instances; one line on stderr.\n"
+              "                                         Not with --temporal-frames: the reprojection assumes a static world, it has no object motion vectors)\n"
+              "                   [--instance-rebuild-above X] (0 = never; with --instance-transform: build again when the refit tree's SAH cost exceeds X\n"
+              "                                         times the built tree's)");
 }
 
 int main(int argc, char** argv) {
@@ -578,6 +602,32 @@ int main(int argc, char** argv) {
             }
         }
         else if (k == "--camera-move") { a.camera_move_given = true; a.camera_move = val(); }
+        else if (k == "--instance-transform") {
+            const std::string v = val();
+            Args::InstanceTransform it{0, {0, 0, 0}, 0.0f, {1, 1, 1}};
+            char tail = 0;
+            int n = std::sscanf(v.c_str(), "%u:%f,%f,%f%c", &it.id, &it.t[0], &it.t[1], &it.t[2], &tail);
+            bool ok = n == 4;
+            if (n == 5 && tail == ':') {
+                n = std::sscanf(v.c_str(), "%u:%f,%f,%f:%f%c", &it.id, &it.t[0], &it.t[1], &it.t[2], &it.ry_deg, &tail);
+                ok = n == 5;
+                if (n == 6 && tail == ':') ok = std::sscanf(v.c_str(), "%u:%f,%f,%f:%f:%f,%f,%f%c", &it.id, &it.t[0], &it.t[1], &it.t[2], &it.ry_deg, &it.s[0], &it.s[1], &it.s[2], &tail) == 8;
+            }
+            for (float f : {it.t[0], it.t[1], it.t[2], it.ry_deg, it.s[0], it.s[1], it.s[2]}) ok = ok && std::isfinite(f);
+            ok = ok && !v.empty() && v[0] >= '0' && v[0] <= '9';
+            for (const Args::InstanceTransform& o : a.instance_transforms) ok = ok && o.id != it.id;
+            if (!ok) { std::fprintf(stderr, "error: invalid value '%s' for '--instance-transform': ID:tx,ty,tz[:ry_deg[:sx,sy,sz]], finite numbers, each ID once\n", v.c_str()); return 2; }
+            a.instance_transforms.push_back(it);
+        }
+        else if (k == "--instance-rebuild-above") {
+            const std::string v = val();
+            char tail = 0;
+            a.instance_rebuild_given = true;
+            if (std::sscanf(v.c_str(), "%f%c", &a.instance_rebuild_above, &tail) != 1 || !(a.instance_rebuild_above >= 0.0f) || !std::isfinite(a.instance_rebuild_above)) {
+                std::fprintf(stderr, "error: invalid value '%s' for '--instance-rebuild-above': 0 or a finite ratio above it\n", v.c_str());
+                return 2;
+            }
+        }
         else if (k == "-h" || k == "--help") { usage(); return 0; }
         else { std::fprintf(stderr, "error: unexpected argument '%s'\n", k.c_str()); usage(); return 2; }
     }
@@ -647,6 +697,13 @@ int main(int argc, char** argv) {
     if (a.half_res && a.denoise) { std::fprintf(stderr, "error: --half-res with --denoise: the upsampled pair goes to --denoise-variance\n"); return 2; }
     if (a.half_res && a.adaptive_threshold != 0.0f) { std::fprintf(stderr, "error: --half-res with --adaptive-threshold: half-resolution rendering takes one sample count per frame\n"); return 2; }
     if (a.half_res && (a.spp == 0 || a.denoise_guide_spp == 0)) { std::fprintf(stderr, "error: --half-res needs --spp and --denoise-guide-spp above 0\n"); return 2; }
+    if (a.instance_rebuild_given && a.instance_transforms.empty()) { std::fprintf(stderr, "error: --instance-rebuild-above needs --instance-transform: it is the move's threshold\n"); return 2; }
+    if (!a.instance_transforms.empty()) {
+        if (a.temporal) { std::fprintf(stderr, "error: --instance-transform with --temporal-frames: the temporal reprojection assumes a static world (no object motion vectors)\n"); return 2; }
+        if (a.gpus > 1) { std::fprintf(stderr, "error: --instance-transform with --gpus %d: a scene built over several GPUs is not moved\n", a.gpus); return 2; }
+        if (a.renderer == "shading-normal") { std::fprintf(stderr, "error: --instance-transform with --renderer shading-normal: pt, nee, mis, normal, albedo, position or depth\n"); return 2; }
+        std::sort(a.instance_transforms.begin(), a.instance_transforms.end(), [](const Args::InstanceTransform& x, const Args::InstanceTransform& y) { return x.id < y.id; });
+    }
     if (a.camera_step_given && !a.temporal) { std::fprintf(stderr, "error: --camera-step needs --temporal-frames: it moves the camera between the frames\n"); return 2; }
     if (a.camera_move != "rebuild" && a.camera_move != "rebase") { std::fprintf(stderr, "error: invalid value '%s' for '--camera-move' (rebuild or rebase)\n", a.camera_move.c_str()); return 2; }
     if (a.camera_move_given && !a.temporal) { std::fprintf(stderr, "error: --camera-move needs --temporal-frames: it says how the scene follows the camera between the frames\n"); return 2; }
@@ -721,9 +778,23 @@ int main(int argc, char** argv) {
             case 19: load_scene_19(scene, camera); break;
             default: std::fprintf(stderr, "scene %u is outside the MI355X hot-path scope (scenes 0-19)\n", a.scene); return 2;
         }
+        for (const Args::InstanceTransform& it : a.instance_transforms) {
+            if (it.id >= scene.instance_count()) { std::fprintf(stderr, "error: invalid value for '--instance-transform': scene %u has no instance %u (%u instances)\n", a.scene, it.id, scene.instance_count()); return 2; }
+            scene.set_instance_dynamic(it.id);
+        }
         std::puts("Start build scene.");                                                // main.rs:103-109
         auto t0 = std::chrono::steady_clock::now();
         if (a.gpus > 1) scene.build_multi(camera, a.gpus); else scene.build(camera);
+        if (!a.instance_transforms.empty()) {
+            std::vector<uint32_t> ids; std::vector<float> matrices(16 * a.instance_transforms.size());
+            for (size_t k = 0; k < a.instance_transforms.size(); ++k) {
+                ids.push_back(a.instance_transforms[k].id);
+                instance_transform_matrix(a.instance_transforms[k], scene.instance_transform(ids.back()), &matrices[16 * k]);
+            }
+            const mi355pt_instance_move_result mr = scene.move_instances(camera, ids, matrices, a.instance_rebuild_above);
+            std::fprintf(stderr, "instance move: rebuilt=%u reason=%u launches=%u sah=%.6g\xe2\x86\x92%.6g host_ms=%.3f device_ms=%.3f\n", mr.rebuilt, mr.reason, mr.launches,
+                         (double)mr.sah_built, (double)mr.sah_after, mr.host_ms, mr.device_ms);
+        }
         std::printf("Finish build scene: %.3f seconds.\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
 
         RendererArgs args{a.width, a.height, a.spp, a.seed, &scene, &camera};

@@ -668,6 +668,7 @@ public:
         uint32_t mat;
         check(mi355pt_scene_add_material(s_, &md, &mat), "mi355pt_scene_add_material");
         check(mi355pt_scene_add_instance(s_, d.geometry_index.id, mat, d.transform.m), "mi355pt_scene_add_instance");
+        instance_l2w_.emplace_back(d.transform.m, d.transform.m + 16);
     }
     void create_primitive(const SingleTrianglePrimitive& d) {      // lowered to a one-triangle mesh with load_obj's tangent rule
         TriangleMeshData m;
@@ -704,6 +705,19 @@ public:
         check(mi355pt_scene_move_camera(s_, &cam.raw(), &r), "mi355pt_scene_move_camera");
         return r;
     }
+    // EXTENSION (include/mi355pt_instances.h): instances of the built scene take new local_to_world matrices (column-major, 16 floats each,
+    // ids strictly ascending) on the device — positions, shading normals, light tables, both trees refit, the tree's SAH cost reported —;
+    // an instance that will move is marked before build().  The temporal accumulation assumes a static world: no object motion vectors
+    void set_instance_dynamic(uint32_t instance) { check(mi355pt_scene_set_instance_dynamic(s_, instance, 1), "mi355pt_scene_set_instance_dynamic"); }
+    mi355pt_instance_move_result move_instances(const Camera& cam, const std::vector<uint32_t>& ids, const std::vector<float>& matrices, float rebuild_above = 0.0f) {
+        mi355pt_instance_move_params p{rebuild_above};
+        mi355pt_instance_move_result r{};
+        check(mi355pt_scene_move_instances(s_, &cam.raw(), ids.data(), matrices.data(), (uint32_t)ids.size(), &p, &r), "mi355pt_scene_move_instances");
+        for (size_t k = 0; k < ids.size(); ++k) instance_l2w_[ids[k]].assign(matrices.begin() + 16 * (long)k, matrices.begin() + 16 * (long)(k + 1));
+        return r;
+    }
+    uint32_t instance_count() const { return (uint32_t)instance_l2w_.size(); }
+    const float* instance_transform(uint32_t instance) const { return instance_l2w_[instance].data(); }   // local_to_world as described / last moved
     // Scene::build over the first `n_devices` GPUs of the node (mi355pt_scene_build_multi): RendererImage::render then shards the frame
     void build_multi(const Camera& cam, int n_devices) {
         std::vector<int> ids((size_t)n_devices);
@@ -716,6 +730,7 @@ public:
     const mi355pt_scene* raw() const { return s_; }
 
 private:
+    std::vector<std::vector<float>> instance_l2w_;      // by instance id
     void add_light(uint32_t kind, float intensity, float a_in, float a_out, const Spectrum& sp, const Transform& t) {
         mi355pt_light_desc ld{}; ld.kind = kind; ld.intensity = intensity; ld.angle_inner = a_in; ld.angle_outer = a_out;
         ld.spectrum = lower_spectrum(sp); std::memcpy(ld.local_to_world, t.m, sizeof(ld.local_to_world));
