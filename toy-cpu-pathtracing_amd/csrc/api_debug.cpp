@@ -129,11 +129,9 @@ int mi355pt_probe_sobol(uint32_t width, uint32_t height, uint32_t spp, uint32_t 
     uint32_t log2_spp = log2_int(spp);
     uint32_t nb4 = log2_int(round_up_pow2(std::max(width, height))) + (log2_spp + 1) / 2;
     DevBuf<uint32_t> d_xys, d_out; DevBuf<uint8_t> d_pat;
-    HIP_TRY(d_xys.alloc((size_t)n * 3)); HIP_TRY(d_out.alloc((size_t)n * per)); HIP_TRY(d_pat.alloc(n_pat));
-    HIP_TRY(hipMemcpy(d_xys.p, xys, sizeof(uint32_t) * 3 * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_pat.p, pattern, n_pat, hipMemcpyHostToDevice));
+    HIP_TRY(d_xys.upload(xys, (size_t)n * 3)); HIP_TRY(d_pat.upload((const uint8_t*)pattern, n_pat)); HIP_TRY(d_out.alloc((size_t)n * per));
     HIP_TRY(launch_probe_sobol(width, seed, log2_spp, nb4, d_xys.p, n, d_pat.p, n_pat, per, d_out.p, nullptr));
-    HIP_TRY(hipMemcpy(out_bits, d_out.p, sizeof(uint32_t) * (size_t)n * per, hipMemcpyDeviceToHost));
+    HIP_TRY(d_out.download(out_bits, (size_t)n * per));
     return MI355PT_OK;
 }
 
@@ -219,15 +217,11 @@ int mi355pt_probe_intersect(const mi355pt_scene* s, const float* o, const float*
     if (!s->impl.built) return fail(MI355PT_E_NOT_BUILT, "scene not built");
     if (n == 0) return MI355PT_OK;
     DevBuf<float> d_o, d_d, d_t, d_n; DevBuf<uint32_t> d_i, d_tr;
-    HIP_TRY(d_o.alloc((size_t)n * 3)); HIP_TRY(d_d.alloc((size_t)n * 3)); HIP_TRY(d_t.alloc(n)); HIP_TRY(d_n.alloc((size_t)n * 3));
-    HIP_TRY(d_i.alloc(n)); HIP_TRY(d_tr.alloc(n));
-    HIP_TRY(hipMemcpy(d_o.p, o, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_d.p, d, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
+    HIP_TRY(d_o.upload(o, (size_t)n * 3)); HIP_TRY(d_d.upload(d, (size_t)n * 3));
+    HIP_TRY(d_t.alloc(n)); HIP_TRY(d_n.alloc((size_t)n * 3)); HIP_TRY(d_i.alloc(n)); HIP_TRY(d_tr.alloc(n));
     HIP_TRY(launch_probe_intersect(s->impl.dev, d_o.p, d_d.p, n, d_t.p, d_i.p, d_tr.p, d_n.p, nullptr));
-    HIP_TRY(hipMemcpy(out_t, d_t.p, sizeof(float) * n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_inst, d_i.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_tri, d_tr.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-    if (out_n) HIP_TRY(hipMemcpy(out_n, d_n.p, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
+    HIP_TRY(d_t.download(out_t, n)); HIP_TRY(d_i.download(out_inst, n)); HIP_TRY(d_tr.download(out_tri, n));
+    HIP_TRY(d_n.download(out_n, (size_t)n * 3));
     return MI355PT_OK;
 }
 
@@ -236,12 +230,9 @@ int mi355pt_probe_occluded(const mi355pt_scene* s, const float* o, const float* 
     if (!s->impl.built) return fail(MI355PT_E_NOT_BUILT, "scene not built");
     if (n == 0) return MI355PT_OK;
     DevBuf<float> d_o, d_d, d_t; DevBuf<uint8_t> d_out;
-    HIP_TRY(d_o.alloc((size_t)n * 3)); HIP_TRY(d_d.alloc((size_t)n * 3)); HIP_TRY(d_t.alloc(n)); HIP_TRY(d_out.alloc(n));
-    HIP_TRY(hipMemcpy(d_o.p, o, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_d.p, d, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_t.p, tmax, sizeof(float) * n, hipMemcpyHostToDevice));
+    HIP_TRY(d_o.upload(o, (size_t)n * 3)); HIP_TRY(d_d.upload(d, (size_t)n * 3)); HIP_TRY(d_t.upload(tmax, n)); HIP_TRY(d_out.alloc(n));
     HIP_TRY(launch_probe_occluded(s->impl.dev, d_o.p, d_d.p, d_t.p, n, d_out.p, nullptr));
-    HIP_TRY(hipMemcpy(out, d_out.p, n, hipMemcpyDeviceToHost));
+    HIP_TRY(d_out.download(out, n));
     return MI355PT_OK;
 }
 

@@ -17,25 +17,16 @@ namespace {
 constexpr size_t RECORD_BYTES = MI355PT_DISPLAY_RECORD_WORDS * sizeof(uint32_t), HIST_BYTES = MI355PT_DISPLAY_HIST_WORDS * sizeof(uint32_t);
 static_assert(MI355PT_DISPLAY_HIST_WORDS == DISPLAY_HIST_WORDS, "the header and the plan agree on the histogram");
 
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b) return false;
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-bool misaligned(const void* p) { return ((uintptr_t)p & 3u) != 0; }
-
 // the checks of a params struct, shared by the meter and the display: the struct is valid or refused as a whole
 int params_check(const mi355pt_display_params* dp, const char* who) {
     const std::string w = std::string(who) + ": ";
     if (dp->tone > MI355PT_TONE_HABLE) return fail(MI355PT_E_INVALID, w + "unknown tone operator");
     if (dp->encode > MI355PT_ENCODE_SRGB) return fail(MI355PT_E_INVALID, w + "unknown encoding");
-    if (!std::isfinite(dp->exposure) || !(dp->exposure > 0.0f)) return fail(MI355PT_E_INVALID, w + "exposure must be finite and > 0 (mi355pt_display_params_default fills the struct)");
+    if (!all_finite_positive({dp->exposure})) return fail(MI355PT_E_INVALID, w + "exposure must be finite and > 0 (mi355pt_display_params_default fills the struct)");
     if (!std::isfinite(dp->white) || !(dp->white >= 0x1p-16f && dp->white <= 0x1p16f)) return fail(MI355PT_E_INVALID, w + "white must be in [2^-16, 2^16]");
     if (dp->log2_lum_min < -126 || dp->log2_lum_min > 95) return fail(MI355PT_E_INVALID, w + "log2_lum_min must be in [-126, 95]: every bin edge is a normal float");
     if ((uint64_t)dp->trim_low + dp->trim_high >= 1024u) return fail(MI355PT_E_INVALID, w + "trim_low + trim_high must be below 1024 (they are 1/1024ths)");
-    const float pos[3] = {dp->key, dp->e_min, dp->e_max};
-    for (float v : pos)
-        if (!std::isfinite(v) || !(v > 0.0f)) return fail(MI355PT_E_INVALID, w + "key, e_min and e_max must be finite and > 0");
+    if (!all_finite_positive({dp->key, dp->e_min, dp->e_max})) return fail(MI355PT_E_INVALID, w + "key, e_min and e_max must be finite and > 0");
     if (dp->e_min > dp->e_max) return fail(MI355PT_E_INVALID, w + "e_min is above e_max");
     if (!(dp->adapt >= 0.0f && dp->adapt <= 1.0f)) return fail(MI355PT_E_INVALID, w + "adapt must be in [0, 1]");
     return MI355PT_OK;
@@ -58,7 +49,7 @@ int meter_check(const float* film, uint32_t width, uint32_t height, uint32_t spp
     if (rc) return rc;
     const size_t need = display_scratch_bytes(width, height), film_bytes = (size_t)width * height * 3 * sizeof(float);
     if (device && scratch_bytes < need) return fail(MI355PT_E_INVALID, "display meter: scratch buffer too small (mi355pt_display_scratch_bytes gives the size)");
-    if (misaligned(scratch) || misaligned(record) || misaligned(prev) || misaligned(hist)) return fail(MI355PT_E_INVALID, "display meter: the scratch buffer, the records and the histogram must be 4-byte aligned");
+    if (misaligned(scratch, 4) || misaligned(record, 4) || misaligned(prev, 4) || misaligned(hist, 4)) return fail(MI355PT_E_INVALID, "display meter: the scratch buffer, the records and the histogram must be 4-byte aligned");
     rc = params_check(dp, who);
     if (rc) return rc;
     const void* outs[2] = {record, hist};
@@ -78,7 +69,7 @@ int display_check(const float* film, uint32_t width, uint32_t height, uint32_t s
     if (!dp || !film || !out) return fail(MI355PT_E_INVALID, "display: null params, film or output pointer");
     int rc = frame_check(width, height, spp, who);
     if (rc) return rc;
-    if (misaligned(record)) return fail(MI355PT_E_INVALID, "display: the record must be 4-byte aligned");
+    if (misaligned(record, 4)) return fail(MI355PT_E_INVALID, "display: the record must be 4-byte aligned");
     rc = params_check(dp, who);
     if (rc) return rc;
     const size_t film_bytes = (size_t)width * height * 3 * sizeof(float);
@@ -138,17 +129,14 @@ int mi355pt_display_meter(const float* film, uint32_t width, uint32_t height, ui
     const size_t n = (size_t)width * height * 3, scratch_bytes = display_scratch_bytes(width, height);
     DevBuf<float> d_film;
     DevBuf<uint32_t> d_scratch, d_record, d_hist;
-    HIP_TRY(d_film.alloc(n));
-    HIP_TRY(hipMemcpy(d_film.p, film, n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(d_film.upload(film, n));
     HIP_TRY(d_scratch.alloc(scratch_bytes / sizeof(uint32_t)));
-    HIP_TRY(d_record.alloc(MI355PT_DISPLAY_RECORD_WORDS));
-    if (hist) HIP_TRY(d_hist.alloc(MI355PT_DISPLAY_HIST_WORDS));
-    if (prev_record) HIP_TRY(hipMemcpy(d_record.p, prev_record, RECORD_BYTES, hipMemcpyHostToDevice));      // metered in place, as the header allows
-    rc = mi355pt_display_meter_device(d_film.p, width, height, spp, dp, prev_record ? d_record.p : nullptr, d_scratch.p, scratch_bytes, d_record.p,
-                                      hist ? d_hist.p : nullptr, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(record, d_record.p, RECORD_BYTES, hipMemcpyDeviceToHost));      // (synchronises the default stream)
-    if (hist) HIP_TRY(hipMemcpy(hist, d_hist.p, HIST_BYTES, hipMemcpyDeviceToHost));
+    HIP_TRY(prev_record ? d_record.upload(prev_record, MI355PT_DISPLAY_RECORD_WORDS) : d_record.alloc(MI355PT_DISPLAY_RECORD_WORDS));      // metered in place, as the header allows
+    HIP_TRY(d_hist.alloc_for(hist, MI355PT_DISPLAY_HIST_WORDS));
+    if ((rc = mi355pt_display_meter_device(d_film.p, width, height, spp, dp, prev_record ? d_record.p : nullptr, d_scratch.p, scratch_bytes, d_record.p, d_hist.p,
+                                           nullptr))) return rc;
+    HIP_TRY(d_record.download(record, MI355PT_DISPLAY_RECORD_WORDS));
+    HIP_TRY(d_hist.download(hist, MI355PT_DISPLAY_HIST_WORDS));
     return MI355PT_OK;
 }
 
@@ -158,16 +146,11 @@ int mi355pt_display(const float* film, uint32_t width, uint32_t height, uint32_t
     const size_t n = (size_t)width * height * 3;
     DevBuf<float> d_film, d_out;
     DevBuf<uint32_t> d_record;
-    HIP_TRY(d_film.alloc(n));
-    HIP_TRY(hipMemcpy(d_film.p, film, n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(d_film.upload(film, n));
+    HIP_TRY(d_record.upload(record, MI355PT_DISPLAY_RECORD_WORDS));
     HIP_TRY(d_out.alloc(n));
-    if (record) {
-        HIP_TRY(d_record.alloc(MI355PT_DISPLAY_RECORD_WORDS));
-        HIP_TRY(hipMemcpy(d_record.p, record, RECORD_BYTES, hipMemcpyHostToDevice));
-    }
-    rc = mi355pt_display_device(d_film.p, width, height, spp, dp, record ? d_record.p : nullptr, d_out.p, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out, d_out.p, n * sizeof(float), hipMemcpyDeviceToHost));      // (synchronises the default stream)
+    if ((rc = mi355pt_display_device(d_film.p, width, height, spp, dp, d_record.p, d_out.p, nullptr))) return rc;
+    HIP_TRY(d_out.download(out, n));
     return MI355PT_OK;
 }
 
@@ -178,19 +161,17 @@ int mi355pt_probe_display_meter_ms(const float* d_film, uint32_t width, uint32_t
     int rc = meter_check(d_film, width, height, spp, dp, nullptr, d_scratch, scratch_bytes, d_record, nullptr, true);
     if (rc) return rc;
     const DisplayMeterArgs a = meter_args(width, height, spp, dp);
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    Event ev[3];
     hipError_t e = hipSuccess;
-    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], nullptr);
+    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = ev[i].create();
+    if (e == hipSuccess) e = ev[0].record(nullptr);
     if (e == hipSuccess) e = launch_display_hist(d_film, a, (uint32_t*)d_scratch, nullptr);
-    if (e == hipSuccess) e = hipEventRecord(ev[1], nullptr);
+    if (e == hipSuccess) e = ev[1].record(nullptr);
     if (e == hipSuccess) e = launch_display_finish((const uint32_t*)d_scratch, a, nullptr, d_record, nullptr, nullptr);
-    if (e == hipSuccess) e = hipEventRecord(ev[2], nullptr);
-    if (e == hipSuccess) e = hipEventSynchronize(ev[2]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&out_ms[0], ev[0], ev[1]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&out_ms[1], ev[1], ev[2]);
-    for (hipEvent_t v : ev)
-        if (v) (void)hipEventDestroy(v);
+    if (e == hipSuccess) e = ev[2].record(nullptr);
+    if (e == hipSuccess) e = ev[2].synchronize();
+    if (e == hipSuccess) e = ev[1].elapsed_ms(ev[0], &out_ms[0]);
+    if (e == hipSuccess) e = ev[2].elapsed_ms(ev[1], &out_ms[1]);
     if (e != hipSuccess) return fail(MI355PT_E_DEVICE, std::string("display meter probe: ") + hipGetErrorString(e));
     return MI355PT_OK;
 }

@@ -1,12 +1,16 @@
-// What api.cpp (include/mi355pt.h, mi355pt_denoise.h) and api_debug.cpp (include/mi355pt_debug.h) share.  Not installed, not an ABI.
+// What the host translation units behind the C ABI share (api.cpp and the api_<stage>.cpp files, one per public header; scene_rebase.cpp,
+// scene_instances.cpp): the scene object and its launch context, fail / HIP_TRY, the device buffer and event holders, and what api.cpp
+// defines for the others.  The pure argument predicates are api_checks.hpp.  Not installed, not an ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <functional>
 #include <string>
 #include <vector>
 
 #include "../../include/mi355pt.h"
+#include "api_checks.hpp"
 #include "launch.hpp"
 #include "launch_plan.hpp"
 #include "scene.hpp"
@@ -76,11 +80,32 @@ int fail(int code, const std::string& msg);   // sets the thread's mi355pt_last_
         if (_e != hipSuccess) return fail(MI355PT_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
     } while (0)
 
+// A device buffer of a host-buffer entry point, freed with the object, and that entry point's staging: synchronous copies on the null
+// stream.  An input the caller did not give and an output it does not want stay null pointers, which is what the _device twin takes for them
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
     ~DevBuf() { (void)hipFree(p); }
     hipError_t alloc(size_t n) { return hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)); }
+    // each does nothing when `host` is null: the device copy of host[0 .. n); n elements for an output wanted in `host`; p[0 .. n) into `host`
+    hipError_t upload(const T* host, size_t n) {
+        const hipError_t e = alloc_for(host, n);
+        return !host || e != hipSuccess ? e : hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice);
+    }
+    hipError_t alloc_for(const T* host, size_t n) { return host ? alloc(n) : hipSuccess; }
+    hipError_t download(T* host, size_t n) const { return host ? hipMemcpy(host, p, n * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess; }
+};
+
+// A HIP event, destroyed with the object: an error between create() and the end of the scope does not leak it
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event&) = delete; Event& operator=(const Event&) = delete;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    hipError_t create() { return hipEventCreate(&e); }
+    hipError_t record(hipStream_t stream) { return hipEventRecord(e, stream); }
+    hipError_t synchronize() { return hipEventSynchronize(e); }
+    hipError_t elapsed_ms(const Event& since, float* ms) const { return hipEventElapsedTime(ms, since.e, e); }
 };
 
 // `aov`: the AOV renderers ignore strategy and max_depth (mi355pt_render_aov), so they are not checked for them
@@ -89,5 +114,18 @@ int check_args(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_
 // but never a split sample range —, with `illuminant_lut` for the albedo kind
 int render_accum_range(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, uint32_t s_begin, uint32_t s_end,
                        float* d_accum, void* hip_stream, mi355pt_stats* stats, const PathOut& pout, int aov_kind = -1, uint32_t illuminant_lut = 0);
+// what the tile-list entry and the adaptive driver ask of (scene, camera, params) beyond check_args
+int check_tiles_args(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p);
+// the scene's launch context with the hash table valid for `seed`; `slot` receives a fresh ring slot
+int get_launch_ctx(const mi355pt_scene* sc, uint32_t seed, LaunchCtx** out, int* slot);
+// the launches of [s_begin, s_end) into d_accum, arguments checked; with d_list, of the tiles d_list[0 .. n_list) (device memory)
+int launch_ranges(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, uint32_t s_begin, uint32_t s_end, float* d_accum,
+                  hipStream_t stream, mi355pt_stats* stats, const uint32_t* d_list, uint32_t n_list,
+                  const PathOut& pout = PathOut{nullptr, nullptr, nullptr, 0u, 0u}, int aov_kind = -1, uint32_t illuminant_lut = 0);
+// What every launch over a ring slot of `lc` shares: the slot's work counter zeroed on `stream`, then launch(d_counter, d_stats), which
+// returns an MI355PT_* code.  stats == NULL: nothing else, fully asynchronous.  Otherwise events around the launch, a wait for it, and
+// *stats = {kernel_ms, launches = 1}; with `counts` the slot's DevStats block is zeroed before the launch and read into *stats after it
+int timed_launch(LaunchCtx* lc, int slot, hipStream_t stream, mi355pt_stats* stats, bool counts,
+                 const std::function<int(unsigned* d_counter, DevStats* d_stats)>& launch);
 
 }  // namespace pt

@@ -13,11 +13,6 @@ using namespace pt;
 
 namespace {
 
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b) return false;
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
 bool bucket_count_ok(uint32_t k) { return k == 4u || k == 8u || k == 16u || k == 32u; }
 
 // every check of mi355pt_robust_combine_device / mi355pt_robust_combine; host arithmetic only
@@ -29,8 +24,7 @@ int combine_check(const float* buckets, uint32_t n_buckets, uint32_t spp_bucket,
     if (!bucket_count_ok(n_buckets)) return fail(MI355PT_E_INVALID, "robust combine: n_buckets must be 4, 8, 16 or 32");
     if (spp_bucket == 0) return fail(MI355PT_E_INVALID, "robust combine: spp_bucket must be > 0");
     if (width == 0 || height == 0) return fail(MI355PT_E_INVALID, "robust combine: zero width or height");
-    if (width > (1u << 24) || height > (1u << 24) || ((uint64_t)width * height) >> 32)
-        return fail(MI355PT_E_INVALID, "robust combine: frame too large (width and height up to 2^24, fewer than 2^32 pixels)");
+    if (frame_too_large(width, height)) return fail(MI355PT_E_INVALID, "robust combine: frame too large (width and height up to 2^24, fewer than 2^32 pixels)");
     const size_t pixels = (size_t)width * height, film_bytes = pixels * 3 * sizeof(float);
     const void* outs[3] = {out, out_half, out_trim};
     const size_t out_bytes[3] = {film_bytes, film_bytes, pixels * 2};
@@ -77,16 +71,14 @@ int mi355pt_robust_combine(const float* buckets, uint32_t n_buckets, uint32_t sp
     const size_t pixels = (size_t)width * height, n = pixels * 3;
     DevBuf<float> d_buckets, d_out, d_half;
     DevBuf<uint8_t> d_trim;
-    HIP_TRY(d_buckets.alloc(n * n_buckets));
-    HIP_TRY(hipMemcpy(d_buckets.p, buckets, n * n_buckets * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(d_buckets.upload(buckets, n * n_buckets));
     HIP_TRY(d_out.alloc(n));
-    if (out_half) HIP_TRY(d_half.alloc(n));
-    if (out_trim) HIP_TRY(d_trim.alloc(pixels * 2));
-    rc = mi355pt_robust_combine_device(d_buckets.p, n_buckets, spp_bucket, width, height, rp, d_out.p, out_half ? d_half.p : nullptr, out_trim ? d_trim.p : nullptr, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out, d_out.p, n * sizeof(float), hipMemcpyDeviceToHost));      // (synchronises the default stream)
-    if (out_half) HIP_TRY(hipMemcpy(out_half, d_half.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_trim) HIP_TRY(hipMemcpy(out_trim, d_trim.p, pixels * 2, hipMemcpyDeviceToHost));
+    HIP_TRY(d_half.alloc_for(out_half, n));
+    HIP_TRY(d_trim.alloc_for(out_trim, pixels * 2));
+    if ((rc = mi355pt_robust_combine_device(d_buckets.p, n_buckets, spp_bucket, width, height, rp, d_out.p, d_half.p, d_trim.p, nullptr))) return rc;
+    HIP_TRY(d_out.download(out, n));
+    HIP_TRY(d_half.download(out_half, n));
+    HIP_TRY(d_trim.download(out_trim, pixels * 2));
     return MI355PT_OK;
 }
 
@@ -130,7 +122,7 @@ int mi355pt_render_robust(const mi355pt_scene* s, const mi355pt_camera* cam, con
     if ((rc = mi355pt_render_buckets_device(s, cam, p, n_buckets, d_buckets.p, nullptr, nullptr))) return rc;
     if ((rc = mi355pt_robust_combine_device(d_buckets.p, n_buckets, p->spp / n_buckets, cam->width, cam->height, rp, d_theta.p, nullptr, nullptr, nullptr))) return rc;
     if ((rc = mi355pt_film_resolve_device(d_theta.p, cam->width * cam->height, 1u, d_rgb.p, nullptr))) return rc;
-    HIP_TRY(hipMemcpy(out_rgb, d_rgb.p, n * sizeof(float), hipMemcpyDeviceToHost));      // (synchronises the default stream)
+    HIP_TRY(d_rgb.download(out_rgb, n));
     return MI355PT_OK;
 }
 

@@ -34,11 +34,9 @@ int temporal_check(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355p
         return fail(MI355PT_E_INVALID, "temporal: the half films of the current frame, the previous frame and the output must all be given or all be NULL");
     if (spp == 0 || (half && (spp & 1u) != 0u)) return fail(MI355PT_E_INVALID, "temporal: spp must be > 0, and even with a half film (it holds the first spp / 2 samples)");
     if (width == 0 || height == 0) return fail(MI355PT_E_INVALID, "temporal: zero width or height");
-    if (width > (1u << 24) || height > (1u << 24) || denoise_grid_blocks(width, height) == 0) return fail(MI355PT_E_INVALID, "temporal: frame too large");
-    const float pos[3] = {tp->pos_tol, tp->min_weight, tp->max_history};
-    for (float v : pos)
-        if (!(std::isfinite(v) && v > 0.0f))
-            return fail(MI355PT_E_INVALID, "temporal: pos_tol, min_weight and max_history must be finite and > 0 (mi355pt_temporal_params_default fills the struct)");
+    if (frame_side_too_large(width, height) || denoise_grid_blocks(width, height) == 0) return fail(MI355PT_E_INVALID, "temporal: frame too large");
+    if (!all_finite_positive({tp->pos_tol, tp->min_weight, tp->max_history}))
+        return fail(MI355PT_E_INVALID, "temporal: pos_tol, min_weight and max_history must be finite and > 0 (mi355pt_temporal_params_default fills the struct)");
     if (tp->max_history < 1.0f) return fail(MI355PT_E_INVALID, "temporal: max_history must be >= 1");
     if (!(tp->normal_cos >= -1.0f && tp->normal_cos <= 1.0f)) return fail(MI355PT_E_INVALID, "temporal: normal_cos must be in [-1, 1]");
     const float* in[11] = {cur->film, cur->half, cur->position, cur->shading_normal, cur->hit, prev ? prev->film : nullptr, prev ? prev->half : nullptr,
@@ -78,14 +76,15 @@ TemporalArgs temporal_args(uint32_t spp, const mi355pt_temporal_view* view, uint
 int rectify_params_check(const mi355pt_temporal_rectify_params* rp) {
     if (!rp) return fail(MI355PT_E_INVALID, "temporal rectify: null rectify_params pointer");
     if (rp->radius < 1 || rp->radius > 3) return fail(MI355PT_E_INVALID, "temporal rectify: radius must be 1, 2 or 3 (mi355pt_temporal_rectify_params_default fills the struct)");
-    if (!(std::isfinite(rp->gamma) && rp->gamma > 0.0f)) return fail(MI355PT_E_INVALID, "temporal rectify: gamma must be finite and > 0");
+    if (!all_finite_positive({rp->gamma})) return fail(MI355PT_E_INVALID, "temporal rectify: gamma must be finite and > 0");
     return MI355PT_OK;
 }
 // ... and the device entry point's scratch
 int rectify_scratch_check(const mi355pt_temporal_frame* cur, const mi355pt_temporal_frame* prev, uint32_t width, uint32_t height, const void* scratch,
                           size_t scratch_bytes, const float* out_film, const float* out_half, const float* out_length) {
+    // (not scratch_verdict: this entry point names the alignment before the size)
     if (!scratch) return fail(MI355PT_E_INVALID, "temporal rectify: null scratch pointer");
-    if (((uintptr_t)scratch & 15u) != 0) return fail(MI355PT_E_INVALID, "temporal rectify: the scratch must be 16-byte aligned");
+    if (misaligned(scratch, 16)) return fail(MI355PT_E_INVALID, "temporal rectify: the scratch must be 16-byte aligned");
     const size_t need = mi355pt_temporal_rectify_scratch_bytes(width, height);
     if (need == 0 || scratch_bytes < need) return fail(MI355PT_E_INVALID, "temporal rectify: scratch smaller than mi355pt_temporal_rectify_scratch_bytes(width, height)");
     const void* other[15] = {cur->film, cur->half, cur->length, cur->position, cur->shading_normal, cur->hit, prev ? prev->film : nullptr,
@@ -111,32 +110,25 @@ int temporal_accumulate_host(const mi355pt_temporal_frame* cur, uint32_t spp, co
     for (int k = 0; k < 2; ++k) {
         if (!host[k]) continue;
         const float* src[6] = {host[k]->film, host[k]->half, k == 0 ? nullptr : host[k]->length, host[k]->position, host[k]->shading_normal, host[k]->hit};
-        const float* dst[6] = {};
-        for (int i = 0; i < 6; ++i) {
-            if (!src[i]) continue;
-            const size_t count = i == 2 ? np : n;
-            HIP_TRY(d_in[k][i].alloc(count));
-            HIP_TRY(hipMemcpy(d_in[k][i].p, src[i], count * sizeof(float), hipMemcpyHostToDevice));
-            dst[i] = d_in[k][i].p;
-        }
-        dev[k].film = dst[0]; dev[k].half = dst[1]; dev[k].length = dst[2]; dev[k].position = dst[3]; dev[k].shading_normal = dst[4]; dev[k].hit = dst[5];
+        const DevBuf<float>* d = d_in[k];
+        for (int i = 0; i < 6; ++i) HIP_TRY(d_in[k][i].upload(src[i], i == 2 ? np : n));
+        dev[k].film = d[0].p; dev[k].half = d[1].p; dev[k].length = d[2].p; dev[k].position = d[3].p; dev[k].shading_normal = d[4].p; dev[k].hit = d[5].p;
     }
     HIP_TRY(d_film.alloc(n));
     HIP_TRY(d_len.alloc(np));
-    if (out_half) HIP_TRY(d_half.alloc(n));
+    HIP_TRY(d_half.alloc_for(out_half, n));
     if (rp) {
         const size_t scratch_bytes = mi355pt_temporal_rectify_scratch_bytes(width, height);
         HIP_TRY(d_scratch.alloc(scratch_bytes));
         rc = mi355pt_temporal_accumulate_rectified_device(&dev[0], spp, prev ? &dev[1] : nullptr, view, width, height, tp, rp, d_scratch.p, scratch_bytes, d_film.p,
-                                                          out_half ? d_half.p : nullptr, d_len.p, nullptr);
+                                                          d_half.p, d_len.p, nullptr);
     } else {
-        rc = mi355pt_temporal_accumulate_device(&dev[0], spp, prev ? &dev[1] : nullptr, view, width, height, tp, d_film.p, out_half ? d_half.p : nullptr, d_len.p,
-                                                nullptr);
+        rc = mi355pt_temporal_accumulate_device(&dev[0], spp, prev ? &dev[1] : nullptr, view, width, height, tp, d_film.p, d_half.p, d_len.p, nullptr);
     }
     if (rc) return rc;
-    HIP_TRY(hipMemcpy(out_film, d_film.p, n * sizeof(float), hipMemcpyDeviceToHost));      // (synchronises the default stream)
-    if (out_half) HIP_TRY(hipMemcpy(out_half, d_half.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_length, d_len.p, np * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(d_film.download(out_film, n));
+    HIP_TRY(d_half.download(out_half, n));
+    HIP_TRY(d_len.download(out_length, np));
     return MI355PT_OK;
 }
 

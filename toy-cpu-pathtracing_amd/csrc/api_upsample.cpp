@@ -26,7 +26,7 @@ int upsample_check(const float* low_film, const float* low_half, uint32_t spp, c
     if (spp == 0 || (half && (spp & 1u) != 0u)) return fail(MI355PT_E_INVALID, "upsample: spp must be > 0, and even with a half film (it holds the first spp / 2 samples)");
     if (width == 0 || height == 0) return fail(MI355PT_E_INVALID, "upsample: zero width or height");
     if ((width & 1u) != 0u || (height & 1u) != 0u) return fail(MI355PT_E_INVALID, "upsample: width and height (the FULL size) must be even: the low frame is width / 2 x height / 2");
-    if (width > (1u << 24) || height > (1u << 24) || denoise_grid_blocks(width, height) == 0) return fail(MI355PT_E_INVALID, "upsample: frame too large");
+    if (frame_side_too_large(width, height) || denoise_grid_blocks(width, height) == 0) return fail(MI355PT_E_INVALID, "upsample: frame too large");
     const float fin[4] = {up->pos_tol, up->emitter_tol, up->min_weight, up->albedo_eps};
     for (float v : fin)
         if (!std::isfinite(v)) return fail(MI355PT_E_INVALID, "upsample: pos_tol, emitter_tol, min_weight and albedo_eps must be finite");
@@ -92,22 +92,14 @@ int mi355pt_upsample(const float* low_film, const float* low_half, uint32_t spp,
     const size_t n_full = (size_t)width * height * 3, n_low = (size_t)(width / 2) * (height / 2) * 3;
     // the low film, the low half film, the guides of the two resolutions in the order of mi355pt_upsample_guides
     const float* src[10] = {low_film, low_half, lg->albedo, lg->shading_normal, lg->position, lg->hit, fg->albedo, fg->shading_normal, fg->position, fg->hit};
-    const float* dst[10] = {};
-    DevBuf<float> d_in[10], d_film, d_half;
-    for (int i = 0; i < 10; ++i) {
-        if (!src[i]) continue;
-        const size_t count = i < 6 ? n_low : n_full;
-        HIP_TRY(d_in[i].alloc(count));
-        HIP_TRY(hipMemcpy(d_in[i].p, src[i], count * sizeof(float), hipMemcpyHostToDevice));
-        dst[i] = d_in[i].p;
-    }
+    DevBuf<float> d[10], d_film, d_half;
+    for (int i = 0; i < 10; ++i) HIP_TRY(d[i].upload(src[i], i < 6 ? n_low : n_full));
     HIP_TRY(d_film.alloc(n_full));
-    if (out_half) HIP_TRY(d_half.alloc(n_full));
-    const mi355pt_upsample_guides dl{dst[2], dst[3], dst[4], dst[5]}, df{dst[6], dst[7], dst[8], dst[9]};
-    rc = mi355pt_upsample_device(dst[0], dst[1], spp, &dl, spp_albedo_low, &df, spp_albedo_full, width, height, up, d_film.p, out_half ? d_half.p : nullptr, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(out_film, d_film.p, n_full * sizeof(float), hipMemcpyDeviceToHost));      // (synchronises the default stream)
-    if (out_half) HIP_TRY(hipMemcpy(out_half, d_half.p, n_full * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(d_half.alloc_for(out_half, n_full));
+    const mi355pt_upsample_guides dl{d[2].p, d[3].p, d[4].p, d[5].p}, df{d[6].p, d[7].p, d[8].p, d[9].p};
+    if ((rc = mi355pt_upsample_device(d[0].p, d[1].p, spp, &dl, spp_albedo_low, &df, spp_albedo_full, width, height, up, d_film.p, d_half.p, nullptr))) return rc;
+    HIP_TRY(d_film.download(out_film, n_full));
+    HIP_TRY(d_half.download(out_half, n_full));
     return MI355PT_OK;
 }
 

@@ -1,4 +1,5 @@
-// Every host-callable function a .hip translation unit defines for api.cpp / api_debug.cpp, declared ONCE: the callers and the defining
+// Every host-callable function a .hip translation unit defines for the host files (api.cpp, the api_*.cpp and scene_*.cpp files, through
+// api_internal.hpp), declared ONCE: the callers and the defining
 // units include this header, so a signature that drifts is a compile error (and PathOut, a kernel parameter, has one definition).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -40,7 +41,7 @@ hipError_t launch_aov(uint32_t kind, const DevScene&, const DevCamera&, const De
 int query_resident_waves_aov(uint32_t kind, uint32_t feat);
 hipError_t launch_aov_resolve(uint32_t kind, const float* d_accum, uint32_t n_values, uint32_t spp, float* d_out, hipStream_t);
 // pt_kernels_gbuffer.hip: the G-buffer pass (include/mi355pt_gbuffer.h): one primary-ray launch, up to four films (nullptr = not wanted).
-// The plan must have block_log2 == 3 and chunks == 1 (api.cpp plan_gbuffer): one pixel per lane, its sums in registers
+// The plan must have block_log2 == 3 and chunks == 1 (api_gbuffer.cpp plan_gbuffer): one pixel per lane, its sums in registers
 struct GbufferFilms { float *albedo, *shading_normal, *position, *hit; };
 hipError_t launch_gbuffer(const DevScene&, const DevCamera&, const DevParams&, uint32_t illuminant_lut, const uint64_t* d_hash, const GbufferFilms&,
                           unsigned* d_counter, DevStats* d_stats, uint32_t feat, int grid, hipStream_t);

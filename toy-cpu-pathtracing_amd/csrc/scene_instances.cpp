@@ -20,11 +20,6 @@ namespace {
 
 double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
 // a buffer of the move's own, allocated by the first move after a build and freed with the scene
 template <typename T>
 hipError_t ensure(SceneImpl* s, T** p, size_t count) {
@@ -122,9 +117,9 @@ int mi355pt_scene_move_instances(mi355pt_scene* s, const mi355pt_camera* cam, co
     if ((e = hipMemcpy(rb.d_moved_bits, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess) return dropped("hipMemcpy", e);
     if (!light_pdf.empty() && (e = hipMemcpy(rb.d_light_pdf, light_pdf.data(), light_pdf.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return dropped("hipMemcpy", e);
     if ((e = hipMemset(rb.d_count, 0, sizeof(uint32_t))) != hipSuccess) return dropped("hipMemset", e);
-    Events ev;
-    if ((e = hipEventCreate(&ev.a)) != hipSuccess || (e = hipEventCreate(&ev.b)) != hipSuccess) return dropped("hipEventCreate", e);
-    if ((e = hipEventRecord(ev.a, stream)) != hipSuccess) return dropped("hipEventRecord", e);
+    Event ev_a, ev_b;
+    if ((e = ev_a.create()) != hipSuccess || (e = ev_b.create()) != hipSuccess) return dropped("hipEventCreate", e);
+    if ((e = ev_a.record(stream)) != hipSuccess) return dropped("hipEventRecord", e);
     if ((e = launch_rebase_tris(d.tris_local, d.instances, (DevTri*)d.tris_render, d.n_tris, true, rb.d_count, stream)) != hipSuccess) return dropped("launch_rebase_tris", e);
     ++r.launches;
     if ((e = launch_shade_refresh((DevTriShade*)d.shade, d.tris_local, d.instances, rb.d_moved_bits, d.lights, rb.d_light_pdf, d.n_tris, (uint32_t)impl.instances.size(),
@@ -144,9 +139,9 @@ int mi355pt_scene_move_instances(mi355pt_scene* s, const mi355pt_camera* cam, co
         if ((e = launch_sah_cost(d.nodes, d.root, rb.d_entries, rb.n_entries, rb.d_sah, stream)) != hipSuccess) return dropped("launch_sah_cost", e);
         r.launches += SAH_COST_LAUNCHES;
     }
-    if ((e = hipEventRecord(ev.b, stream)) != hipSuccess || (e = hipEventSynchronize(ev.b)) != hipSuccess) return dropped("hipEventSynchronize", e);
+    if ((e = ev_b.record(stream)) != hipSuccess || (e = ev_b.synchronize()) != hipSuccess) return dropped("hipEventSynchronize", e);
     float ms = 0.0f;
-    if ((e = hipEventElapsedTime(&ms, ev.a, ev.b)) != hipSuccess) return dropped("hipEventElapsedTime", e);
+    if ((e = ev_b.elapsed_ms(ev_a, &ms)) != hipSuccess) return dropped("hipEventElapsedTime", e);
     r.device_ms = ms;
     uint32_t n_degenerate = 0;
     if ((e = hipMemcpy(&n_degenerate, rb.d_count, sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess) return dropped("hipMemcpy", e);

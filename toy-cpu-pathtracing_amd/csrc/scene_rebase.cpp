@@ -30,11 +30,6 @@ int upload_words(SceneImpl* s, const std::vector<uint32_t>& v, uint32_t** out, s
     return MI355PT_OK;
 }
 
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
 int digests_out(const LoweredScene& ls, const LowerReport& rep, bool gpu_builder, char* names_buf, size_t names_len, uint64_t* digests, uint32_t* n) {
     std::vector<std::string> names; std::vector<uint64_t> dig;
     lowering_digests(ls, rep, &names, &dig);
@@ -216,10 +211,10 @@ int mi355pt_scene_move_camera(mi355pt_scene* s, const mi355pt_camera* cam, mi355
     if (!rec.lights.empty() && (e = hipMemcpy((void*)d.lights, rec.lights.data(), rec.lights.size() * sizeof(DevLight), hipMemcpyHostToDevice)) != hipSuccess) return dropped("hipMemcpy", e);
     if (!rec.light_tris.empty() && (e = hipMemcpy((void*)d.light_tris, rec.light_tris.data(), rec.light_tris.size() * sizeof(DevLightTri), hipMemcpyHostToDevice)) != hipSuccess) return dropped("hipMemcpy", e);
     if ((e = hipMemset(rb.d_count, 0, sizeof(uint32_t))) != hipSuccess) return dropped("hipMemset", e);
-    Events ev;
-    if ((e = hipEventCreate(&ev.a)) != hipSuccess || (e = hipEventCreate(&ev.b)) != hipSuccess) return dropped("hipEventCreate", e);
+    Event ev_a, ev_b;
+    if ((e = ev_a.create()) != hipSuccess || (e = ev_b.create()) != hipSuccess) return dropped("hipEventCreate", e);
     hipStream_t stream = nullptr;
-    if ((e = hipEventRecord(ev.a, stream)) != hipSuccess) return dropped("hipEventRecord", e);
+    if ((e = ev_a.record(stream)) != hipSuccess) return dropped("hipEventRecord", e);
 #if !PT_NODE_Q16
     if ((e = launch_rebase_tris(d.tris_local, d.instances, (DevTri*)d.tris_render, d.n_tris, !rb.tris_are_local, rb.d_count, stream)) != hipSuccess) return dropped("launch_rebase_tris", e);
     ++r.launches;
@@ -234,9 +229,9 @@ int mi355pt_scene_move_camera(mi355pt_scene* s, const mi355pt_camera* cam, mi355
         ++r.launches;
     }
 #endif
-    if ((e = hipEventRecord(ev.b, stream)) != hipSuccess || (e = hipEventSynchronize(ev.b)) != hipSuccess) return dropped("hipEventSynchronize", e);
+    if ((e = ev_b.record(stream)) != hipSuccess || (e = ev_b.synchronize()) != hipSuccess) return dropped("hipEventSynchronize", e);
     float ms = 0.0f;
-    if ((e = hipEventElapsedTime(&ms, ev.a, ev.b)) != hipSuccess) return dropped("hipEventElapsedTime", e);
+    if ((e = ev_b.elapsed_ms(ev_a, &ms)) != hipSuccess) return dropped("hipEventElapsedTime", e);
     r.device_ms = ms;
     uint32_t n_degenerate = 0;
     if ((e = hipMemcpy(&n_degenerate, rb.d_count, sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess) return dropped("hipMemcpy", e);
