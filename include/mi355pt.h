@@ -367,10 +367,19 @@ const char* mi355pt_version(void);
 /* EXTENSION, no reference counterpart: mi355pt_scene_set_instance_dynamic, mi355pt_instance_move_params, mi355pt_instance_move_result and
  * mi355pt_scene_move_instances — new local_to_world matrices for instances of the built scene, applied on the device: positions
  * re-transformed, the moved instances' shading normals and light pdfs refreshed, both trees refit, moved area lights' tables recomputed, and
- * the SAH cost of the refit tree reported so that the caller knows when to build again.  Refit only; the temporal accumulation assumes a
- * static world and has no object motion vectors.  Declared in its own header, which this one always includes (ahead of the
- * variance-guided denoiser's, which stays the last one). */
+ * the SAH cost of the refit tree reported so that the caller knows when to build again.  Refit only; the temporal accumulation of
+ * mi355pt_temporal.h assumes a static world: accumulate across an instance move with the object motion vectors of mi355pt_motion.h below.
+ * Declared in its own header, which this one always includes (ahead of the variance-guided denoiser's, which stays the last one). */
 #include "mi355pt_instances.h"
+
+/* ---------------- object motion vectors ---------------- */
+/* EXTENSION, no reference counterpart: mi355pt_motion_xform, mi355pt_render_ids_device and mi355pt_render_ids (which instance a pixel shows:
+ * one primary ray through the pixel centre), mi355pt_motion_table (host: where the points of each instance were one frame ago) and
+ * mi355pt_temporal_accumulate_motion_device, mi355pt_temporal_accumulate_motion, mi355pt_temporal_accumulate_rectified_motion_device and
+ * mi355pt_temporal_accumulate_rectified_motion — the twins of the temporal accumulation and its rectified form that carry a pixel's hit
+ * through its instance's motion, so that the history survives an instance move.  Declared in its own header, which this one always
+ * includes (ahead of the variance-guided denoiser's, which stays the last one). */
+#include "mi355pt_motion.h"
 
 /* ---------------- variance-guided denoiser ---------------- */
 /* EXTENSION, no reference counterpart: a second filter beside the one above, which it leaves as it is — mi355pt_denoise_var_params,

@@ -31,8 +31,8 @@
  * instance that was lowered as a pure translation stays one (give it a rotation and the call rebuilds), and a scene in local-triangle mode
  * rebuilds on every move — mark what will move with mi355pt_scene_set_instance_dynamic BEFORE the build.  A triangle that becomes or
  * stops being degenerate (an exactly zero cross product in render space) rebuilds.  Scenes built with mi355pt_scene_build_multi are not
- * moved.  The temporal accumulation (mi355pt_temporal.h) reprojects a hit into the previous CAMERA and assumes a static world: it has no
- * object motion vectors, so do not accumulate across an instance move.
+ * moved.  The temporal accumulation (mi355pt_temporal.h) reprojects a hit into the previous CAMERA and assumes a static world: across an
+ * instance move accumulate with the object motion vectors of mi355pt_motion.h (the ID pass, the motion table, the motion-aware twins).
  */
 #ifndef MI355PT_INSTANCES_H
 #define MI355PT_INSTANCES_H

@@ -30,5 +30,17 @@ enum class Scratch { OK, MISSING, TOO_SMALL, MISALIGNED };
 inline Scratch scratch_verdict(const void* p, size_t have, size_t need, size_t align) {
     return !p ? Scratch::MISSING : have < need ? Scratch::TOO_SMALL : misaligned(p, align) ? Scratch::MISALIGNED : Scratch::OK;
 }
+// what is wrong with the id buffers and the table of a motion-aware accumulation (include/mi355pt_motion.h): the first that applies, in
+// this order.  ids_prev may be null; `outs`: the call's n_outs output pointers (null ones among them) and, for the rectified form, its scratch
+enum class Motion { OK, MISSING, NO_ENTRIES, MISALIGNED, ALIASES_OUTPUT };
+inline Motion motion_verdict(const void* ids_cur, const void* ids_prev, const void* table, uint32_t n_entries, size_t table_align, const void* const* outs,
+                             int n_outs) {
+    if (!ids_cur || !table) return Motion::MISSING;
+    if (n_entries == 0u) return Motion::NO_ENTRIES;
+    if (misaligned(table, table_align)) return Motion::MISALIGNED;
+    for (int i = 0; i < n_outs; ++i)
+        if (outs[i] && (outs[i] == ids_cur || outs[i] == ids_prev || outs[i] == table)) return Motion::ALIASES_OUTPUT;
+    return Motion::OK;
+}
 
 }  // namespace pt

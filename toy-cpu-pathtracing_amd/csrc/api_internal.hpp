@@ -26,6 +26,7 @@ struct LaunchCtx {
     int waves[2][2][3] = {{{0}}};     // [instrumented][sampler][strategy]: resident waves of the kernel that combination launches (0: not asked yet)
     int aov_waves[3] = {0, 0, 0};     // [MI355PT_AOV_*]: the same for the AOV kernel of this scene's feature set
     int gbuffer_waves = 0;            // ... and for the G-buffer kernel (pt_kernels_gbuffer.hip)
+    int ids_waves = 0;                // ... and for the ID pass (pt_kernels_ids.hip)
     uint64_t* d_hash = nullptr;
     uint32_t hash_seed = 0;
     bool hash_valid = false;
@@ -127,5 +128,14 @@ int launch_ranges(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355
 // *stats = {kernel_ms, launches = 1}; with `counts` the slot's DevStats block is zeroed before the launch and read into *stats after it
 int timed_launch(LaunchCtx* lc, int slot, hipStream_t stream, mi355pt_stats* stats, bool counts,
                  const std::function<int(unsigned* d_counter, DevStats* d_stats)>& launch);
+// api_temporal.cpp, for api_motion.cpp's twins: every check of mi355pt_temporal_accumulate[_device], what mi355pt_temporal_rectify.h adds
+// to them, and the kernels' arguments from the checked ones
+int temporal_check(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev, const mi355pt_temporal_view* view, uint32_t width,
+                   uint32_t height, const mi355pt_temporal_params* tp, const float* out_film, const float* out_half, const float* out_length);
+int rectify_params_check(const mi355pt_temporal_rectify_params* rp);
+int rectify_scratch_check(const mi355pt_temporal_frame* cur, const mi355pt_temporal_frame* prev, uint32_t width, uint32_t height, const void* scratch,
+                          size_t scratch_bytes, const float* out_film, const float* out_half, const float* out_length);
+TemporalFrameDev frame_dev(const mi355pt_temporal_frame& f);
+TemporalArgs temporal_args(uint32_t spp, const mi355pt_temporal_view* view, uint32_t width, uint32_t height, const mi355pt_temporal_params* tp);
 
 }  // namespace pt

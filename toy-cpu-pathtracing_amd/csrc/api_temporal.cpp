@@ -20,6 +20,11 @@ bool normalize3(const float v[3], double out[3]) {
     return true;
 }
 
+}  // namespace
+
+// (declared in api_internal.hpp: api_motion.cpp runs the same checks and builds the same kernel arguments)
+namespace pt {
+
 // every check of mi355pt_temporal_accumulate_device / mi355pt_temporal_accumulate; host arithmetic only
 int temporal_check(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev, const mi355pt_temporal_view* view, uint32_t width,
                    uint32_t height, const mi355pt_temporal_params* tp, const float* out_film, const float* out_half, const float* out_length) {
@@ -94,6 +99,10 @@ int rectify_scratch_check(const mi355pt_temporal_frame* cur, const mi355pt_tempo
         if (q == scratch) return fail(MI355PT_E_INVALID, "temporal rectify: the scratch must not be one of the inputs or outputs");
     return MI355PT_OK;
 }
+
+}  // namespace pt
+
+namespace {
 
 // the two host-buffer entry points: device copies of the films, the device entry point (rectified when rp is given, with a scratch of its
 // own) on the default stream, the outputs copied back.  Every argument has been checked.

@@ -85,6 +85,21 @@ hipError_t launch_temporal_accumulate(const TemporalFrameDev& cur, const Tempora
 constexpr size_t TEMPORAL_RECTIFY_RECORD_BYTES = 32;
 hipError_t launch_temporal_rectify(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, uint32_t radius, float gamma, void* d_scratch,
                                    float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
+// pt_kernels_ids.hip: the ID pass (include/mi355pt_motion.h): one primary ray through every pixel centre, instance + 1 of the closest hit or
+// 0 into d_ids.  The plan must have block_log2 == 3 and chunks == 1 (api_motion.cpp, the G-buffer pass's plan): one pixel per lane
+hipError_t launch_ids(const DevScene&, const DevCamera&, const DevParams&, uint32_t* d_ids, unsigned* d_counter, DevStats* d_stats, int grid, hipStream_t);
+int query_resident_waves_ids();
+// pt_kernels_temporal.hip / pt_kernels_temporal_rectify.hip: the motion-aware twins of the two launchers above (include/mi355pt_motion.h),
+// of a frame WITH a previous frame (the first frame has nothing to reproject: api_motion.cpp sends it to launch_temporal_accumulate).
+// A table record as the kernels load it: six 16-byte loads, so the table is 16-byte aligned.  ids_prev == nullptr: no id test of the taps;
+// last_entry = n_entries - 1, the clamp of a pixel's id.  args.delta is not read
+struct MotionXformDev { float a[9], b[3], n[9], pad[3]; };
+static_assert(sizeof(MotionXformDev) == 96, "a motion record is six float4");
+struct MotionArgs { const uint32_t* ids_cur; const uint32_t* ids_prev; const MotionXformDev* table; uint32_t last_entry; };
+hipError_t launch_temporal_accumulate_motion(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const MotionArgs& motion,
+                                             float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
+hipError_t launch_temporal_rectify_motion(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const MotionArgs& motion, uint32_t radius,
+                                          float gamma, void* d_scratch, float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
 // pt_kernels_upsample.hip: the guided half-resolution upsample (include/mi355pt_upsample.h): one launch on the grid of denoise_grid_blocks
 // over the FULL frame.  The G-buffer sums of one resolution as the kernel takes them (albedo == nullptr: not given, then on both sides);
 // low_half == nullptr: no half film (then out_half is not written).  The launcher fills UpsampleArgs::blocks_x

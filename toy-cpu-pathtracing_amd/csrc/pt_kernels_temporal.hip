@@ -25,7 +25,30 @@ __global__ __launch_bounds__(DN_BLOCK_X * DN_BLOCK_Y) void temporal_accumulate_k
                                                                                       float* __restrict__ out_film, float* __restrict__ out_half,
                                                                                       float* __restrict__ out_length) {
 #define PT_TP_RECORD false
+#define PT_TP_MOTION false
 #include "pt_temporal_gather.inc"
+#undef PT_TP_MOTION
+#undef PT_TP_RECORD
+
+    out_length[p] = L;
+    if constexpr (HAS_HALF) {
+        out_half[3 * p] = m1[0]; out_half[3 * p + 1] = m1[1]; out_half[3 * p + 2] = m1[2];
+        out_film[3 * p] = m1[0] + m2[0]; out_film[3 * p + 1] = m1[1] + m2[1]; out_film[3 * p + 2] = m1[2] + m2[2];
+    } else {
+        out_film[3 * p] = m1[0]; out_film[3 * p + 1] = m1[1]; out_film[3 * p + 2] = m1[2];
+    }
+}
+
+// The motion-aware twin (include/mi355pt_motion.h): the same body with PT_TP_MOTION, the same epilogue.  Launched with a previous frame
+// only (HAS_PREV == true): the first frame reprojects nothing and takes the kernel above
+template <bool HAS_HALF, bool HAS_PREV, bool HAS_PREV_IDS>
+__global__ __launch_bounds__(DN_BLOCK_X * DN_BLOCK_Y) void temporal_accumulate_motion_kernel(TemporalFrameDev cur, TemporalFrameDev prev, TemporalArgs a,
+                                                                                             MotionArgs mo, float* __restrict__ out_film,
+                                                                                             float* __restrict__ out_half, float* __restrict__ out_length) {
+#define PT_TP_RECORD false
+#define PT_TP_MOTION true
+#include "pt_temporal_gather.inc"
+#undef PT_TP_MOTION
 #undef PT_TP_RECORD
 
     out_length[p] = L;
@@ -51,6 +74,22 @@ hipError_t launch_temporal_accumulate(const TemporalFrameDev& cur, const Tempora
     if (has_half && prev) PT_TP_LAUNCH(true, true);
     else if (has_half) PT_TP_LAUNCH(true, false);
     else if (prev) PT_TP_LAUNCH(false, true);
+    else PT_TP_LAUNCH(false, false);
+#undef PT_TP_LAUNCH
+    return hipGetLastError();
+}
+
+// (called from api_motion.cpp, which has checked every argument)
+hipError_t launch_temporal_accumulate_motion(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const MotionArgs& motion,
+                                             float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t stream) {
+    args.blocks_x = (uint32_t)(((uint64_t)args.width + DN_BLOCK_X - 1) / DN_BLOCK_X);
+    const dim3 grid(denoise_grid_blocks(args.width, args.height)), block(DN_BLOCK_X, DN_BLOCK_Y);
+    const bool has_half = cur.half != nullptr, has_ids = motion.ids_prev != nullptr;
+#define PT_TP_LAUNCH(HALF, IDS) \
+    hipLaunchKernelGGL((temporal_accumulate_motion_kernel<HALF, true, IDS>), grid, block, 0, stream, cur, prev, args, motion, d_out_film, d_out_half, d_out_length)
+    if (has_half && has_ids) PT_TP_LAUNCH(true, true);
+    else if (has_half) PT_TP_LAUNCH(true, false);
+    else if (has_ids) PT_TP_LAUNCH(false, true);
     else PT_TP_LAUNCH(false, false);
 #undef PT_TP_LAUNCH
     return hipGetLastError();

@@ -32,7 +32,24 @@ template <bool HAS_HALF, bool HAS_PREV>
 __global__ __launch_bounds__(DN_BLOCK_X * DN_BLOCK_Y) void temporal_gather_kernel(TemporalFrameDev cur, TemporalFrameDev prev, TemporalArgs a,
                                                                                   float4* __restrict__ record) {
 #define PT_TP_RECORD true
+#define PT_TP_MOTION false
 #include "pt_temporal_gather.inc"
+#undef PT_TP_MOTION
+#undef PT_TP_RECORD
+
+    record[2 * p] = make_float4(m1[0], m1[1], m1[2], m2[0]);
+    record[2 * p + 1] = make_float4(m2[1], m2[2], L, 0.0f);
+}
+
+// The motion-aware twin of the gather (include/mi355pt_motion.h): the same body with PT_TP_MOTION, the same record.  The rectifying
+// kernel below reads the records of either
+template <bool HAS_HALF, bool HAS_PREV, bool HAS_PREV_IDS>
+__global__ __launch_bounds__(DN_BLOCK_X * DN_BLOCK_Y) void temporal_gather_motion_kernel(TemporalFrameDev cur, TemporalFrameDev prev, TemporalArgs a,
+                                                                                         MotionArgs mo, float4* __restrict__ record) {
+#define PT_TP_RECORD true
+#define PT_TP_MOTION true
+#include "pt_temporal_gather.inc"
+#undef PT_TP_MOTION
 #undef PT_TP_RECORD
 
     record[2 * p] = make_float4(m1[0], m1[1], m1[2], m2[0]);
@@ -178,6 +195,27 @@ hipError_t launch_temporal_rectify(const TemporalFrameDev& cur, const TemporalFr
     const bool has_half = cur.half != nullptr;
     if (has_half) hipLaunchKernelGGL((temporal_gather_kernel<true, true>), grid, block, 0, stream, cur, prev, args, record);
     else hipLaunchKernelGGL((temporal_gather_kernel<false, true>), grid, block, 0, stream, cur, prev, args, record);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (has_half) launch_rectify_radius<true>(radius, grid, block, stream, cur, args, gamma, record, d_out_film, d_out_half, d_out_length);
+    else launch_rectify_radius<false>(radius, grid, block, stream, cur, args, gamma, record, d_out_film, d_out_half, d_out_length);
+    return hipGetLastError();
+}
+
+// (called from api_motion.cpp, which has checked every argument)
+hipError_t launch_temporal_rectify_motion(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const MotionArgs& motion, uint32_t radius,
+                                          float gamma, void* d_scratch, float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t stream) {
+    if (radius < 1 || radius > 3) return hipErrorInvalidValue;
+    args.blocks_x = (uint32_t)(((uint64_t)args.width + DN_BLOCK_X - 1) / DN_BLOCK_X);
+    const dim3 grid(denoise_grid_blocks(args.width, args.height)), block(DN_BLOCK_X, DN_BLOCK_Y);
+    float4* record = (float4*)d_scratch;
+    const bool has_half = cur.half != nullptr, has_ids = motion.ids_prev != nullptr;
+#define PT_TR_GATHER(HALF, IDS) hipLaunchKernelGGL((temporal_gather_motion_kernel<HALF, true, IDS>), grid, block, 0, stream, cur, prev, args, motion, record)
+    if (has_half && has_ids) PT_TR_GATHER(true, true);
+    else if (has_half) PT_TR_GATHER(true, false);
+    else if (has_ids) PT_TR_GATHER(false, true);
+    else PT_TR_GATHER(false, false);
+#undef PT_TR_GATHER
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (has_half) launch_rectify_radius<true>(radius, grid, block, stream, cur, args, gamma, record, d_out_film, d_out_half, d_out_length);

@@ -7,6 +7,10 @@
 //                           history m1 = hist1, m2 = hist2 (hist, 0 without a half film), L = min(Lh + 1, max_history), or L = 0 and
 //                           m1 = m2 = 0 for a pixel without history.
 // A thread outside the frame has returned.
+//   PT_TP_MOTION == false   the static world of mi355pt_temporal.h: Xp = X + a.delta.  The text of the kernels as they were.
+//   PT_TP_MOTION == true    include/mi355pt_motion.h: the including kernel has one more template parameter, bool HAS_PREV_IDS, and one
+//                           more kernel parameter, MotionArgs mo.  The pixel's id picks a record of mo.table, which carries X and nrm
+//                           into the previous render space (a.delta is not read); with HAS_PREV_IDS a tap must show the pixel's id.
 //
 // A pixel's hit position is projected into the previous camera, and the previous frame's accumulated films are gathered with a 2 x 2
 // bilinear footprint.  The four taps' loads are UNCONDITIONAL, at indices clamped to the frame: whether a pixel has a history at all (no
@@ -36,10 +40,26 @@
 
     if constexpr (HAS_PREV) {
         // geometry of p (h == 0 makes NaNs and infinities: `ok` selects them away)
+#if PT_TP_MOTION
+        // the pixel's id and its motion record (six 16-byte loads), issued ahead of the geometry's divisions: one dependent round trip
+        // more than the static kernel has, and it is over when the quotients are
+        const uint32_t idc = mo.ids_cur[p];
+        const float4* const mrec = (const float4*)(mo.table + (idc < mo.last_entry ? idc : mo.last_entry));
+        const float4 m0 = mrec[0], m1r = mrec[1], m2r = mrec[2], m3 = mrec[3], m4 = mrec[4], m5 = mrec[5];
+#endif
         const float3u P = tp_load3(cur.position, p), N = tp_load3(cur.shading_normal, p);
         const float hx = cur.hit[3 * p], h = cur.hit[3 * p + 1];
+#if PT_TP_MOTION
+        // a = m0.xyzw m1r.xyzw m2r.x,  b = m2r.yzw,  n = m3.xyzw m4.xyzw m5.x: Xp = a X + b, nrm = n nrm — both in the previous render space
+        const float X0 = P.x / h, X1 = P.y / h, X2 = P.z / h;
+        const float Xx = tp_dot(m0.x, m0.y, m0.z, X0, X1, X2) + m2r.y, Xy = tp_dot(m0.w, m1r.x, m1r.y, X0, X1, X2) + m2r.z,
+                    Xz = tp_dot(m1r.z, m1r.w, m2r.x, X0, X1, X2) + m2r.w;
+        const float n0 = 2.0f * (N.x / h) - 1.0f, n1 = 2.0f * (N.y / h) - 1.0f, n2 = 2.0f * (N.z / h) - 1.0f;
+        const float nx = tp_dot(m3.x, m3.y, m3.z, n0, n1, n2), ny = tp_dot(m3.w, m4.x, m4.y, n0, n1, n2), nz = tp_dot(m4.z, m4.w, m5.x, n0, n1, n2);
+#else
         const float Xx = P.x / h + a.delta[0], Xy = P.y / h + a.delta[1], Xz = P.z / h + a.delta[2];        // Xp
         const float nx = 2.0f * (N.x / h) - 1.0f, ny = 2.0f * (N.y / h) - 1.0f, nz = 2.0f * (N.z / h) - 1.0f;
+#endif
         const float t = hx / h;
         // projection into the previous image
         const float vx = tp_dot(a.rows[0], a.rows[1], a.rows[2], Xx, Xy, Xz);
@@ -60,6 +80,9 @@
         float w[4], len[4], hq[4];
         bool inside[4];
         float3u Pq[4], Nq[4], f[4], g[4];
+#if PT_TP_MOTION
+        bool same[4] = {true, true, true, true};          // the tap shows the pixel's instance (always, without the previous frame's ids)
+#endif
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int qx = x0 + (k & 1), qy = y0 + (k >> 1);
@@ -71,6 +94,9 @@
             Pq[k] = tp_load3(prev.position, q); Nq[k] = tp_load3(prev.shading_normal, q);
             f[k] = tp_load3(prev.film, q);
             if constexpr (HAS_HALF) g[k] = tp_load3(prev.half, q);
+#if PT_TP_MOTION
+            if constexpr (HAS_PREV_IDS) same[k] = mo.ids_prev[q] == idc;
+#endif
         }
         // The film values are needed only where the tap turns out valid, and the compiler would sink their loads into a branch on that
         // (it turns a select whose operand is a load into control flow): the gathers would wait for the geometry loads and the arithmetic on
@@ -86,7 +112,11 @@
             const float pd = fabsf(tp_dot(ex, ey, ez, nx, ny, nz));
             const float qnx = 2.0f * (Nq[k].x / hq[k]) - 1.0f, qny = 2.0f * (Nq[k].y / hq[k]) - 1.0f, qnz = 2.0f * (Nq[k].z / hq[k]) - 1.0f;
             const float nd = tp_dot(nx, ny, nz, qnx, qny, qnz);
+#if PT_TP_MOTION
+            const bool valid = ok && inside[k] && hq[k] > 0.0f && len[k] > 0.0f && pd <= tol && nd >= a.normal_cos && same[k];
+#else
             const bool valid = ok && inside[k] && hq[k] > 0.0f && len[k] > 0.0f && pd <= tol && nd >= a.normal_cos;
+#endif
             w[k] = valid ? bw[k] : 0.0f;
             len[k] = valid ? len[k] : 0.0f;
             f[k] = float3u{valid ? f[k].x : 0.0f, valid ? f[k].y : 0.0f, valid ? f[k].z : 0.0f};

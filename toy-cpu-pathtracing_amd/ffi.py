@@ -162,6 +162,11 @@ class TemporalRectifyParams(C.Structure):
     _fields_ = [("radius", C.c_uint32), ("gamma", C.c_float)]
 
 
+class MotionXform(C.Structure):
+    """mi355pt_motion_xform (include/mi355pt_motion.h): X_prev = a X_cur + b, nrm_prev = n nrm_cur between two frames' render spaces; 96 bytes"""
+    _fields_ = [("a", C.c_float * 9), ("b", C.c_float * 3), ("n", C.c_float * 9), ("pad", C.c_float * 3)]
+
+
 class UpsampleParams(C.Structure):
     """mi355pt_upsample_params (include/mi355pt_upsample.h); Product.upsample_params_default() fills it — a zeroed one is refused"""
     _fields_ = [("pos_tol", C.c_float), ("normal_cos", C.c_float), ("emitter_tol", C.c_float), ("min_weight", C.c_float), ("albedo_eps", C.c_float)]
@@ -273,6 +278,9 @@ ROBUST_SYMBOLS = ["robust_params_default", "robust_combine_device", "robust_comb
 REBASE_SYMBOLS = ["scene_move_camera"]
 # ... and include/mi355pt_instances.h, the instance-move block (tests/test_instance_move.py)
 INSTANCES_SYMBOLS = ["scene_set_instance_dynamic", "scene_move_instances"]
+# ... and include/mi355pt_motion.h, the object-motion block (tests/test_motion.py)
+MOTION_SYMBOLS = ["render_ids_device", "render_ids", "motion_table", "temporal_accumulate_motion_device", "temporal_accumulate_motion",
+                  "temporal_accumulate_rectified_motion_device", "temporal_accumulate_rectified_motion"]
 ADAPTIVE_SYMBOLS = ["adaptive_scratch_bytes", "adaptive_step_device", "film_normalize_tiles_device", "render_adaptive_device", "render_adaptive"]
 
 
@@ -684,6 +692,17 @@ class Product(Backend):
             lib.mi355pt_robust_combine.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RobustParams), C.c_void_p, C.c_void_p, C.c_void_p]
             lib.mi355pt_render_buckets_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
             lib.mi355pt_render_robust.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.POINTER(RobustParams), C.c_void_p]
+        if hasattr(lib, "mi355pt_temporal_accumulate_motion_device"):  # (absent from an older build loaded through MI355PT_LIB)
+            frame4 = [C.POINTER(TemporalFrame), C.c_uint32, C.POINTER(TemporalFrame), C.POINTER(TemporalView), C.c_uint32, C.c_uint32, C.POINTER(TemporalParams)]
+            motion4 = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]                      # ids_cur, ids_prev, table, n_entries
+            lib.mi355pt_render_ids_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+            lib.mi355pt_render_ids.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p, C.POINTER(Stats)]
+            lib.mi355pt_motion_table.argtypes = [C.POINTER(Camera), C.POINTER(Camera), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+            lib.mi355pt_temporal_accumulate_motion_device.argtypes = frame4 + motion4 + [C.c_void_p] * 4
+            lib.mi355pt_temporal_accumulate_motion.argtypes = frame4 + motion4 + [C.c_void_p] * 3
+            lib.mi355pt_temporal_accumulate_rectified_motion_device.argtypes = frame4 + [C.POINTER(TemporalRectifyParams), C.c_void_p, C.c_size_t] + motion4 + \
+                [C.c_void_p] * 4
+            lib.mi355pt_temporal_accumulate_rectified_motion.argtypes = frame4 + [C.POINTER(TemporalRectifyParams)] + motion4 + [C.c_void_p] * 3
         if not hasattr(lib, "mi355pt_render_sample_log"):     # an older build loaded through MI355PT_LIB for an A/B timing run
             return
         lib.mi355pt_sample_log_records.argtypes = [C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]
@@ -893,6 +912,66 @@ class Product(Backend):
                                                                   C.byref(view) if view is not None else None, w, h, C.byref(params), C.byref(rectify_params),
                                                                   out_film.ctypes.data, out_half.ctypes.data if out_half is not None else None,
                                                                   out_len.ctypes.data), "temporal_accumulate_rectified")
+        return out_film, out_half, out_len
+
+    # ---- object motion vectors (include/mi355pt_motion.h): the ID pass, the motion table and the motion-aware twins of the accumulation ----
+    def render_ids_device(self, scene, cam, params, d_ids_ptr, stream=None, stats=None):
+        """mi355pt_render_ids_device: instance + 1 of the closest hit through every pixel centre (0: a miss) into W x H u32 on the device"""
+        self.check(self.lib.mi355pt_render_ids_device(scene.h, C.byref(cam), C.byref(params), C.c_void_p(d_ids_ptr), C.c_void_p(stream or 0),
+                                                      C.byref(stats) if stats is not None else None), "render_ids_device")
+
+    def render_ids(self, scene, cam, params):
+        """mi355pt_render_ids -> (H, W) uint32"""
+        ids = np.zeros((cam.height, cam.width), np.uint32)
+        self.check(self.lib.mi355pt_render_ids(scene.h, C.byref(cam), C.byref(params), ids.ctypes.data, None), "render_ids")
+        return ids
+
+    def motion_table(self, cur_cam, prev_cam, l2w_cur, l2w_prev):
+        """mi355pt_motion_table (host only): l2w_cur / l2w_prev are n matrices (row-major 4 x 4 each, as add_instance takes them)
+        -> (n + 1, 24) float32, one row per mi355pt_motion_xform (a 0:9, b 9:12, n 12:21, pad 21:24); entry 0 is the static one"""
+        mc, mp = (np.ascontiguousarray(np.asarray(m, np.float32).reshape(-1, 4, 4).transpose(0, 2, 1)).reshape(-1, 16) for m in (l2w_cur, l2w_prev))   # column-major
+        assert mc.shape == mp.shape
+        out = np.zeros((mc.shape[0] + 1, 24), np.float32)
+        self.check(self.lib.mi355pt_motion_table(C.byref(cur_cam), C.byref(prev_cam), mc.ctypes.data, mp.ctypes.data, mc.shape[0], out.ctypes.data), "motion_table")
+        return out
+
+    def temporal_accumulate_motion_device(self, cur, spp, prev, view, width, height, params, d_ids_cur_ptr, d_ids_prev_ptr, d_table_ptr, n_entries,
+                                          d_out_film_ptr, d_out_half_ptr, d_out_length_ptr, rectify_params=None, d_scratch_ptr=None, scratch_bytes=0, stream=None):
+        """mi355pt_temporal_accumulate_motion_device or, with rectify_params (and a scratch), mi355pt_temporal_accumulate_rectified_motion_device:
+        the arguments of their twins plus the current ids, the previous ids (None: no id test of the taps) and the table, all device pointers"""
+        fc = TemporalFrame(*[C.c_void_p(cur.get(k) or None) for k in TEMPORAL_FILMS])
+        fp = TemporalFrame(*[C.c_void_p(prev.get(k) or None) for k in TEMPORAL_FILMS]) if prev is not None else None
+        head = (C.byref(fc), spp, C.byref(fp) if fp is not None else None, C.byref(view) if view is not None else None, width, height, C.byref(params))
+        tail = (C.c_void_p(d_ids_cur_ptr), C.c_void_p(d_ids_prev_ptr or 0), C.c_void_p(d_table_ptr), n_entries, C.c_void_p(d_out_film_ptr),
+                C.c_void_p(d_out_half_ptr or 0), C.c_void_p(d_out_length_ptr), C.c_void_p(stream or 0))
+        if rectify_params is None:
+            self.check(self.lib.mi355pt_temporal_accumulate_motion_device(*head, *tail), "temporal_accumulate_motion_device")
+        else:
+            self.check(self.lib.mi355pt_temporal_accumulate_rectified_motion_device(*head, C.byref(rectify_params), C.c_void_p(d_scratch_ptr), scratch_bytes, *tail),
+                       "temporal_accumulate_rectified_motion_device")
+
+    def temporal_accumulate_motion(self, cur, spp, prev, view, ids_cur, ids_prev, table, params=None, rectify_params=None):
+        """mi355pt_temporal_accumulate_motion (or, with rectify_params, mi355pt_temporal_accumulate_rectified_motion) on host arrays, as
+        temporal_accumulate; ids (H, W) uint32, table (n_entries, 24) float32 -> (out_film, out_half or None, out_length)"""
+        def host(frame):
+            keep = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in frame.items() if v is not None}
+            return keep, TemporalFrame(*[keep[k].ctypes.data if k in keep else None for k in TEMPORAL_FILMS])
+        kc, fc = host(cur)
+        kp, fp = host(prev) if prev is not None else (None, None)
+        h, w = kc["film"].shape[:2]
+        ic = np.ascontiguousarray(ids_cur, dtype=np.uint32)
+        ip = np.ascontiguousarray(ids_prev, dtype=np.uint32) if ids_prev is not None else None
+        tab = np.ascontiguousarray(table, dtype=np.float32).reshape(-1, 24)
+        params = params if params is not None else self.temporal_params_default()
+        out_film, out_len = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32)
+        out_half = np.zeros((h, w, 3), np.float32) if "half" in kc else None
+        head = (C.byref(fc), spp, C.byref(fp) if fp is not None else None, C.byref(view) if view is not None else None, w, h, C.byref(params))
+        tail = (ic.ctypes.data, ip.ctypes.data if ip is not None else None, tab.ctypes.data, tab.shape[0], out_film.ctypes.data,
+                out_half.ctypes.data if out_half is not None else None, out_len.ctypes.data)
+        if rectify_params is None:
+            self.check(self.lib.mi355pt_temporal_accumulate_motion(*head, *tail), "temporal_accumulate_motion")
+        else:
+            self.check(self.lib.mi355pt_temporal_accumulate_rectified_motion(*head, C.byref(rectify_params), *tail), "temporal_accumulate_rectified_motion")
         return out_film, out_half, out_len
 
     # ---- guided half-resolution rendering (include/mi355pt_upsample.h): a film traced at W/2 x H/2 rebuilt at W x H through both G-buffers ----

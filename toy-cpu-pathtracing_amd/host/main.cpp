@@ -51,6 +51,10 @@ struct Args {   // main.rs:20-53
     // frame.  --instance-rebuild-above 0 (the library's default): never build again because of the tree's SAH cost
     struct InstanceTransform { uint32_t id; float t[3]; float ry_deg; float s[3]; };
     std::vector<InstanceTransform> instance_transforms; bool instance_rebuild_given = false; float instance_rebuild_above = 0.0f;
+    // nor object motion vectors (mi355pt_motion.h): --instance-step ID:tx,ty,tz[:ry_deg], repeatable, with --temporal-frames — in frame k the
+    // instance's local_to_world is the scene's with T . R_y applied k times (the way --camera-step moves the camera); the instances are marked
+    // dynamic before the build and moved on the device between the frames, and the accumulation is the motion-aware one
+    std::vector<InstanceTransform> instance_steps;
 };
 
 // T . R_y . S . local_to_world (column-major): T R S composed in double and rounded to float, the product in double and rounded to float
@@ -318,6 +322,9 @@ static void follow_camera(Scene& scene, const Camera& moved, const Args& a, uint
 // then mi355pt_temporal_accumulate_device (with --temporal-rectify: mi355pt_temporal_accumulate_rectified_device, radius and gamma from
 // --temporal-rectify-radius / --temporal-rectify-gamma or the defaults) against the previous frame's accumulated films.  After the last frame optionally the
 // variance-guided filter on the accumulated pair (spp 2), then Sensor::to_rgb.  Returns the device seconds of the beauty launches.
+// With --instance-step (mi355pt_motion.h) the named instances take their step once more before every frame but the first
+// (mi355pt_scene_move_instances), and each frame adds one ID pass, the motion table of the two frames' matrices and cameras, and the
+// motion-aware twin of the accumulation with the previous frame's ids.
 static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params p, const Args& a, std::vector<float>& pixels) {
     const mi355pt_camera base = camera.raw();
     const uint32_t n_pixels = base.width * base.height, guide_spp = a.denoise_guide_spp;
@@ -338,16 +345,32 @@ static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params
     if (a.temporal_rectify_gamma_given) rp.gamma = a.temporal_rectify_gamma;
     const size_t rectify_bytes = a.temporal_rectify ? mi355pt_temporal_rectify_scratch_bytes(base.width, base.height) : sizeof(float);
     DeviceFilm rectify_scratch(rectify_bytes);
+    // --instance-step (mi355pt_motion.h): the frame's ids in two sets that alternate like the G-buffer, the motion table, every instance's
+    // local_to_world in this frame and in the one before
+    const bool stepping = !a.instance_steps.empty();
+    const uint32_t n_inst = scene.instance_count();
+    DeviceFilm ids0(stepping ? len_bytes : sizeof(float)), ids1(stepping ? len_bytes : sizeof(float));
+    DeviceFilm table(stepping ? ((size_t)n_inst + 1) * sizeof(mi355pt_motion_xform) : sizeof(float));
+    uint32_t* ids[2] = {(uint32_t*)ids0.p, (uint32_t*)ids1.p};
+    std::vector<float> l2w_prev(stepping ? 16 * (size_t)n_inst : 0);
     mi355pt_camera cam = base, cam_prev = base;
     double kernel_ms = 0.0;
     for (uint32_t k = 0; k < a.temporal_frames; ++k) {
         const int c = (int)(k & 1u), q = c ^ 1;
         cam_prev = cam;
         for (int i = 0; i < 3; ++i) cam.position[i] = base.position[i] + (float)k * a.camera_step[i];
-        if (k > 0 && moving) {
-            Camera moved(base.fov_deg, base.width, base.height);
-            moved.set_look_to({cam.position[0], cam.position[1], cam.position[2]}, {cam.direction[0], cam.direction[1], cam.direction[2]}, {cam.up[0], cam.up[1], cam.up[2]});
-            follow_camera(scene, moved, a, k);
+        Camera moved(base.fov_deg, base.width, base.height);
+        moved.set_look_to({cam.position[0], cam.position[1], cam.position[2]}, {cam.direction[0], cam.direction[1], cam.direction[2]}, {cam.up[0], cam.up[1], cam.up[2]});
+        if (k > 0 && moving) follow_camera(scene, moved, a, k);
+        for (uint32_t i = 0; stepping && i < n_inst; ++i) std::memcpy(&l2w_prev[16 * (size_t)i], scene.instance_transform(i), 16 * sizeof(float));
+        if (k > 0 && stepping) {      // the step once more on top of the last frame's matrix, at the camera the scene is at now
+            std::vector<uint32_t> step_ids; std::vector<float> matrices(16 * a.instance_steps.size());
+            for (size_t j = 0; j < a.instance_steps.size(); ++j) {
+                step_ids.push_back(a.instance_steps[j].id);
+                instance_transform_matrix(a.instance_steps[j], scene.instance_transform(step_ids.back()), &matrices[16 * j]);
+            }
+            const mi355pt_instance_move_result mr = scene.move_instances(moved, step_ids, matrices);
+            std::fprintf(stderr, "instance step, frame %u: rebuilt=%u reason=%u host_ms=%.3f device_ms=%.3f\n", k, mr.rebuilt, mr.reason, mr.host_ms, mr.device_ms);
         }
         p.seed = a.seed + k;
         bool ok = hipMemset(normal[c], 0, film_bytes) == hipSuccess && hipMemset(position[c], 0, film_bytes) == hipSuccess && hipMemset(hit[c], 0, film_bytes) == hipSuccess &&
@@ -371,7 +394,22 @@ static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params
         const mi355pt_temporal_frame prev{acc[q], half ? acch[q] : nullptr, len[q], position[q], normal[q], hit[q]};
         mi355pt_temporal_view view{};
         if (k > 0) check(mi355pt_temporal_view_from_cameras(&cam, &cam_prev, &view), "mi355pt_temporal_view_from_cameras");
-        if (a.temporal_rectify)
+        if (stepping) {               // one ID pass, the table of the two frames' matrices and cameras, the motion-aware accumulation with the previous ids
+            scene.ids_device(cam, g, ids[c]);
+            const std::vector<mi355pt_motion_xform> host_table = scene.motion_table(cam, cam_prev, l2w_prev);
+            if (hipMemcpy(table.p, host_table.data(), host_table.size() * sizeof(mi355pt_motion_xform), hipMemcpyHostToDevice) != hipSuccess)
+                throw std::runtime_error("mi355pt: copying the motion table failed");
+            const mi355pt_motion_xform* d_table = (const mi355pt_motion_xform*)table.p;
+            if (a.temporal_rectify)
+                check(mi355pt_temporal_accumulate_rectified_motion_device(&cur, p.spp, k > 0 ? &prev : nullptr, k > 0 ? &view : nullptr, base.width, base.height, &tp,
+                                                                          &rp, rectify_scratch.p, rectify_bytes, ids[c], k > 0 ? ids[q] : nullptr, d_table, n_inst + 1,
+                                                                          acc[c], half ? acch[c] : nullptr, len[c], nullptr),
+                      "mi355pt_temporal_accumulate_rectified_motion_device");
+            else
+                check(mi355pt_temporal_accumulate_motion_device(&cur, p.spp, k > 0 ? &prev : nullptr, k > 0 ? &view : nullptr, base.width, base.height, &tp, ids[c],
+                                                                k > 0 ? ids[q] : nullptr, d_table, n_inst + 1, acc[c], half ? acch[c] : nullptr, len[c], nullptr),
+                      "mi355pt_temporal_accumulate_motion_device");
+        } else if (a.temporal_rectify)
             check(mi355pt_temporal_accumulate_rectified_device(&cur, p.spp, k > 0 ? &prev : nullptr, k > 0 ? &view : nullptr, base.width, base.height, &tp, &rp,
                                                                rectify_scratch.p, rectify_bytes, acc[c], half ? acch[c] : nullptr, len[c], nullptr),
                   "mi355pt_temporal_accumulate_rectified_device");
@@ -537,7 +575,11 @@ static void usage() {
               "                   [--instance-transform ID:tx,ty,tz[:ry_deg[:sx,sy,sz]]] (repeatable; pt|nee|mis|normal|albedo|position|depth: the scene is\n"
               "                                         built as described with instance ID marked dynamic, then its local_to_world becomes\n"
               "                                         T . R_y . S . local_to_world on the device, mi355pt_scene_move_instances; one line on stderr.\n"
-              "                                         Not with --temporal-frames: the reprojection assumes a static world, it has no object motion vectors)\n"
+              "                                         Not with --temporal-frames: a pose set once before the frame has no motion; --instance-step moves\n"
+              "                                         instances across the frames with the object motion vectors of mi355pt_motion.h)\n"
+              "                   [--instance-step ID:tx,ty,tz[:ry_deg]] (repeatable, distinct IDs; with --temporal-frames: in frame k the instance's local_to_world\n"
+              "                                         is the scene's with T . R_y applied k times; the instances are moved on the device between the frames,\n"
+              "                                         and each frame adds an ID pass, a motion table and the motion-aware accumulation.  Not with --half-res)\n"
               "                   [--instance-rebuild-above X] (0 = never; with --instance-transform: build again when the refit tree's SAH cost exceeds X\n"
               "                                         times the built tree's)");
 }
@@ -619,6 +661,19 @@ int main(int argc, char** argv) {
             if (!ok) { std::fprintf(stderr, "error: invalid value '%s' for '--instance-transform': ID:tx,ty,tz[:ry_deg[:sx,sy,sz]], finite numbers, each ID once\n", v.c_str()); return 2; }
             a.instance_transforms.push_back(it);
         }
+        else if (k == "--instance-step") {
+            const std::string v = val();
+            Args::InstanceTransform it{0, {0, 0, 0}, 0.0f, {1, 1, 1}};
+            char tail = 0;
+            int n = std::sscanf(v.c_str(), "%u:%f,%f,%f%c", &it.id, &it.t[0], &it.t[1], &it.t[2], &tail);
+            bool ok = n == 4;
+            if (n == 5 && tail == ':') ok = std::sscanf(v.c_str(), "%u:%f,%f,%f:%f%c", &it.id, &it.t[0], &it.t[1], &it.t[2], &it.ry_deg, &tail) == 5;
+            for (float f : {it.t[0], it.t[1], it.t[2], it.ry_deg}) ok = ok && std::isfinite(f);
+            ok = ok && !v.empty() && v[0] >= '0' && v[0] <= '9';
+            for (const Args::InstanceTransform& o : a.instance_steps) ok = ok && o.id != it.id;
+            if (!ok) { std::fprintf(stderr, "error: invalid value '%s' for '--instance-step': ID:tx,ty,tz[:ry_deg], finite numbers, each ID once\n", v.c_str()); return 2; }
+            a.instance_steps.push_back(it);
+        }
         else if (k == "--instance-rebuild-above") {
             const std::string v = val();
             char tail = 0;
@@ -698,6 +753,14 @@ int main(int argc, char** argv) {
     if (a.half_res && a.adaptive_threshold != 0.0f) { std::fprintf(stderr, "error: --half-res with --adaptive-threshold: half-resolution rendering takes one sample count per frame\n"); return 2; }
     if (a.half_res && (a.spp == 0 || a.denoise_guide_spp == 0)) { std::fprintf(stderr, "error: --half-res needs --spp and --denoise-guide-spp above 0\n"); return 2; }
     if (a.instance_rebuild_given && a.instance_transforms.empty()) { std::fprintf(stderr, "error: --instance-rebuild-above needs --instance-transform: it is the move's threshold\n"); return 2; }
+    if (!a.instance_steps.empty()) {
+        for (const Args::InstanceTransform& st : a.instance_steps)
+            for (const Args::InstanceTransform& it : a.instance_transforms)
+                if (st.id == it.id) { std::fprintf(stderr, "error: --instance-step and --instance-transform both name instance %u: one of them\n", st.id); return 2; }
+        if (!a.temporal) { std::fprintf(stderr, "error: --instance-step needs --temporal-frames: it moves the instance between the frames\n"); return 2; }
+        if (a.half_res) { std::fprintf(stderr, "error: --instance-step with --half-res: the motion-aware accumulation runs at full size only\n"); return 2; }
+        std::sort(a.instance_steps.begin(), a.instance_steps.end(), [](const Args::InstanceTransform& x, const Args::InstanceTransform& y) { return x.id < y.id; });
+    }
     if (!a.instance_transforms.empty()) {
         if (a.temporal) { std::fprintf(stderr, "error: --instance-transform with --temporal-frames: the temporal reprojection assumes a static world (no object motion vectors)\n"); return 2; }
         if (a.gpus > 1) { std::fprintf(stderr, "error: --instance-transform with --gpus %d: a scene built over several GPUs is not moved\n", a.gpus); return 2; }
@@ -780,6 +843,10 @@ int main(int argc, char** argv) {
         }
         for (const Args::InstanceTransform& it : a.instance_transforms) {
             if (it.id >= scene.instance_count()) { std::fprintf(stderr, "error: invalid value for '--instance-transform': scene %u has no instance %u (%u instances)\n", a.scene, it.id, scene.instance_count()); return 2; }
+            scene.set_instance_dynamic(it.id);
+        }
+        for (const Args::InstanceTransform& it : a.instance_steps) {
+            if (it.id >= scene.instance_count()) { std::fprintf(stderr, "error: invalid value for '--instance-step': scene %u has no instance %u (%u instances)\n", a.scene, it.id, scene.instance_count()); return 2; }
             scene.set_instance_dynamic(it.id);
         }
         std::puts("Start build scene.");                                                // main.rs:103-109

@@ -707,7 +707,19 @@ public:
     }
     // EXTENSION (include/mi355pt_instances.h): instances of the built scene take new local_to_world matrices (column-major, 16 floats each,
     // ids strictly ascending) on the device — positions, shading normals, light tables, both trees refit, the tree's SAH cost reported —;
-    // an instance that will move is marked before build().  The temporal accumulation assumes a static world: no object motion vectors
+    // an instance that will move is marked before build().  Across a move the temporal accumulation takes the object motion vectors of
+    // include/mi355pt_motion.h: ids_device() says which instance a pixel shows, motion_table() where each instance's points were a frame ago
+    void ids_device(const mi355pt_camera& cam, const mi355pt_params& p, uint32_t* d_ids) const {
+        check(mi355pt_render_ids_device(s_, &cam, &p, d_ids, nullptr, nullptr), "mi355pt_render_ids_device");
+    }
+    // every instance's local_to_world in the previous frame (n x 16, column-major) against the scene's current ones -> instance_count() + 1 records
+    std::vector<mi355pt_motion_xform> motion_table(const mi355pt_camera& cur, const mi355pt_camera& prev, const std::vector<float>& l2w_prev) const {
+        std::vector<float> l2w_cur;
+        for (const std::vector<float>& m : instance_l2w_) l2w_cur.insert(l2w_cur.end(), m.begin(), m.end());
+        std::vector<mi355pt_motion_xform> out(instance_l2w_.size() + 1);
+        check(mi355pt_motion_table(&cur, &prev, l2w_cur.data(), l2w_prev.data(), (uint32_t)instance_l2w_.size(), out.data()), "mi355pt_motion_table");
+        return out;
+    }
     void set_instance_dynamic(uint32_t instance) { check(mi355pt_scene_set_instance_dynamic(s_, instance, 1), "mi355pt_scene_set_instance_dynamic"); }
     mi355pt_instance_move_result move_instances(const Camera& cam, const std::vector<uint32_t>& ids, const std::vector<float>& matrices, float rebuild_above = 0.0f) {
         mi355pt_instance_move_params p{rebuild_above};
