@@ -157,6 +157,7 @@ static int launch_range(const mi355pt_scene* s, const mi355pt_camera* cam, const
             DevScene dev = s->impl.dev;
             dev.cam_lists = use_camera_lists(key, dp.block_log2, camera_lists_enabled()) ? 1u : 0u;
             dev.queue_stage = use_queue_staging(key, queue_staging_enabled()) ? 1u : 0u;
+            dev.light_queue = use_light_queue(key, light_queue_enabled()) ? 1u : 0u;
             HIP_TRY(launch_pt(key, dev, dc, dp, plan.n_tiles,
                               lc->d_hash, d_accum, lc->d_partial, d_counter, d_list ? nullptr : d_stats, plan.grid, stream, pout, lc->d_defer));
         }

@@ -32,7 +32,7 @@ struct LaunchCtx {
     bool hash_valid = false;
     unsigned* d_counters = nullptr;   // CTX_RING counters
     DevStats* d_stats = nullptr;      // CTX_RING blocks
-    float* d_defer = nullptr;         // the resident waves' queues (pt_kernel.hpp queue_bytes_per_wave: 10 / 40 / 16 KB per wave by kernel), sized for the largest launch seen
+    float* d_defer = nullptr;         // the resident waves' queues (pt_kernel.hpp queue_bytes_per_wave: 24 / 40 / 16 KB per wave by kernel), sized for the largest launch seen
     size_t defer_bytes = 0;
     float* d_partial = nullptr;       // per-chunk film tiles of split launches (tiles * chunks * 64 * 3 floats), grown on demand;
     size_t partial_bytes = 0;         // reused by consecutive launches: one stream at a time per scene

@@ -235,4 +235,11 @@ inline bool use_queue_staging(const KernelKey& key, bool enabled) { return enabl
 // the host-side switch, read per launch: MI355PT_NO_QUEUE_STAGING=1 (any value but "0") sends every record through the global stack; default on
 inline bool queue_staging_enabled() { const char* e = getenv("MI355PT_NO_QUEUE_STAGING"); return !(e && e[0] != '\0' && !(e[0] == '0' && e[1] == '\0')); }
 
+// ---- the light-hit queue (tail_queue_plan.hpp lq_*, pt_kernel_body.inc) ----
+// Do the kernels with one tail queue push the paths that arrive at an emitter to the wave's light-hit queue (DevScene::light_queue)?  The
+// kernels without the code (two queues, the instrumented ones, the plain path tracer) ignore the flag.  `enabled`: light_queue_enabled().
+inline bool use_light_queue(const KernelKey& key, bool enabled) { return enabled && !key.stats; }
+// the host-side switch, read per launch: MI355PT_NO_LIGHT_QUEUE=1 (any value but "0") evaluates every emitter hit in place; default on
+inline bool light_queue_enabled() { const char* e = getenv("MI355PT_NO_LIGHT_QUEUE"); return !(e && e[0] != '\0' && !(e[0] == '0' && e[1] == '\0')); }
+
 }  // namespace pt

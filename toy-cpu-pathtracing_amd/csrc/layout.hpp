@@ -242,8 +242,11 @@ struct DevScene {
                                   // lowered scene; the launcher sets it in its own copy, per launch (launch_plan.hpp use_camera_lists)
     const DevEnv* envs;           // every infinite light of the scene (Scene sums them all: scene.rs:185-231)
     uint32_t n_envs;
-    uint32_t queue_stage;         // 1: the kernels with one tail queue hand a pass its fresh records through LDS (tail_queue_plan.hpp).  0 in the lowered
+    uint16_t queue_stage;         // 1: the kernels with one tail queue hand a pass its fresh records through LDS (tail_queue_plan.hpp).  0 in the lowered
                                   // scene; set per launch like cam_lists (launch_plan.hpp use_queue_staging)
+    uint16_t light_queue;         // 1: the kernels with one tail queue evaluate emitter hits 64 at a time from the wave's light-hit queue (pt_kernel.hpp);
+                                  // 0: in place.  0 in the lowered scene; set per launch (launch_plan.hpp use_light_queue).  (The two flags share one
+                                  // dword: DevScene keeps its size, and the kernels that read neither keep their code)
 };
 
 struct DevCamera {

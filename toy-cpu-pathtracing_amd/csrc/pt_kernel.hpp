@@ -179,12 +179,26 @@ constexpr uint32_t TQ_F4 = 5u;                                           // floa
 #ifndef PT_TAILQ_RING1
 #define PT_TAILQ_RING1 128u
 #endif
+// LIGHT-HIT QUEUE (the kernels with ONE tail queue; tail_queue_plan.hpp lq_*, tests/test_light_queue.py).  The last minority branch of the
+// front: a BSDF-sampled ray of the Cornell room reaches the ceiling light with a probability of 1 to 2 %, so in a good third of the
+// iterations one or two lanes of 64 ran the whole emitter evaluation (pt_path.hpp emitter_hit: surface, material and spectrum records — three
+// dependent loads —, the radiance, the MIS weight) while the wave waited.  A path that arrives at an emitter ends there.  So the front
+// pushes it — L, T, the spawning sample's f and pdf, the vertex left, the ray direction, the hit, the wavelengths, the pixel: 7 float4 =
+// 112 B, field-major on a stack of LQ_SLOTS entries behind the tail queue's in the wave's region of the queue buffer — and the lane is
+// free: no throughput update, no roulette draw for a path that ends regardless.  When 64 wait, one pass right after the front (every lane
+// is free, no path state is live) calls emitter_hit for a full wave and finishes the 64 samples to the film; when the work item is done
+// one last pass takes what is left.  A sample's arithmetic is what it was — per-sample values are bit for bit those of the in-place
+// path, tests/test_light_queue_gpu.py —, the schedule is the wave's own: frames bit-identical from run to run; a pixel's samples reach the
+// film tile in another order, as when the queues became stacks.  MI355PT_NO_LIGHT_QUEUE=1 (launch_plan.hpp, DevScene::light_queue)
+// evaluates in place again: the A/B control (profiles/light_queue_ab.json).
+constexpr uint32_t LQ_F4 = 7u;                                           // float4 per record of the light-hit queue (112 B)
+constexpr bool light_queue_of(uint32_t FEAT, uint32_t MODE) { return tail_queue_of(FEAT, MODE) && (FEAT & FEAT_CC) == 0u; }
 // Queue memory of one resident wave of pt_kernel<STATS, FEAT, MODE> / pt_kernel_tiles<FEAT, MODE> (STATS = false), in bytes: what that
-// kernel's queues hold and nothing more — 10 KB for one stack (5 float4 x 128 entries), 40 KB for the clearcoat kernels' two (2 x 5 x 256),
+// kernel's queues hold and nothing more — 24 KB for one stack and the light-hit queue ((5 + 7) float4 x 128 entries), 40 KB for the clearcoat kernels' two (2 x 5 x 256),
 // 16 KB for the instrumented kernels' deferral ring, 0 for a kernel without a queue.  The ONE statement of the per-wave stride: the kernel
 // body places its queues with it (q_base) and the launcher sizes the buffer with it for the kernel it selected (query_defer_bytes_per_wave).
 constexpr size_t queue_bytes_per_wave(bool STATS, uint32_t FEAT, uint32_t MODE) {
-    if (!STATS && tail_queue_of(FEAT, MODE)) return (size_t)16u * TQ_F4 * ((FEAT & FEAT_CC) != 0u ? QUEUE_MAX * QUEUE_RING : PT_TAILQ_RING1);
+    if (!STATS && tail_queue_of(FEAT, MODE)) return (size_t)16u * TQ_F4 * ((FEAT & FEAT_CC) != 0u ? QUEUE_MAX * QUEUE_RING : PT_TAILQ_RING1) + (light_queue_of(FEAT, MODE) ? (size_t)16u * LQ_F4 * LQ_SLOTS : (size_t)0);
     return defer_classes_of(FEAT, MODE) != 0u ? (size_t)16u * DEFER_F4 * DEFER_RING : (size_t)0;
 }
 // MODE compiles the renderer strategy and the sampler in (MODE_GENERIC reads them from DevParams): the branches on

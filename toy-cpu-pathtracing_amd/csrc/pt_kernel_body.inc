@@ -142,6 +142,23 @@
         constexpr bool STAGE = TAILQ && TQ_CLASSES == 0u;
         static_assert(STACK_DEPTH * 64 >= (int)(TQ_STAGE_SLOTS * TQ_F4 * 4u) && TQ_STAGE_SLOTS == 64u, "a pass's worth of staged tail-queue records fits the traversal stack's LDS");
         float4* const s_stage = (float4*)s_stack;
+        // LIGHT-HIT QUEUE (pt_kernel.hpp; one queue only, like the staging): the paths that arrive at an emitter wait on a stack of their own
+        // behind the tail queue's, field-major over LQ_SLOTS (float4 k of slot s at lq_base + k * LQ_SLOTS + s), and are evaluated and
+        // finished 64 at a time.  sc.light_queue == 0 (launch_plan.hpp use_light_queue): in place, in the front.
+        constexpr bool LIGHTQ = STAGE && light_queue_of(FEAT, MODE);
+        float4* const lq_base = LIGHTQ ? q_base + TQ_F4 * PT_TAILQ_RING1 : nullptr;
+        uint32_t lq_count = 0u;                                    // records waiting; wave-uniform; 0 between work items
+        // the record: what emitter_hit reads and what finishing the sample needs (the sampler's state, the depth and the throughput's update are not: the path ends)
+        auto lq_put = [&](float4* r, const Path& Q, const Hit& h, uint32_t pix) {
+            const uint32_t fl = (Q.wl.term ? 1u : 0u) | (Q.from_camera ? 2u : 0u) | (Q.prev_spec ? 4u : 0u) | ((pix & 63u) << 3);
+            r[0u * LQ_SLOTS] = make_float4(__uint_as_float(Q.smp.morton), __uint_as_float(fl), Q.wl.lam0, __uint_as_float(h.tri));
+            r[1u * LQ_SLOTS] = make_float4(Q.T[0], Q.T[1], Q.T[2], Q.T[3]);
+            r[2u * LQ_SLOTS] = make_float4(Q.L[0], Q.L[1], Q.L[2], Q.L[3]);
+            r[3u * LQ_SLOTS] = make_float4(Q.pf[0], Q.pf[1], Q.pf[2], Q.pf[3]);
+            r[4u * LQ_SLOTS] = make_float4(Q.rd.x, Q.rd.y, Q.rd.z, Q.p_pdf);
+            r[5u * LQ_SLOTS] = make_float4(Q.prev_pos.x, Q.prev_pos.y, Q.prev_pos.z, h.b0);
+            r[6u * LQ_SLOTS] = make_float4(h.b1, h.b2, 0.0f, 0.0f);
+        };
         while (true) {
             unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, ts4 = 0, tsa = 0, tsb = 0;
             uint32_t bsdf_classes = 0u;
@@ -161,7 +178,7 @@
                 pool_next = min(pool_next + (uint32_t)__popcll(m_needy), pool_size);
             }
             if (!__any(active)) {
-                if (pool_next >= pool_size && q_tail == q_head && (q_count | q2_count) == 0u) break;
+                if (pool_next >= pool_size && q_tail == q_head && (q_count | q2_count | lq_count) == 0u) break;   // (light-hit records left: one more iteration, rayless, whose front is followed by the last pass)
                 // (queued paths are taken AFTER the shading stage: with nothing left to start, an iteration without rays still has to get there)
                 if (!((DEFER != 0u || TAILQ) && pool_next >= pool_size)) continue;
             }
@@ -302,14 +319,31 @@
                 bool end_path = dying;                         // (a dying path's last connection has just been resolved)
                 const bool front = active && !dying && !susp;
                 unpark(P);
+                // the paths that arrive at an emitter end there: they wait in the light-hit queue, and their lanes are free
+                // (an emitter hit that contributes nothing — NEE after a non-specular bounce — is not queued: the front ends it unevaluated)
+                // (they skip the front — no throughput update, no roulette draw for a path that ends regardless — and are stored below, with the
+                // tail queue's pushes: one release for both.  sc.light_queue == 0: not stored; they keep their lanes, which evaluate them
+                // below, in place, from their registers — the same statements the pass runs.  lq_void: an emitter hit that adds nothing ends here)
+                bool lq_push = false, lq_void = false;
+                if constexpr (LIGHTQ) {
+                    const bool on_emitter = front && got && (hit.mclass & 7u) == MT_EMISSIVE;
+                    lq_void = on_emitter && emitter_hit_is_void<STATS>(prm, P.from_camera, P.prev_spec);
+                    lq_push = on_emitter && !lq_void;
+                }
+                const unsigned long long m_lq = (LIGHTQ && sc.light_queue != 0u) ? __ballot(lq_push) : 0ull;
                 {
                     ShadeCtx C0;
                     C0.cont = false;
-                    if (front) end_path = shade_vertex_head<STATS, FEAT, 1>(P, sc, prm, sctx, got, hit, sh, st, tsa, C0);
+                    if constexpr (LIGHTQ) {
+                        if (front && !lq_push && !lq_void) end_path = shade_vertex_head<STATS, FEAT, 3>(P, sc, prm, sctx, got, hit, sh, st, tsa, C0);
+                        if (lq_void) end_path = true;
+                    } else {
+                        if (front) end_path = shade_vertex_head<STATS, FEAT, 1>(P, sc, prm, sctx, got, hit, sh, st, tsa, C0);
+                    }
                 }
                 dying = false;
                 // the paths that go on wait in the queue of their sort class; their lanes are free
-                const bool go_on = front && !end_path;
+                const bool go_on = front && !lq_push && !end_path;
                 const bool cls2 = TQ_CLASSES != 0u && ((TQ_CLASSES >> (hit.mclass & 31u)) & 1u) != 0u;
                 const unsigned long long m_on1 = __ballot(go_on && !cls2), m_on2 = TQ_CLASSES != 0u ? __ballot(go_on && cls2) : 0ull;
                 // one queue: a pass is due after this push?  Then it takes every record of the push, and they wait in LDS (wave-uniform;
@@ -321,7 +355,14 @@
                     n_on1 = (uint32_t)__popcll(m_on1);
                     stage = sc.queue_stage != 0u && tq_stage_pushes(q_count, n_on1, pool_next >= pool_size, (uint32_t)PT_TAILQ_MIN);
                 }
-                if ((m_on1 | m_on2) != 0ull) {
+                if ((m_on1 | m_on2 | m_lq) != 0ull) {
+                    if constexpr (LIGHTQ) {
+                        if (lq_push && m_lq != 0ull) {
+                            lq_put(lq_base + (lq_push_slot(lq_count, rank_below(m_lq)) & (LQ_SLOTS - 1u)), P, hit, my_pix);
+                            active = false;
+                        }
+                        lq_count += (uint32_t)__popcll(m_lq);
+                    }
                     if (go_on) {
                         if (STAGE && stage) tq_put(s_stage + tq_stage_push_index(rank_below(m_on1)), TQ_STAGE_SLOTS, P, hit, my_pix);
                         else {
@@ -336,6 +377,37 @@
                 }
                 if (active && end_path) { finish_path(); active = false; }
                 park(P, false);                                 // (nothing of these lanes' records is needed any more: the queue has them)
+                // The emitter hits.  With the queue: every lane is free and no path state is live — do 64 records wait, or is the work item
+                // done and some are left?  Then a pass: the newest min(64, count), one per lane.  Without it: the lanes that arrived at an
+                // emitter, as they stand.  Either way emitter_hit and what finish_path does, in ONE place
+                if constexpr (LIGHTQ) {
+                    bool ev = lq_push;
+                    if (sc.light_queue != 0u) {
+                        ev = false;
+                        if (lq_pass_due(lq_count, pool_next >= pool_size && q_count == 0u)) {
+                            const uint32_t n = lq_pass_take(lq_count);
+                            ev = lane < n;
+                            if (ev) {
+                                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                                const float4* r = lq_base + (lq_pop_slot(lq_count, n, lane) & (LQ_SLOTS - 1u));
+                                const float4 a = r[0u * LQ_SLOTS], b = r[1u * LQ_SLOTS], c = r[2u * LQ_SLOTS], d = r[3u * LQ_SLOTS], e4 = r[4u * LQ_SLOTS], f = r[5u * LQ_SLOTS], g = r[6u * LQ_SLOTS];
+                                const uint32_t fl = __float_as_uint(a.y);
+                                P.smp.morton = __float_as_uint(a.x); P.wl.lam0 = a.z; P.wl.term = (fl & 1u) != 0u;
+                                P.from_camera = (fl & 2u) != 0u; P.prev_spec = (fl & 4u) != 0u; my_pix = (fl >> 3) & 63u;
+                                P.T[0] = b.x; P.T[1] = b.y; P.T[2] = b.z; P.T[3] = b.w; P.L[0] = c.x; P.L[1] = c.y; P.L[2] = c.z; P.L[3] = c.w;
+                                P.pf[0] = d.x; P.pf[1] = d.y; P.pf[2] = d.z; P.pf[3] = d.w;
+                                P.rd = mk3(e4.x, e4.y, e4.z); P.p_pdf = e4.w; P.prev_pos = mk3(f.x, f.y, f.z);
+                                hit.b0 = f.w; hit.b1 = g.x; hit.b2 = g.y; hit.tri = __float_as_uint(a.w);
+                            }
+                            lq_count -= n;
+                        }
+                    }
+                    if (ev) {
+                        emitter_hit<STATS, FEAT>(sc, prm, hit, P.rd, P.T, P.pf, P.p_pdf, P.prev_pos, P.wl, P.from_camera, P.prev_spec, P.L, st);
+                        finish_path();
+                        active = false;
+                    }
+                }
                 if (STATS) ts3 = ts4 = __builtin_amdgcn_s_memtime();
                 // the back of the vertex and its tail for a full wave of queued paths — of ONE class while new paths still arrive (the class
                 // with its own queue first); when the work item has nothing new left, whatever waits in either queue shares the passes

@@ -302,6 +302,93 @@ PT_DEV f3 camera_ray_dir(const DevCamera& cam, uint32_t px, uint32_t py, f2 uv) 
     return normalize(s * dc.x + uu * dc.y + (-ff) * dc.z);
 }
 
+// The contribution of a path that arrives at an emitter (evaluate_emissive_surface :54-73; base_renderer.rs:190-194 for a camera ray;
+// calculate_bsdf_contribution pt :33-47, nee :120-137, mis :151-181 for a BSDF-sampled one), added into L with the strategy's weight.  Such a
+// path ends there, so this is all an emitter hit has left to compute.  The kernels with the light-hit queue (pt_kernel.hpp LIGHT-HIT QUEUE)
+// call it: from the pass that evaluates 64 queued hits at once, or, the queue switched off, for the lanes that hold such a hit.  It takes
+// what it reads explicitly — the queue's record is exactly these arguments — and the expression order is the one every film was recorded
+// with: (T * ((pf * Le) * tf)) * w.  The same statements as the emitter part of shade_vertex_head, PHASES 0 and 1, which every other
+// kernel runs (see the note there: a change to one side belongs on the other as well).
+// Under NEE (strategy 1) an emitter reached by a non-specular bounce has weight 0 and nothing is added: the callers of this function end
+// such a path without queueing or evaluating it (emitter_hit_is_void).
+template <bool STATS>
+PT_DEV bool emitter_hit_is_void(const DevParams& prm, bool from_camera, bool prev_spec) {
+    return !STATS && prm.strategy == 1u && !from_camera && !prev_spec;
+}
+template <bool STATS, uint32_t FEAT>
+PT_DEV void emitter_contribution(const DevScene& sc, const DevParams& prm, const Surface& sf, const DevMaterial* mat, const float* T, const float* pf,
+                                 float p_pdf, f3 prev_pos, const Wl& wl, bool from_camera, bool prev_spec, float* L, StatCounters& st) {
+    if (emitter_hit_is_void<STATS>(prm, from_camera, prev_spec)) return;
+    float Le[4] = {0, 0, 0, 0};
+    DevSpectrum rs = load_spectrum(&mat->color);
+    eval_spectrum<STATS, (FEAT & FEAT_EMTEX) != 0, (FEAT & FEAT_EMTEX) != 0>(sc, rs, wl, sf.uv, Le, st);
+    float inten = mat->intensity;
+    if ((FEAT & FEAT_EMTEX) && mat->metallic_tex != 0xffffffffu) { float t3[3]; bilinear_rgb(sc, mat->metallic_tex, sf.uv, t3); inten = t3[0]; }   // FloatParameter::texture intensity at the hit (emissive_material.rs:55-56)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) Le[i] = Le[i] * inten;
+    if (from_camera) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) L[i] = L[i] + T[i] * Le[i];      // :190-194
+        return;
+    }
+    float tf = 1.0f / p_pdf;
+    float w = 1.0f;
+    if (prm.strategy == 1u) w = prev_spec ? 1.0f : 0.0f;
+    else if (prm.strategy == 2u && !prev_spec) {
+        // Scene::pdf_light_sample (scene.rs:156-182); light probability = phi-weighted pick
+        float wsum = 0.0f, wme = 0.0f;
+        if (!(FEAT & FEAT_MLIGHT) || sc.n_lights == 1u) {
+            // one light (every BASELINE config): phi(lambda) is Le * area, already evaluated — unless the radiance is a
+            // texture, whose phi is taken at uv (0.5, 0.5) (EmissiveMaterial::average_intensity, emissive_material.rs:61-79)
+            float sum = 0.0f;
+            float area = sc.lights[0].area_sum;
+            if ((FEAT & FEAT_EMTEX) && (mat->color.kind == SPK_TEXTURE || mat->metallic_tex != 0xffffffffu)) {
+                float ph[4];
+                DevSpectrum ls = load_spectrum(&mat->color);
+                eval_spectrum<false, true, true>(sc, ls, wl, f2{0.5f, 0.5f}, ph, st);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) sum += (ph[i] * mat->intensity_avg) * area;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) sum += Le[i] * area;
+            }
+            wsum = wme = sum / 4.0f;
+        } else
+        for (uint32_t li = 0; li < sc.n_lights; ++li) {
+            DevLight lt = sc.lights[li];
+            const DevMaterial* lm = sc.materials + lt.material;
+            float ph[4];
+            DevSpectrum ls = load_spectrum(&lm->color);
+            eval_spectrum<false, (FEAT & FEAT_EMTEX) != 0, (FEAT & FEAT_EMTEX) != 0>(sc, ls, wl, f2{0.5f, 0.5f}, ph, st);
+            float inten_l = lm->intensity_avg;
+            float sum = 0.0f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sum += (ph[i] * inten_l) * lt.area_sum;
+            float wt = sum / 4.0f;
+            wsum += wt;
+            if (li == sf.light) wme = wt;
+        }
+        float probability = wsum == 0.0f ? 0.0f : wme / wsum;
+        f3 dv = prev_pos - sf.p;
+        float distance = length(dv);
+        f3 wo_l = -normalize(dv);
+        float pdf_dir = sf.light_pdf_area * (distance * distance) / fabsf(dot(sf.ng, wo_l));
+        w = balance_heuristic(p_pdf, probability * pdf_dir);
+    }
+    if (w != 0.0f || prm.strategy != 1u) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) L[i] = L[i] + (T[i] * ((pf[i] * Le[i]) * tf)) * w;
+    }
+}
+// ... the surface from the hit first (the front of the tail queue's vertex and the light-hit queue's pass, which have not loaded it)
+template <bool STATS, uint32_t FEAT>
+PT_DEV void emitter_hit(const DevScene& sc, const DevParams& prm, const Hit& hit, f3 rd, const float* T, const float* pf, float p_pdf, f3 prev_pos,
+                        const Wl& wl, bool from_camera, bool prev_spec, float* L, StatCounters& st) {
+    if (emitter_hit_is_void<STATS>(prm, from_camera, prev_spec)) return;
+    const Surface sf = load_surface(sc, hit, rd);
+    emitter_contribution<STATS, FEAT>(sc, prm, sf, sc.materials + sf.material, T, pf, p_pdf, prev_pos, wl, from_camera, prev_spec, L, st);
+}
+
 // One path vertex in two halves.  The closest-hit result of P.ro/P.rd arrives (got/hit):
 //   shade_vertex_head  accounts emission (with the strategy's weight), applies throughput + Russian roulette, builds the shading frames
 //                      and draws the BSDF's random numbers; returns true when the path ends here, else C.cont is set;
@@ -330,6 +417,11 @@ PT_DEV void shade_ctx_idle_cc(ShadeCtx& C) {
 // throughput, Russian roulette, the depth test: what decides whether the path goes on —; 2 = only its back for a path that went on — the
 // surface again from the hit, shading frames, the BSDF's random numbers — whose result feeds shade_vertex_tail.  1 then 2 on the same
 // (P, hit) compute exactly what 0 computes: the sampler's dimensions are consumed in the same order.
+// 3 = the front as in 1 for a caller that has taken the paths whose hit is on an emitter out (the kernels with the light-hit queue,
+// pt_kernel.hpp: emitter_hit is all such a path has left, and they call it themselves): no emitter code in the front at all.
+// (PHASES 0 and 1 keep the emitter evaluation as the statements they were compiled from — emitter_contribution restates them —: calling
+// the function from here re-schedules every kernel without the queue, scratch +8 ... +68 B per lane on the gfx950 disassembly, and those
+// kernels are measured as they are.  A change to one side belongs on the other as well.)
 template <bool STATS, uint32_t FEAT, int PHASE = 0>
 PT_DEV bool shade_vertex_head(Path& P, const DevScene& sc, const DevParams& prm, const SamplerCtx& sctx, bool got, const Hit& hit, ShadowReq& sh,
                            StatCounters& st, unsigned long long& tsa, ShadeCtx& C) {
@@ -394,11 +486,11 @@ PT_DEV bool shade_vertex_head(Path& P, const DevScene& sc, const DevParams& prm,
         // PHASE 1 (the front of the tail queue's vertex) knows the material TYPE from the hit (DevTri::pad[0], Hit::mclass) and needs the surface
         // for emitters only: every other lane skips the ten loads and the normalisations here — the back of the vertex computes the surface once
         Surface sf; const DevMaterial* mat = nullptr; uint32_t mtype;
-        if (PHASE == 1) {
+        if (PHASE == 1 || PHASE == 3) {
             mtype = hit.mclass & 7u;
-            if (mtype == MT_EMISSIVE) { sf = load_surface(sc, hit, rd); mat = sc.materials + sf.material; }
+            if (PHASE == 1 && mtype == MT_EMISSIVE) { sf = load_surface(sc, hit, rd); mat = sc.materials + sf.material; }
         } else { sf = load_surface(sc, hit, rd); mat = sc.materials + sf.material; mtype = mat->type; }
-        const bool emissive = PHASE != 2 && mtype == MT_EMISSIVE;            // (PHASE 2: the path went on, so the surface is not an emitter)
+        const bool emissive = PHASE != 2 && PHASE != 3 && mtype == MT_EMISSIVE;   // (PHASE 2: the path went on, so the surface is not an emitter; 3: the caller's word)
         float Le[4] = {0, 0, 0, 0};
         if constexpr (PHASE != 2) {
         if (emissive) {                                                      // evaluate_emissive_surface :54-73
@@ -497,7 +589,7 @@ PT_DEV bool shade_vertex_head(Path& P, const DevScene& sc, const DevParams& prm,
             if (depth > prm.max_depth || emissive) end_path = true;           // as_bsdf_material() == None (:199-202)
         }
         }   // PHASE != 2
-        if (PHASE != 1 && !end_path) {
+        if (PHASE != 1 && PHASE != 3 && !end_path) {
             if (STATS) { st.bounces++; tsa = __builtin_amdgcn_s_memtime(); }
             Frame fr, fw_num;
             if constexpr (numeric_frames<FEAT>()) shading_frames_numeric(sf.ns, sf.tangent, fr, fw_num);

@@ -60,4 +60,20 @@ constexpr TqStagePop tq_stage_pop(uint32_t count, uint32_t n_push, uint32_t n_ta
     return TqStagePop{slot, slot >= count, slot >= count ? slot - count : 0u};
 }
 
+// ---- the light-hit queue (the kernels with ONE tail queue; pt_kernel.hpp LIGHT-HIT QUEUE) ----
+// A second stack of the wave, for the paths whose hit is on an emitter: they end there, and what is left of them — the emitter's radiance
+// with the strategy's weight, the film — is computed 64 at a time.  Same arithmetic as the tail queue's: `count` records wait in slots
+// [0, count), the pushing lanes write consecutive slots on top by rank, a pass pops the newest min(64, count) by rank.  A pass is due as
+// soon as 64 wait — the front has just pushed and every lane is free — so at most 63 stay behind and an iteration adds at most 64: the
+// count never exceeds LQ_MAX_WAITING, inside the LQ_SLOTS of the stack.  When the work item is done (its pool spent, no lane active, the
+// tail queue empty) one last pass takes what is left, fewer than 64.
+constexpr uint32_t LQ_SLOTS = 128u;               // entries of the stack
+constexpr uint32_t LQ_PASS = 64u;                 // records a full pass takes: one per lane
+constexpr uint32_t LQ_MAX_WAITING = 127u;         // the bound of the count
+constexpr uint32_t lq_push_slot(uint32_t count, uint32_t rank) { return count + rank; }
+constexpr bool lq_pass_due(uint32_t count, bool item_done) { return count >= LQ_PASS || (item_done && count != 0u); }
+constexpr uint32_t lq_pass_take(uint32_t count) { return count < LQ_PASS ? count : LQ_PASS; }
+// slot popped by lane `rank` of the n = lq_pass_take(count) lanes of the pass
+constexpr uint32_t lq_pop_slot(uint32_t count, uint32_t n, uint32_t rank) { return count - n + rank; }
+
 }  // namespace pt
