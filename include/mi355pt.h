@@ -381,6 +381,14 @@ const char* mi355pt_version(void);
  * includes (ahead of the variance-guided denoiser's, which stays the last one). */
 #include "mi355pt_motion.h"
 
+/* ---------------- mesh deformation on a built scene ---------------- */
+/* EXTENSION, no reference counterpart: mi355pt_mesh_update and mi355pt_scene_deform_meshes — new vertex arrays (positions, normals,
+ * tangents) for meshes of the built scene, applied on the device: the local triangle and shading records replaced from one staging buffer,
+ * then the instance move's sequence (positions re-transformed, shading normals and light pdfs refreshed, both trees refit, the SAH cost
+ * reported).  Refit only, no topology change; works in every lowering class.  Declared in its own header, which this one always includes
+ * (ahead of the variance-guided denoiser's, which stays the last one). */
+#include "mi355pt_deform.h"
+
 /* ---------------- variance-guided denoiser ---------------- */
 /* EXTENSION, no reference counterpart: a second filter beside the one above, which it leaves as it is — mi355pt_denoise_var_params,
  * mi355pt_denoise_var_params_default, mi355pt_denoise_var_scratch_bytes, mi355pt_denoise_var_device and mi355pt_denoise_var: an a-trous

@@ -1,5 +1,5 @@
 // What the host translation units behind the C ABI share (api.cpp and the api_<stage>.cpp files, one per public header; scene_rebase.cpp,
-// scene_instances.cpp): the scene object and its launch context, fail / HIP_TRY, the device buffer and event holders, and what api.cpp
+// scene_instances.cpp, scene_deform.cpp): the scene object and its launch context, fail / HIP_TRY, the device buffer and event holders, and what api.cpp
 // defines for the others.  The pure argument predicates are api_checks.hpp.  Not installed, not an ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -96,6 +96,18 @@ struct DevBuf {
     hipError_t alloc_for(const T* host, size_t n) { return host ? alloc(n) : hipSuccess; }
     hipError_t download(T* host, size_t n) const { return host ? hipMemcpy(host, p, n * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess; }
 };
+
+// A buffer of a move's own (scene_instances.cpp, scene_deform.cpp), allocated by the first move after a build and freed with the scene
+template <typename T>
+hipError_t ensure(SceneImpl* s, T** p, size_t count) {
+    if (*p) return hipSuccess;
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, std::max<size_t>(count * sizeof(T), 16));
+    if (e != hipSuccess) return e;
+    s->allocs.push_back(q);
+    *p = (T*)q;
+    return hipSuccess;
+}
 
 // A HIP event, destroyed with the object: an error between create() and the end of the scope does not leak it
 struct Event {

@@ -166,6 +166,12 @@ hipError_t launch_shade_refresh(DevTriShade* d_shade, const DevTriLocal* d_local
 size_t sah_scratch_floats(uint32_t n_entries);
 hipError_t launch_sah_cost(const DevNode* d_nodes, int32_t root, const uint32_t* d_entries, uint32_t n_entries, float* d_scratch, hipStream_t);
 constexpr uint32_t SAH_COST_LAUNCHES = 2;
+// pt_kernels_deform.hip: a mesh deformation on a built scene (include/mi355pt_deform.h, scene_deform.cpp).  launch_deform_tris: the positions
+// of the local records and rows 0 - 2 of the shading records of the leaf-order triangles whose instance has a slot in d_table
+// (deform_plan.hpp deform_table: n_instances words, then from word slots_at on n_slots slot records), gathered from d_staging through the
+// index pool d_mesh_idx; the triangles of every other instance are not written
+hipError_t launch_deform_tris(DevTriLocal* d_local, DevTriShade* d_shade, const uint32_t* d_table, const float* d_staging, const uint32_t* d_mesh_idx, uint32_t n_tris,
+                              uint32_t n_instances, uint32_t slots_at, uint32_t n_slots, hipStream_t);
 
 // Resident 64-thread blocks (= waves) of `kernel` on the current device: the persistent grid size of the EXACT instantiation a launch takes
 // (the register count, and so the occupancy, differs between instantiations and between translation units with their own backend flags).

@@ -73,6 +73,12 @@ struct RebaseState {
     float* d_light_pdf = nullptr;             // light_pdf_area per light triangle
     bool sah_built_valid = false;
     float sah_built = 0.0f;
+    // mi355pt_scene_deform_meshes (scene_deform.cpp): allocated by the first deformation after a build (all in SceneImpl::allocs)
+    float* d_deform_staging = nullptr;        // deform_plan.hpp: the new arrays of one call, sized for every mesh of the scene at once
+    uint32_t* d_deform_table = nullptr;       // ... the slot per instance and the slot records
+    uint32_t* d_mesh_idx = nullptr;           // ... the index buffers of all meshes, one after the other
+    std::vector<uint32_t> mesh_idx_offset;    // first word of mesh g in that pool (n_meshes + 1 entries)
+    std::vector<uint8_t> mesh_idx_uploaded;   // per mesh: its indices are on the device (uploaded once per build, by its first deformation)
     float tree_cam_pos[3] = {0, 0, 0};        // the camera position the tree was BUILT for (build_cam_pos follows the moves)
     size_t n_degenerate = 0; int bvh_depth = 0, stack_need = 0; std::string collapse_method;   // the build's LowerReport (mi355pt_scene_debug_device_digest)
 };

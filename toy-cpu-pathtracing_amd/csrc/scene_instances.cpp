@@ -20,18 +20,6 @@ namespace {
 
 double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 
-// a buffer of the move's own, allocated by the first move after a build and freed with the scene
-template <typename T>
-hipError_t ensure(SceneImpl* s, T** p, size_t count) {
-    if (*p) return hipSuccess;
-    void* q = nullptr;
-    const hipError_t e = hipMalloc(&q, std::max<size_t>(count * sizeof(T), 16));
-    if (e != hipSuccess) return e;
-    s->allocs.push_back(q);
-    *p = (T*)q;
-    return hipSuccess;
-}
-
 }  // namespace
 
 extern "C" {

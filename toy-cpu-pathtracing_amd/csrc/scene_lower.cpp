@@ -613,6 +613,12 @@ void mesh_local_bounds(const SceneImpl& scene, std::vector<MeshBounds>* out) {
     for (size_t i = 0; i < scene.meshes.size(); ++i) mesh_aabb(scene.meshes[i], (*out)[i].lo, (*out)[i].hi);
 }
 
+void mesh_local_bounds_of(const SceneImpl& scene, uint32_t geom, MeshBounds* out) { mesh_aabb(scene.meshes[geom], out->lo, out->hi); }
+
+bool local_triangle_degenerate(const HostMesh& mesh, uint32_t tri) {
+    return degenerate(vertex(mesh, mesh.idx[3 * tri]), vertex(mesh, mesh.idx[3 * tri + 1]), vertex(mesh, mesh.idx[3 * tri + 2]));
+}
+
 // lower_geometry's loop without its per-triangle work: the same functions in the same order on the same inputs
 int lower_camera_records(const SceneImpl& scene, const mi355pt_camera* cam, const std::vector<MeshBounds>& bounds, const std::vector<DevLight>& built_lights,
                          const std::vector<DevLightTri>& built_light_tris, CameraRecords* out, std::string* err, const uint8_t* moved,

@@ -101,6 +101,12 @@ void keep_topology(const LoweredGeometry& geo, const BvhOut& bvh, const mi355pt_
 // degenerate() on the render-space vertices of triangle `tri` of instance `instance`, whose lowered record is `di`
 bool render_triangle_degenerate(const SceneImpl& scene, const DevInstance& di, uint32_t instance, uint32_t tri);
 
+// What NEW VERTICES of a mesh change besides (mi355pt_scene_deform_meshes, scene_deform.cpp): one mesh's entry of mesh_local_bounds again,
+// and degenerate() on the LOCAL vertices of triangle `tri` of a mesh — the set the tree leaves out in local-triangle mode.  With the
+// instances of the deformed meshes marked in `moved`, lower_camera_records gives an emissive one its area tables from the new vertices
+void mesh_local_bounds_of(const SceneImpl& scene, uint32_t geom, MeshBounds* out);
+bool local_triangle_degenerate(const HostMesh& mesh, uint32_t tri);
+
 // scene_info's text; ms = {bvh_ms, bvh_device_ms, collapse_ms} or null to leave the three timings out (what the digests are recorded with)
 std::string lowering_info(const LoweredScene& ls, const LowerReport& rep, bool gpu_builder, const double* ms);
 

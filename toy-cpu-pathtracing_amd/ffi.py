@@ -213,6 +213,8 @@ MOVE_REASON = ["rebased", "same_position", "degenerate_set_changed", "instance_c
 
 # mi355pt_instance_move_result.reason: MOVE_REASON plus the two of include/mi355pt_instances.h
 INSTANCE_MOVE_REASON = MOVE_REASON + ["same_transforms", "sah_degraded"]
+# ... plus the one of include/mi355pt_deform.h (mi355pt_scene_deform_meshes reports through the same result struct)
+DEFORM_REASON = INSTANCE_MOVE_REASON + ["same_vertices"]
 
 
 class InstanceMoveParams(C.Structure):
@@ -226,9 +228,14 @@ class InstanceMoveResult(C.Structure):
                 ("host_ms", C.c_double), ("device_ms", C.c_double)]
 
     def as_dict(self):
-        return {"rebuilt": int(self.rebuilt), "reason": INSTANCE_MOVE_REASON[self.reason], "launches": int(self.launches),
+        return {"rebuilt": int(self.rebuilt), "reason": DEFORM_REASON[self.reason], "launches": int(self.launches),
                 "sah_built": np.float32(self.sah_built), "sah_after": np.float32(self.sah_after), "host_ms": float(self.host_ms),
                 "device_ms": float(self.device_ms)}
+
+
+class MeshUpdate(C.Structure):
+    """mi355pt_mesh_update (include/mi355pt_deform.h)"""
+    _fields_ = [("geom", C.c_uint32), ("pos", C.POINTER(C.c_float)), ("nrm", C.POINTER(C.c_float)), ("tri_tangent", C.POINTER(C.c_float))]
 
 
 def make_camera(position, direction, up, width, height, fov_deg=45.0):
@@ -246,7 +253,7 @@ def _ptr(a, ty):
 
 
 # every symbol include/mi355pt.h declares (tests/test_abi.py checks the built library exports all of them) ...
-DEBUG_SYMBOLS = ["debug_unlock", "scene_debug_set_lowering", "scene_debug_lowering_digest", "scene_debug_camera_candidates", "scene_debug_move_digest", "scene_debug_move_export", "scene_debug_device_digest", "scene_debug_pinned_digest", "scene_debug_pinned_export", "scene_debug_pin_host_tree", "scene_debug_set_instance_transform", "debug_sah_cost", "scene_export_bvh", "probe_bvh_collapse", "probe_bvh_collapse_nodes", "probe_sobol", "probe_sincos", "probe_intersect", "probe_occluded",
+DEBUG_SYMBOLS = ["debug_unlock", "scene_debug_set_lowering", "scene_debug_lowering_digest", "scene_debug_camera_candidates", "scene_debug_move_digest", "scene_debug_move_export", "scene_debug_device_digest", "scene_debug_pinned_digest", "scene_debug_pinned_export", "scene_debug_pin_host_tree", "scene_debug_set_instance_transform", "scene_debug_set_mesh_vertices", "debug_sah_cost", "scene_export_bvh", "probe_bvh_collapse", "probe_bvh_collapse_nodes", "probe_sobol", "probe_sincos", "probe_intersect", "probe_occluded",
                  "sample_log_records", "render_sample_log", "probe_radiance", "probe_display_meter_ms"]     # ... and include/mi355pt_debug.h
 ABI_SYMBOLS = [
     "scene_create", "scene_destroy", "scene_set_rgb2spec", "scene_add_lut470", "scene_add_tex_rgb8", "scene_add_mesh",
@@ -281,6 +288,8 @@ INSTANCES_SYMBOLS = ["scene_set_instance_dynamic", "scene_move_instances"]
 # ... and include/mi355pt_motion.h, the object-motion block (tests/test_motion.py)
 MOTION_SYMBOLS = ["render_ids_device", "render_ids", "motion_table", "temporal_accumulate_motion_device", "temporal_accumulate_motion",
                   "temporal_accumulate_rectified_motion_device", "temporal_accumulate_rectified_motion"]
+# ... and include/mi355pt_deform.h, the mesh-deformation block (tests/test_deform.py)
+DEFORM_SYMBOLS = ["scene_deform_meshes"]
 ADAPTIVE_SYMBOLS = ["adaptive_scratch_bytes", "adaptive_step_device", "film_normalize_tiles_device", "render_adaptive_device", "render_adaptive"]
 
 
@@ -505,6 +514,34 @@ class SceneHandle:
         res = InstanceMoveResult()
         self.b.check(fn(self.h, C.byref(cam), _ptr(idv, C.c_uint32), _ptr(cols, C.c_float), idv.size, C.byref(prm), C.byref(res)), "scene_move_instances")
         return res.as_dict()
+
+    def _mesh_updates(self, meshes):
+        """{geom: (pos, nrm or None, tangent or None)} -> (a ctypes array of MeshUpdate in ascending geom order, the arrays it points into)"""
+        keep, ups = [], (MeshUpdate * len(meshes))()
+        for k, geom in enumerate(sorted(meshes)):
+            arrays = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in meshes[geom]]
+            keep.append(arrays)
+            ups[k] = MeshUpdate(geom, *[_ptr(a, C.c_float) for a in arrays])
+        return ups, keep
+
+    def deform_meshes(self, cam, meshes, rebuild_above=0.0):
+        """mi355pt_scene_deform_meshes (include/mi355pt_deform.h, product only): new vertex arrays {geom: (pos (n_vert, 3), nrm (n_vert, 3) or
+        None = keep, per-triangle tangent (n_tri, 3) or None = keep)} for meshes of the built scene, applied on the device -> move_instances'
+        dictionary ("reason" a DEFORM_REASON name)"""
+        fn = self.b.fn("scene_deform_meshes")
+        fn.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(MeshUpdate), C.c_uint32, C.POINTER(InstanceMoveParams), C.POINTER(InstanceMoveResult)]
+        ups, keep = self._mesh_updates(meshes)
+        prm = InstanceMoveParams(rebuild_above)
+        res = InstanceMoveResult()
+        self.b.check(fn(self.h, C.byref(cam), ups, len(meshes), C.byref(prm), C.byref(res)), "scene_deform_meshes")
+        return res.as_dict()
+
+    def debug_set_mesh_vertices(self, meshes):
+        """mi355pt_scene_debug_set_mesh_vertices (host only, product only): deform_meshes' description update alone, on an unbuilt scene"""
+        fn = self.b.fn("scene_debug_set_mesh_vertices")
+        fn.argtypes = [C.c_void_p, C.POINTER(MeshUpdate), C.c_uint32]
+        ups, keep = self._mesh_updates(meshes)
+        self.b.check(fn(self.h, ups, len(meshes)), "scene_debug_set_mesh_vertices")
 
     def debug_pin_host_tree(self, cam):
         """mi355pt_scene_debug_pin_host_tree (host only, product only): what a build keeps on the host, for an unbuilt scene"""

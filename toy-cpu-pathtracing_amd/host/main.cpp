@@ -55,7 +55,20 @@ struct Args {   // main.rs:20-53
     // instance's local_to_world is the scene's with T . R_y applied k times (the way --camera-step moves the camera); the instances are marked
     // dynamic before the build and moved on the device between the frames, and the accumulation is the motion-aware one
     std::vector<InstanceTransform> instance_steps;
+    // nor deforming meshes of the built scene (mi355pt_deform.h): --mesh-wave GEOM:amp,wavelength[,phase_step], repeatable — the scene is
+    // built as described, then every vertex of mesh GEOM takes y += amp sin(2 pi x / wavelength + phase_step) with area-weighted vertex
+    // normals recomputed on the host, applied on the device before the frame.  --instance-rebuild-above applies to it
+    struct MeshWave { uint32_t geom; float amp, wavelength, phase_step; };
+    std::vector<MeshWave> mesh_waves;
 };
+
+// the positions of a mesh under a wave along x that displaces y (local space), in double and rounded to float
+std::vector<float> waved_positions(const Args::MeshWave& w, const std::vector<float>& pos) {
+    std::vector<float> out(pos);
+    for (size_t v = 0; v * 3 < pos.size(); ++v)
+        out[3 * v + 1] = (float)((double)pos[3 * v + 1] + (double)w.amp * std::sin(2.0 * 3.14159265358979323846 * (double)pos[3 * v] / (double)w.wavelength + (double)w.phase_step));
+    return out;
+}
 
 // T . R_y . S . local_to_world (column-major): T R S composed in double and rounded to float, the product in double and rounded to float
 void instance_transform_matrix(const Args::InstanceTransform& it, const float* l2w, float* out) {
@@ -581,7 +594,12 @@ static void usage() {
               "                                         is the scene's with T . R_y applied k times; the instances are moved on the device between the frames,\n"
               "                                         and each frame adds an ID pass, a motion table and the motion-aware accumulation.  Not with --half-res)\n"
               "                   [--instance-rebuild-above X] (0 = never; with --instance-transform: build again when the refit tree's SAH cost exceeds X\n"
-              "                                         times the built tree's)");
+              "                                         times the built tree's; applies to --mesh-wave too)\n"
+              "                   [--mesh-wave GEOM:amp,wavelength[,phase_step]] (repeatable, distinct GEOMs; pt|nee|mis|normal|albedo|position|depth: the scene is\n"
+              "                                         built as described, then every vertex of mesh GEOM takes y += amp sin(2 pi x / wavelength + phase_step)\n"
+              "                                         in local space, with area-weighted vertex normals, on the device: mi355pt_scene_deform_meshes; one line\n"
+              "                                         on stderr.  Not with --temporal-frames: the reprojection assumes rigid motion per instance, motion\n"
+              "                                         vectors for deforming meshes are a later change)");
 }
 
 int main(int argc, char** argv) {
@@ -674,6 +692,19 @@ int main(int argc, char** argv) {
             if (!ok) { std::fprintf(stderr, "error: invalid value '%s' for '--instance-step': ID:tx,ty,tz[:ry_deg], finite numbers, each ID once\n", v.c_str()); return 2; }
             a.instance_steps.push_back(it);
         }
+        else if (k == "--mesh-wave") {
+            const std::string v = val();
+            Args::MeshWave w{0, 0.0f, 0.0f, 0.0f};
+            char tail = 0;
+            int n = std::sscanf(v.c_str(), "%u:%f,%f%c", &w.geom, &w.amp, &w.wavelength, &tail);
+            bool ok = n == 3;
+            if (n == 4 && tail == ',') ok = std::sscanf(v.c_str(), "%u:%f,%f,%f%c", &w.geom, &w.amp, &w.wavelength, &w.phase_step, &tail) == 4;
+            ok = ok && std::isfinite(w.amp) && std::isfinite(w.wavelength) && std::isfinite(w.phase_step) && w.wavelength != 0.0f;
+            ok = ok && !v.empty() && v[0] >= '0' && v[0] <= '9';
+            for (const Args::MeshWave& o : a.mesh_waves) ok = ok && o.geom != w.geom;
+            if (!ok) { std::fprintf(stderr, "error: invalid value '%s' for '--mesh-wave': GEOM:amp,wavelength[,phase_step], finite numbers, a wavelength other than 0, each GEOM once\n", v.c_str()); return 2; }
+            a.mesh_waves.push_back(w);
+        }
         else if (k == "--instance-rebuild-above") {
             const std::string v = val();
             char tail = 0;
@@ -752,7 +783,13 @@ int main(int argc, char** argv) {
     if (a.half_res && a.denoise) { std::fprintf(stderr, "error: --half-res with --denoise: the upsampled pair goes to --denoise-variance\n"); return 2; }
     if (a.half_res && a.adaptive_threshold != 0.0f) { std::fprintf(stderr, "error: --half-res with --adaptive-threshold: half-resolution rendering takes one sample count per frame\n"); return 2; }
     if (a.half_res && (a.spp == 0 || a.denoise_guide_spp == 0)) { std::fprintf(stderr, "error: --half-res needs --spp and --denoise-guide-spp above 0\n"); return 2; }
-    if (a.instance_rebuild_given && a.instance_transforms.empty()) { std::fprintf(stderr, "error: --instance-rebuild-above needs --instance-transform: it is the move's threshold\n"); return 2; }
+    if (a.instance_rebuild_given && a.instance_transforms.empty() && a.mesh_waves.empty()) { std::fprintf(stderr, "error: --instance-rebuild-above needs --instance-transform or --mesh-wave: it is the move's threshold\n"); return 2; }
+    if (!a.mesh_waves.empty()) {
+        if (a.temporal) { std::fprintf(stderr, "error: --mesh-wave with --temporal-frames: the temporal reprojection assumes rigid motion per instance (no motion vectors for deforming meshes yet)\n"); return 2; }
+        if (a.gpus > 1) { std::fprintf(stderr, "error: --mesh-wave with --gpus %d: a scene built over several GPUs is not deformed\n", a.gpus); return 2; }
+        if (a.renderer == "shading-normal") { std::fprintf(stderr, "error: --mesh-wave with --renderer shading-normal: pt, nee, mis, normal, albedo, position or depth\n"); return 2; }
+        std::sort(a.mesh_waves.begin(), a.mesh_waves.end(), [](const Args::MeshWave& x, const Args::MeshWave& y) { return x.geom < y.geom; });
+    }
     if (!a.instance_steps.empty()) {
         for (const Args::InstanceTransform& st : a.instance_steps)
             for (const Args::InstanceTransform& it : a.instance_transforms)
@@ -849,6 +886,8 @@ int main(int argc, char** argv) {
             if (it.id >= scene.instance_count()) { std::fprintf(stderr, "error: invalid value for '--instance-step': scene %u has no instance %u (%u instances)\n", a.scene, it.id, scene.instance_count()); return 2; }
             scene.set_instance_dynamic(it.id);
         }
+        for (const Args::MeshWave& w : a.mesh_waves)
+            if (w.geom >= scene.mesh_count()) { std::fprintf(stderr, "error: invalid value for '--mesh-wave': scene %u has no mesh %u (%u meshes)\n", a.scene, w.geom, scene.mesh_count()); return 2; }
         std::puts("Start build scene.");                                                // main.rs:103-109
         auto t0 = std::chrono::steady_clock::now();
         if (a.gpus > 1) scene.build_multi(camera, a.gpus); else scene.build(camera);
@@ -860,6 +899,17 @@ int main(int argc, char** argv) {
             }
             const mi355pt_instance_move_result mr = scene.move_instances(camera, ids, matrices, a.instance_rebuild_above);
             std::fprintf(stderr, "instance move: rebuilt=%u reason=%u launches=%u sah=%.6g\xe2\x86\x92%.6g host_ms=%.3f device_ms=%.3f\n", mr.rebuilt, mr.reason, mr.launches,
+                         (double)mr.sah_built, (double)mr.sah_after, mr.host_ms, mr.device_ms);
+        }
+        if (!a.mesh_waves.empty()) {
+            std::vector<uint32_t> geoms; std::vector<std::vector<float>> pos, nrm;
+            for (const Args::MeshWave& w : a.mesh_waves) {
+                geoms.push_back(w.geom);
+                pos.push_back(waved_positions(w, scene.mesh(w.geom).pos));
+                nrm.push_back(area_weighted_normals(scene.mesh(w.geom), pos.back()));
+            }
+            const mi355pt_instance_move_result mr = scene.deform_meshes(camera, geoms, pos, nrm, a.instance_rebuild_above);
+            std::fprintf(stderr, "mesh deform: rebuilt=%u reason=%u launches=%u sah=%.6g\xe2\x86\x92%.6g host_ms=%.3f device_ms=%.3f\n", mr.rebuilt, mr.reason, mr.launches,
                          (double)mr.sah_built, (double)mr.sah_after, mr.host_ms, mr.device_ms);
         }
         std::printf("Finish build scene: %.3f seconds.\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());

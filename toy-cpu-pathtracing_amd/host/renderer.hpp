@@ -576,6 +576,24 @@ inline void compute_tangents(TriangleMeshData& out) {
     }
 }
 
+// Area-weighted vertex normals of a mesh whose positions changed (--mesh-wave, main.cpp): every triangle adds its un-normalised cross
+// product — twice its area along its normal — to its three vertices; the library normalises what it is given (mi355pt_scene_deform_meshes).
+// A vertex no triangle with area touches keeps the normal it had.
+inline std::vector<float> area_weighted_normals(const TriangleMeshData& m, const std::vector<float>& pos) {
+    std::vector<double> acc(pos.size(), 0.0);
+    auto P = [&](uint32_t i) { return Vec3{pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]}; };
+    for (size_t t = 0; t + 2 < m.idx.size(); t += 3) {
+        const Vec3 n = v_cross(v_sub(P(m.idx[t + 1]), P(m.idx[t])), v_sub(P(m.idx[t + 2]), P(m.idx[t])));
+        for (int k = 0; k < 3; ++k) { acc[3 * m.idx[t + k]] += n.x; acc[3 * m.idx[t + k] + 1] += n.y; acc[3 * m.idx[t + k] + 2] += n.z; }
+    }
+    std::vector<float> nrm(m.nrm);
+    for (size_t v = 0; v * 3 < pos.size(); ++v) {
+        const double l = std::sqrt(acc[3 * v] * acc[3 * v] + acc[3 * v + 1] * acc[3 * v + 1] + acc[3 * v + 2] * acc[3 * v + 2]);
+        if (l > 0.0) for (int a = 0; a < 3; ++a) nrm[3 * v + a] = (float)(acc[3 * v + a] / l);
+    }
+    return nrm;
+}
+
 inline TriangleMeshData load_obj_file(const std::string& path) {
     std::ifstream f(path);
     if (!f) throw std::runtime_error("cannot open OBJ " + path);
@@ -648,6 +666,7 @@ public:
         uint32_t id;
         check(mi355pt_scene_add_mesh(s_, m.pos.data(), m.nrm.data(), m.uv.empty() ? nullptr : m.uv.data(), m.tangent.empty() ? nullptr : m.tangent.data(),
                                      m.idx.data(), (uint32_t)(m.pos.size() / 3), (uint32_t)(m.idx.size() / 3), &id), "mi355pt_scene_add_mesh");
+        meshes_.push_back(std::move(m));
         return {id};
     }
     void create_primitive(const GeometryPrimitive& d) {
@@ -681,6 +700,7 @@ public:
         compute_tangents(m);
         uint32_t id;
         check(mi355pt_scene_add_mesh(s_, m.pos.data(), m.nrm.data(), m.uv.data(), m.tangent.data(), m.idx.data(), 3, 1, &id), "mi355pt_scene_add_mesh");
+        meshes_.push_back(std::move(m));
         create_primitive(GeometryPrimitive{{id}, d.surface_material, d.transform});
     }
     void create_primitive(const EnvironmentLightPrimitive& d) {
@@ -728,6 +748,20 @@ public:
         for (size_t k = 0; k < ids.size(); ++k) instance_l2w_[ids[k]].assign(matrices.begin() + 16 * (long)k, matrices.begin() + 16 * (long)(k + 1));
         return r;
     }
+    // EXTENSION (include/mi355pt_deform.h): meshes of the built scene take new positions and normals (tangents stay) on the device — the
+    // local records replaced, then the instance move's sequence —; geoms strictly ascending, the arrays sized like the mesh's own
+    mi355pt_instance_move_result deform_meshes(const Camera& cam, const std::vector<uint32_t>& geoms, const std::vector<std::vector<float>>& pos,
+                                               const std::vector<std::vector<float>>& nrm, float rebuild_above = 0.0f) {
+        std::vector<mi355pt_mesh_update> ups(geoms.size());
+        for (size_t k = 0; k < geoms.size(); ++k) ups[k] = mi355pt_mesh_update{geoms[k], pos[k].data(), nrm[k].data(), nullptr};
+        mi355pt_instance_move_params p{rebuild_above};
+        mi355pt_instance_move_result r{};
+        check(mi355pt_scene_deform_meshes(s_, &cam.raw(), ups.data(), (uint32_t)ups.size(), &p, &r), "mi355pt_scene_deform_meshes");
+        for (size_t k = 0; k < geoms.size(); ++k) { meshes_[geoms[k]].pos = pos[k]; meshes_[geoms[k]].nrm = nrm[k]; }
+        return r;
+    }
+    uint32_t mesh_count() const { return (uint32_t)meshes_.size(); }
+    const TriangleMeshData& mesh(uint32_t geom) const { return meshes_[geom]; }      // as loaded / last deformed
     uint32_t instance_count() const { return (uint32_t)instance_l2w_.size(); }
     const float* instance_transform(uint32_t instance) const { return instance_l2w_[instance].data(); }   // local_to_world as described / last moved
     // Scene::build over the first `n_devices` GPUs of the node (mi355pt_scene_build_multi): RendererImage::render then shards the frame
@@ -743,6 +777,7 @@ public:
 
 private:
     std::vector<std::vector<float>> instance_l2w_;      // by instance id
+    std::vector<TriangleMeshData> meshes_;              // by geometry id
     void add_light(uint32_t kind, float intensity, float a_in, float a_out, const Spectrum& sp, const Transform& t) {
         mi355pt_light_desc ld{}; ld.kind = kind; ld.intensity = intensity; ld.angle_inner = a_in; ld.angle_outer = a_out;
         ld.spectrum = lower_spectrum(sp); std::memcpy(ld.local_to_world, t.m, sizeof(ld.local_to_world));
