@@ -389,6 +389,15 @@ const char* mi355pt_version(void);
  * (ahead of the variance-guided denoiser's, which stays the last one). */
 #include "mi355pt_deform.h"
 
+/* ---------------- per-pixel motion vectors ---------------- */
+/* EXTENSION, no reference counterpart: mi355pt_flow_pixel, mi355pt_scene_flow_mark and mi355pt_scene_flow_marked (a scene-owned copy of
+ * last frame's triangle positions), mi355pt_render_flow_device and mi355pt_render_flow (per pixel: where the primary hit's point of its
+ * triangle was one frame ago) and mi355pt_temporal_accumulate_flow_device, mi355pt_temporal_accumulate_flow,
+ * mi355pt_temporal_accumulate_rectified_flow_device and mi355pt_temporal_accumulate_rectified_flow — the twins of the temporal accumulation
+ * that add the pixel's record, so that the history survives camera moves, instance moves, deformations and any mix of them.  Declared in its
+ * own header, which this one always includes (ahead of the variance-guided denoiser's, which stays the last one). */
+#include "mi355pt_flow.h"
+
 /* ---------------- variance-guided denoiser ---------------- */
 /* EXTENSION, no reference counterpart: a second filter beside the one above, which it leaves as it is — mi355pt_denoise_var_params,
  * mi355pt_denoise_var_params_default, mi355pt_denoise_var_scratch_bytes, mi355pt_denoise_var_device and mi355pt_denoise_var: an a-trous

@@ -141,6 +141,20 @@ int mi355pt_render_sample_log(const mi355pt_scene* s, const mi355pt_camera* cam,
 int mi355pt_probe_radiance(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, const uint32_t* xys,
                            uint32_t n, float* out_L, float* out_lambda, float* out_pdf);
 
+/* ---------------- per-pixel motion (include/mi355pt_flow.h) ---------------- */
+/* mi355pt_render_flow with the hit it was computed from: the same kernel compiled with one more flag, which also writes per pixel
+ * {u32 tri, f32 b0, b1, b2} — the leaf-order triangle and the barycentrics as the traversal returned them; a miss writes four zero words,
+ * a pixel outside the shard reads 0 — into out_hits (host, W x H x 16 bytes).  Host buffers; the checks of mi355pt_render_flow. */
+int mi355pt_render_flow_debug(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* params, mi355pt_flow_pixel* flow /* W*H */,
+                              uint32_t* ids /* W*H or NULL */, void* out_hits /* W*H*16 bytes */, mi355pt_stats* stats);
+/* The mark's triangle array (mi355pt_scene_flow_mark) in mi355pt_scene_export_bvh's triangle layout and calling convention: out_tris NULL
+ * for the count; *n_tris holds the buffer's capacity on entry.  Synchronises the device.  MI355PT_E_INVALID for a scene without a mark. */
+int mi355pt_scene_export_flow_mark(const mi355pt_scene* s, void* out_tris, uint32_t* n_tris);
+/* Which triangle of which instance a leaf-order triangle is, as the device's shading records say: out_ids[2 i] = the instance (the index
+ * mi355pt_scene_add_instance returned), out_ids[2 i + 1] = the triangle's index inside its mesh.  Same calling convention (out_ids NULL for
+ * the count).  The tests compare the flow pass's hits with the oracle's (primitive, triangle) through it. */
+int mi355pt_scene_export_triangle_ids(const mi355pt_scene* s, uint32_t* out_ids /* 2 per triangle */, uint32_t* n_tris);
+
 
 #ifdef __cplusplus
 }

@@ -38,8 +38,8 @@
  * exactly zero cross product, in the space the lowering decides it in) rebuilds.  No topology change, no device-pointer input: the
  * description on the host holds the vertices for the fallback and the digests.  Scenes built with mi355pt_scene_build_multi are not
  * deformed.  The temporal accumulation (mi355pt_temporal.h) assumes a static world and the object motion vectors of mi355pt_motion.h a
- * rigid motion per instance: neither reprojects across a deformation (motion vectors for deforming meshes are a later change) — start the
- * accumulation again after this call.
+ * rigid motion per instance: neither reprojects across a deformation — start those accumulations again after this call, or use the
+ * per-pixel motion records of mi355pt_flow.h, which follow it.
  */
 #ifndef MI355PT_DEFORM_H
 #define MI355PT_DEFORM_H

@@ -211,6 +211,56 @@ int mi355pt_scene_export_bvh(const mi355pt_scene* s, void* out_nodes, uint32_t* 
     return MI355PT_OK;
 }
 
+int mi355pt_render_flow_debug(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, mi355pt_flow_pixel* flow, uint32_t* ids, void* out_hits,
+                              mi355pt_stats* stats) {
+    if (!out_hits) return fail(MI355PT_E_INVALID, "flow debug: null hit buffer");
+    int rc = flow_check(s, cam, p, flow, 1, ids);
+    if (rc) return rc;
+    const size_t np = (size_t)cam->width * cam->height;
+    DevBuf<mi355pt_flow_pixel> d_flow;
+    DevBuf<uint32_t> d_ids;
+    DevBuf<float4> d_hits;
+    HIP_TRY(d_flow.alloc(np));
+    HIP_TRY(hipMemset(d_flow.p, 0, np * sizeof(mi355pt_flow_pixel)));
+    HIP_TRY(d_ids.alloc_for(ids, np));
+    if (ids) HIP_TRY(hipMemset(d_ids.p, 0, np * sizeof(uint32_t)));
+    HIP_TRY(d_hits.alloc(np));
+    HIP_TRY(hipMemset(d_hits.p, 0, np * sizeof(float4)));
+    if ((rc = render_flow_launch(s, cam, p, d_flow.p, d_ids.p, d_hits.p, nullptr, stats))) return rc;
+    HIP_TRY(d_flow.download(flow, np));
+    HIP_TRY(d_ids.download(ids, np));
+    HIP_TRY(d_hits.download((float4*)out_hits, np));
+    return MI355PT_OK;
+}
+
+int mi355pt_scene_export_flow_mark(const mi355pt_scene* s, void* out_tris, uint32_t* n_tris) {
+    if (!s || !n_tris) return fail(MI355PT_E_INVALID, "null argument");
+    if (!s->impl.built) return fail(MI355PT_E_NOT_BUILT, "scene not built");
+    if (!s->impl.rebase.flow_marked) return fail(MI355PT_E_INVALID, "the scene holds no mark (mi355pt_scene_flow_mark)");
+    const uint32_t n = s->impl.dev.n_tris;
+    if (out_tris) {
+        if (*n_tris < n) return fail(MI355PT_E_INVALID, "triangle buffer too small");
+        HIP_TRY(hipDeviceSynchronize());      // the mark's copy is asynchronous on the caller's stream
+        if (n) HIP_TRY(hipMemcpy(out_tris, s->impl.rebase.d_tris_prev, sizeof(DevTri) * n, hipMemcpyDeviceToHost));
+    }
+    *n_tris = n;
+    return MI355PT_OK;
+}
+
+int mi355pt_scene_export_triangle_ids(const mi355pt_scene* s, uint32_t* out_ids, uint32_t* n_tris) {
+    if (!s || !n_tris) return fail(MI355PT_E_INVALID, "null argument");
+    if (!s->impl.built) return fail(MI355PT_E_NOT_BUILT, "scene not built");
+    const uint32_t n = s->impl.dev.n_tris;
+    if (out_ids) {
+        if (*n_tris < n) return fail(MI355PT_E_INVALID, "id buffer too small");
+        std::vector<DevTriShade> shade(n);
+        if (n) HIP_TRY(hipMemcpy(shade.data(), s->impl.dev.shade, sizeof(DevTriShade) * n, hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < n; ++i) { out_ids[2 * (size_t)i] = shade[i].instance; out_ids[2 * (size_t)i + 1] = shade[i].local_tri; }
+    }
+    *n_tris = n;
+    return MI355PT_OK;
+}
+
 int mi355pt_probe_intersect(const mi355pt_scene* s, const float* o, const float* d, uint32_t n, float* out_t, uint32_t* out_inst, uint32_t* out_tri,
                             float* out_n) {
     if (!s || !o || !d || !out_t || !out_inst || !out_tri) return fail(MI355PT_E_INVALID, "null argument");

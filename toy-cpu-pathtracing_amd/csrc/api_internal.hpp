@@ -27,6 +27,7 @@ struct LaunchCtx {
     int aov_waves[3] = {0, 0, 0};     // [MI355PT_AOV_*]: the same for the AOV kernel of this scene's feature set
     int gbuffer_waves = 0;            // ... and for the G-buffer kernel (pt_kernels_gbuffer.hip)
     int ids_waves = 0;                // ... and for the ID pass (pt_kernels_ids.hip)
+    int flow_waves[2] = {0, 0};       // ... and for the flow pass (pt_kernels_flow.hip): [0] the production kernel, [1] its debug twin
     uint64_t* d_hash = nullptr;
     uint32_t hash_seed = 0;
     bool hash_valid = false;
@@ -149,5 +150,14 @@ int rectify_scratch_check(const mi355pt_temporal_frame* cur, const mi355pt_tempo
                           size_t scratch_bytes, const float* out_film, const float* out_half, const float* out_length);
 TemporalFrameDev frame_dev(const mi355pt_temporal_frame& f);
 TemporalArgs temporal_args(uint32_t spp, const mi355pt_temporal_view* view, uint32_t width, uint32_t height, const mi355pt_temporal_params* tp);
+// api_motion.cpp, for api_flow.cpp and api_debug.cpp, whose flow pass is the ID pass's launch: every check of mi355pt_render_ids[_device]
+// (`out`: the per-pixel output buffer) and the launch's shape
+int ids_check(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, const void* out);
+LaunchPlan plan_ids(const mi355pt_camera* cam, const mi355pt_params* p, int waves);
+// api_flow.cpp, for api_debug.cpp's mi355pt_render_flow_debug: the checks and the launch of mi355pt_render_flow_device; with d_hits the
+// kernel's debug twin, which also writes 16 bytes per pixel there
+int flow_check(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, const void* flow, size_t flow_align, const void* ids);
+int render_flow_launch(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, mi355pt_flow_pixel* d_flow, uint32_t* d_ids, void* d_hits,
+                       void* hip_stream, mi355pt_stats* stats);
 
 }  // namespace pt

@@ -14,10 +14,8 @@ using namespace pt;
 
 static_assert(sizeof(mi355pt_motion_xform) == sizeof(MotionXform) && sizeof(mi355pt_motion_xform) == sizeof(MotionXformDev), "one layout of a motion record");
 
-namespace {
-
-// every check of the two ID entry points; host memory only
-int ids_check(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, const uint32_t* ids) {
+// every check of the two ID entry points (and, with its records in the place of the ids, of the flow pass: api_flow.cpp); host memory only
+int pt::ids_check(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, const void* ids) {
     if (!ids) return fail(MI355PT_E_INVALID, "ids: null id buffer");
     if (!s || !cam || !p) return fail(MI355PT_E_INVALID, "null argument");
     if (cam->width == 0 || cam->height == 0) return fail(MI355PT_E_INVALID, "ids: zero-sized frame");
@@ -27,7 +25,7 @@ int ids_check(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_p
 
 // The ID launch's shape: the G-buffer pass's (api_gbuffer.cpp plan_gbuffer) for one sample — the AOV plan with the work item pinned to a
 // whole 8x8 tile, one pixel per lane
-LaunchPlan plan_ids(const mi355pt_camera* cam, const mi355pt_params* p, int waves) {
+LaunchPlan pt::plan_ids(const mi355pt_camera* cam, const mi355pt_params* p, int waves) {
     LaunchPlan plan = plan_launch(cam, p, 0u, 1u, waves, true);
     DevParams& dp = plan.params;
     dp.block_log2 = 3u; dp.sample_prefix_digits = 0u;
@@ -35,6 +33,8 @@ LaunchPlan plan_ids(const mi355pt_camera* cam, const mi355pt_params* p, int wave
     plan.grid = (int)std::min<uint32_t>(dp.n_work, (uint32_t)waves);
     return plan;
 }
+
+namespace {
 
 // what mi355pt_motion.h adds to temporal_check (and, with a scratch, to the rectified form's checks)
 int motion_check(const uint32_t* ids_cur, const uint32_t* ids_prev, const mi355pt_motion_xform* table, uint32_t n_entries, size_t table_align,

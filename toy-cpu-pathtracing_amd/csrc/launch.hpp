@@ -100,6 +100,25 @@ hipError_t launch_temporal_accumulate_motion(const TemporalFrameDev& cur, const 
                                              float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
 hipError_t launch_temporal_rectify_motion(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const MotionArgs& motion, uint32_t radius,
                                           float gamma, void* d_scratch, float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
+// pt_kernels_flow.hip: the flow pass (include/mi355pt_flow.h): the ID pass's launch with a 32-byte motion record per pixel from the hit's
+// triangle in d_tris_prev (the scene's mark) and in DevScene::tris_render.  d_flow is 16-byte aligned; d_ids == nullptr: not wanted;
+// d_hits != nullptr (16 bytes per pixel: tri, b0, b1, b2) takes the debug twin of the kernel.  The plan is launch_ids's
+struct FlowPixelDev { float d[3]; uint32_t id; float dn[3]; uint32_t pad; };
+static_assert(sizeof(FlowPixelDev) == 32, "a flow record is two float4");
+hipError_t launch_flow(const DevScene&, const DevCamera&, const DevParams&, const DevTri* d_tris_prev, FlowPixelDev* d_flow, uint32_t* d_ids, void* d_hits,
+                       unsigned* d_counter, DevStats* d_stats, int grid, hipStream_t);
+int query_resident_waves_flow(bool debug);
+// pt_kernels_temporal_flow.hip: the flow-aware twins of the two temporal launchers (include/mi355pt_flow.h), of a frame WITH a previous frame.
+// A pixel's record is two 16-byte loads.  ids_prev == nullptr: no id test of the taps (ids_cur is then not read).  args.delta is not read.
+// The rectified form's second launch is pt_kernels_temporal_rectify.hip's own blend, through launch_temporal_rectify_blend
+struct FlowArgs { const uint32_t* ids_cur; const uint32_t* ids_prev; const FlowPixelDev* flow; };
+hipError_t launch_temporal_accumulate_flow(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const FlowArgs& flow,
+                                           float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
+hipError_t launch_temporal_rectify_flow(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const FlowArgs& flow, uint32_t radius,
+                                        float gamma, void* d_scratch, float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
+// pt_kernels_temporal_rectify.hip: the rectifying blend alone, over gather records that are in d_scratch already (args.blocks_x filled)
+hipError_t launch_temporal_rectify_blend(const TemporalFrameDev& cur, const TemporalArgs& args, uint32_t radius, float gamma, const void* d_scratch,
+                                         float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
 // pt_kernels_upsample.hip: the guided half-resolution upsample (include/mi355pt_upsample.h): one launch on the grid of denoise_grid_blocks
 // over the FULL frame.  The G-buffer sums of one resolution as the kernel takes them (albedo == nullptr: not given, then on both sides);
 // low_half == nullptr: no half film (then out_half is not written).  The launcher fills UpsampleArgs::blocks_x

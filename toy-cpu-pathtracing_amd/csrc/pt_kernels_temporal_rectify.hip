@@ -202,6 +202,17 @@ hipError_t launch_temporal_rectify(const TemporalFrameDev& cur, const TemporalFr
     return hipGetLastError();
 }
 
+// (called from pt_kernels_temporal_flow.hip, whose gather has written the records: the second launch of the two launchers around it)
+hipError_t launch_temporal_rectify_blend(const TemporalFrameDev& cur, const TemporalArgs& args, uint32_t radius, float gamma, const void* d_scratch,
+                                         float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t stream) {
+    if (radius < 1 || radius > 3) return hipErrorInvalidValue;
+    const dim3 grid(denoise_grid_blocks(args.width, args.height)), block(DN_BLOCK_X, DN_BLOCK_Y);
+    const float4* record = (const float4*)d_scratch;
+    if (cur.half != nullptr) launch_rectify_radius<true>(radius, grid, block, stream, cur, args, gamma, record, d_out_film, d_out_half, d_out_length);
+    else launch_rectify_radius<false>(radius, grid, block, stream, cur, args, gamma, record, d_out_film, d_out_half, d_out_length);
+    return hipGetLastError();
+}
+
 // (called from api_motion.cpp, which has checked every argument)
 hipError_t launch_temporal_rectify_motion(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const MotionArgs& motion, uint32_t radius,
                                           float gamma, void* d_scratch, float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t stream) {

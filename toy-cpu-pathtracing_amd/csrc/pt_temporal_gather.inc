@@ -11,6 +11,9 @@
 //   PT_TP_MOTION == true    include/mi355pt_motion.h: the including kernel has one more template parameter, bool HAS_PREV_IDS, and one
 //                           more kernel parameter, MotionArgs mo.  The pixel's id picks a record of mo.table, which carries X and nrm
 //                           into the previous render space (a.delta is not read); with HAS_PREV_IDS a tap must show the pixel's id.
+//   PT_TP_MOTION == 2       include/mi355pt_flow.h: the template parameters of PT_TP_MOTION == true, and FlowArgs fl in the place of mo.
+//                           The pixel's own record of fl.flow is ADDED to X and to nrm (a.delta is not read); with HAS_PREV_IDS a tap
+//                           must show fl.ids_cur[p], which is not read otherwise.
 //
 // A pixel's hit position is projected into the previous camera, and the previous frame's accumulated films are gathered with a 2 x 2
 // bilinear footprint.  The four taps' loads are UNCONDITIONAL, at indices clamped to the frame: whether a pixel has a history at all (no
@@ -40,7 +43,13 @@
 
     if constexpr (HAS_PREV) {
         // geometry of p (h == 0 makes NaNs and infinities: `ok` selects them away)
-#if PT_TP_MOTION
+#if PT_TP_MOTION == 2
+        // the pixel's motion record (two 16-byte loads, coalesced) and, for the id test, its id — issued ahead of the geometry's divisions
+        const float4* const frec = (const float4*)(fl.flow + p);
+        const float4 fr0 = frec[0], fr1 = frec[1];
+        uint32_t idc = 0u;
+        if constexpr (HAS_PREV_IDS) idc = fl.ids_cur[p];
+#elif PT_TP_MOTION
         // the pixel's id and its motion record (six 16-byte loads), issued ahead of the geometry's divisions: one dependent round trip
         // more than the static kernel has, and it is over when the quotients are
         const uint32_t idc = mo.ids_cur[p];
@@ -49,7 +58,10 @@
 #endif
         const float3u P = tp_load3(cur.position, p), N = tp_load3(cur.shading_normal, p);
         const float hx = cur.hit[3 * p], h = cur.hit[3 * p + 1];
-#if PT_TP_MOTION
+#if PT_TP_MOTION == 2
+        const float Xx = P.x / h + fr0.x, Xy = P.y / h + fr0.y, Xz = P.z / h + fr0.z;                      // Xp = X + d
+        const float nx = (2.0f * (N.x / h) - 1.0f) + fr1.x, ny = (2.0f * (N.y / h) - 1.0f) + fr1.y, nz = (2.0f * (N.z / h) - 1.0f) + fr1.z;
+#elif PT_TP_MOTION
         // a = m0.xyzw m1r.xyzw m2r.x,  b = m2r.yzw,  n = m3.xyzw m4.xyzw m5.x: Xp = a X + b, nrm = n nrm — both in the previous render space
         const float X0 = P.x / h, X1 = P.y / h, X2 = P.z / h;
         const float Xx = tp_dot(m0.x, m0.y, m0.z, X0, X1, X2) + m2r.y, Xy = tp_dot(m0.w, m1r.x, m1r.y, X0, X1, X2) + m2r.z,
@@ -94,7 +106,9 @@
             Pq[k] = tp_load3(prev.position, q); Nq[k] = tp_load3(prev.shading_normal, q);
             f[k] = tp_load3(prev.film, q);
             if constexpr (HAS_HALF) g[k] = tp_load3(prev.half, q);
-#if PT_TP_MOTION
+#if PT_TP_MOTION == 2
+            if constexpr (HAS_PREV_IDS) same[k] = fl.ids_prev[q] == idc;
+#elif PT_TP_MOTION
             if constexpr (HAS_PREV_IDS) same[k] = mo.ids_prev[q] == idc;
 #endif
         }

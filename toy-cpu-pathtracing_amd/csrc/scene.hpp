@@ -79,6 +79,10 @@ struct RebaseState {
     uint32_t* d_mesh_idx = nullptr;           // ... the index buffers of all meshes, one after the other
     std::vector<uint32_t> mesh_idx_offset;    // first word of mesh g in that pool (n_meshes + 1 entries)
     std::vector<uint8_t> mesh_idx_uploaded;   // per mesh: its indices are on the device (uploaded once per build, by its first deformation)
+    // mi355pt_scene_flow_mark (api_flow.cpp): allocated by the first mark after a build (in SceneImpl::allocs).  Every build starts from a fresh
+    // RebaseState (SceneImpl::release), so a build — a move's fallback included — drops the mark
+    DevTri* d_tris_prev = nullptr;            // the render-space leaf-order triangles as they were when the mark was taken (n_tris records)
+    bool flow_marked = false;
     float tree_cam_pos[3] = {0, 0, 0};        // the camera position the tree was BUILT for (build_cam_pos follows the moves)
     size_t n_degenerate = 0; int bvh_depth = 0, stack_need = 0; std::string collapse_method;   // the build's LowerReport (mi355pt_scene_debug_device_digest)
 };

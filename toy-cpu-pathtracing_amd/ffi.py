@@ -254,7 +254,8 @@ def _ptr(a, ty):
 
 # every symbol include/mi355pt.h declares (tests/test_abi.py checks the built library exports all of them) ...
 DEBUG_SYMBOLS = ["debug_unlock", "scene_debug_set_lowering", "scene_debug_lowering_digest", "scene_debug_camera_candidates", "scene_debug_move_digest", "scene_debug_move_export", "scene_debug_device_digest", "scene_debug_pinned_digest", "scene_debug_pinned_export", "scene_debug_pin_host_tree", "scene_debug_set_instance_transform", "scene_debug_set_mesh_vertices", "debug_sah_cost", "scene_export_bvh", "probe_bvh_collapse", "probe_bvh_collapse_nodes", "probe_sobol", "probe_sincos", "probe_intersect", "probe_occluded",
-                 "sample_log_records", "render_sample_log", "probe_radiance", "probe_display_meter_ms"]     # ... and include/mi355pt_debug.h
+                 "sample_log_records", "render_sample_log", "probe_radiance", "probe_display_meter_ms",
+                 "render_flow_debug", "scene_export_flow_mark", "scene_export_triangle_ids"]     # ... and include/mi355pt_debug.h
 ABI_SYMBOLS = [
     "scene_create", "scene_destroy", "scene_set_rgb2spec", "scene_add_lut470", "scene_add_tex_rgb8", "scene_add_mesh",
     "scene_add_material", "scene_add_instance", "scene_add_delta_light", "scene_add_environment_light", "scene_set_bvh_builder", "scene_build", "render", "render_accum_device", "film_resolve_device",
@@ -290,6 +291,13 @@ MOTION_SYMBOLS = ["render_ids_device", "render_ids", "motion_table", "temporal_a
                   "temporal_accumulate_rectified_motion_device", "temporal_accumulate_rectified_motion"]
 # ... and include/mi355pt_deform.h, the mesh-deformation block (tests/test_deform.py)
 DEFORM_SYMBOLS = ["scene_deform_meshes"]
+# ... and include/mi355pt_flow.h, the per-pixel motion block (tests/test_flow.py)
+FLOW_SYMBOLS = ["scene_flow_mark", "scene_flow_marked", "render_flow_device", "render_flow", "temporal_accumulate_flow_device", "temporal_accumulate_flow",
+                "temporal_accumulate_rectified_flow_device", "temporal_accumulate_rectified_flow"]
+FLOW_DEBUG_SYMBOLS = ["render_flow_debug", "scene_export_flow_mark", "scene_export_triangle_ids"]      # include/mi355pt_debug.h
+# mi355pt_flow_pixel as a NumPy record: 32 bytes
+FLOW_PIXEL = np.dtype([("d", np.float32, 3), ("id", np.uint32), ("dn", np.float32, 3), ("pad", np.uint32)])
+FLOW_HIT = np.dtype([("tri", np.uint32), ("b", np.float32, 3)])           # mi355pt_render_flow_debug's hit record: 16 bytes
 ADAPTIVE_SYMBOLS = ["adaptive_scratch_bytes", "adaptive_step_device", "film_normalize_tiles_device", "render_adaptive_device", "render_adaptive"]
 
 
@@ -740,6 +748,21 @@ class Product(Backend):
             lib.mi355pt_temporal_accumulate_rectified_motion_device.argtypes = frame4 + [C.POINTER(TemporalRectifyParams), C.c_void_p, C.c_size_t] + motion4 + \
                 [C.c_void_p] * 4
             lib.mi355pt_temporal_accumulate_rectified_motion.argtypes = frame4 + [C.POINTER(TemporalRectifyParams)] + motion4 + [C.c_void_p] * 3
+        if hasattr(lib, "mi355pt_render_flow_device"):  # (absent from an older build loaded through MI355PT_LIB)
+            frame4 = [C.POINTER(TemporalFrame), C.c_uint32, C.POINTER(TemporalFrame), C.POINTER(TemporalView), C.c_uint32, C.c_uint32, C.POINTER(TemporalParams)]
+            flow3 = [C.c_void_p, C.c_void_p, C.c_void_p]                                    # ids_cur, ids_prev, flow
+            lib.mi355pt_scene_flow_mark.argtypes = [C.c_void_p, C.c_void_p]
+            lib.mi355pt_scene_flow_marked.argtypes = [C.c_void_p]
+            lib.mi355pt_render_flow_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+            lib.mi355pt_render_flow.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+            lib.mi355pt_render_flow_debug.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+            lib.mi355pt_scene_export_flow_mark.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+            lib.mi355pt_scene_export_triangle_ids.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+            lib.mi355pt_temporal_accumulate_flow_device.argtypes = frame4 + flow3 + [C.c_void_p] * 4
+            lib.mi355pt_temporal_accumulate_flow.argtypes = frame4 + flow3 + [C.c_void_p] * 3
+            lib.mi355pt_temporal_accumulate_rectified_flow_device.argtypes = frame4 + [C.POINTER(TemporalRectifyParams), C.c_void_p, C.c_size_t] + flow3 + \
+                [C.c_void_p] * 4
+            lib.mi355pt_temporal_accumulate_rectified_flow.argtypes = frame4 + [C.POINTER(TemporalRectifyParams)] + flow3 + [C.c_void_p] * 3
         if not hasattr(lib, "mi355pt_render_sample_log"):     # an older build loaded through MI355PT_LIB for an A/B timing run
             return
         lib.mi355pt_sample_log_records.argtypes = [C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]
@@ -1009,6 +1032,93 @@ class Product(Backend):
             self.check(self.lib.mi355pt_temporal_accumulate_motion(*head, *tail), "temporal_accumulate_motion")
         else:
             self.check(self.lib.mi355pt_temporal_accumulate_rectified_motion(*head, C.byref(rectify_params), *tail), "temporal_accumulate_rectified_motion")
+        return out_film, out_half, out_len
+
+    # ---- per-pixel motion vectors (include/mi355pt_flow.h): the mark, the flow pass and the flow-aware twins of the accumulation ----
+    def scene_flow_mark(self, scene, stream=None):
+        """mi355pt_scene_flow_mark: the scene keeps a copy of its current render-space triangle positions (asynchronous on `stream`)"""
+        self.check(self.lib.mi355pt_scene_flow_mark(scene.h, C.c_void_p(stream or 0)), "scene_flow_mark")
+
+    def scene_flow_marked(self, scene):
+        return bool(self.lib.mi355pt_scene_flow_marked(scene.h))
+
+    def render_flow_device(self, scene, cam, params, d_flow_ptr, d_ids_ptr=None, stream=None, stats=None):
+        """mi355pt_render_flow_device: W x H mi355pt_flow_pixel records (and, with d_ids_ptr, the ID pass's u32) on the device"""
+        self.check(self.lib.mi355pt_render_flow_device(scene.h, C.byref(cam), C.byref(params), C.c_void_p(d_flow_ptr), C.c_void_p(d_ids_ptr or 0),
+                                                       C.c_void_p(stream or 0), C.byref(stats) if stats is not None else None), "render_flow_device")
+
+    def render_flow(self, scene, cam, params, want_ids=True):
+        """mi355pt_render_flow -> ((H, W) FLOW_PIXEL records, (H, W) uint32 or None)"""
+        flow = np.zeros((cam.height, cam.width), FLOW_PIXEL)
+        ids = np.zeros((cam.height, cam.width), np.uint32) if want_ids else None
+        self.check(self.lib.mi355pt_render_flow(scene.h, C.byref(cam), C.byref(params), flow.ctypes.data, ids.ctypes.data if want_ids else None, None), "render_flow")
+        return flow, ids
+
+    def render_flow_debug(self, scene, cam, params):
+        """mi355pt_render_flow_debug (include/mi355pt_debug.h) -> ((H, W) FLOW_PIXEL, (H, W) uint32, (H, W) FLOW_HIT): the records, the ids and
+        the hits {tri, b0, b1, b2} the records were computed from"""
+        flow = np.zeros((cam.height, cam.width), FLOW_PIXEL)
+        ids = np.zeros((cam.height, cam.width), np.uint32)
+        hits = np.zeros((cam.height, cam.width), FLOW_HIT)
+        self.check(self.lib.mi355pt_render_flow_debug(scene.h, C.byref(cam), C.byref(params), flow.ctypes.data, ids.ctypes.data, hits.ctypes.data, None),
+                   "render_flow_debug")
+        return flow, ids, hits
+
+    def scene_export_flow_mark(self, scene):
+        """mi355pt_scene_export_flow_mark (include/mi355pt_debug.h) -> (n_tris, 12) float32: the mark's 48-byte records (p0 p1 p2 in words 0 - 8)"""
+        n = C.c_uint32(0)
+        self.check(self.lib.mi355pt_scene_export_flow_mark(scene.h, None, C.byref(n)), "scene_export_flow_mark")
+        out = np.zeros((n.value, 12), np.float32)
+        self.check(self.lib.mi355pt_scene_export_flow_mark(scene.h, out.ctypes.data, C.byref(n)), "scene_export_flow_mark")
+        return out
+
+    def scene_export_triangle_ids(self, scene):
+        """mi355pt_scene_export_triangle_ids (include/mi355pt_debug.h) -> (n_tris, 2) uint32: (instance, triangle inside its mesh) per leaf-order triangle"""
+        n = C.c_uint32(0)
+        self.check(self.lib.mi355pt_scene_export_triangle_ids(scene.h, None, C.byref(n)), "scene_export_triangle_ids")
+        out = np.zeros((n.value, 2), np.uint32)
+        self.check(self.lib.mi355pt_scene_export_triangle_ids(scene.h, out.ctypes.data, C.byref(n)), "scene_export_triangle_ids")
+        return out
+
+    def temporal_accumulate_flow_device(self, cur, spp, prev, view, width, height, params, d_ids_cur_ptr, d_ids_prev_ptr, d_flow_ptr, d_out_film_ptr,
+                                        d_out_half_ptr, d_out_length_ptr, rectify_params=None, d_scratch_ptr=None, scratch_bytes=0, stream=None):
+        """mi355pt_temporal_accumulate_flow_device or, with rectify_params (and a scratch), mi355pt_temporal_accumulate_rectified_flow_device:
+        the arguments of their twins plus the current ids (None without previous ids), the previous ids (None: no id test of the taps) and
+        the flow records, all device pointers"""
+        fc = TemporalFrame(*[C.c_void_p(cur.get(k) or None) for k in TEMPORAL_FILMS])
+        fp = TemporalFrame(*[C.c_void_p(prev.get(k) or None) for k in TEMPORAL_FILMS]) if prev is not None else None
+        head = (C.byref(fc), spp, C.byref(fp) if fp is not None else None, C.byref(view) if view is not None else None, width, height, C.byref(params))
+        tail = (C.c_void_p(d_ids_cur_ptr or 0), C.c_void_p(d_ids_prev_ptr or 0), C.c_void_p(d_flow_ptr), C.c_void_p(d_out_film_ptr),
+                C.c_void_p(d_out_half_ptr or 0), C.c_void_p(d_out_length_ptr), C.c_void_p(stream or 0))
+        if rectify_params is None:
+            self.check(self.lib.mi355pt_temporal_accumulate_flow_device(*head, *tail), "temporal_accumulate_flow_device")
+        else:
+            self.check(self.lib.mi355pt_temporal_accumulate_rectified_flow_device(*head, C.byref(rectify_params), C.c_void_p(d_scratch_ptr), scratch_bytes, *tail),
+                       "temporal_accumulate_rectified_flow_device")
+
+    def temporal_accumulate_flow(self, cur, spp, prev, view, ids_cur, ids_prev, flow, params=None, rectify_params=None):
+        """mi355pt_temporal_accumulate_flow (or, with rectify_params, mi355pt_temporal_accumulate_rectified_flow) on host arrays, as
+        temporal_accumulate; ids (H, W) uint32 or None, flow (H, W) FLOW_PIXEL -> (out_film, out_half or None, out_length)"""
+        def host(frame):
+            keep = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in frame.items() if v is not None}
+            return keep, TemporalFrame(*[keep[k].ctypes.data if k in keep else None for k in TEMPORAL_FILMS])
+        kc, fc = host(cur)
+        kp, fp = host(prev) if prev is not None else (None, None)
+        h, w = kc["film"].shape[:2]
+        ic = np.ascontiguousarray(ids_cur, dtype=np.uint32) if ids_cur is not None else None
+        ip = np.ascontiguousarray(ids_prev, dtype=np.uint32) if ids_prev is not None else None
+        fl = np.ascontiguousarray(flow, dtype=FLOW_PIXEL)
+        assert fl.shape == (h, w)
+        params = params if params is not None else self.temporal_params_default()
+        out_film, out_len = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32)
+        out_half = np.zeros((h, w, 3), np.float32) if "half" in kc else None
+        head = (C.byref(fc), spp, C.byref(fp) if fp is not None else None, C.byref(view) if view is not None else None, w, h, C.byref(params))
+        tail = (ic.ctypes.data if ic is not None else None, ip.ctypes.data if ip is not None else None, fl.ctypes.data, out_film.ctypes.data,
+                out_half.ctypes.data if out_half is not None else None, out_len.ctypes.data)
+        if rectify_params is None:
+            self.check(self.lib.mi355pt_temporal_accumulate_flow(*head, *tail), "temporal_accumulate_flow")
+        else:
+            self.check(self.lib.mi355pt_temporal_accumulate_rectified_flow(*head, C.byref(rectify_params), *tail), "temporal_accumulate_rectified_flow")
         return out_film, out_half, out_len
 
     # ---- guided half-resolution rendering (include/mi355pt_upsample.h): a film traced at W/2 x H/2 rebuilt at W x H through both G-buffers ----

@@ -60,15 +60,20 @@ struct Args {   // main.rs:20-53
     // normals recomputed on the host, applied on the device before the frame.  --instance-rebuild-above applies to it
     struct MeshWave { uint32_t geom; float amp, wavelength, phase_step; };
     std::vector<MeshWave> mesh_waves;
+    // nor per-pixel motion vectors (mi355pt_flow.h): --flow with --temporal-frames — every frame marks the scene, takes its moves (--camera-step,
+    // --instance-step, --mesh-wave, any mix) in place, and accumulates through the flow pass's records; frame k of --mesh-wave then deforms the
+    // ORIGINAL vertices with phase k * phase_step
+    bool flow = false;
 };
 
 // the positions of a mesh under a wave along x that displaces y (local space), in double and rounded to float
-std::vector<float> waved_positions(const Args::MeshWave& w, const std::vector<float>& pos) {
+std::vector<float> waved_positions(const Args::MeshWave& w, const std::vector<float>& pos, double phase) {
     std::vector<float> out(pos);
     for (size_t v = 0; v * 3 < pos.size(); ++v)
-        out[3 * v + 1] = (float)((double)pos[3 * v + 1] + (double)w.amp * std::sin(2.0 * 3.14159265358979323846 * (double)pos[3 * v] / (double)w.wavelength + (double)w.phase_step));
+        out[3 * v + 1] = (float)((double)pos[3 * v + 1] + (double)w.amp * std::sin(2.0 * 3.14159265358979323846 * (double)pos[3 * v] / (double)w.wavelength + phase));
     return out;
 }
+std::vector<float> waved_positions(const Args::MeshWave& w, const std::vector<float>& pos) { return waved_positions(w, pos, (double)w.phase_step); }
 
 // T . R_y . S . local_to_world (column-major): T R S composed in double and rounded to float, the product in double and rounded to float
 void instance_transform_matrix(const Args::InstanceTransform& it, const float* l2w, float* out) {
@@ -324,7 +329,7 @@ static double render_gbuffer_float(const Scene& scene, const Camera& camera, mi3
 // --camera-move: the scene of the --temporal-frames loops at the next frame's camera position.  rebuild (the default): mi355pt_scene_build
 // again.  rebase: mi355pt_scene_move_camera — the built scene re-based and refit on the device — and one line per frame on stderr
 static void follow_camera(Scene& scene, const Camera& moved, const Args& a, uint32_t frame) {
-    if (a.camera_move != "rebase") { scene.build(moved); return; }
+    if (a.camera_move != "rebase" && !(a.flow && !a.camera_move_given)) { scene.build(moved); return; }      // (--flow moves in place unless told to rebuild)
     const mi355pt_move_result r = scene.move_camera(moved);
     std::fprintf(stderr, "camera move, frame %u: rebuilt=%u host_ms=%.3f device_ms=%.3f\n", frame, r.rebuilt, r.host_ms, r.device_ms);
 }
@@ -366,6 +371,14 @@ static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params
     DeviceFilm table(stepping ? ((size_t)n_inst + 1) * sizeof(mi355pt_motion_xform) : sizeof(float));
     uint32_t* ids[2] = {(uint32_t*)ids0.p, (uint32_t*)ids1.p};
     std::vector<float> l2w_prev(stepping ? 16 * (size_t)n_inst : 0);
+    // --flow (mi355pt_flow.h): the frame's motion records, the ids in the two alternating sets above, and the ORIGINAL vertices of the meshes
+    // under --mesh-wave, which frame k deforms with phase k * phase_step
+    const bool flowing = a.flow;
+    DeviceFilm flow_ids0(flowing && !stepping ? len_bytes : sizeof(float)), flow_ids1(flowing && !stepping ? len_bytes : sizeof(float));
+    if (flowing && !stepping) { ids[0] = (uint32_t*)flow_ids0.p; ids[1] = (uint32_t*)flow_ids1.p; }
+    DeviceFilm flow_records(flowing ? (size_t)n_pixels * sizeof(mi355pt_flow_pixel) : sizeof(float));
+    std::vector<std::vector<float>> wave_home;
+    for (const Args::MeshWave& w : a.mesh_waves) wave_home.push_back(scene.mesh(w.geom).pos);
     mi355pt_camera cam = base, cam_prev = base;
     double kernel_ms = 0.0;
     for (uint32_t k = 0; k < a.temporal_frames; ++k) {
@@ -374,6 +387,7 @@ static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params
         for (int i = 0; i < 3; ++i) cam.position[i] = base.position[i] + (float)k * a.camera_step[i];
         Camera moved(base.fov_deg, base.width, base.height);
         moved.set_look_to({cam.position[0], cam.position[1], cam.position[2]}, {cam.direction[0], cam.direction[1], cam.direction[2]}, {cam.up[0], cam.up[1], cam.up[2]});
+        if (flowing && k > 0) scene.flow_mark();      // the positions of frame k - 1, ahead of every move of frame k
         if (k > 0 && moving) follow_camera(scene, moved, a, k);
         for (uint32_t i = 0; stepping && i < n_inst; ++i) std::memcpy(&l2w_prev[16 * (size_t)i], scene.instance_transform(i), 16 * sizeof(float));
         if (k > 0 && stepping) {      // the step once more on top of the last frame's matrix, at the camera the scene is at now
@@ -385,6 +399,19 @@ static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params
             const mi355pt_instance_move_result mr = scene.move_instances(moved, step_ids, matrices);
             std::fprintf(stderr, "instance step, frame %u: rebuilt=%u reason=%u host_ms=%.3f device_ms=%.3f\n", k, mr.rebuilt, mr.reason, mr.host_ms, mr.device_ms);
         }
+        if (flowing && !a.mesh_waves.empty()) {      // frame k's wave on the original vertices (frame 0: phase 0)
+            std::vector<uint32_t> geoms; std::vector<std::vector<float>> pos, nrm;
+            for (size_t j = 0; j < a.mesh_waves.size(); ++j) {
+                geoms.push_back(a.mesh_waves[j].geom);
+                pos.push_back(waved_positions(a.mesh_waves[j], wave_home[j], (double)k * (double)a.mesh_waves[j].phase_step));
+                nrm.push_back(area_weighted_normals(scene.mesh(geoms.back()), pos.back()));
+            }
+            const mi355pt_instance_move_result mr = scene.deform_meshes(moved, geoms, pos, nrm, a.instance_rebuild_above);
+            std::fprintf(stderr, "mesh deform, frame %u: rebuilt=%u reason=%u host_ms=%.3f device_ms=%.3f\n", k, mr.rebuilt, mr.reason, mr.host_ms, mr.device_ms);
+        }
+        // a move that built the scene again dropped the mark: this frame has no previous one
+        const bool first = k == 0 || (flowing && !scene.flow_marked());
+        if (flowing && k > 0 && first) std::fprintf(stderr, "flow, frame %u: a move rebuilt the scene, the accumulation restarts\n", k);
         p.seed = a.seed + k;
         bool ok = hipMemset(normal[c], 0, film_bytes) == hipSuccess && hipMemset(position[c], 0, film_bytes) == hipSuccess && hipMemset(hit[c], 0, film_bytes) == hipSuccess &&
                   hipMemset(beauty.p, 0, film_bytes) == hipSuccess;
@@ -407,7 +434,19 @@ static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params
         const mi355pt_temporal_frame prev{acc[q], half ? acch[q] : nullptr, len[q], position[q], normal[q], hit[q]};
         mi355pt_temporal_view view{};
         if (k > 0) check(mi355pt_temporal_view_from_cameras(&cam, &cam_prev, &view), "mi355pt_temporal_view_from_cameras");
-        if (stepping) {               // one ID pass, the table of the two frames' matrices and cameras, the motion-aware accumulation with the previous ids
+        if (flowing) {                // the flow pass against the mark (a first frame: the ids alone), the flow-aware accumulation with the previous ids
+            mi355pt_flow_pixel* d_flow = (mi355pt_flow_pixel*)flow_records.p;
+            if (first) scene.ids_device(cam, g, ids[c]); else scene.flow_device(cam, g, d_flow, ids[c]);
+            if (a.temporal_rectify)
+                check(mi355pt_temporal_accumulate_rectified_flow_device(&cur, p.spp, first ? nullptr : &prev, first ? nullptr : &view, base.width, base.height, &tp, &rp,
+                                                                        rectify_scratch.p, rectify_bytes, ids[c], first ? nullptr : ids[q], d_flow, acc[c],
+                                                                        half ? acch[c] : nullptr, len[c], nullptr),
+                      "mi355pt_temporal_accumulate_rectified_flow_device");
+            else
+                check(mi355pt_temporal_accumulate_flow_device(&cur, p.spp, first ? nullptr : &prev, first ? nullptr : &view, base.width, base.height, &tp, ids[c],
+                                                              first ? nullptr : ids[q], d_flow, acc[c], half ? acch[c] : nullptr, len[c], nullptr),
+                      "mi355pt_temporal_accumulate_flow_device");
+        } else if (stepping) {               // one ID pass, the table of the two frames' matrices and cameras, the motion-aware accumulation with the previous ids
             scene.ids_device(cam, g, ids[c]);
             const std::vector<mi355pt_motion_xform> host_table = scene.motion_table(cam, cam_prev, l2w_prev);
             if (hipMemcpy(table.p, host_table.data(), host_table.size() * sizeof(mi355pt_motion_xform), hipMemcpyHostToDevice) != hipSuccess)
@@ -595,11 +634,15 @@ static void usage() {
               "                                         and each frame adds an ID pass, a motion table and the motion-aware accumulation.  Not with --half-res)\n"
               "                   [--instance-rebuild-above X] (0 = never; with --instance-transform: build again when the refit tree's SAH cost exceeds X\n"
               "                                         times the built tree's; applies to --mesh-wave too)\n"
+              "                   [--flow] (with --temporal-frames: per-pixel motion vectors — every frame marks the scene, takes --camera-step, --instance-step and\n"
+              "                                         --mesh-wave in place (frame k's wave: the original vertices at phase k * phase_step) and accumulates through\n"
+              "                                         the flow pass; a move that rebuilds restarts the accumulation; the camera follows as with --camera-move rebase unless\n"
+              "                                         --camera-move rebuild is given.  Not with --half-res)\n"
               "                   [--mesh-wave GEOM:amp,wavelength[,phase_step]] (repeatable, distinct GEOMs; pt|nee|mis|normal|albedo|position|depth: the scene is\n"
               "                                         built as described, then every vertex of mesh GEOM takes y += amp sin(2 pi x / wavelength + phase_step)\n"
               "                                         in local space, with area-weighted vertex normals, on the device: mi355pt_scene_deform_meshes; one line\n"
-              "                                         on stderr.  Not with --temporal-frames: the reprojection assumes rigid motion per instance, motion\n"
-              "                                         vectors for deforming meshes are a later change)");
+              "                                         on stderr.  With --temporal-frames only under --flow: the other reprojections assume a static world\n"
+              "                                         or rigid motion per instance)");
 }
 
 int main(int argc, char** argv) {
@@ -633,6 +676,7 @@ int main(int argc, char** argv) {
         else if (k == "--temporal-rectify-radius") { a.temporal_rectify_radius_given = true; a.temporal_rectify_radius = (uint32_t)std::stoul(val()); }
         else if (k == "--temporal-rectify-gamma") { a.temporal_rectify_gamma_given = true; a.temporal_rectify_gamma = std::stof(val()); }
         else if (k == "--half-res") a.half_res = true;
+        else if (k == "--flow") a.flow = true;
         else if (k == "--half-res-albedo") a.half_res_albedo = true;
         else if (k == "--tone-map") a.tone_map = val();
         else if (k == "--white") { a.white_given = true; a.white = std::stof(val()); }
@@ -776,6 +820,8 @@ int main(int argc, char** argv) {
         if (a.robust_scale_given && !(std::isfinite(a.robust_scale) && a.robust_scale >= 0.0f)) { std::fprintf(stderr, "error: --robust-scale must be finite and not below 0\n"); return 2; }
         if (a.robust_scale_given) robust_params.gini_scale = a.robust_scale;
     }
+    if (a.flow && !a.temporal) { std::fprintf(stderr, "error: --flow needs --temporal-frames: it carries the accumulation across the frames' moves\n"); return 2; }
+    if (a.flow && a.half_res) { std::fprintf(stderr, "error: --flow with --half-res: the flow-aware accumulation runs at full size only\n"); return 2; }
     if (a.half_res_albedo && !a.half_res) { std::fprintf(stderr, "error: --half-res-albedo needs --half-res: it demodulates the film that --half-res upsamples\n"); return 2; }
     if (a.half_res && aov) { std::fprintf(stderr, "error: --half-res with --renderer %s: half-resolution rendering is for the path renderers (pt, nee, mis)\n", a.renderer.c_str()); return 2; }
     if (a.half_res && (a.width == 0 || a.height == 0 || (a.width & 1u) != 0 || (a.height & 1u) != 0)) { std::fprintf(stderr, "error: --half-res needs an even --width and --height above 0 (got %u x %u)\n", a.width, a.height); return 2; }
@@ -785,7 +831,7 @@ int main(int argc, char** argv) {
     if (a.half_res && (a.spp == 0 || a.denoise_guide_spp == 0)) { std::fprintf(stderr, "error: --half-res needs --spp and --denoise-guide-spp above 0\n"); return 2; }
     if (a.instance_rebuild_given && a.instance_transforms.empty() && a.mesh_waves.empty()) { std::fprintf(stderr, "error: --instance-rebuild-above needs --instance-transform or --mesh-wave: it is the move's threshold\n"); return 2; }
     if (!a.mesh_waves.empty()) {
-        if (a.temporal) { std::fprintf(stderr, "error: --mesh-wave with --temporal-frames: the temporal reprojection assumes rigid motion per instance (no motion vectors for deforming meshes yet)\n"); return 2; }
+        if (a.temporal && !a.flow) { std::fprintf(stderr, "error: --mesh-wave with --temporal-frames: the temporal reprojection assumes rigid motion per instance (no motion vectors for deforming meshes yet)\n"); return 2; }
         if (a.gpus > 1) { std::fprintf(stderr, "error: --mesh-wave with --gpus %d: a scene built over several GPUs is not deformed\n", a.gpus); return 2; }
         if (a.renderer == "shading-normal") { std::fprintf(stderr, "error: --mesh-wave with --renderer shading-normal: pt, nee, mis, normal, albedo, position or depth\n"); return 2; }
         std::sort(a.mesh_waves.begin(), a.mesh_waves.end(), [](const Args::MeshWave& x, const Args::MeshWave& y) { return x.geom < y.geom; });
@@ -901,7 +947,7 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "instance move: rebuilt=%u reason=%u launches=%u sah=%.6g\xe2\x86\x92%.6g host_ms=%.3f device_ms=%.3f\n", mr.rebuilt, mr.reason, mr.launches,
                          (double)mr.sah_built, (double)mr.sah_after, mr.host_ms, mr.device_ms);
         }
-        if (!a.mesh_waves.empty()) {
+        if (!a.mesh_waves.empty() && !a.flow) {      // (--flow: the frames deform, render_temporal)
             std::vector<uint32_t> geoms; std::vector<std::vector<float>> pos, nrm;
             for (const Args::MeshWave& w : a.mesh_waves) {
                 geoms.push_back(w.geom);

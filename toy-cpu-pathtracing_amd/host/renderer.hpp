@@ -740,6 +740,13 @@ public:
         check(mi355pt_motion_table(&cur, &prev, l2w_cur.data(), l2w_prev.data(), (uint32_t)instance_l2w_.size(), out.data()), "mi355pt_motion_table");
         return out;
     }
+    // include/mi355pt_flow.h: flow_mark() keeps the current triangle positions as last frame's, flow_device() gives every pixel its motion record
+    // (and its id) against the mark, flow_marked() says whether the mark survived the moves since (a build drops it)
+    void flow_mark() { check(mi355pt_scene_flow_mark(s_, nullptr), "mi355pt_scene_flow_mark"); }
+    bool flow_marked() const { return mi355pt_scene_flow_marked(s_) != 0; }
+    void flow_device(const mi355pt_camera& cam, const mi355pt_params& p, mi355pt_flow_pixel* d_flow, uint32_t* d_ids) const {
+        check(mi355pt_render_flow_device(s_, &cam, &p, d_flow, d_ids, nullptr, nullptr), "mi355pt_render_flow_device");
+    }
     void set_instance_dynamic(uint32_t instance) { check(mi355pt_scene_set_instance_dynamic(s_, instance, 1), "mi355pt_scene_set_instance_dynamic"); }
     mi355pt_instance_move_result move_instances(const Camera& cam, const std::vector<uint32_t>& ids, const std::vector<float>& matrices, float rebuild_above = 0.0f) {
         mi355pt_instance_move_params p{rebuild_above};
