@@ -30,6 +30,12 @@ enum class Scratch { OK, MISSING, TOO_SMALL, MISALIGNED };
 inline Scratch scratch_verdict(const void* p, size_t have, size_t need, size_t align) {
     return !p ? Scratch::MISSING : have < need ? Scratch::TOO_SMALL : misaligned(p, align) ? Scratch::MISALIGNED : Scratch::OK;
 }
+// is one of the call's n_outs output pointers (null ones among them, which are none) one of the three inputs a, b, c?
+inline bool output_is_one_of(const void* const* outs, int n_outs, const void* a, const void* b, const void* c) {
+    for (int i = 0; i < n_outs; ++i)
+        if (outs[i] && (outs[i] == a || outs[i] == b || outs[i] == c)) return true;
+    return false;
+}
 // what is wrong with the id buffers and the table of a motion-aware accumulation (include/mi355pt_motion.h): the first that applies, in
 // this order.  ids_prev may be null; `outs`: the call's n_outs output pointers (null ones among them) and, for the rectified form, its scratch
 enum class Motion { OK, MISSING, NO_ENTRIES, MISALIGNED, ALIASES_OUTPUT };
@@ -38,9 +44,7 @@ inline Motion motion_verdict(const void* ids_cur, const void* ids_prev, const vo
     if (!ids_cur || !table) return Motion::MISSING;
     if (n_entries == 0u) return Motion::NO_ENTRIES;
     if (misaligned(table, table_align)) return Motion::MISALIGNED;
-    for (int i = 0; i < n_outs; ++i)
-        if (outs[i] && (outs[i] == ids_cur || outs[i] == ids_prev || outs[i] == table)) return Motion::ALIASES_OUTPUT;
-    return Motion::OK;
+    return output_is_one_of(outs, n_outs, ids_cur, ids_prev, table) ? Motion::ALIASES_OUTPUT : Motion::OK;
 }
 
 }  // namespace pt

@@ -1,7 +1,7 @@
 // The mi355pt_flow.h surface of libmi355pt.so: the mark (a scene-owned copy of last frame's triangle positions), the flow pass (the ID
-// pass's launch, api_motion.cpp, with a motion record per pixel) and the flow-aware twins of the temporal accumulation and of its rectified
-// form, which run api_temporal.cpp's checks and add their own (flow_checks.hpp).  Host C++ only, like api.cpp; the kernels are in
-// pt_kernels_flow.hip and pt_kernels_temporal_flow.hip.
+// pass's launch, api_motion.cpp, with a motion record per pixel) and the four flow forms of the temporal accumulation: single calls of
+// api_temporal.cpp's driver with a flow carry, whose own check (flow_checks.hpp) is here.  Host C++ only, like api.cpp; the flow pass's
+// kernels are in pt_kernels_flow.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -48,13 +48,10 @@ int pt::render_flow_launch(const mi355pt_scene* s, const mi355pt_camera* cam, co
     });
 }
 
-namespace {
-
 // what mi355pt_flow.h adds to temporal_check (and, with a scratch, to the rectified form's checks)
-int flow_in_check(const uint32_t* ids_cur, const uint32_t* ids_prev, const mi355pt_flow_pixel* flow, size_t flow_align, const void* out_film, const void* out_half,
-                  const void* out_length, const void* scratch) {
-    const void* outs[4] = {out_film, out_half, out_length, scratch};
-    switch (flow_in_verdict(ids_cur, ids_prev, flow, flow_align, outs, 4)) {
+int pt::flow_in_check(const TemporalCarry& carry, const TemporalCall& c, const void* scratch) {
+    const void* outs[4] = {c.out_film, c.out_half, c.out_length, scratch};
+    switch (flow_in_verdict(carry.ids_cur, carry.ids_prev, carry.flow, carry.align, outs, 4)) {
         case FlowIn::MISSING: return fail(MI355PT_E_INVALID, "temporal flow: null record buffer");
         case FlowIn::MISALIGNED: return fail(MI355PT_E_INVALID, "temporal flow: the record buffer must be 16-byte aligned");
         case FlowIn::PREV_IDS_ALONE: return fail(MI355PT_E_INVALID, "temporal flow: the previous frame's ids need the current frame's");
@@ -64,47 +61,12 @@ int flow_in_check(const uint32_t* ids_cur, const uint32_t* ids_prev, const mi355
     return MI355PT_OK;
 }
 
-// the two host-buffer entry points, after api_motion.cpp's motion_accumulate_host: device copies of the films, the ids and the records, the
-// device entry point (rectified when rp is given, with a scratch of its own) on the default stream, the outputs copied back.  Every
-// argument has been checked.
-int flow_accumulate_host(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev, const mi355pt_temporal_view* view, uint32_t width,
-                         uint32_t height, const mi355pt_temporal_params* tp, const mi355pt_temporal_rectify_params* rp, const uint32_t* ids_cur,
-                         const uint32_t* ids_prev, const mi355pt_flow_pixel* flow, float* out_film, float* out_half, float* out_length) {
-    int rc = MI355PT_OK;
-    const size_t np = (size_t)width * height, n = np * 3;
-    DevBuf<float> d_in[2][6], d_film, d_half, d_len;
-    DevBuf<uint32_t> d_ids[2];
-    DevBuf<mi355pt_flow_pixel> d_flow;
-    DevBuf<unsigned char> d_scratch;
-    mi355pt_temporal_frame dev[2] = {};
-    const mi355pt_temporal_frame* host[2] = {cur, prev};
-    for (int k = 0; k < 2; ++k) {
-        if (!host[k]) continue;
-        const float* src[6] = {host[k]->film, host[k]->half, k == 0 ? nullptr : host[k]->length, host[k]->position, host[k]->shading_normal, host[k]->hit};
-        const DevBuf<float>* d = d_in[k];
-        for (int i = 0; i < 6; ++i) HIP_TRY(d_in[k][i].upload(src[i], i == 2 ? np : n));
-        dev[k].film = d[0].p; dev[k].half = d[1].p; dev[k].length = d[2].p; dev[k].position = d[3].p; dev[k].shading_normal = d[4].p; dev[k].hit = d[5].p;
-    }
-    HIP_TRY(d_ids[0].upload(ids_cur, np));
-    HIP_TRY(d_ids[1].upload(ids_prev, np));
-    HIP_TRY(d_flow.upload(flow, np));
-    HIP_TRY(d_film.alloc(n));
-    HIP_TRY(d_len.alloc(np));
-    HIP_TRY(d_half.alloc_for(out_half, n));
-    if (rp) {
-        const size_t scratch_bytes = mi355pt_temporal_rectify_scratch_bytes(width, height);
-        HIP_TRY(d_scratch.alloc(scratch_bytes));
-        rc = mi355pt_temporal_accumulate_rectified_flow_device(&dev[0], spp, prev ? &dev[1] : nullptr, view, width, height, tp, rp, d_scratch.p, scratch_bytes,
-                                                               d_ids[0].p, d_ids[1].p, d_flow.p, d_film.p, d_half.p, d_len.p, nullptr);
-    } else {
-        rc = mi355pt_temporal_accumulate_flow_device(&dev[0], spp, prev ? &dev[1] : nullptr, view, width, height, tp, d_ids[0].p, d_ids[1].p, d_flow.p, d_film.p,
-                                                     d_half.p, d_len.p, nullptr);
-    }
-    if (rc) return rc;
-    HIP_TRY(d_film.download(out_film, n));
-    HIP_TRY(d_half.download(out_half, n));
-    HIP_TRY(d_len.download(out_length, np));
-    return MI355PT_OK;
+namespace {
+
+TemporalCarry flow_carry(const uint32_t* ids_cur, const uint32_t* ids_prev, const mi355pt_flow_pixel* flow, size_t align) {
+    TemporalCarry carry;
+    carry.kind = TemporalCarry::FLOW; carry.ids_cur = ids_cur; carry.ids_prev = ids_prev; carry.flow = flow; carry.align = align;
+    return carry;
 }
 
 }  // namespace
@@ -155,27 +117,14 @@ int mi355pt_temporal_accumulate_flow_device(const mi355pt_temporal_frame* cur, u
                                             uint32_t width, uint32_t height, const mi355pt_temporal_params* tp, const uint32_t* d_ids_cur,
                                             const uint32_t* d_ids_prev, const mi355pt_flow_pixel* d_flow, float* d_out_film, float* d_out_half,
                                             float* d_out_length, void* hip_stream) {
-    int rc = temporal_check(cur, spp, prev, view, width, height, tp, d_out_film, d_out_half, d_out_length);
-    if (rc) return rc;
-    if ((rc = flow_in_check(d_ids_cur, d_ids_prev, d_flow, 16, d_out_film, d_out_half, d_out_length, nullptr))) return rc;
-    const TemporalArgs a = temporal_args(spp, view, width, height, tp);
-    const TemporalFrameDev dc = frame_dev(*cur);
-    if (!prev) {      // the first frame: nothing to reproject
-        HIP_TRY(launch_temporal_accumulate(dc, nullptr, a, d_out_film, d_out_half, d_out_length, (hipStream_t)hip_stream));
-        return MI355PT_OK;
-    }
-    HIP_TRY(launch_temporal_accumulate_flow(dc, frame_dev(*prev), a, FlowArgs{d_ids_cur, d_ids_prev, (const FlowPixelDev*)d_flow}, d_out_film, d_out_half,
-                                            d_out_length, (hipStream_t)hip_stream));
-    return MI355PT_OK;
+    return temporal_accumulate_device({cur, spp, prev, view, width, height, tp, d_out_film, d_out_half, d_out_length}, flow_carry(d_ids_cur, d_ids_prev, d_flow, 16),
+                                      nullptr, hip_stream);
 }
 
 int mi355pt_temporal_accumulate_flow(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev, const mi355pt_temporal_view* view,
                                      uint32_t width, uint32_t height, const mi355pt_temporal_params* tp, const uint32_t* ids_cur, const uint32_t* ids_prev,
                                      const mi355pt_flow_pixel* flow, float* out_film, float* out_half, float* out_length) {
-    int rc = temporal_check(cur, spp, prev, view, width, height, tp, out_film, out_half, out_length);
-    if (rc) return rc;
-    if ((rc = flow_in_check(ids_cur, ids_prev, flow, 1, out_film, out_half, out_length, nullptr))) return rc;
-    return flow_accumulate_host(cur, spp, prev, view, width, height, tp, nullptr, ids_cur, ids_prev, flow, out_film, out_half, out_length);
+    return temporal_accumulate_host({cur, spp, prev, view, width, height, tp, out_film, out_half, out_length}, flow_carry(ids_cur, ids_prev, flow, 1), nullptr);
 }
 
 int mi355pt_temporal_accumulate_rectified_flow_device(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev,
@@ -183,31 +132,17 @@ int mi355pt_temporal_accumulate_rectified_flow_device(const mi355pt_temporal_fra
                                                       const mi355pt_temporal_rectify_params* rp, void* d_scratch, size_t scratch_bytes, const uint32_t* d_ids_cur,
                                                       const uint32_t* d_ids_prev, const mi355pt_flow_pixel* d_flow, float* d_out_film, float* d_out_half,
                                                       float* d_out_length, void* hip_stream) {
-    int rc = temporal_check(cur, spp, prev, view, width, height, tp, d_out_film, d_out_half, d_out_length);
-    if (rc) return rc;
-    if ((rc = rectify_params_check(rp))) return rc;
-    if ((rc = rectify_scratch_check(cur, prev, width, height, d_scratch, scratch_bytes, d_out_film, d_out_half, d_out_length))) return rc;
-    if ((rc = flow_in_check(d_ids_cur, d_ids_prev, d_flow, 16, d_out_film, d_out_half, d_out_length, d_scratch))) return rc;
-    const TemporalArgs a = temporal_args(spp, view, width, height, tp);
-    const TemporalFrameDev dc = frame_dev(*cur);
-    if (!prev) {      // the first frame: nothing to reproject or rectify, the scratch stays as it is
-        HIP_TRY(launch_temporal_accumulate(dc, nullptr, a, d_out_film, d_out_half, d_out_length, (hipStream_t)hip_stream));
-        return MI355PT_OK;
-    }
-    HIP_TRY(launch_temporal_rectify_flow(dc, frame_dev(*prev), a, FlowArgs{d_ids_cur, d_ids_prev, (const FlowPixelDev*)d_flow}, rp->radius, rp->gamma, d_scratch,
-                                         d_out_film, d_out_half, d_out_length, (hipStream_t)hip_stream));
-    return MI355PT_OK;
+    const TemporalRectify rect{rp, d_scratch, scratch_bytes};
+    return temporal_accumulate_device({cur, spp, prev, view, width, height, tp, d_out_film, d_out_half, d_out_length}, flow_carry(d_ids_cur, d_ids_prev, d_flow, 16),
+                                      &rect, hip_stream);
 }
 
 int mi355pt_temporal_accumulate_rectified_flow(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev,
                                                const mi355pt_temporal_view* view, uint32_t width, uint32_t height, const mi355pt_temporal_params* tp,
                                                const mi355pt_temporal_rectify_params* rp, const uint32_t* ids_cur, const uint32_t* ids_prev,
                                                const mi355pt_flow_pixel* flow, float* out_film, float* out_half, float* out_length) {
-    int rc = temporal_check(cur, spp, prev, view, width, height, tp, out_film, out_half, out_length);
-    if (rc) return rc;
-    if ((rc = rectify_params_check(rp))) return rc;
-    if ((rc = flow_in_check(ids_cur, ids_prev, flow, 1, out_film, out_half, out_length, nullptr))) return rc;
-    return flow_accumulate_host(cur, spp, prev, view, width, height, tp, rp, ids_cur, ids_prev, flow, out_film, out_half, out_length);
+    const TemporalRectify rect{rp};
+    return temporal_accumulate_host({cur, spp, prev, view, width, height, tp, out_film, out_half, out_length}, flow_carry(ids_cur, ids_prev, flow, 1), &rect);
 }
 
 }  // extern "C"

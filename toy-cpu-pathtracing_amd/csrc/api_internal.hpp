@@ -1,6 +1,6 @@
 // What the host translation units behind the C ABI share (api.cpp and the api_<stage>.cpp files, one per public header; scene_rebase.cpp,
-// scene_instances.cpp, scene_deform.cpp): the scene object and its launch context, fail / HIP_TRY, the device buffer and event holders, and what api.cpp
-// defines for the others.  The pure argument predicates are api_checks.hpp.  Not installed, not an ABI.
+// scene_instances.cpp, scene_deform.cpp): the scene object and its launch context, fail / HIP_TRY, the device buffer and event holders, what api.cpp
+// defines for the others, and api_temporal.cpp's driver of the temporal accumulations.  The pure argument predicates are api_checks.hpp.  Not installed, not an ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -141,15 +141,30 @@ int launch_ranges(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355
 // *stats = {kernel_ms, launches = 1}; with `counts` the slot's DevStats block is zeroed before the launch and read into *stats after it
 int timed_launch(LaunchCtx* lc, int slot, hipStream_t stream, mi355pt_stats* stats, bool counts,
                  const std::function<int(unsigned* d_counter, DevStats* d_stats)>& launch);
-// api_temporal.cpp, for api_motion.cpp's twins: every check of mi355pt_temporal_accumulate[_device], what mi355pt_temporal_rectify.h adds
-// to them, and the kernels' arguments from the checked ones
-int temporal_check(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev, const mi355pt_temporal_view* view, uint32_t width,
-                   uint32_t height, const mi355pt_temporal_params* tp, const float* out_film, const float* out_half, const float* out_length);
-int rectify_params_check(const mi355pt_temporal_rectify_params* rp);
-int rectify_scratch_check(const mi355pt_temporal_frame* cur, const mi355pt_temporal_frame* prev, uint32_t width, uint32_t height, const void* scratch,
-                          size_t scratch_bytes, const float* out_film, const float* out_half, const float* out_length);
-TemporalFrameDev frame_dev(const mi355pt_temporal_frame& f);
-TemporalArgs temporal_args(uint32_t spp, const mi355pt_temporal_view* view, uint32_t width, uint32_t height, const mi355pt_temporal_params* tp);
+// api_temporal.cpp: the one driver behind the twelve mi355pt_temporal_accumulate* entry points of mi355pt_temporal.h,
+// mi355pt_temporal_rectify.h, mi355pt_motion.h and mi355pt_flow.h.  A call is its base arguments ...
+struct TemporalCall {
+    const mi355pt_temporal_frame* cur; uint32_t spp; const mi355pt_temporal_frame* prev; const mi355pt_temporal_view* view; uint32_t width, height;
+    const mi355pt_temporal_params* tp; float *out_film, *out_half, *out_length;
+};
+// ... how a pixel's hit is carried one frame back: by the view alone, through the per-instance table or through the per-pixel records
+// (`align`: what is asked of the table or the records, 16 for a device form, 1 for a host form) ...
+struct TemporalCarry {
+    enum Kind { NONE, TABLE, FLOW } kind = NONE;
+    const uint32_t *ids_cur = nullptr, *ids_prev = nullptr;
+    const mi355pt_motion_xform* table = nullptr; uint32_t n_entries = 0;
+    const mi355pt_flow_pixel* flow = nullptr;
+    size_t align = 1;
+};
+// ... and, for a rectified form, its parameters (a host form has no scratch: the driver allocates one)
+struct TemporalRectify { const mi355pt_temporal_rectify_params* rp; void* scratch = nullptr; size_t scratch_bytes = 0; };
+// The checks in their one order — temporal_check, the rectify parameters, the scratch (device form), the carry's own —, then the launches on
+// `hip_stream`, or the host form's staging around them on the null stream.  rect == nullptr: not rectified
+int temporal_accumulate_device(const TemporalCall& c, const TemporalCarry& carry, const TemporalRectify* rect, void* hip_stream);
+int temporal_accumulate_host(const TemporalCall& c, const TemporalCarry& carry, const TemporalRectify* rect);
+// the carries' own checks (api_motion.cpp, api_flow.cpp); scratch: the rectified device form's, which counts among the outputs, or nullptr
+int motion_check(const TemporalCarry& carry, const TemporalCall& c, const void* scratch);
+int flow_in_check(const TemporalCarry& carry, const TemporalCall& c, const void* scratch);
 // api_motion.cpp, for api_flow.cpp and api_debug.cpp, whose flow pass is the ID pass's launch: every check of mi355pt_render_ids[_device]
 // (`out`: the per-pixel output buffer) and the launch's shape
 int ids_check(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, const void* out);

@@ -1,7 +1,6 @@
-// The mi355pt_motion.h surface of libmi355pt.so: the ID pass, the motion table (host arithmetic, motion_plan.hpp) and the motion-aware
-// twins of the temporal accumulation and of its rectified form, which run api_temporal.cpp's checks and add their own.  Host C++ only, like
-// api.cpp, whose launch context and timed launch the ID pass uses; the kernels are in pt_kernels_ids.hip, pt_kernels_temporal.hip and
-// pt_kernels_temporal_rectify.hip.
+// The mi355pt_motion.h surface of libmi355pt.so: the ID pass, the motion table (host arithmetic, motion_plan.hpp) and the four table forms
+// of the temporal accumulation: single calls of api_temporal.cpp's driver with a table carry, whose own check is here.  Host C++ only, like
+// api.cpp, whose launch context and timed launch the ID pass uses; the ID pass's kernel is in pt_kernels_ids.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -34,13 +33,10 @@ LaunchPlan pt::plan_ids(const mi355pt_camera* cam, const mi355pt_params* p, int 
     return plan;
 }
 
-namespace {
-
 // what mi355pt_motion.h adds to temporal_check (and, with a scratch, to the rectified form's checks)
-int motion_check(const uint32_t* ids_cur, const uint32_t* ids_prev, const mi355pt_motion_xform* table, uint32_t n_entries, size_t table_align,
-                 const void* out_film, const void* out_half, const void* out_length, const void* scratch) {
-    const void* outs[4] = {out_film, out_half, out_length, scratch};
-    switch (motion_verdict(ids_cur, ids_prev, table, n_entries, table_align, outs, 4)) {
+int pt::motion_check(const TemporalCarry& carry, const TemporalCall& c, const void* scratch) {
+    const void* outs[4] = {c.out_film, c.out_half, c.out_length, scratch};
+    switch (motion_verdict(carry.ids_cur, carry.ids_prev, carry.table, carry.n_entries, carry.align, outs, 4)) {
         case Motion::MISSING: return fail(MI355PT_E_INVALID, "temporal motion: null current id buffer or motion table");
         case Motion::NO_ENTRIES: return fail(MI355PT_E_INVALID, "temporal motion: n_entries must be > 0 (entry 0 is the static one)");
         case Motion::MISALIGNED: return fail(MI355PT_E_INVALID, "temporal motion: the motion table must be 16-byte aligned");
@@ -50,52 +46,12 @@ int motion_check(const uint32_t* ids_cur, const uint32_t* ids_prev, const mi355p
     return MI355PT_OK;
 }
 
-// the two host-buffer entry points, after api_temporal.cpp's temporal_accumulate_host: device copies of the films, the ids and the table,
-// the device entry point (rectified when rp is given, with a scratch of its own) on the default stream, the outputs copied back.  Every
-// argument has been checked.
-int motion_accumulate_host(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev, const mi355pt_temporal_view* view,
-                           uint32_t width, uint32_t height, const mi355pt_temporal_params* tp, const mi355pt_temporal_rectify_params* rp,
-                           const uint32_t* ids_cur, const uint32_t* ids_prev, const mi355pt_motion_xform* table, uint32_t n_entries, float* out_film,
-                           float* out_half, float* out_length) {
-    int rc = MI355PT_OK;
-    const size_t np = (size_t)width * height, n = np * 3;
-    DevBuf<float> d_in[2][6], d_film, d_half, d_len;
-    DevBuf<uint32_t> d_ids[2];
-    DevBuf<mi355pt_motion_xform> d_table;
-    DevBuf<unsigned char> d_scratch;
-    mi355pt_temporal_frame dev[2] = {};
-    const mi355pt_temporal_frame* host[2] = {cur, prev};
-    for (int k = 0; k < 2; ++k) {
-        if (!host[k]) continue;
-        const float* src[6] = {host[k]->film, host[k]->half, k == 0 ? nullptr : host[k]->length, host[k]->position, host[k]->shading_normal, host[k]->hit};
-        const DevBuf<float>* d = d_in[k];
-        for (int i = 0; i < 6; ++i) HIP_TRY(d_in[k][i].upload(src[i], i == 2 ? np : n));
-        dev[k].film = d[0].p; dev[k].half = d[1].p; dev[k].length = d[2].p; dev[k].position = d[3].p; dev[k].shading_normal = d[4].p; dev[k].hit = d[5].p;
-    }
-    HIP_TRY(d_ids[0].upload(ids_cur, np));
-    HIP_TRY(d_ids[1].upload(ids_prev, np));
-    HIP_TRY(d_table.upload(table, n_entries));
-    HIP_TRY(d_film.alloc(n));
-    HIP_TRY(d_len.alloc(np));
-    HIP_TRY(d_half.alloc_for(out_half, n));
-    if (rp) {
-        const size_t scratch_bytes = mi355pt_temporal_rectify_scratch_bytes(width, height);
-        HIP_TRY(d_scratch.alloc(scratch_bytes));
-        rc = mi355pt_temporal_accumulate_rectified_motion_device(&dev[0], spp, prev ? &dev[1] : nullptr, view, width, height, tp, rp, d_scratch.p, scratch_bytes,
-                                                                 d_ids[0].p, d_ids[1].p, d_table.p, n_entries, d_film.p, d_half.p, d_len.p, nullptr);
-    } else {
-        rc = mi355pt_temporal_accumulate_motion_device(&dev[0], spp, prev ? &dev[1] : nullptr, view, width, height, tp, d_ids[0].p, d_ids[1].p, d_table.p,
-                                                       n_entries, d_film.p, d_half.p, d_len.p, nullptr);
-    }
-    if (rc) return rc;
-    HIP_TRY(d_film.download(out_film, n));
-    HIP_TRY(d_half.download(out_half, n));
-    HIP_TRY(d_len.download(out_length, np));
-    return MI355PT_OK;
-}
+namespace {
 
-MotionArgs motion_args(const uint32_t* ids_cur, const uint32_t* ids_prev, const mi355pt_motion_xform* table, uint32_t n_entries) {
-    return MotionArgs{ids_cur, ids_prev, (const MotionXformDev*)table, n_entries - 1u};
+TemporalCarry table_carry(const uint32_t* ids_cur, const uint32_t* ids_prev, const mi355pt_motion_xform* table, uint32_t n_entries, size_t align) {
+    TemporalCarry carry;
+    carry.kind = TemporalCarry::TABLE; carry.ids_cur = ids_cur; carry.ids_prev = ids_prev; carry.table = table; carry.n_entries = n_entries; carry.align = align;
+    return carry;
 }
 
 }  // namespace
@@ -146,27 +102,15 @@ int mi355pt_temporal_accumulate_motion_device(const mi355pt_temporal_frame* cur,
                                               uint32_t width, uint32_t height, const mi355pt_temporal_params* tp, const uint32_t* d_ids_cur,
                                               const uint32_t* d_ids_prev, const mi355pt_motion_xform* d_table, uint32_t n_entries, float* d_out_film,
                                               float* d_out_half, float* d_out_length, void* hip_stream) {
-    int rc = temporal_check(cur, spp, prev, view, width, height, tp, d_out_film, d_out_half, d_out_length);
-    if (rc) return rc;
-    if ((rc = motion_check(d_ids_cur, d_ids_prev, d_table, n_entries, 16, d_out_film, d_out_half, d_out_length, nullptr))) return rc;
-    const TemporalArgs a = temporal_args(spp, view, width, height, tp);
-    const TemporalFrameDev dc = frame_dev(*cur);
-    if (!prev) {      // the first frame: nothing to reproject
-        HIP_TRY(launch_temporal_accumulate(dc, nullptr, a, d_out_film, d_out_half, d_out_length, (hipStream_t)hip_stream));
-        return MI355PT_OK;
-    }
-    HIP_TRY(launch_temporal_accumulate_motion(dc, frame_dev(*prev), a, motion_args(d_ids_cur, d_ids_prev, d_table, n_entries), d_out_film, d_out_half,
-                                              d_out_length, (hipStream_t)hip_stream));
-    return MI355PT_OK;
+    return temporal_accumulate_device({cur, spp, prev, view, width, height, tp, d_out_film, d_out_half, d_out_length},
+                                      table_carry(d_ids_cur, d_ids_prev, d_table, n_entries, 16), nullptr, hip_stream);
 }
 
 int mi355pt_temporal_accumulate_motion(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev, const mi355pt_temporal_view* view,
                                        uint32_t width, uint32_t height, const mi355pt_temporal_params* tp, const uint32_t* ids_cur, const uint32_t* ids_prev,
                                        const mi355pt_motion_xform* table, uint32_t n_entries, float* out_film, float* out_half, float* out_length) {
-    int rc = temporal_check(cur, spp, prev, view, width, height, tp, out_film, out_half, out_length);
-    if (rc) return rc;
-    if ((rc = motion_check(ids_cur, ids_prev, table, n_entries, 1, out_film, out_half, out_length, nullptr))) return rc;
-    return motion_accumulate_host(cur, spp, prev, view, width, height, tp, nullptr, ids_cur, ids_prev, table, n_entries, out_film, out_half, out_length);
+    return temporal_accumulate_host({cur, spp, prev, view, width, height, tp, out_film, out_half, out_length}, table_carry(ids_cur, ids_prev, table, n_entries, 1),
+                                    nullptr);
 }
 
 int mi355pt_temporal_accumulate_rectified_motion_device(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev,
@@ -174,31 +118,18 @@ int mi355pt_temporal_accumulate_rectified_motion_device(const mi355pt_temporal_f
                                                         const mi355pt_temporal_rectify_params* rp, void* d_scratch, size_t scratch_bytes,
                                                         const uint32_t* d_ids_cur, const uint32_t* d_ids_prev, const mi355pt_motion_xform* d_table,
                                                         uint32_t n_entries, float* d_out_film, float* d_out_half, float* d_out_length, void* hip_stream) {
-    int rc = temporal_check(cur, spp, prev, view, width, height, tp, d_out_film, d_out_half, d_out_length);
-    if (rc) return rc;
-    if ((rc = rectify_params_check(rp))) return rc;
-    if ((rc = rectify_scratch_check(cur, prev, width, height, d_scratch, scratch_bytes, d_out_film, d_out_half, d_out_length))) return rc;
-    if ((rc = motion_check(d_ids_cur, d_ids_prev, d_table, n_entries, 16, d_out_film, d_out_half, d_out_length, d_scratch))) return rc;
-    const TemporalArgs a = temporal_args(spp, view, width, height, tp);
-    const TemporalFrameDev dc = frame_dev(*cur);
-    if (!prev) {      // the first frame: nothing to reproject or rectify, the scratch stays as it is
-        HIP_TRY(launch_temporal_accumulate(dc, nullptr, a, d_out_film, d_out_half, d_out_length, (hipStream_t)hip_stream));
-        return MI355PT_OK;
-    }
-    HIP_TRY(launch_temporal_rectify_motion(dc, frame_dev(*prev), a, motion_args(d_ids_cur, d_ids_prev, d_table, n_entries), rp->radius, rp->gamma, d_scratch,
-                                           d_out_film, d_out_half, d_out_length, (hipStream_t)hip_stream));
-    return MI355PT_OK;
+    const TemporalRectify rect{rp, d_scratch, scratch_bytes};
+    return temporal_accumulate_device({cur, spp, prev, view, width, height, tp, d_out_film, d_out_half, d_out_length},
+                                      table_carry(d_ids_cur, d_ids_prev, d_table, n_entries, 16), &rect, hip_stream);
 }
 
 int mi355pt_temporal_accumulate_rectified_motion(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev,
                                                  const mi355pt_temporal_view* view, uint32_t width, uint32_t height, const mi355pt_temporal_params* tp,
                                                  const mi355pt_temporal_rectify_params* rp, const uint32_t* ids_cur, const uint32_t* ids_prev,
                                                  const mi355pt_motion_xform* table, uint32_t n_entries, float* out_film, float* out_half, float* out_length) {
-    int rc = temporal_check(cur, spp, prev, view, width, height, tp, out_film, out_half, out_length);
-    if (rc) return rc;
-    if ((rc = rectify_params_check(rp))) return rc;
-    if ((rc = motion_check(ids_cur, ids_prev, table, n_entries, 1, out_film, out_half, out_length, nullptr))) return rc;
-    return motion_accumulate_host(cur, spp, prev, view, width, height, tp, rp, ids_cur, ids_prev, table, n_entries, out_film, out_half, out_length);
+    const TemporalRectify rect{rp};
+    return temporal_accumulate_host({cur, spp, prev, view, width, height, tp, out_film, out_half, out_length}, table_carry(ids_cur, ids_prev, table, n_entries, 1),
+                                    &rect);
 }
 
 }  // extern "C"

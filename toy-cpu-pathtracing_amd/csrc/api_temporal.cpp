@@ -1,6 +1,8 @@
-// The mi355pt_temporal.h surface of libmi355pt.so: the view of a camera pair (host arithmetic), the argument checks and the two entry
-// points of the temporal reprojection — and the mi355pt_temporal_rectify.h surface, which adds its own checks to the same ones and two entry
-// points of the same shape.  Host C++ only, like api.cpp; the kernels are pt_kernels_temporal.hip and pt_kernels_temporal_rectify.hip.
+// The mi355pt_temporal.h and mi355pt_temporal_rectify.h surfaces of libmi355pt.so: the view of a camera pair (host arithmetic), the four
+// entry points of the temporal reprojection and of its rectified form — and the one driver behind them and behind the eight carry forms of
+// api_motion.cpp and api_flow.cpp (api_internal.hpp): the checks in their one order, the launches with the first-frame rule,
+// the host forms' staging.  Host C++ only, like api.cpp; the kernels are pt_kernels_temporal.hip, pt_kernels_temporal_rectify.hip and
+// pt_kernels_temporal_flow.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -20,12 +22,7 @@ bool normalize3(const float v[3], double out[3]) {
     return true;
 }
 
-}  // namespace
-
-// (declared in api_internal.hpp: api_motion.cpp runs the same checks and builds the same kernel arguments)
-namespace pt {
-
-// every check of mi355pt_temporal_accumulate_device / mi355pt_temporal_accumulate; host arithmetic only
+// the checks every form runs first; host arithmetic only
 int temporal_check(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev, const mi355pt_temporal_view* view, uint32_t width,
                    uint32_t height, const mi355pt_temporal_params* tp, const float* out_film, const float* out_half, const float* out_length) {
     if (!cur || !tp || !out_film || !out_length) return fail(MI355PT_E_INVALID, "temporal: null current frame, params, output film or output length pointer");
@@ -100,22 +97,73 @@ int rectify_scratch_check(const mi355pt_temporal_frame* cur, const mi355pt_tempo
     return MI355PT_OK;
 }
 
-}  // namespace pt
+// the checks of a call in their one order; `device`: a _device form, whose scratch is the caller's
+int call_check(const TemporalCall& c, const TemporalCarry& carry, const TemporalRectify* rect, bool device) {
+    int rc = temporal_check(c.cur, c.spp, c.prev, c.view, c.width, c.height, c.tp, c.out_film, c.out_half, c.out_length);
+    if (rc) return rc;
+    if (rect && (rc = rectify_params_check(rect->rp))) return rc;
+    const void* scratch = rect && device ? rect->scratch : nullptr;
+    if (rect && device && (rc = rectify_scratch_check(c.cur, c.prev, c.width, c.height, scratch, rect->scratch_bytes, c.out_film, c.out_half, c.out_length))) return rc;
+    switch (carry.kind) {
+        case TemporalCarry::TABLE: return motion_check(carry, c, scratch);
+        case TemporalCarry::FLOW: return flow_in_check(carry, c, scratch);
+        case TemporalCarry::NONE: break;
+    }
+    return MI355PT_OK;
+}
 
-namespace {
+// The launches of a checked call whose buffers are all on the device.  The first frame (no previous one) has nothing to reproject or to
+// rectify: whatever the form, it is the plain kernel, and a scratch stays as it is.  Otherwise the carry's accumulation, or for a rectified
+// form the carry's gather into the scratch and then the one rectifying blend
+int run_device(const TemporalCall& c, const TemporalCarry& carry, const TemporalRectify* rect, hipStream_t stream) {
+    const TemporalArgs a = temporal_args(c.spp, c.view, c.width, c.height, c.tp);
+    const TemporalFrameDev dc = frame_dev(*c.cur);
+    if (!c.prev) {
+        HIP_TRY(launch_temporal_accumulate(dc, nullptr, a, c.out_film, c.out_half, c.out_length, stream));
+        return MI355PT_OK;
+    }
+    const TemporalFrameDev dp = frame_dev(*c.prev);
+    const MotionArgs mo{carry.ids_cur, carry.ids_prev, (const MotionXformDev*)carry.table, carry.n_entries - 1u};
+    const FlowArgs fl{carry.ids_cur, carry.ids_prev, (const FlowPixelDev*)carry.flow};
+    switch (carry.kind) {
+        case TemporalCarry::NONE:
+            if (rect) HIP_TRY(launch_temporal_gather(dc, dp, a, rect->scratch, stream));
+            else HIP_TRY(launch_temporal_accumulate(dc, &dp, a, c.out_film, c.out_half, c.out_length, stream));
+            break;
+        case TemporalCarry::TABLE:
+            if (rect) HIP_TRY(launch_temporal_gather_motion(dc, dp, a, mo, rect->scratch, stream));
+            else HIP_TRY(launch_temporal_accumulate_motion(dc, dp, a, mo, c.out_film, c.out_half, c.out_length, stream));
+            break;
+        case TemporalCarry::FLOW:
+            if (rect) HIP_TRY(launch_temporal_gather_flow(dc, dp, a, fl, rect->scratch, stream));
+            else HIP_TRY(launch_temporal_accumulate_flow(dc, dp, a, fl, c.out_film, c.out_half, c.out_length, stream));
+            break;
+    }
+    if (rect) HIP_TRY(launch_temporal_rectify_blend(dc, a, rect->rp->radius, rect->rp->gamma, rect->scratch, c.out_film, c.out_half, c.out_length, stream));
+    return MI355PT_OK;
+}
 
-// the two host-buffer entry points: device copies of the films, the device entry point (rectified when rp is given, with a scratch of its
-// own) on the default stream, the outputs copied back.  Every argument has been checked.
-int temporal_accumulate_host(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev, const mi355pt_temporal_view* view,
-                             uint32_t width, uint32_t height, const mi355pt_temporal_params* tp, const mi355pt_temporal_rectify_params* rp, float* out_film,
-                             float* out_half, float* out_length) {
-    int rc = MI355PT_OK;
-    const size_t np = (size_t)width * height, n = np * 3;
+}  // namespace
+
+int pt::temporal_accumulate_device(const TemporalCall& c, const TemporalCarry& carry, const TemporalRectify* rect, void* hip_stream) {
+    const int rc = call_check(c, carry, rect, true);
+    return rc ? rc : run_device(c, carry, rect, (hipStream_t)hip_stream);
+}
+
+// A host form: its own checks (no scratch, no alignment asked), then device copies of the films, of the ids when given and of the table or
+// the records, the launches of the device form (rectified: with a scratch of its own) on the null stream, the outputs copied back
+int pt::temporal_accumulate_host(const TemporalCall& c, const TemporalCarry& carry, const TemporalRectify* rect) {
+    const int rc = call_check(c, carry, rect, false);
+    if (rc) return rc;
+    const size_t np = (size_t)c.width * c.height, n = np * 3;
     // the films of the two frames in the order of mi355pt_temporal_frame (length: W x H; the current frame's is ignored)
     DevBuf<float> d_in[2][6], d_film, d_half, d_len;
+    DevBuf<uint32_t> d_ids[2];
+    DevBuf<mi355pt_motion_xform> d_table;
+    DevBuf<mi355pt_flow_pixel> d_flow;
     DevBuf<unsigned char> d_scratch;
     mi355pt_temporal_frame dev[2] = {};
-    const mi355pt_temporal_frame* host[2] = {cur, prev};
+    const mi355pt_temporal_frame* host[2] = {c.cur, c.prev};
     for (int k = 0; k < 2; ++k) {
         if (!host[k]) continue;
         const float* src[6] = {host[k]->film, host[k]->half, k == 0 ? nullptr : host[k]->length, host[k]->position, host[k]->shading_normal, host[k]->hit};
@@ -123,25 +171,29 @@ int temporal_accumulate_host(const mi355pt_temporal_frame* cur, uint32_t spp, co
         for (int i = 0; i < 6; ++i) HIP_TRY(d_in[k][i].upload(src[i], i == 2 ? np : n));
         dev[k].film = d[0].p; dev[k].half = d[1].p; dev[k].length = d[2].p; dev[k].position = d[3].p; dev[k].shading_normal = d[4].p; dev[k].hit = d[5].p;
     }
+    HIP_TRY(d_ids[0].upload(carry.ids_cur, np));
+    HIP_TRY(d_ids[1].upload(carry.ids_prev, np));
+    HIP_TRY(d_table.upload(carry.table, carry.n_entries));
+    HIP_TRY(d_flow.upload(carry.flow, np));
     HIP_TRY(d_film.alloc(n));
     HIP_TRY(d_len.alloc(np));
-    HIP_TRY(d_half.alloc_for(out_half, n));
-    if (rp) {
-        const size_t scratch_bytes = mi355pt_temporal_rectify_scratch_bytes(width, height);
-        HIP_TRY(d_scratch.alloc(scratch_bytes));
-        rc = mi355pt_temporal_accumulate_rectified_device(&dev[0], spp, prev ? &dev[1] : nullptr, view, width, height, tp, rp, d_scratch.p, scratch_bytes, d_film.p,
-                                                          d_half.p, d_len.p, nullptr);
-    } else {
-        rc = mi355pt_temporal_accumulate_device(&dev[0], spp, prev ? &dev[1] : nullptr, view, width, height, tp, d_film.p, d_half.p, d_len.p, nullptr);
+    HIP_TRY(d_half.alloc_for(c.out_half, n));
+    TemporalRectify d_rect{rect ? rect->rp : nullptr};
+    if (rect) {
+        d_rect.scratch_bytes = mi355pt_temporal_rectify_scratch_bytes(c.width, c.height);
+        HIP_TRY(d_scratch.alloc(d_rect.scratch_bytes));
+        d_rect.scratch = d_scratch.p;
     }
-    if (rc) return rc;
-    HIP_TRY(d_film.download(out_film, n));
-    HIP_TRY(d_half.download(out_half, n));
-    HIP_TRY(d_len.download(out_length, np));
+    TemporalCarry d_carry = carry;
+    d_carry.ids_cur = d_ids[0].p; d_carry.ids_prev = d_ids[1].p; d_carry.table = d_table.p; d_carry.flow = d_flow.p;
+    const TemporalCall d_call{&dev[0], c.spp, c.prev ? &dev[1] : nullptr, c.view, c.width, c.height, c.tp, d_film.p, d_half.p, d_len.p};
+    const int run = run_device(d_call, d_carry, rect ? &d_rect : nullptr, nullptr);
+    if (run) return run;
+    HIP_TRY(d_film.download(c.out_film, n));
+    HIP_TRY(d_half.download(c.out_half, n));
+    HIP_TRY(d_len.download(c.out_length, np));
     return MI355PT_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -180,19 +232,12 @@ int mi355pt_temporal_view_from_cameras(const mi355pt_camera* cur, const mi355pt_
 int mi355pt_temporal_accumulate_device(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev, const mi355pt_temporal_view* view,
                                        uint32_t width, uint32_t height, const mi355pt_temporal_params* tp, float* d_out_film, float* d_out_half,
                                        float* d_out_length, void* hip_stream) {
-    int rc = temporal_check(cur, spp, prev, view, width, height, tp, d_out_film, d_out_half, d_out_length);
-    if (rc) return rc;
-    const TemporalArgs a = temporal_args(spp, view, width, height, tp);
-    const TemporalFrameDev dc = frame_dev(*cur), dp = prev ? frame_dev(*prev) : TemporalFrameDev{};
-    HIP_TRY(launch_temporal_accumulate(dc, prev ? &dp : nullptr, a, d_out_film, d_out_half, d_out_length, (hipStream_t)hip_stream));
-    return MI355PT_OK;
+    return temporal_accumulate_device({cur, spp, prev, view, width, height, tp, d_out_film, d_out_half, d_out_length}, TemporalCarry{}, nullptr, hip_stream);
 }
 
 int mi355pt_temporal_accumulate(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev, const mi355pt_temporal_view* view,
                                 uint32_t width, uint32_t height, const mi355pt_temporal_params* tp, float* out_film, float* out_half, float* out_length) {
-    int rc = temporal_check(cur, spp, prev, view, width, height, tp, out_film, out_half, out_length);
-    if (rc) return rc;
-    return temporal_accumulate_host(cur, spp, prev, view, width, height, tp, nullptr, out_film, out_half, out_length);
+    return temporal_accumulate_host({cur, spp, prev, view, width, height, tp, out_film, out_half, out_length}, TemporalCarry{}, nullptr);
 }
 
 /* ---- mi355pt_temporal_rectify.h ---- */
@@ -212,27 +257,15 @@ int mi355pt_temporal_accumulate_rectified_device(const mi355pt_temporal_frame* c
                                                  const mi355pt_temporal_view* view, uint32_t width, uint32_t height, const mi355pt_temporal_params* tp,
                                                  const mi355pt_temporal_rectify_params* rp, void* d_scratch, size_t scratch_bytes, float* d_out_film,
                                                  float* d_out_half, float* d_out_length, void* hip_stream) {
-    int rc = temporal_check(cur, spp, prev, view, width, height, tp, d_out_film, d_out_half, d_out_length);
-    if (rc) return rc;
-    if ((rc = rectify_params_check(rp))) return rc;
-    if ((rc = rectify_scratch_check(cur, prev, width, height, d_scratch, scratch_bytes, d_out_film, d_out_half, d_out_length))) return rc;
-    const TemporalArgs a = temporal_args(spp, view, width, height, tp);
-    const TemporalFrameDev dc = frame_dev(*cur);
-    if (!prev) {      // the first frame: nothing to rectify, the scratch stays as it is
-        HIP_TRY(launch_temporal_accumulate(dc, nullptr, a, d_out_film, d_out_half, d_out_length, (hipStream_t)hip_stream));
-        return MI355PT_OK;
-    }
-    HIP_TRY(launch_temporal_rectify(dc, frame_dev(*prev), a, rp->radius, rp->gamma, d_scratch, d_out_film, d_out_half, d_out_length, (hipStream_t)hip_stream));
-    return MI355PT_OK;
+    const TemporalRectify rect{rp, d_scratch, scratch_bytes};
+    return temporal_accumulate_device({cur, spp, prev, view, width, height, tp, d_out_film, d_out_half, d_out_length}, TemporalCarry{}, &rect, hip_stream);
 }
 
 int mi355pt_temporal_accumulate_rectified(const mi355pt_temporal_frame* cur, uint32_t spp, const mi355pt_temporal_frame* prev, const mi355pt_temporal_view* view,
                                           uint32_t width, uint32_t height, const mi355pt_temporal_params* tp, const mi355pt_temporal_rectify_params* rp,
                                           float* out_film, float* out_half, float* out_length) {
-    int rc = temporal_check(cur, spp, prev, view, width, height, tp, out_film, out_half, out_length);
-    if (rc) return rc;
-    if ((rc = rectify_params_check(rp))) return rc;
-    return temporal_accumulate_host(cur, spp, prev, view, width, height, tp, rp, out_film, out_half, out_length);
+    const TemporalRectify rect{rp};
+    return temporal_accumulate_host({cur, spp, prev, view, width, height, tp, out_film, out_half, out_length}, TemporalCarry{}, &rect);
 }
 
 }  // extern "C"

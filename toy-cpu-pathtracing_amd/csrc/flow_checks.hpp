@@ -1,4 +1,4 @@
-// The pure predicates of api_flow.cpp's argument checks (include/mi355pt_flow.h), beside api_checks.hpp's, whose misaligned() they use.
+// The pure predicates of api_flow.cpp's argument checks (include/mi355pt_flow.h), beside api_checks.hpp's, whose misaligned() and output_is_one_of() they use.
 // Host arithmetic only, no HIP: compiles with a plain C++ compiler (tests/flow_checks_check.cpp walks them, plain and under ASan + UBSan).
 // They answer with a verdict; the refusal's code and text stay at the caller's fail(...).
 #pragma once
@@ -25,9 +25,7 @@ inline FlowIn flow_in_verdict(const void* ids_cur, const void* ids_prev, const v
     if (!flow) return FlowIn::MISSING;
     if (misaligned(flow, flow_align)) return FlowIn::MISALIGNED;
     if (ids_prev && !ids_cur) return FlowIn::PREV_IDS_ALONE;
-    for (int i = 0; i < n_outs; ++i)
-        if (outs[i] && (outs[i] == flow || outs[i] == ids_cur || outs[i] == ids_prev)) return FlowIn::ALIASES_OUTPUT;
-    return FlowIn::OK;
+    return output_is_one_of(outs, n_outs, flow, ids_cur, ids_prev) ? FlowIn::ALIASES_OUTPUT : FlowIn::OK;
 }
 
 }  // namespace pt

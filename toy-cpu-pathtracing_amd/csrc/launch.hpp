@@ -66,9 +66,10 @@ size_t denoise_var_scratch_bytes(uint32_t width, uint32_t height);
 hipError_t launch_denoise_var(const float* d_beauty, const float* d_half, uint32_t spp_b, const uint32_t* d_tile_spp, const float* d_albedo, uint32_t spp_a,
                               const float* d_normal, uint32_t spp_n, uint32_t width, uint32_t height, uint32_t levels, float sigma_lum, float sigma_normal,
                               float sigma_albedo, float albedo_eps, float lum_eps, void* d_scratch, float* d_out, hipStream_t);
-// pt_kernels_temporal.hip: the temporal reprojection (include/mi355pt_temporal.h): one launch on the grid of denoise_grid_blocks.
-// A frame's films as the kernel takes them (half == nullptr: no half film; length is read of the previous frame only); prev == nullptr:
-// the first frame.  The launcher fills TemporalArgs::blocks_x
+// pt_kernels_temporal.hip, pt_kernels_temporal_rectify.hip, pt_kernels_temporal_flow.hip: the temporal reprojection
+// (include/mi355pt_temporal.h, mi355pt_temporal_rectify.h, mi355pt_motion.h, mi355pt_flow.h), every launch on the grid of
+// denoise_grid_blocks; api_temporal.cpp's driver composes them.  A frame's films as the kernels take them (half == nullptr: no half film;
+// length is read of the previous frame only).  Every launcher fills its own copy of TemporalArgs::blocks_x
 struct TemporalFrameDev { const float *film = nullptr, *half = nullptr, *length = nullptr, *position = nullptr, *shading_normal = nullptr, *hit = nullptr; };
 struct TemporalArgs {
     uint32_t width, height, blocks_x;
@@ -77,48 +78,43 @@ struct TemporalArgs {
     float delta[3], rows[9], sx, sy, cx, cy;
     float pos_tol, normal_cos, min_weight, max_history;
 };
+// How a pixel's hit is carried into the previous frame beside the view: a per-instance table (a record as the kernels load it: six 16-byte
+// loads, so the table is 16-byte aligned; last_entry = n_entries - 1, the clamp of a pixel's id) or a 32-byte record per pixel (two
+// 16-byte loads; ids_cur is read only with ids_prev).  ids_prev == nullptr: no id test of the taps.  With either, args.delta is not read
+struct MotionXformDev { float a[9], b[3], n[9], pad[3]; };
+static_assert(sizeof(MotionXformDev) == 96, "a motion record is six float4");
+struct MotionArgs { const uint32_t* ids_cur; const uint32_t* ids_prev; const MotionXformDev* table; uint32_t last_entry; };
+struct FlowPixelDev { float d[3]; uint32_t id; float dn[3]; uint32_t pad; };
+static_assert(sizeof(FlowPixelDev) == 32, "a flow record is two float4");
+struct FlowArgs { const uint32_t* ids_cur; const uint32_t* ids_prev; const FlowPixelDev* flow; };
+// The accumulation in one launch, each carry's kernels in its unit (temporal, temporal, flow).  prev == nullptr: the first frame, which
+// every form sends to the plain kernel; the table and the flow kernels run WITH a previous frame only
 hipError_t launch_temporal_accumulate(const TemporalFrameDev& cur, const TemporalFrameDev* prev, TemporalArgs args, float* d_out_film, float* d_out_half,
                                       float* d_out_length, hipStream_t);
-// pt_kernels_temporal_rectify.hip: the rectified accumulation (include/mi355pt_temporal_rectify.h) of a frame WITH a previous frame: two
-// launches on the same grid, the gather into d_scratch (TEMPORAL_RECTIFY_RECORD_BYTES per pixel, 16-byte aligned) and the rectifying blend.
-// radius is 1 .. 3.  The launcher fills TemporalArgs::blocks_x
+hipError_t launch_temporal_accumulate_motion(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const MotionArgs& motion,
+                                             float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
+hipError_t launch_temporal_accumulate_flow(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const FlowArgs& flow,
+                                           float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
+// The rectified accumulation of a frame WITH a previous frame in two launches: a carry's gather (rectify, rectify, flow) into d_scratch
+// (TEMPORAL_RECTIFY_RECORD_BYTES per pixel, 16-byte aligned), then the one rectifying blend over those records.  radius is 1 .. 3
 constexpr size_t TEMPORAL_RECTIFY_RECORD_BYTES = 32;
-hipError_t launch_temporal_rectify(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, uint32_t radius, float gamma, void* d_scratch,
-                                   float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
+hipError_t launch_temporal_gather(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, void* d_scratch, hipStream_t);
+hipError_t launch_temporal_gather_motion(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const MotionArgs& motion, void* d_scratch,
+                                         hipStream_t);
+hipError_t launch_temporal_gather_flow(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const FlowArgs& flow, void* d_scratch,
+                                       hipStream_t);
+hipError_t launch_temporal_rectify_blend(const TemporalFrameDev& cur, TemporalArgs args, uint32_t radius, float gamma, const void* d_scratch, float* d_out_film,
+                                         float* d_out_half, float* d_out_length, hipStream_t);
 // pt_kernels_ids.hip: the ID pass (include/mi355pt_motion.h): one primary ray through every pixel centre, instance + 1 of the closest hit or
 // 0 into d_ids.  The plan must have block_log2 == 3 and chunks == 1 (api_motion.cpp, the G-buffer pass's plan): one pixel per lane
 hipError_t launch_ids(const DevScene&, const DevCamera&, const DevParams&, uint32_t* d_ids, unsigned* d_counter, DevStats* d_stats, int grid, hipStream_t);
 int query_resident_waves_ids();
-// pt_kernels_temporal.hip / pt_kernels_temporal_rectify.hip: the motion-aware twins of the two launchers above (include/mi355pt_motion.h),
-// of a frame WITH a previous frame (the first frame has nothing to reproject: api_motion.cpp sends it to launch_temporal_accumulate).
-// A table record as the kernels load it: six 16-byte loads, so the table is 16-byte aligned.  ids_prev == nullptr: no id test of the taps;
-// last_entry = n_entries - 1, the clamp of a pixel's id.  args.delta is not read
-struct MotionXformDev { float a[9], b[3], n[9], pad[3]; };
-static_assert(sizeof(MotionXformDev) == 96, "a motion record is six float4");
-struct MotionArgs { const uint32_t* ids_cur; const uint32_t* ids_prev; const MotionXformDev* table; uint32_t last_entry; };
-hipError_t launch_temporal_accumulate_motion(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const MotionArgs& motion,
-                                             float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
-hipError_t launch_temporal_rectify_motion(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const MotionArgs& motion, uint32_t radius,
-                                          float gamma, void* d_scratch, float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
 // pt_kernels_flow.hip: the flow pass (include/mi355pt_flow.h): the ID pass's launch with a 32-byte motion record per pixel from the hit's
 // triangle in d_tris_prev (the scene's mark) and in DevScene::tris_render.  d_flow is 16-byte aligned; d_ids == nullptr: not wanted;
 // d_hits != nullptr (16 bytes per pixel: tri, b0, b1, b2) takes the debug twin of the kernel.  The plan is launch_ids's
-struct FlowPixelDev { float d[3]; uint32_t id; float dn[3]; uint32_t pad; };
-static_assert(sizeof(FlowPixelDev) == 32, "a flow record is two float4");
 hipError_t launch_flow(const DevScene&, const DevCamera&, const DevParams&, const DevTri* d_tris_prev, FlowPixelDev* d_flow, uint32_t* d_ids, void* d_hits,
                        unsigned* d_counter, DevStats* d_stats, int grid, hipStream_t);
 int query_resident_waves_flow(bool debug);
-// pt_kernels_temporal_flow.hip: the flow-aware twins of the two temporal launchers (include/mi355pt_flow.h), of a frame WITH a previous frame.
-// A pixel's record is two 16-byte loads.  ids_prev == nullptr: no id test of the taps (ids_cur is then not read).  args.delta is not read.
-// The rectified form's second launch is pt_kernels_temporal_rectify.hip's own blend, through launch_temporal_rectify_blend
-struct FlowArgs { const uint32_t* ids_cur; const uint32_t* ids_prev; const FlowPixelDev* flow; };
-hipError_t launch_temporal_accumulate_flow(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const FlowArgs& flow,
-                                           float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
-hipError_t launch_temporal_rectify_flow(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const FlowArgs& flow, uint32_t radius,
-                                        float gamma, void* d_scratch, float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
-// pt_kernels_temporal_rectify.hip: the rectifying blend alone, over gather records that are in d_scratch already (args.blocks_x filled)
-hipError_t launch_temporal_rectify_blend(const TemporalFrameDev& cur, const TemporalArgs& args, uint32_t radius, float gamma, const void* d_scratch,
-                                         float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
 // pt_kernels_upsample.hip: the guided half-resolution upsample (include/mi355pt_upsample.h): one launch on the grid of denoise_grid_blocks
 // over the FULL frame.  The G-buffer sums of one resolution as the kernel takes them (albedo == nullptr: not given, then on both sides);
 // low_half == nullptr: no half film (then out_half is not written).  The launcher fills UpsampleArgs::blocks_x

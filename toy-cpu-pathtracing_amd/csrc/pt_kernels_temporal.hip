@@ -62,36 +62,25 @@ __global__ __launch_bounds__(DN_BLOCK_X * DN_BLOCK_Y) void temporal_accumulate_m
 
 }  // namespace
 
-// ---- host side (declared in launch.hpp; called from api_temporal.cpp, which has checked every argument) ----
+// ---- host side (declared in launch.hpp; called from api_temporal.cpp's driver, which has checked every argument) ----
 hipError_t launch_temporal_accumulate(const TemporalFrameDev& cur, const TemporalFrameDev* prev, TemporalArgs args, float* d_out_film, float* d_out_half,
                                       float* d_out_length, hipStream_t stream) {
-    args.blocks_x = (uint32_t)(((uint64_t)args.width + DN_BLOCK_X - 1) / DN_BLOCK_X);
-    const dim3 grid(denoise_grid_blocks(args.width, args.height)), block(DN_BLOCK_X, DN_BLOCK_Y);
+    const TpShape sh = tp_shape(args);
     const TemporalFrameDev pv = prev ? *prev : TemporalFrameDev{};
-    const bool has_half = cur.half != nullptr;
-#define PT_TP_LAUNCH(HALF, PREV) \
-    hipLaunchKernelGGL((temporal_accumulate_kernel<HALF, PREV>), grid, block, 0, stream, cur, pv, args, d_out_film, d_out_half, d_out_length)
-    if (has_half && prev) PT_TP_LAUNCH(true, true);
-    else if (has_half) PT_TP_LAUNCH(true, false);
-    else if (prev) PT_TP_LAUNCH(false, true);
-    else PT_TP_LAUNCH(false, false);
-#undef PT_TP_LAUNCH
+    tp_dispatch(cur.half != nullptr, prev != nullptr, [&](auto half, auto has_prev) {
+        hipLaunchKernelGGL((temporal_accumulate_kernel<decltype(half)::value, decltype(has_prev)::value>), sh.grid, sh.block, 0, stream, cur, pv, args, d_out_film,
+                           d_out_half, d_out_length);
+    });
     return hipGetLastError();
 }
 
-// (called from api_motion.cpp, which has checked every argument)
 hipError_t launch_temporal_accumulate_motion(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const MotionArgs& motion,
                                              float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t stream) {
-    args.blocks_x = (uint32_t)(((uint64_t)args.width + DN_BLOCK_X - 1) / DN_BLOCK_X);
-    const dim3 grid(denoise_grid_blocks(args.width, args.height)), block(DN_BLOCK_X, DN_BLOCK_Y);
-    const bool has_half = cur.half != nullptr, has_ids = motion.ids_prev != nullptr;
-#define PT_TP_LAUNCH(HALF, IDS) \
-    hipLaunchKernelGGL((temporal_accumulate_motion_kernel<HALF, true, IDS>), grid, block, 0, stream, cur, prev, args, motion, d_out_film, d_out_half, d_out_length)
-    if (has_half && has_ids) PT_TP_LAUNCH(true, true);
-    else if (has_half) PT_TP_LAUNCH(true, false);
-    else if (has_ids) PT_TP_LAUNCH(false, true);
-    else PT_TP_LAUNCH(false, false);
-#undef PT_TP_LAUNCH
+    const TpShape sh = tp_shape(args);
+    tp_dispatch(cur.half != nullptr, motion.ids_prev != nullptr, [&](auto half, auto ids) {
+        hipLaunchKernelGGL((temporal_accumulate_motion_kernel<decltype(half)::value, true, decltype(ids)::value>), sh.grid, sh.block, 0, stream, cur, prev, args,
+                           motion, d_out_film, d_out_half, d_out_length);
+    });
     return hipGetLastError();
 }
 

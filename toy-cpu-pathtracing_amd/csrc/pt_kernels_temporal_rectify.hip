@@ -26,8 +26,6 @@ namespace pt {
 
 namespace {
 
-static_assert(TEMPORAL_RECTIFY_RECORD_BYTES == 2 * sizeof(float4), "a scratch record is two float4");
-
 template <bool HAS_HALF, bool HAS_PREV>
 __global__ __launch_bounds__(DN_BLOCK_X * DN_BLOCK_Y) void temporal_gather_kernel(TemporalFrameDev cur, TemporalFrameDev prev, TemporalArgs a,
                                                                                   float4* __restrict__ record) {
@@ -37,8 +35,7 @@ __global__ __launch_bounds__(DN_BLOCK_X * DN_BLOCK_Y) void temporal_gather_kerne
 #undef PT_TP_MOTION
 #undef PT_TP_RECORD
 
-    record[2 * p] = make_float4(m1[0], m1[1], m1[2], m2[0]);
-    record[2 * p + 1] = make_float4(m2[1], m2[2], L, 0.0f);
+    tp_write_record(record, p, m1, m2, L);
 }
 
 // The motion-aware twin of the gather (include/mi355pt_motion.h): the same body with PT_TP_MOTION, the same record.  The rectifying
@@ -52,8 +49,7 @@ __global__ __launch_bounds__(DN_BLOCK_X * DN_BLOCK_Y) void temporal_gather_motio
 #undef PT_TP_MOTION
 #undef PT_TP_RECORD
 
-    record[2 * p] = make_float4(m1[0], m1[1], m1[2], m2[0]);
-    record[2 * p + 1] = make_float4(m2[1], m2[2], L, 0.0f);
+    tp_write_record(record, p, m1, m2, L);
 }
 
 // the cleaned current values of pixel p: (c1, c2) with a half film, (c, 0) without — as the gather's body forms them
@@ -173,10 +169,10 @@ __global__ __launch_bounds__(DN_BLOCK_X * DN_BLOCK_Y) void temporal_rectify_kern
 }
 
 template <bool HAS_HALF>
-void launch_rectify_radius(uint32_t radius, dim3 grid, dim3 block, hipStream_t stream, const TemporalFrameDev& cur, const TemporalArgs& args, float gamma,
+void launch_rectify_radius(uint32_t radius, const TpShape& sh, hipStream_t stream, const TemporalFrameDev& cur, const TemporalArgs& args, float gamma,
                            const float4* record, float* d_out_film, float* d_out_half, float* d_out_length) {
 #define PT_TR_LAUNCH(R) \
-    hipLaunchKernelGGL((temporal_rectify_kernel<HAS_HALF, R>), grid, block, 0, stream, cur, args, gamma, record, d_out_film, d_out_half, d_out_length)
+    hipLaunchKernelGGL((temporal_rectify_kernel<HAS_HALF, R>), sh.grid, sh.block, 0, stream, cur, args, gamma, record, d_out_film, d_out_half, d_out_length)
     if (radius == 1) PT_TR_LAUNCH(1);
     else if (radius == 2) PT_TR_LAUNCH(2);
     else PT_TR_LAUNCH(3);
@@ -185,52 +181,32 @@ void launch_rectify_radius(uint32_t radius, dim3 grid, dim3 block, hipStream_t s
 
 }  // namespace
 
-// ---- host side (declared in launch.hpp; called from api_temporal.cpp, which has checked every argument) ----
-hipError_t launch_temporal_rectify(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, uint32_t radius, float gamma, void* d_scratch,
-                                   float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t stream) {
-    if (radius < 1 || radius > 3) return hipErrorInvalidValue;
-    args.blocks_x = (uint32_t)(((uint64_t)args.width + DN_BLOCK_X - 1) / DN_BLOCK_X);
-    const dim3 grid(denoise_grid_blocks(args.width, args.height)), block(DN_BLOCK_X, DN_BLOCK_Y);
-    float4* record = (float4*)d_scratch;
-    const bool has_half = cur.half != nullptr;
-    if (has_half) hipLaunchKernelGGL((temporal_gather_kernel<true, true>), grid, block, 0, stream, cur, prev, args, record);
-    else hipLaunchKernelGGL((temporal_gather_kernel<false, true>), grid, block, 0, stream, cur, prev, args, record);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (has_half) launch_rectify_radius<true>(radius, grid, block, stream, cur, args, gamma, record, d_out_film, d_out_half, d_out_length);
-    else launch_rectify_radius<false>(radius, grid, block, stream, cur, args, gamma, record, d_out_film, d_out_half, d_out_length);
+// ---- host side (declared in launch.hpp; called from api_temporal.cpp's driver, which has checked every argument) ----
+hipError_t launch_temporal_gather(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, void* d_scratch, hipStream_t stream) {
+    const TpShape sh = tp_shape(args);
+    if (cur.half != nullptr) hipLaunchKernelGGL((temporal_gather_kernel<true, true>), sh.grid, sh.block, 0, stream, cur, prev, args, (float4*)d_scratch);
+    else hipLaunchKernelGGL((temporal_gather_kernel<false, true>), sh.grid, sh.block, 0, stream, cur, prev, args, (float4*)d_scratch);
     return hipGetLastError();
 }
 
-// (called from pt_kernels_temporal_flow.hip, whose gather has written the records: the second launch of the two launchers around it)
-hipError_t launch_temporal_rectify_blend(const TemporalFrameDev& cur, const TemporalArgs& args, uint32_t radius, float gamma, const void* d_scratch,
-                                         float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t stream) {
+// the second launch of every rectified form, over the records one of the three gathers has written
+hipError_t launch_temporal_rectify_blend(const TemporalFrameDev& cur, TemporalArgs args, uint32_t radius, float gamma, const void* d_scratch, float* d_out_film,
+                                         float* d_out_half, float* d_out_length, hipStream_t stream) {
     if (radius < 1 || radius > 3) return hipErrorInvalidValue;
-    const dim3 grid(denoise_grid_blocks(args.width, args.height)), block(DN_BLOCK_X, DN_BLOCK_Y);
+    const TpShape sh = tp_shape(args);
     const float4* record = (const float4*)d_scratch;
-    if (cur.half != nullptr) launch_rectify_radius<true>(radius, grid, block, stream, cur, args, gamma, record, d_out_film, d_out_half, d_out_length);
-    else launch_rectify_radius<false>(radius, grid, block, stream, cur, args, gamma, record, d_out_film, d_out_half, d_out_length);
+    if (cur.half != nullptr) launch_rectify_radius<true>(radius, sh, stream, cur, args, gamma, record, d_out_film, d_out_half, d_out_length);
+    else launch_rectify_radius<false>(radius, sh, stream, cur, args, gamma, record, d_out_film, d_out_half, d_out_length);
     return hipGetLastError();
 }
 
-// (called from api_motion.cpp, which has checked every argument)
-hipError_t launch_temporal_rectify_motion(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const MotionArgs& motion, uint32_t radius,
-                                          float gamma, void* d_scratch, float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t stream) {
-    if (radius < 1 || radius > 3) return hipErrorInvalidValue;
-    args.blocks_x = (uint32_t)(((uint64_t)args.width + DN_BLOCK_X - 1) / DN_BLOCK_X);
-    const dim3 grid(denoise_grid_blocks(args.width, args.height)), block(DN_BLOCK_X, DN_BLOCK_Y);
-    float4* record = (float4*)d_scratch;
-    const bool has_half = cur.half != nullptr, has_ids = motion.ids_prev != nullptr;
-#define PT_TR_GATHER(HALF, IDS) hipLaunchKernelGGL((temporal_gather_motion_kernel<HALF, true, IDS>), grid, block, 0, stream, cur, prev, args, motion, record)
-    if (has_half && has_ids) PT_TR_GATHER(true, true);
-    else if (has_half) PT_TR_GATHER(true, false);
-    else if (has_ids) PT_TR_GATHER(false, true);
-    else PT_TR_GATHER(false, false);
-#undef PT_TR_GATHER
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (has_half) launch_rectify_radius<true>(radius, grid, block, stream, cur, args, gamma, record, d_out_film, d_out_half, d_out_length);
-    else launch_rectify_radius<false>(radius, grid, block, stream, cur, args, gamma, record, d_out_film, d_out_half, d_out_length);
+hipError_t launch_temporal_gather_motion(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const MotionArgs& motion, void* d_scratch,
+                                         hipStream_t stream) {
+    const TpShape sh = tp_shape(args);
+    tp_dispatch(cur.half != nullptr, motion.ids_prev != nullptr, [&](auto half, auto ids) {
+        hipLaunchKernelGGL((temporal_gather_motion_kernel<decltype(half)::value, true, decltype(ids)::value>), sh.grid, sh.block, 0, stream, cur, prev, args, motion,
+                           (float4*)d_scratch);
+    });
     return hipGetLastError();
 }
 

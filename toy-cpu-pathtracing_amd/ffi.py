@@ -908,11 +908,32 @@ class Product(Backend):
         self.check(self.lib.mi355pt_temporal_view_from_cameras(C.byref(cur), C.byref(prev), C.byref(v)), "temporal_view_from_cameras")
         return v
 
+    @staticmethod
+    def _temporal_frames(cur, prev, host):
+        """The `cur` / `prev` dicts of the temporal_accumulate* methods (prev None: no previous frame) -> (TemporalFrame, TemporalFrame or
+        None, keep).  host False: the values are device pointers; host True: arrays, and keep = [cur's, prev's] dicts of the contiguous
+        float32 arrays the frames point into, which must outlive the call"""
+        frames, keep = [], []
+        for frame in (cur, prev):
+            if frame is None:
+                frames.append(None)
+            elif host:
+                keep.append({k: np.ascontiguousarray(v, dtype=np.float32) for k, v in frame.items() if v is not None})
+                frames.append(TemporalFrame(*[keep[-1][k].ctypes.data if k in keep[-1] else None for k in TEMPORAL_FILMS]))
+            else:
+                frames.append(TemporalFrame(*[C.c_void_p(frame.get(k) or None) for k in TEMPORAL_FILMS]))
+        return frames[0], frames[1], keep
+
+    @staticmethod
+    def _temporal_outputs(kc):
+        """The outputs of a host call on the current frame's arrays `kc` -> (h, w, out_film, out_half or None, out_length)"""
+        h, w = kc["film"].shape[:2]
+        return h, w, np.zeros((h, w, 3), np.float32), np.zeros((h, w, 3), np.float32) if "half" in kc else None, np.zeros((h, w), np.float32)
+
     def temporal_accumulate_device(self, cur, spp, prev, view, width, height, params, d_out_film_ptr, d_out_half_ptr, d_out_length_ptr, stream=None):
         """mi355pt_temporal_accumulate_device: `cur` / `prev` map film names (TEMPORAL_FILMS) to device pointers (a name left out or None is
         NULL); prev and view None = the first frame; d_out_half_ptr None or 0 without a half film"""
-        fc = TemporalFrame(*[C.c_void_p(cur.get(k) or None) for k in TEMPORAL_FILMS])
-        fp = TemporalFrame(*[C.c_void_p(prev.get(k) or None) for k in TEMPORAL_FILMS]) if prev is not None else None
+        fc, fp, _ = self._temporal_frames(cur, prev, host=False)
         self.check(self.lib.mi355pt_temporal_accumulate_device(C.byref(fc), spp, C.byref(fp) if fp is not None else None,
                                                                C.byref(view) if view is not None else None, width, height, C.byref(params),
                                                                C.c_void_p(d_out_film_ptr), C.c_void_p(d_out_half_ptr or 0), C.c_void_p(d_out_length_ptr),
@@ -921,15 +942,9 @@ class Product(Backend):
     def temporal_accumulate(self, cur, spp, prev=None, view=None, params=None):
         """mi355pt_temporal_accumulate on host arrays: `cur` / `prev` map film names to (H, W, 3) float32 arrays ((H, W) for length)
         -> (out_film, out_half or None, out_length)"""
-        def host(frame):
-            keep = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in frame.items() if v is not None}
-            return keep, TemporalFrame(*[keep[k].ctypes.data if k in keep else None for k in TEMPORAL_FILMS])
-        kc, fc = host(cur)
-        kp, fp = host(prev) if prev is not None else (None, None)
-        h, w = kc["film"].shape[:2]
+        fc, fp, keep = self._temporal_frames(cur, prev, host=True)
+        h, w, out_film, out_half, out_len = self._temporal_outputs(keep[0])
         params = params if params is not None else self.temporal_params_default()
-        out_film, out_len = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32)
-        out_half = np.zeros((h, w, 3), np.float32) if "half" in kc else None
         self.check(self.lib.mi355pt_temporal_accumulate(C.byref(fc), spp, C.byref(fp) if fp is not None else None,
                                                         C.byref(view) if view is not None else None, w, h, C.byref(params), out_film.ctypes.data,
                                                         out_half.ctypes.data if out_half is not None else None, out_len.ctypes.data), "temporal_accumulate")
@@ -948,8 +963,7 @@ class Product(Backend):
                                              d_out_half_ptr, d_out_length_ptr, stream=None):
         """mi355pt_temporal_accumulate_rectified_device: the arguments of temporal_accumulate_device, the rectification's parameters and a
         device scratch of temporal_rectify_scratch_bytes(width, height) bytes"""
-        fc = TemporalFrame(*[C.c_void_p(cur.get(k) or None) for k in TEMPORAL_FILMS])
-        fp = TemporalFrame(*[C.c_void_p(prev.get(k) or None) for k in TEMPORAL_FILMS]) if prev is not None else None
+        fc, fp, _ = self._temporal_frames(cur, prev, host=False)
         self.check(self.lib.mi355pt_temporal_accumulate_rectified_device(C.byref(fc), spp, C.byref(fp) if fp is not None else None,
                                                                          C.byref(view) if view is not None else None, width, height, C.byref(params),
                                                                          C.byref(rectify_params), C.c_void_p(d_scratch_ptr), scratch_bytes,
@@ -958,16 +972,10 @@ class Product(Backend):
 
     def temporal_accumulate_rectified(self, cur, spp, prev=None, view=None, params=None, rectify_params=None):
         """mi355pt_temporal_accumulate_rectified on host arrays, as temporal_accumulate -> (out_film, out_half or None, out_length)"""
-        def host(frame):
-            keep = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in frame.items() if v is not None}
-            return keep, TemporalFrame(*[keep[k].ctypes.data if k in keep else None for k in TEMPORAL_FILMS])
-        kc, fc = host(cur)
-        kp, fp = host(prev) if prev is not None else (None, None)
-        h, w = kc["film"].shape[:2]
+        fc, fp, keep = self._temporal_frames(cur, prev, host=True)
+        h, w, out_film, out_half, out_len = self._temporal_outputs(keep[0])
         params = params if params is not None else self.temporal_params_default()
         rectify_params = rectify_params if rectify_params is not None else self.temporal_rectify_params_default()
-        out_film, out_len = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32)
-        out_half = np.zeros((h, w, 3), np.float32) if "half" in kc else None
         self.check(self.lib.mi355pt_temporal_accumulate_rectified(C.byref(fc), spp, C.byref(fp) if fp is not None else None,
                                                                   C.byref(view) if view is not None else None, w, h, C.byref(params), C.byref(rectify_params),
                                                                   out_film.ctypes.data, out_half.ctypes.data if out_half is not None else None,
@@ -999,8 +1007,7 @@ class Product(Backend):
                                           d_out_film_ptr, d_out_half_ptr, d_out_length_ptr, rectify_params=None, d_scratch_ptr=None, scratch_bytes=0, stream=None):
         """mi355pt_temporal_accumulate_motion_device or, with rectify_params (and a scratch), mi355pt_temporal_accumulate_rectified_motion_device:
         the arguments of their twins plus the current ids, the previous ids (None: no id test of the taps) and the table, all device pointers"""
-        fc = TemporalFrame(*[C.c_void_p(cur.get(k) or None) for k in TEMPORAL_FILMS])
-        fp = TemporalFrame(*[C.c_void_p(prev.get(k) or None) for k in TEMPORAL_FILMS]) if prev is not None else None
+        fc, fp, _ = self._temporal_frames(cur, prev, host=False)
         head = (C.byref(fc), spp, C.byref(fp) if fp is not None else None, C.byref(view) if view is not None else None, width, height, C.byref(params))
         tail = (C.c_void_p(d_ids_cur_ptr), C.c_void_p(d_ids_prev_ptr or 0), C.c_void_p(d_table_ptr), n_entries, C.c_void_p(d_out_film_ptr),
                 C.c_void_p(d_out_half_ptr or 0), C.c_void_p(d_out_length_ptr), C.c_void_p(stream or 0))
@@ -1013,18 +1020,12 @@ class Product(Backend):
     def temporal_accumulate_motion(self, cur, spp, prev, view, ids_cur, ids_prev, table, params=None, rectify_params=None):
         """mi355pt_temporal_accumulate_motion (or, with rectify_params, mi355pt_temporal_accumulate_rectified_motion) on host arrays, as
         temporal_accumulate; ids (H, W) uint32, table (n_entries, 24) float32 -> (out_film, out_half or None, out_length)"""
-        def host(frame):
-            keep = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in frame.items() if v is not None}
-            return keep, TemporalFrame(*[keep[k].ctypes.data if k in keep else None for k in TEMPORAL_FILMS])
-        kc, fc = host(cur)
-        kp, fp = host(prev) if prev is not None else (None, None)
-        h, w = kc["film"].shape[:2]
+        fc, fp, keep = self._temporal_frames(cur, prev, host=True)
+        h, w, out_film, out_half, out_len = self._temporal_outputs(keep[0])
         ic = np.ascontiguousarray(ids_cur, dtype=np.uint32)
         ip = np.ascontiguousarray(ids_prev, dtype=np.uint32) if ids_prev is not None else None
         tab = np.ascontiguousarray(table, dtype=np.float32).reshape(-1, 24)
         params = params if params is not None else self.temporal_params_default()
-        out_film, out_len = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32)
-        out_half = np.zeros((h, w, 3), np.float32) if "half" in kc else None
         head = (C.byref(fc), spp, C.byref(fp) if fp is not None else None, C.byref(view) if view is not None else None, w, h, C.byref(params))
         tail = (ic.ctypes.data, ip.ctypes.data if ip is not None else None, tab.ctypes.data, tab.shape[0], out_film.ctypes.data,
                 out_half.ctypes.data if out_half is not None else None, out_len.ctypes.data)
@@ -1085,8 +1086,7 @@ class Product(Backend):
         """mi355pt_temporal_accumulate_flow_device or, with rectify_params (and a scratch), mi355pt_temporal_accumulate_rectified_flow_device:
         the arguments of their twins plus the current ids (None without previous ids), the previous ids (None: no id test of the taps) and
         the flow records, all device pointers"""
-        fc = TemporalFrame(*[C.c_void_p(cur.get(k) or None) for k in TEMPORAL_FILMS])
-        fp = TemporalFrame(*[C.c_void_p(prev.get(k) or None) for k in TEMPORAL_FILMS]) if prev is not None else None
+        fc, fp, _ = self._temporal_frames(cur, prev, host=False)
         head = (C.byref(fc), spp, C.byref(fp) if fp is not None else None, C.byref(view) if view is not None else None, width, height, C.byref(params))
         tail = (C.c_void_p(d_ids_cur_ptr or 0), C.c_void_p(d_ids_prev_ptr or 0), C.c_void_p(d_flow_ptr), C.c_void_p(d_out_film_ptr),
                 C.c_void_p(d_out_half_ptr or 0), C.c_void_p(d_out_length_ptr), C.c_void_p(stream or 0))
@@ -1099,19 +1099,13 @@ class Product(Backend):
     def temporal_accumulate_flow(self, cur, spp, prev, view, ids_cur, ids_prev, flow, params=None, rectify_params=None):
         """mi355pt_temporal_accumulate_flow (or, with rectify_params, mi355pt_temporal_accumulate_rectified_flow) on host arrays, as
         temporal_accumulate; ids (H, W) uint32 or None, flow (H, W) FLOW_PIXEL -> (out_film, out_half or None, out_length)"""
-        def host(frame):
-            keep = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in frame.items() if v is not None}
-            return keep, TemporalFrame(*[keep[k].ctypes.data if k in keep else None for k in TEMPORAL_FILMS])
-        kc, fc = host(cur)
-        kp, fp = host(prev) if prev is not None else (None, None)
-        h, w = kc["film"].shape[:2]
+        fc, fp, keep = self._temporal_frames(cur, prev, host=True)
+        h, w, out_film, out_half, out_len = self._temporal_outputs(keep[0])
         ic = np.ascontiguousarray(ids_cur, dtype=np.uint32) if ids_cur is not None else None
         ip = np.ascontiguousarray(ids_prev, dtype=np.uint32) if ids_prev is not None else None
         fl = np.ascontiguousarray(flow, dtype=FLOW_PIXEL)
         assert fl.shape == (h, w)
         params = params if params is not None else self.temporal_params_default()
-        out_film, out_len = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32)
-        out_half = np.zeros((h, w, 3), np.float32) if "half" in kc else None
         head = (C.byref(fc), spp, C.byref(fp) if fp is not None else None, C.byref(view) if view is not None else None, w, h, C.byref(params))
         tail = (ic.ctypes.data if ic is not None else None, ip.ctypes.data if ip is not None else None, fl.ctypes.data, out_film.ctypes.data,
                 out_half.ctypes.data if out_half is not None else None, out_len.ctypes.data)

@@ -334,6 +334,35 @@ static void follow_camera(Scene& scene, const Camera& moved, const Args& a, uint
     std::fprintf(stderr, "camera move, frame %u: rebuilt=%u host_ms=%.3f device_ms=%.3f\n", frame, r.rebuilt, r.host_ms, r.device_ms);
 }
 
+// One frame of the accumulation on device buffers: the entry point of the carry (ids_cur == nullptr: none; a table of n_entries records, or
+// else flow records) and of --temporal-rectify (rect != nullptr: its parameters, with the scratch).  The name check() gets is the entry
+// point's that ran
+struct TemporalCarryArgs { const uint32_t *ids_cur = nullptr, *ids_prev = nullptr; const mi355pt_motion_xform* table = nullptr; uint32_t n_entries = 0; const mi355pt_flow_pixel* flow = nullptr; };
+static void temporal_accumulate(const mi355pt_temporal_frame& cur, uint32_t spp, const mi355pt_temporal_frame* prev, const mi355pt_temporal_view* view, uint32_t width,
+                                uint32_t height, const mi355pt_temporal_params& tp, const TemporalCarryArgs& carry, const mi355pt_temporal_rectify_params* rect,
+                                void* scratch, size_t scratch_bytes, float* out_film, float* out_half, float* out_length) {
+    const uint32_t *ic = carry.ids_cur, *ip = carry.ids_prev;
+    if (carry.flow && rect)
+        check(mi355pt_temporal_accumulate_rectified_flow_device(&cur, spp, prev, view, width, height, &tp, rect, scratch, scratch_bytes, ic, ip, carry.flow, out_film,
+                                                                out_half, out_length, nullptr), "mi355pt_temporal_accumulate_rectified_flow_device");
+    else if (carry.flow)
+        check(mi355pt_temporal_accumulate_flow_device(&cur, spp, prev, view, width, height, &tp, ic, ip, carry.flow, out_film, out_half, out_length, nullptr),
+              "mi355pt_temporal_accumulate_flow_device");
+    else if (carry.table && rect)
+        check(mi355pt_temporal_accumulate_rectified_motion_device(&cur, spp, prev, view, width, height, &tp, rect, scratch, scratch_bytes, ic, ip, carry.table,
+                                                                  carry.n_entries, out_film, out_half, out_length, nullptr),
+              "mi355pt_temporal_accumulate_rectified_motion_device");
+    else if (carry.table)
+        check(mi355pt_temporal_accumulate_motion_device(&cur, spp, prev, view, width, height, &tp, ic, ip, carry.table, carry.n_entries, out_film, out_half, out_length,
+                                                        nullptr), "mi355pt_temporal_accumulate_motion_device");
+    else if (rect)
+        check(mi355pt_temporal_accumulate_rectified_device(&cur, spp, prev, view, width, height, &tp, rect, scratch, scratch_bytes, out_film, out_half, out_length,
+                                                           nullptr), "mi355pt_temporal_accumulate_rectified_device");
+    else
+        check(mi355pt_temporal_accumulate_device(&cur, spp, prev, view, width, height, &tp, out_film, out_half, out_length, nullptr),
+              "mi355pt_temporal_accumulate_device");
+}
+
 // --temporal-frames N [--camera-step dx,dy,dz]: N frames of --spp samples, frame k with seed + k and the camera at position + k * step (the
 // scene follows as --camera-move says: built again, mi355pt_scene_build bakes the position in, or re-based on the device).  Per frame one G-buffer launch at --denoise-guide-spp
 // (shading normal, position, hit — and albedo when --denoise-variance follows), the beauty film (and the half film with --denoise-variance),
@@ -434,40 +463,21 @@ static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params
         const mi355pt_temporal_frame prev{acc[q], half ? acch[q] : nullptr, len[q], position[q], normal[q], hit[q]};
         mi355pt_temporal_view view{};
         if (k > 0) check(mi355pt_temporal_view_from_cameras(&cam, &cam_prev, &view), "mi355pt_temporal_view_from_cameras");
+        TemporalCarryArgs carry;
         if (flowing) {                // the flow pass against the mark (a first frame: the ids alone), the flow-aware accumulation with the previous ids
-            mi355pt_flow_pixel* d_flow = (mi355pt_flow_pixel*)flow_records.p;
-            if (first) scene.ids_device(cam, g, ids[c]); else scene.flow_device(cam, g, d_flow, ids[c]);
-            if (a.temporal_rectify)
-                check(mi355pt_temporal_accumulate_rectified_flow_device(&cur, p.spp, first ? nullptr : &prev, first ? nullptr : &view, base.width, base.height, &tp, &rp,
-                                                                        rectify_scratch.p, rectify_bytes, ids[c], first ? nullptr : ids[q], d_flow, acc[c],
-                                                                        half ? acch[c] : nullptr, len[c], nullptr),
-                      "mi355pt_temporal_accumulate_rectified_flow_device");
-            else
-                check(mi355pt_temporal_accumulate_flow_device(&cur, p.spp, first ? nullptr : &prev, first ? nullptr : &view, base.width, base.height, &tp, ids[c],
-                                                              first ? nullptr : ids[q], d_flow, acc[c], half ? acch[c] : nullptr, len[c], nullptr),
-                      "mi355pt_temporal_accumulate_flow_device");
-        } else if (stepping) {               // one ID pass, the table of the two frames' matrices and cameras, the motion-aware accumulation with the previous ids
+            carry.flow = (mi355pt_flow_pixel*)flow_records.p;
+            if (first) scene.ids_device(cam, g, ids[c]); else scene.flow_device(cam, g, (mi355pt_flow_pixel*)flow_records.p, ids[c]);
+        } else if (stepping) {        // one ID pass, the table of the two frames' matrices and cameras, the motion-aware accumulation with the previous ids
             scene.ids_device(cam, g, ids[c]);
             const std::vector<mi355pt_motion_xform> host_table = scene.motion_table(cam, cam_prev, l2w_prev);
             if (hipMemcpy(table.p, host_table.data(), host_table.size() * sizeof(mi355pt_motion_xform), hipMemcpyHostToDevice) != hipSuccess)
                 throw std::runtime_error("mi355pt: copying the motion table failed");
-            const mi355pt_motion_xform* d_table = (const mi355pt_motion_xform*)table.p;
-            if (a.temporal_rectify)
-                check(mi355pt_temporal_accumulate_rectified_motion_device(&cur, p.spp, k > 0 ? &prev : nullptr, k > 0 ? &view : nullptr, base.width, base.height, &tp,
-                                                                          &rp, rectify_scratch.p, rectify_bytes, ids[c], k > 0 ? ids[q] : nullptr, d_table, n_inst + 1,
-                                                                          acc[c], half ? acch[c] : nullptr, len[c], nullptr),
-                      "mi355pt_temporal_accumulate_rectified_motion_device");
-            else
-                check(mi355pt_temporal_accumulate_motion_device(&cur, p.spp, k > 0 ? &prev : nullptr, k > 0 ? &view : nullptr, base.width, base.height, &tp, ids[c],
-                                                                k > 0 ? ids[q] : nullptr, d_table, n_inst + 1, acc[c], half ? acch[c] : nullptr, len[c], nullptr),
-                      "mi355pt_temporal_accumulate_motion_device");
-        } else if (a.temporal_rectify)
-            check(mi355pt_temporal_accumulate_rectified_device(&cur, p.spp, k > 0 ? &prev : nullptr, k > 0 ? &view : nullptr, base.width, base.height, &tp, &rp,
-                                                               rectify_scratch.p, rectify_bytes, acc[c], half ? acch[c] : nullptr, len[c], nullptr),
-                  "mi355pt_temporal_accumulate_rectified_device");
-        else
-            check(mi355pt_temporal_accumulate_device(&cur, p.spp, k > 0 ? &prev : nullptr, k > 0 ? &view : nullptr, base.width, base.height, &tp, acc[c],
-                                                     half ? acch[c] : nullptr, len[c], nullptr), "mi355pt_temporal_accumulate_device");
+            carry.table = (const mi355pt_motion_xform*)table.p; carry.n_entries = n_inst + 1;
+        }
+        const bool has_prev = flowing ? !first : k > 0;
+        if (flowing || stepping) { carry.ids_cur = ids[c]; carry.ids_prev = has_prev ? ids[q] : nullptr; }
+        temporal_accumulate(cur, p.spp, has_prev ? &prev : nullptr, has_prev ? &view : nullptr, base.width, base.height, tp, carry, a.temporal_rectify ? &rp : nullptr,
+                            rectify_scratch.p, rectify_bytes, acc[c], half ? acch[c] : nullptr, len[c]);
         display_stage.meter(acc[c], base.width, base.height, half ? 2u : 1u);      // --auto-exposure: every frame, with the previous frame's record
     }
     const int last = (int)((a.temporal_frames - 1) & 1u);
@@ -564,13 +574,8 @@ static double render_half_res(Scene& scene, const Camera& camera, mi355pt_params
         const mi355pt_temporal_frame prev{acc[q], half ? acch[q] : nullptr, len[q], position[q], normal[q], hit[q]};
         mi355pt_temporal_view view{};
         if (k > 0) check(mi355pt_temporal_view_from_cameras(&cam, &cam_prev, &view), "mi355pt_temporal_view_from_cameras");
-        if (a.temporal_rectify)
-            check(mi355pt_temporal_accumulate_rectified_device(&cur, up_spp, k > 0 ? &prev : nullptr, k > 0 ? &view : nullptr, base.width, base.height, &tp, &rp,
-                                                               rectify_scratch.p, rectify_bytes, acc[c], half ? acch[c] : nullptr, len[c], nullptr),
-                  "mi355pt_temporal_accumulate_rectified_device");
-        else
-            check(mi355pt_temporal_accumulate_device(&cur, up_spp, k > 0 ? &prev : nullptr, k > 0 ? &view : nullptr, base.width, base.height, &tp, acc[c],
-                                                     half ? acch[c] : nullptr, len[c], nullptr), "mi355pt_temporal_accumulate_device");
+        temporal_accumulate(cur, up_spp, k > 0 ? &prev : nullptr, k > 0 ? &view : nullptr, base.width, base.height, tp, TemporalCarryArgs{},
+                            a.temporal_rectify ? &rp : nullptr, rectify_scratch.p, rectify_bytes, acc[c], half ? acch[c] : nullptr, len[c]);
         display_stage.meter(acc[c], base.width, base.height, up_spp);      // --auto-exposure: every frame, with the previous frame's record
     }
     const float* film = a.temporal ? acc[c] : up.p;           // the pair that leaves the loop: spp 2 with a half film; a mean without (the accumulation's, the upsample's)
