@@ -398,6 +398,15 @@ const char* mi355pt_version(void);
  * own header, which this one always includes (ahead of the variance-guided denoiser's, which stays the last one). */
 #include "mi355pt_flow.h"
 
+/* ---------------- sample budget by reprojected history ---------------- */
+/* EXTENSION, no reference counterpart: mi355pt_budget_params, mi355pt_budget_motion, mi355pt_temporal_budget_device and
+ * mi355pt_temporal_budget (the history probe: the geometric half of the temporal gather on the G-buffers alone, per pixel the history
+ * length the accumulation will find and per 8 x 8 tile a sample count), mi355pt_render_budget_device (renders those per-tile counts over
+ * the tile-list renders), mi355pt_film_pair_normalize_tiles_device and mi355pt_film_pair_normalize_tiles (the per-tile-count pair as a film
+ * pair with spp = 2 for the accumulation calls, which stay as they are) and mi355pt_temporal_length_credit_device.  Declared in its own
+ * header, which this one always includes (ahead of the variance-guided denoiser's, which stays the last one). */
+#include "mi355pt_budget.h"
+
 /* ---------------- variance-guided denoiser ---------------- */
 /* EXTENSION, no reference counterpart: a second filter beside the one above, which it leaves as it is — mi355pt_denoise_var_params,
  * mi355pt_denoise_var_params_default, mi355pt_denoise_var_scratch_bytes, mi355pt_denoise_var_device and mi355pt_denoise_var: an a-trous

@@ -60,6 +60,9 @@ hipError_t launch_adaptive_step(const float* d_film, float* d_half, uint32_t wid
                                 float threshold, float dark_eps, uint32_t level_spp, uint32_t max_spp, void* d_scratch, uint32_t* d_list,
                                 uint32_t* d_count, hipStream_t);
 hipError_t launch_normalize_tiles(const float* d_film, const uint32_t* d_tile_spp, uint32_t width, uint32_t height, float* d_mean, hipStream_t);
+// ... and the step's second launch alone: the ascending list of the tiles whose flag is not 0 and their number (pt_kernels_budget.hip's
+// select pass is followed by it)
+hipError_t launch_adaptive_compact(const uint32_t* d_flags, uint32_t n_tiles, uint32_t* d_list, uint32_t* d_count, hipStream_t);
 // pt_kernels_denoise_var.hip: the variance-guided a-trous denoiser (include/mi355pt_denoise_var.h); its level launches take the grid of
 // denoise_grid_blocks.  d_tile_spp == nullptr: every pixel has spp_b samples
 size_t denoise_var_scratch_bytes(uint32_t width, uint32_t height);
@@ -105,6 +108,23 @@ hipError_t launch_temporal_gather_flow(const TemporalFrameDev& cur, const Tempor
                                        hipStream_t);
 hipError_t launch_temporal_rectify_blend(const TemporalFrameDev& cur, TemporalArgs args, uint32_t radius, float gamma, const void* d_scratch, float* d_out_film,
                                          float* d_out_half, float* d_out_length, hipStream_t);
+// pt_kernels_budget.hip: the sample budget by reprojected history (include/mi355pt_budget.h).  How the probe carries a pixel: table != nullptr
+// the per-instance table (last_entry = n_entries - 1), flow != nullptr the per-pixel records, neither the static world (args.delta);
+// ids_prev == nullptr: no id test of the taps.  The probe's per-tile part: the launcher fills tiles_x and n_tiles
+struct BudgetCarryDev { const uint32_t* ids_cur; const uint32_t* ids_prev; const MotionXformDev* table; uint32_t last_entry; const FlowPixelDev* flow; };
+struct BudgetTilesDev { uint32_t tiles_x, n_tiles, base_spp, max_spp; float target_history; };
+// ONE launch: per pixel the history length the accumulation will gather (d_pred, nullptr: not wanted), per tile its minimum and the
+// count budget_plan.hpp's formula gives.  prev == nullptr: the first frame, no G-buffer is read.  args.spp and args.half_spp are not read
+hipError_t launch_budget_probe(const TemporalFrameDev& cur, const TemporalFrameDev* prev, TemporalArgs args, const BudgetCarryDev& carry, BudgetTilesDev tiles,
+                               float* d_pred, float* d_tile_len, uint32_t* d_tile_spp, hipStream_t);
+// TWO launches: the flags "clamped tile_spp > level_spp" into d_scratch (one u32 per tile) with H := F on the flagged tiles, then
+// launch_adaptive_compact into d_list and d_count
+hipError_t launch_budget_select(const float* d_film, float* d_half, uint32_t width, uint32_t height, const uint32_t* d_tile_spp, uint32_t level_spp,
+                                uint32_t base_spp, uint32_t max_spp, void* d_scratch, uint32_t* d_list, uint32_t* d_count, hipStream_t);
+// both films / (float)(tile_spp / 2) of the pixel's tile (in place allowed); length += tile_spp / base_spp - 1, capped, where tile_spp > base_spp
+hipError_t launch_pair_normalize_tiles(const float* d_film, const float* d_half, const uint32_t* d_tile_spp, uint32_t width, uint32_t height, float* d_out_film,
+                                       float* d_out_half, hipStream_t);
+hipError_t launch_length_credit(float* d_length, const uint32_t* d_tile_spp, uint32_t base_spp, float max_history, uint32_t width, uint32_t height, hipStream_t);
 // pt_kernels_ids.hip: the ID pass (include/mi355pt_motion.h): one primary ray through every pixel centre, instance + 1 of the closest hit or
 // 0 into d_ids.  The plan must have block_log2 == 3 and chunks == 1 (api_motion.cpp, the G-buffer pass's plan): one pixel per lane
 hipError_t launch_ids(const DevScene&, const DevCamera&, const DevParams&, uint32_t* d_ids, unsigned* d_counter, DevStats* d_stats, int grid, hipStream_t);

@@ -109,6 +109,11 @@ hipError_t launch_adaptive_step(const float* d_film, float* d_half, uint32_t wid
     return hipGetLastError();
 }
 
+hipError_t launch_adaptive_compact(const uint32_t* d_flags, uint32_t n_tiles, uint32_t* d_list, uint32_t* d_count, hipStream_t stream) {
+    hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(AD_COMPACT_BLOCK), 0, stream, d_flags, n_tiles, d_list, d_count);
+    return hipGetLastError();
+}
+
 hipError_t launch_normalize_tiles(const float* d_film, const uint32_t* d_tile_spp, uint32_t width, uint32_t height, float* d_mean, hipStream_t stream) {
     if (adaptive_tile_count(width, height) == 0u) return hipErrorInvalidValue;
     const size_t n_pix = (size_t)width * height;

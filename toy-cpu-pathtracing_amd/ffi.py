@@ -167,6 +167,16 @@ class MotionXform(C.Structure):
     _fields_ = [("a", C.c_float * 9), ("b", C.c_float * 3), ("n", C.c_float * 9), ("pad", C.c_float * 3)]
 
 
+class BudgetParams(C.Structure):
+    """mi355pt_budget_params (include/mi355pt_budget.h): a zeroed struct is refused"""
+    _fields_ = [("base_spp", C.c_uint32), ("max_spp", C.c_uint32), ("target_history", C.c_float)]
+
+
+class BudgetMotion(C.Structure):
+    """mi355pt_budget_motion: device or host pointers; all zero = the static world"""
+    _fields_ = [("ids_cur", C.c_void_p), ("ids_prev", C.c_void_p), ("table", C.c_void_p), ("n_entries", C.c_uint32), ("flow", C.c_void_p)]
+
+
 class UpsampleParams(C.Structure):
     """mi355pt_upsample_params (include/mi355pt_upsample.h); Product.upsample_params_default() fills it — a zeroed one is refused"""
     _fields_ = [("pos_tol", C.c_float), ("normal_cos", C.c_float), ("emitter_tol", C.c_float), ("min_weight", C.c_float), ("albedo_eps", C.c_float)]
@@ -298,6 +308,9 @@ FLOW_DEBUG_SYMBOLS = ["render_flow_debug", "scene_export_flow_mark", "scene_expo
 # mi355pt_flow_pixel as a NumPy record: 32 bytes
 FLOW_PIXEL = np.dtype([("d", np.float32, 3), ("id", np.uint32), ("dn", np.float32, 3), ("pad", np.uint32)])
 FLOW_HIT = np.dtype([("tri", np.uint32), ("b", np.float32, 3)])           # mi355pt_render_flow_debug's hit record: 16 bytes
+# ... and include/mi355pt_budget.h, the sample-budget block (tests/test_budget.py)
+BUDGET_SYMBOLS = ["temporal_budget_device", "temporal_budget", "render_budget_device", "film_pair_normalize_tiles_device", "film_pair_normalize_tiles",
+                  "temporal_length_credit_device"]
 ADAPTIVE_SYMBOLS = ["adaptive_scratch_bytes", "adaptive_step_device", "film_normalize_tiles_device", "render_adaptive_device", "render_adaptive"]
 
 
@@ -763,6 +776,16 @@ class Product(Backend):
             lib.mi355pt_temporal_accumulate_rectified_flow_device.argtypes = frame4 + [C.POINTER(TemporalRectifyParams), C.c_void_p, C.c_size_t] + flow3 + \
                 [C.c_void_p] * 4
             lib.mi355pt_temporal_accumulate_rectified_flow.argtypes = frame4 + [C.POINTER(TemporalRectifyParams)] + flow3 + [C.c_void_p] * 3
+        if hasattr(lib, "mi355pt_temporal_budget_device"):  # (absent from an older build loaded through MI355PT_LIB)
+            probe8 = [C.POINTER(TemporalFrame), C.POINTER(TemporalFrame), C.POINTER(TemporalView), C.c_uint32, C.c_uint32, C.POINTER(TemporalParams),
+                      C.POINTER(BudgetMotion), C.POINTER(BudgetParams)]
+            lib.mi355pt_temporal_budget_device.argtypes = probe8 + [C.c_void_p] * 4
+            lib.mi355pt_temporal_budget.argtypes = probe8 + [C.c_void_p] * 3
+            lib.mi355pt_render_budget_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(BudgetParams)] + [C.c_void_p] * 5 + \
+                [C.c_size_t, C.c_void_p, C.POINTER(AdaptiveResult)]
+            lib.mi355pt_film_pair_normalize_tiles_device.argtypes = [C.c_void_p] * 3 + [C.c_uint32, C.c_uint32] + [C.c_void_p] * 3
+            lib.mi355pt_film_pair_normalize_tiles.argtypes = [C.c_void_p] * 3 + [C.c_uint32, C.c_uint32] + [C.c_void_p] * 2
+            lib.mi355pt_temporal_length_credit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p]
         if not hasattr(lib, "mi355pt_render_sample_log"):     # an older build loaded through MI355PT_LIB for an A/B timing run
             return
         lib.mi355pt_sample_log_records.argtypes = [C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]
@@ -1114,6 +1137,72 @@ class Product(Backend):
         else:
             self.check(self.lib.mi355pt_temporal_accumulate_rectified_flow(*head, C.byref(rectify_params), *tail), "temporal_accumulate_rectified_flow")
         return out_film, out_half, out_len
+
+    # ---- the sample budget by reprojected history (include/mi355pt_budget.h): probe, driver, pair normalise, length credit ----
+    @staticmethod
+    def budget_params(base_spp, max_spp, target_history):
+        return BudgetParams(base_spp, max_spp, target_history)
+
+    @staticmethod
+    def budget_motion(ids_cur=None, ids_prev=None, table=None, n_entries=0, flow=None):
+        """mi355pt_budget_motion from pointers (ints; None = NULL)"""
+        return BudgetMotion(ids_cur or None, ids_prev or None, table or None, n_entries, flow or None)
+
+    def temporal_budget_device(self, cur, prev, view, width, height, params, motion, budget, d_pred_ptr, d_tile_len_ptr, d_tile_spp_ptr, stream=None):
+        """mi355pt_temporal_budget_device: `cur` / `prev` as temporal_accumulate_device takes them (film and half are not read); motion a
+        BudgetMotion of device pointers or None; d_pred_ptr None or 0: P is not wanted"""
+        fc, fp, _ = self._temporal_frames(cur, prev, host=False)
+        self.check(self.lib.mi355pt_temporal_budget_device(C.byref(fc), C.byref(fp) if fp is not None else None, C.byref(view) if view is not None else None,
+                                                           width, height, C.byref(params), C.byref(motion) if motion is not None else None, C.byref(budget),
+                                                           C.c_void_p(d_pred_ptr or 0), C.c_void_p(d_tile_len_ptr), C.c_void_p(d_tile_spp_ptr),
+                                                           C.c_void_p(stream or 0)), "temporal_budget_device")
+
+    def temporal_budget(self, cur, prev, view, budget, params=None, ids_cur=None, ids_prev=None, table=None, flow=None):
+        """mi355pt_temporal_budget on host arrays: `cur` / `prev` map film names to arrays (position, shading_normal, hit; length of prev);
+        ids (H, W) uint32 or None, table (n_entries, 24) float32 or None, flow (H, W) FLOW_PIXEL or None
+        -> (P (H, W) float32, tile_len (tiles_y, tiles_x) float32, tile_spp (tiles_y, tiles_x) uint32)"""
+        fc, fp, keep = self._temporal_frames(cur, prev, host=True)
+        h, w = keep[0]["hit"].shape[:2]
+        ty, tx = (h + 7) // 8, (w + 7) // 8
+        pred, tile_len, tile_spp = np.zeros((h, w), np.float32), np.zeros((ty, tx), np.float32), np.zeros((ty, tx), np.uint32)
+        params = params if params is not None else self.temporal_params_default()
+        ic = np.ascontiguousarray(ids_cur, dtype=np.uint32) if ids_cur is not None else None
+        ip = np.ascontiguousarray(ids_prev, dtype=np.uint32) if ids_prev is not None else None
+        tab = np.ascontiguousarray(table, dtype=np.float32).reshape(-1, 24) if table is not None else None
+        fl = np.ascontiguousarray(flow, dtype=FLOW_PIXEL) if flow is not None else None
+        data = lambda a: a.ctypes.data if a is not None else None   # noqa: E731
+        motion = BudgetMotion(data(ic), data(ip), data(tab), tab.shape[0] if tab is not None else 0, data(fl))
+        self.check(self.lib.mi355pt_temporal_budget(C.byref(fc), C.byref(fp) if fp is not None else None, C.byref(view) if view is not None else None, w, h,
+                                                    C.byref(params), C.byref(motion), C.byref(budget), pred.ctypes.data, tile_len.ctypes.data,
+                                                    tile_spp.ctypes.data), "temporal_budget")
+        return pred, tile_len, tile_spp
+
+    def render_budget_device(self, scene, cam, params, budget, d_tile_spp_ptr, d_film_ptr, d_half_ptr, d_list_ptr, d_scratch_ptr, scratch_bytes, stream=None):
+        """mi355pt_render_budget_device -> AdaptiveResult (passes, tiles_at_max, total_samples)"""
+        res = AdaptiveResult()
+        self.check(self.lib.mi355pt_render_budget_device(scene.h, C.byref(cam), C.byref(params), C.byref(budget), C.c_void_p(d_tile_spp_ptr),
+                                                         C.c_void_p(d_film_ptr), C.c_void_p(d_half_ptr), C.c_void_p(d_list_ptr), C.c_void_p(d_scratch_ptr),
+                                                         scratch_bytes, C.c_void_p(stream or 0), C.byref(res)), "render_budget_device")
+        return res
+
+    def film_pair_normalize_tiles_device(self, d_film_ptr, d_half_ptr, d_tile_spp_ptr, width, height, d_out_film_ptr, d_out_half_ptr, stream=None):
+        self.check(self.lib.mi355pt_film_pair_normalize_tiles_device(C.c_void_p(d_film_ptr), C.c_void_p(d_half_ptr), C.c_void_p(d_tile_spp_ptr), width, height,
+                                                                     C.c_void_p(d_out_film_ptr), C.c_void_p(d_out_half_ptr), C.c_void_p(stream or 0)),
+                   "film_pair_normalize_tiles_device")
+
+    def film_pair_normalize_tiles(self, film, half, tile_spp):
+        """mi355pt_film_pair_normalize_tiles on host arrays -> (out_film, out_half): a film pair with spp = 2"""
+        f, hf = np.ascontiguousarray(film, dtype=np.float32), np.ascontiguousarray(half, dtype=np.float32)
+        ts = np.ascontiguousarray(tile_spp, dtype=np.uint32)
+        h, w = f.shape[:2]
+        out_film, out_half = np.zeros_like(f), np.zeros_like(hf)
+        self.check(self.lib.mi355pt_film_pair_normalize_tiles(f.ctypes.data, hf.ctypes.data, ts.ctypes.data, w, h, out_film.ctypes.data, out_half.ctypes.data),
+                   "film_pair_normalize_tiles")
+        return out_film, out_half
+
+    def temporal_length_credit_device(self, d_length_ptr, d_tile_spp_ptr, base_spp, max_history, width, height, stream=None):
+        self.check(self.lib.mi355pt_temporal_length_credit_device(C.c_void_p(d_length_ptr), C.c_void_p(d_tile_spp_ptr), base_spp, max_history, width, height,
+                                                                  C.c_void_p(stream or 0)), "temporal_length_credit_device")
 
     # ---- guided half-resolution rendering (include/mi355pt_upsample.h): a film traced at W/2 x H/2 rebuilt at W x H through both G-buffers ----
     def upsample_params_default(self):

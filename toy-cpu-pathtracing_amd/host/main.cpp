@@ -64,6 +64,9 @@ struct Args {   // main.rs:20-53
     // --instance-step, --mesh-wave, any mix) in place, and accumulates through the flow pass's records; frame k of --mesh-wave then deforms the
     // ORIGINAL vertices with phase k * phase_step
     bool flow = false;
+    // nor a sample budget by reprojected history (mi355pt_budget.h): --temporal-budget TARGET with --temporal-frames — every frame probes where its
+    // history will be missing, renders --spp samples everywhere and up to --temporal-budget-max-spp (8 x --spp) on the tiles that start over
+    bool temporal_budget = false, temporal_budget_max_given = false; float temporal_budget_target = 0.0f; uint32_t temporal_budget_max_spp = 0;
 };
 
 // the positions of a mesh under a wave along x that displaces y (local space), in double and rounded to float
@@ -372,16 +375,25 @@ static void temporal_accumulate(const mi355pt_temporal_frame& cur, uint32_t spp,
 // With --instance-step (mi355pt_motion.h) the named instances take their step once more before every frame but the first
 // (mi355pt_scene_move_instances), and each frame adds one ID pass, the motion table of the two frames' matrices and cameras, and the
 // motion-aware twin of the accumulation with the previous frame's ids.
+// With --temporal-budget (mi355pt_budget.h) the order per frame is: G-buffer, ids / flow records, the history probe, the budget driver (--spp
+// is its base count, the sample sequence that of the maximum), the pair normalise, the accumulation the other flags select with spp = 2 (always
+// with the half film: the driver renders the pair), the length credit; the seconds returned are then wall time around the driver.
 static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params p, const Args& a, std::vector<float>& pixels) {
     const mi355pt_camera base = camera.raw();
     const uint32_t n_pixels = base.width * base.height, guide_spp = a.denoise_guide_spp;
     const size_t film_bytes = (size_t)n_pixels * 3 * sizeof(float), len_bytes = (size_t)n_pixels * sizeof(float);
     const bool half = a.denoise_variance, moving = a.camera_step[0] != 0.0f || a.camera_step[1] != 0.0f || a.camera_step[2] != 0.0f;
-    const size_t opt = half ? film_bytes : sizeof(float);
+    const bool budgeting = a.temporal_budget, pair = half || budgeting;      // the accumulation runs on a film pair
+    const size_t opt = half ? film_bytes : sizeof(float), popt = pair ? film_bytes : sizeof(float);
+    const mi355pt_budget_params bp{p.spp, a.temporal_budget_max_given ? a.temporal_budget_max_spp : 8u * p.spp, a.temporal_budget_target};
+    const size_t n_tiles = (size_t)((base.width + 7u) / 8u) * ((base.height + 7u) / 8u);
+    const size_t budget_scratch_bytes = budgeting ? mi355pt_adaptive_scratch_bytes(base.width, base.height) : sizeof(float);
+    DeviceFilm tile_len(budgeting ? n_tiles * sizeof(float) : sizeof(float)), tile_spp(budgeting ? n_tiles * sizeof(uint32_t) : sizeof(float));
+    DeviceFilm tile_list(budgeting ? n_tiles * sizeof(uint32_t) : sizeof(float)), budget_scratch(budget_scratch_bytes);
     // two sets that alternate: the frame's G-buffer films and its accumulated pair with the length film
     DeviceFilm normal0(film_bytes), normal1(film_bytes), position0(film_bytes), position1(film_bytes), hit0(film_bytes), hit1(film_bytes);
-    DeviceFilm acc0(film_bytes), acc1(film_bytes), acch0(opt), acch1(opt), len0(len_bytes), len1(len_bytes);
-    DeviceFilm beauty(film_bytes), bhalf(opt), albedo(opt), rgb(film_bytes);
+    DeviceFilm acc0(film_bytes), acc1(film_bytes), acch0(popt), acch1(popt), len0(len_bytes), len1(len_bytes);
+    DeviceFilm beauty(film_bytes), bhalf(popt), albedo(opt), rgb(film_bytes);
     float *normal[2] = {normal0.p, normal1.p}, *position[2] = {position0.p, position1.p}, *hit[2] = {hit0.p, hit1.p};
     float *acc[2] = {acc0.p, acc1.p}, *acch[2] = {acch0.p, acch1.p}, *len[2] = {len0.p, len1.p};
     mi355pt_temporal_params tp;
@@ -445,24 +457,17 @@ static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params
         bool ok = hipMemset(normal[c], 0, film_bytes) == hipSuccess && hipMemset(position[c], 0, film_bytes) == hipSuccess && hipMemset(hit[c], 0, film_bytes) == hipSuccess &&
                   hipMemset(beauty.p, 0, film_bytes) == hipSuccess;
         if (half) ok = ok && hipMemset(bhalf.p, 0, film_bytes) == hipSuccess && hipMemset(albedo.p, 0, film_bytes) == hipSuccess;
+        if (budgeting && !half) ok = ok && hipMemset(bhalf.p, 0, film_bytes) == hipSuccess;
         if (!ok) throw std::runtime_error("mi355pt: clearing the frame's films failed");
         mi355pt_params g = p;
         g.spp = guide_spp;
         const mi355pt_gbuffer_films films{half ? albedo.p : nullptr, normal[c], position[c], hit[c]};
         check(mi355pt_render_gbuffer_accum_device(scene.raw(), &cam, &g, scene.d65_lut(), 0, guide_spp, &films, nullptr, nullptr), "mi355pt_render_gbuffer_accum_device");
-        mi355pt_stats st0{}, st1{};
-        if (half) {
-            check(mi355pt_render_accum_device(scene.raw(), &cam, &p, 0, p.spp / 2, bhalf.p, nullptr, &st0), "mi355pt_render_accum_device");
-            if (hipMemcpy(beauty.p, bhalf.p, film_bytes, hipMemcpyDeviceToDevice) != hipSuccess) throw std::runtime_error("mi355pt: copying the half film failed");
-            check(mi355pt_render_accum_device(scene.raw(), &cam, &p, p.spp / 2, p.spp, beauty.p, nullptr, &st1), "mi355pt_render_accum_device");
-        } else {
-            check(mi355pt_render_accum_device(scene.raw(), &cam, &p, 0, p.spp, beauty.p, nullptr, &st0), "mi355pt_render_accum_device");
-        }
-        kernel_ms += st0.kernel_ms + st1.kernel_ms;
-        const mi355pt_temporal_frame cur{beauty.p, half ? bhalf.p : nullptr, nullptr, position[c], normal[c], hit[c]};
-        const mi355pt_temporal_frame prev{acc[q], half ? acch[q] : nullptr, len[q], position[q], normal[q], hit[q]};
+        const mi355pt_temporal_frame cur{beauty.p, pair ? bhalf.p : nullptr, nullptr, position[c], normal[c], hit[c]};
+        const mi355pt_temporal_frame prev{acc[q], pair ? acch[q] : nullptr, len[q], position[q], normal[q], hit[q]};
         mi355pt_temporal_view view{};
         if (k > 0) check(mi355pt_temporal_view_from_cameras(&cam, &cam_prev, &view), "mi355pt_temporal_view_from_cameras");
+        // how the frame's pixels are carried one frame back (no launch of it depends on the beauty film, which follows)
         TemporalCarryArgs carry;
         if (flowing) {                // the flow pass against the mark (a first frame: the ids alone), the flow-aware accumulation with the previous ids
             carry.flow = (mi355pt_flow_pixel*)flow_records.p;
@@ -476,9 +481,42 @@ static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params
         }
         const bool has_prev = flowing ? !first : k > 0;
         if (flowing || stepping) { carry.ids_cur = ids[c]; carry.ids_prev = has_prev ? ids[q] : nullptr; }
-        temporal_accumulate(cur, p.spp, has_prev ? &prev : nullptr, has_prev ? &view : nullptr, base.width, base.height, tp, carry, a.temporal_rectify ? &rp : nullptr,
-                            rectify_scratch.p, rectify_bytes, acc[c], half ? acch[c] : nullptr, len[c]);
-        display_stage.meter(acc[c], base.width, base.height, half ? 2u : 1u);      // --auto-exposure: every frame, with the previous frame's record
+        uint32_t frame_spp = p.spp;
+        if (budgeting) {              // probe, driver, pair normalise: the frame becomes a film pair with spp = 2
+            const mi355pt_budget_motion motion{carry.ids_cur, carry.ids_prev, carry.table, carry.n_entries, carry.flow};
+            check(mi355pt_temporal_budget_device(&cur, has_prev ? &prev : nullptr, has_prev ? &view : nullptr, base.width, base.height, &tp, &motion, &bp, nullptr,
+                                                 tile_len.p, (uint32_t*)tile_spp.p, nullptr), "mi355pt_temporal_budget_device");
+            mi355pt_params pb = p;
+            pb.spp = bp.max_spp;
+            mi355pt_adaptive_result res{};
+            if (hipDeviceSynchronize() != hipSuccess) throw std::runtime_error("mi355pt: waiting for the history probe failed");
+            const auto t0 = std::chrono::steady_clock::now();
+            check(mi355pt_render_budget_device(scene.raw(), &cam, &pb, &bp, (const uint32_t*)tile_spp.p, beauty.p, bhalf.p, (uint32_t*)tile_list.p, budget_scratch.p,
+                                               budget_scratch_bytes, nullptr, &res), "mi355pt_render_budget_device");
+            if (hipDeviceSynchronize() != hipSuccess) throw std::runtime_error("mi355pt: waiting for the budget driver failed");
+            kernel_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            std::fprintf(stderr, "temporal budget, frame %u: passes=%u tiles_at_max=%u total_samples=%llu (uniform %u spp: %llu)\n", k, res.passes, res.tiles_at_max,
+                         (unsigned long long)res.total_samples, p.spp, (unsigned long long)p.spp * n_pixels);
+            check(mi355pt_film_pair_normalize_tiles_device(beauty.p, bhalf.p, (const uint32_t*)tile_spp.p, base.width, base.height, beauty.p, bhalf.p, nullptr),
+                  "mi355pt_film_pair_normalize_tiles_device");
+            frame_spp = 2;
+        } else {
+            mi355pt_stats st0{}, st1{};
+            if (half) {
+                check(mi355pt_render_accum_device(scene.raw(), &cam, &p, 0, p.spp / 2, bhalf.p, nullptr, &st0), "mi355pt_render_accum_device");
+                if (hipMemcpy(beauty.p, bhalf.p, film_bytes, hipMemcpyDeviceToDevice) != hipSuccess) throw std::runtime_error("mi355pt: copying the half film failed");
+                check(mi355pt_render_accum_device(scene.raw(), &cam, &p, p.spp / 2, p.spp, beauty.p, nullptr, &st1), "mi355pt_render_accum_device");
+            } else {
+                check(mi355pt_render_accum_device(scene.raw(), &cam, &p, 0, p.spp, beauty.p, nullptr, &st0), "mi355pt_render_accum_device");
+            }
+            kernel_ms += st0.kernel_ms + st1.kernel_ms;
+        }
+        temporal_accumulate(cur, frame_spp, has_prev ? &prev : nullptr, has_prev ? &view : nullptr, base.width, base.height, tp, carry, a.temporal_rectify ? &rp : nullptr,
+                            rectify_scratch.p, rectify_bytes, acc[c], pair ? acch[c] : nullptr, len[c]);
+        if (budgeting)
+            check(mi355pt_temporal_length_credit_device(len[c], (const uint32_t*)tile_spp.p, bp.base_spp, tp.max_history, base.width, base.height, nullptr),
+                  "mi355pt_temporal_length_credit_device");
+        display_stage.meter(acc[c], base.width, base.height, pair ? 2u : 1u);      // --auto-exposure: every frame, with the previous frame's record
     }
     const int last = (int)((a.temporal_frames - 1) & 1u);
     if (half) {
@@ -490,7 +528,7 @@ static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params
         display_stage.resolve(out.p, base.width, base.height, 1, rgb.p);
         if (hipMemcpy(pixels.data(), rgb.p, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the frame back failed");
     } else {
-        display_stage.resolve(acc[last], base.width, base.height, 1, rgb.p);
+        display_stage.resolve(acc[last], base.width, base.height, pair ? 2u : 1u, rgb.p);      // (--temporal-budget alone: a pair, spp 2)
         if (hipMemcpy(pixels.data(), rgb.p, film_bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("mi355pt: copying the frame back failed");
     }
     return kernel_ms * 1e-3;
@@ -639,6 +677,9 @@ static void usage() {
               "                                         and each frame adds an ID pass, a motion table and the motion-aware accumulation.  Not with --half-res)\n"
               "                   [--instance-rebuild-above X] (0 = never; with --instance-transform: build again when the refit tree's SAH cost exceeds X\n"
               "                                         times the built tree's; applies to --mesh-wave too)\n"
+              "                   [--temporal-budget TARGET] (with --temporal-frames: every frame probes the history length its pixels will find, renders --spp\n"
+              "                                         samples everywhere and doubles them, up to --temporal-budget-max-spp, on the 8 x 8 tiles that would not reach\n"
+              "                                         TARGET frames' worth; --spp a power of two; not with --half-res)  [--temporal-budget-max-spp M] (8 x --spp)\n"
               "                   [--flow] (with --temporal-frames: per-pixel motion vectors — every frame marks the scene, takes --camera-step, --instance-step and\n"
               "                                         --mesh-wave in place (frame k's wave: the original vertices at phase k * phase_step) and accumulates through\n"
               "                                         the flow pass; a move that rebuilds restarts the accumulation; the camera follows as with --camera-move rebase unless\n"
@@ -682,6 +723,8 @@ int main(int argc, char** argv) {
         else if (k == "--temporal-rectify-gamma") { a.temporal_rectify_gamma_given = true; a.temporal_rectify_gamma = std::stof(val()); }
         else if (k == "--half-res") a.half_res = true;
         else if (k == "--flow") a.flow = true;
+        else if (k == "--temporal-budget") { a.temporal_budget = true; a.temporal_budget_target = std::stof(val()); }
+        else if (k == "--temporal-budget-max-spp") { a.temporal_budget_max_given = true; a.temporal_budget_max_spp = (uint32_t)std::stoul(val()); }
         else if (k == "--half-res-albedo") a.half_res_albedo = true;
         else if (k == "--tone-map") a.tone_map = val();
         else if (k == "--white") { a.white_given = true; a.white = std::stof(val()); }
@@ -826,6 +869,15 @@ int main(int argc, char** argv) {
         if (a.robust_scale_given) robust_params.gini_scale = a.robust_scale;
     }
     if (a.flow && !a.temporal) { std::fprintf(stderr, "error: --flow needs --temporal-frames: it carries the accumulation across the frames' moves\n"); return 2; }
+    if ((a.temporal_budget || a.temporal_budget_max_given) && !a.temporal) { std::fprintf(stderr, "error: --temporal-budget and --temporal-budget-max-spp need --temporal-frames: they budget its frames' samples\n"); return 2; }
+    if (a.temporal_budget_max_given && !a.temporal_budget) { std::fprintf(stderr, "error: --temporal-budget-max-spp needs --temporal-budget\n"); return 2; }
+    if (a.temporal_budget && a.half_res) { std::fprintf(stderr, "error: --temporal-budget with --half-res: the budget's tiles would be the low frame's\n"); return 2; }
+    if (a.temporal_budget) {
+        const auto pow2 = [](uint32_t v) { return v != 0 && (v & (v - 1)) == 0; };
+        if (!(std::isfinite(a.temporal_budget_target) && a.temporal_budget_target >= 1.0f)) { std::fprintf(stderr, "error: --temporal-budget must be finite and at least 1 (the history length a tile should reach)\n"); return 2; }
+        if (a.spp < 2 || !pow2(a.spp) || a.spp > (1u << 28)) { std::fprintf(stderr, "error: --temporal-budget needs a --spp that is a power of two, at least 2: it is the budget's base count\n"); return 2; }
+        if (a.temporal_budget_max_given && (!pow2(a.temporal_budget_max_spp) || a.temporal_budget_max_spp < a.spp)) { std::fprintf(stderr, "error: --temporal-budget-max-spp must be a power of two, at least --spp\n"); return 2; }
+    }
     if (a.flow && a.half_res) { std::fprintf(stderr, "error: --flow with --half-res: the flow-aware accumulation runs at full size only\n"); return 2; }
     if (a.half_res_albedo && !a.half_res) { std::fprintf(stderr, "error: --half-res-albedo needs --half-res: it demodulates the film that --half-res upsamples\n"); return 2; }
     if (a.half_res && aov) { std::fprintf(stderr, "error: --half-res with --renderer %s: half-resolution rendering is for the path renderers (pt, nee, mis)\n", a.renderer.c_str()); return 2; }
