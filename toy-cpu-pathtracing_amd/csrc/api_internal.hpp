@@ -1,10 +1,11 @@
 // What the host translation units behind the C ABI share (api.cpp and the api_<stage>.cpp files, one per public header; scene_rebase.cpp,
-// scene_instances.cpp, scene_deform.cpp): the scene object and its launch context, fail / HIP_TRY, the device buffer and event holders, what api.cpp
+// scene_instances.cpp, scene_deform.cpp, scene_update.cpp, scene_debug.cpp): the scene object and its launch context, fail / HIP_TRY, the device buffer and event holders, what api.cpp
 // defines for the others, and api_temporal.cpp's driver of the temporal accumulations.  The pure argument predicates are api_checks.hpp.  Not installed, not an ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <functional>
 #include <string>
 #include <vector>
@@ -98,7 +99,7 @@ struct DevBuf {
     hipError_t download(T* host, size_t n) const { return host ? hipMemcpy(host, p, n * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess; }
 };
 
-// A buffer of a move's own (scene_instances.cpp, scene_deform.cpp), allocated by the first move after a build and freed with the scene
+// A buffer of the updates in place (scene_update.cpp), allocated by the first update after a build that needs it and freed with the scene
 template <typename T>
 hipError_t ensure(SceneImpl* s, T** p, size_t count) {
     if (*p) return hipSuccess;
@@ -122,6 +123,7 @@ struct Event {
     hipError_t elapsed_ms(const Event& since, float* ms) const { return hipEventElapsedTime(ms, since.e, e); }
 };
 
+inline double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }   // host_ms of an entry point
 // `aov`: the AOV renderers ignore strategy and max_depth (mi355pt_render_aov), so they are not checked for them
 int check_args(const mi355pt_scene* s, const mi355pt_camera* cam, const mi355pt_params* p, bool aov = false);
 // aov_kind < 0: the path-tracing kernels; MI355PT_AOV_*: the AOV kernel (pt_kernels_aov.hip) over the same work items and work counter —

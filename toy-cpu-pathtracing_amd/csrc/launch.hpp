@@ -182,7 +182,7 @@ struct RobustArgs {
     float gini_scale;
 };
 hipError_t launch_robust_combine(const float* d_buckets, uint32_t n_buckets, const RobustArgs& args, float* d_out, float* d_out_half, uint8_t* d_out_trim, hipStream_t);
-// pt_kernels_rebase.hip: a camera move on a built scene (include/mi355pt_rebase.h, scene_rebase.cpp).  launch_rebase_tris: the render-space
+// pt_kernels_rebase.hip: a camera move on a built scene (include/mi355pt_rebase.h, scene_rebase.cpp; every launch below from scene_update.cpp).  launch_rebase_tris: the render-space
 // positions of all n_tris leaf-order triangles from the local records and the instance matrices; count_degenerate adds the number of
 // triangles whose cross product is exactly zero to *d_degenerate_count (which the caller has cleared).  launch_refit_bvh2_height: the boxes of
 // the `count` (node, side) entries from d_entries[first] on — ONE height group of rebase_plan.hpp's plan; the caller launches the groups
@@ -191,7 +191,7 @@ hipError_t launch_rebase_tris(const DevTriLocal* d_local, const DevInstance* d_i
                               uint32_t* d_degenerate_count, hipStream_t);
 hipError_t launch_refit_bvh2_height(DevNode* d_nodes, const DevTri* d_tris_render, const uint32_t* d_entries, uint32_t first, uint32_t count, hipStream_t);
 hipError_t launch_refit_nodes4(DevNode4* d_nodes4, const DevNode* d_nodes, const uint32_t* d_slot_src, uint32_t n_slots, int32_t root, hipStream_t);
-// pt_kernels_instances.hip: an instance move on a built scene (include/mi355pt_instances.h, scene_instances.cpp).  launch_shade_refresh: ng
+// pt_kernels_instances.hip: an instance move on a built scene (include/mi355pt_instances.h, scene_instances.cpp; launched from scene_update.cpp).  launch_shade_refresh: ng
 // and light_pdf_area of the leaf-order shading records whose instance has its bit set in d_moved_bits ((n_instances + 31) / 32 words);
 // d_light_pdf: light_pdf_area per light triangle, indexed DevLight::first_tri + local_tri.  launch_sah_cost: TWO launches, the block sums of
 // the terms of all n_entries plan entries and the one-block finish; d_scratch holds sah_scratch_floats(n_entries) floats and receives
@@ -201,7 +201,7 @@ hipError_t launch_shade_refresh(DevTriShade* d_shade, const DevTriLocal* d_local
 size_t sah_scratch_floats(uint32_t n_entries);
 hipError_t launch_sah_cost(const DevNode* d_nodes, int32_t root, const uint32_t* d_entries, uint32_t n_entries, float* d_scratch, hipStream_t);
 constexpr uint32_t SAH_COST_LAUNCHES = 2;
-// pt_kernels_deform.hip: a mesh deformation on a built scene (include/mi355pt_deform.h, scene_deform.cpp).  launch_deform_tris: the positions
+// pt_kernels_deform.hip: a mesh deformation on a built scene (include/mi355pt_deform.h, scene_deform.cpp; launched from scene_update.cpp).  launch_deform_tris: the positions
 // of the local records and rows 0 - 2 of the shading records of the leaf-order triangles whose instance has a slot in d_table
 // (deform_plan.hpp deform_table: n_instances words, then from word slots_at on n_slots slot records), gathered from d_staging through the
 // index pool d_mesh_idx; the triangles of every other instance are not written

@@ -59,7 +59,7 @@ __global__ __launch_bounds__(DF_BLOCK) void deform_tris_kernel(DevTriLocal* __re
 
 }  // namespace
 
-// ---- host side (declared in launch.hpp; called from scene_deform.cpp) ----
+// ---- host side (declared in launch.hpp; called from scene_update.cpp) ----
 hipError_t launch_deform_tris(DevTriLocal* d_local, DevTriShade* d_shade, const uint32_t* d_table, const float* d_staging, const uint32_t* d_mesh_idx, uint32_t n_tris,
                               uint32_t n_instances, uint32_t slots_at, uint32_t n_slots, hipStream_t stream) {
     if (n_tris == 0 || n_instances == 0 || n_slots == 0 || (slots_at & 3u) != 0u) return hipErrorInvalidValue;

@@ -106,7 +106,7 @@ inline dim3 blocks_for(uint32_t n) { return dim3((n + IM_BLOCK - 1u) / IM_BLOCK)
 
 }  // namespace
 
-// ---- host side (declared in launch.hpp; called from scene_instances.cpp) ----
+// ---- host side (declared in launch.hpp; called from scene_update.cpp) ----
 hipError_t launch_shade_refresh(DevTriShade* d_shade, const DevTriLocal* d_local, const DevInstance* d_instances, const uint32_t* d_moved_bits, const DevLight* d_lights,
                                 const float* d_light_pdf, uint32_t n_tris, uint32_t n_instances, uint32_t n_lights, uint32_t n_light_pdf, hipStream_t stream) {
     if (n_tris == 0 || n_instances == 0) return hipErrorInvalidValue;

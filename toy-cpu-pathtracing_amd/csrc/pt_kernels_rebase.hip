@@ -89,7 +89,7 @@ inline dim3 blocks_for(uint32_t n) { return dim3((n + RB_BLOCK - 1u) / RB_BLOCK)
 
 }  // namespace
 
-// ---- host side (declared in launch.hpp; called from scene_rebase.cpp) ----
+// ---- host side (declared in launch.hpp; called from scene_update.cpp) ----
 hipError_t launch_rebase_tris(const DevTriLocal* d_local, const DevInstance* d_instances, DevTri* d_render, uint32_t n_tris, bool count_degenerate,
                               uint32_t* d_degenerate_count, hipStream_t stream) {
     if (n_tris == 0) return hipErrorInvalidValue;

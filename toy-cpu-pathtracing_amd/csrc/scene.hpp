@@ -43,7 +43,7 @@ struct LoweredScene;   // scene_lower.hpp
 struct LowerReport;
 
 struct MeshBounds { float lo[3], hi[3]; };   // a mesh's local AABB (scene_lower.cpp mesh_local_bounds)
-// What mi355pt_scene_move_camera (scene_rebase.cpp) keeps beside the lowered scene, made by SceneImpl::build.  Not part of LoweredScene: what
+// What the updates in place (scene_rebase.cpp, scene_instances.cpp, scene_deform.cpp; their device step scene_update.cpp) keep beside the lowered scene, made by SceneImpl::build.  Not part of LoweredScene: what
 // the upload takes and the digests hash stays what it was.
 struct RebaseState {
     bool ready = false;                       // false: a move builds again (MI355PT_MOVE_UNSUPPORTED_BUILD)
@@ -66,14 +66,14 @@ struct RebaseState {
     std::vector<DevNode4> tree_nodes4;        // ... and its 4-wide collapse (links and used slots; the boxes follow a refit)
     int32_t tree_root4 = 0;
     std::vector<uint32_t> kept;               // build index -> triangle of the build, when it left triangles out (else the identity, not stored)
-    // mi355pt_scene_move_instances (scene_instances.cpp): allocated / computed by the first move after a build (all in SceneImpl::allocs)
+    // mi355pt_scene_move_instances (scene_instances.cpp, scene_update.cpp): allocated / computed by the first move after a build (all in SceneImpl::allocs)
     uint32_t n_entries = 0;                   // RebasePlan::entries.size()
     float* d_sah = nullptr;                   // launch_sah_cost's scratch
     uint32_t* d_moved_bits = nullptr;         // one bit per instance
     float* d_light_pdf = nullptr;             // light_pdf_area per light triangle
     bool sah_built_valid = false;
     float sah_built = 0.0f;
-    // mi355pt_scene_deform_meshes (scene_deform.cpp): allocated by the first deformation after a build (all in SceneImpl::allocs)
+    // mi355pt_scene_deform_meshes (scene_deform.cpp, scene_update.cpp): allocated by the first deformation after a build (all in SceneImpl::allocs)
     float* d_deform_staging = nullptr;        // deform_plan.hpp: the new arrays of one call, sized for every mesh of the scene at once
     uint32_t* d_deform_table = nullptr;       // ... the slot per instance and the slot records
     uint32_t* d_mesh_idx = nullptr;           // ... the index buffers of all meshes, one after the other

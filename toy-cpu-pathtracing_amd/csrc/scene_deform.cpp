@@ -1,25 +1,20 @@
 // Deforming meshes of a built scene (include/mi355pt_deform.h): the call itself and its host-only twin of the debug surface.  Host C++
-// only; the kernel is pt_kernels_deform.hip, the rest of the move the instance move's launches (pt_kernels_rebase.hip,
-// pt_kernels_instances.hip); the layout host and device share is deform_plan.hpp.  The side tables are RebaseState's (scene.hpp); the host
-// form the tests hold the deformation to is mi355pt_scene_debug_pinned_digest (scene_rebase.cpp).
+// only; the device half is scene_update.cpp's step, the kernel is pt_kernels_deform.hip, the rest of the move the instance move's launches
+// (pt_kernels_rebase.hip, pt_kernels_instances.hip); the layout host and device share is deform_plan.hpp.  The side tables are
+// RebaseState's (scene.hpp); the host form the tests hold the deformation to is mi355pt_scene_debug_pinned_digest (scene_debug.cpp).
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/mi355pt_debug.h"
-#include "api_internal.hpp"
-#include "deform_plan.hpp"
-#include "scene_lower.hpp"
+#include "scene_update.hpp"
 
 using namespace pt;
 
 namespace {
-
-double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 
 // one update, checked: the arrays as the description will hold them
 struct Checked {
@@ -129,20 +124,13 @@ int mi355pt_scene_deform_meshes(mi355pt_scene* s, const mi355pt_camera* cam, con
     std::vector<float> light_pdf;
     if (int rc = lower_camera_records(impl, cam, rb.bounds, rb.lights, rb.light_tris, &rec, &err, plan.moved.data(), &light_pdf)) return done(fail(rc, err));
     // (no matrix changed, so the classes of the lowering — DevInstance::identity, tris_are_local — are the build's: nothing to compare)
-    for (size_t k = 0; k + 1 < rb.left_out.size(); k += 2)        // a triangle the tree leaves out may no longer be degenerate (render space)
-        if (plan.moved[rb.left_out[k]] && !render_triangle_degenerate(impl, rec.instances[rb.left_out[k]], rb.left_out[k], rb.left_out[k + 1])) return rebuild(MI355PT_MOVE_DEGENERATE_SET_CHANGED);
+    if (!left_out_stay_degenerate(impl, rec.instances, plan.moved.data())) return rebuild(MI355PT_MOVE_DEGENERATE_SET_CHANGED);   // a triangle the tree leaves out may no longer be degenerate (render space)
     if (rb.tris_are_local)                                        // ... and the local-space set, either way
         for (size_t k = 0; k < changed.size(); ++k) {
             const HostMesh& m = impl.meshes[changed[k].geom];
             for (uint32_t t = 0; t < m.n_tri; ++t) if ((local_triangle_degenerate(m, t) ? 1 : 0) != deg_before[k][t]) return rebuild(MI355PT_MOVE_DEGENERATE_SET_CHANGED);
         }
 
-    DevScene& d = impl.dev;
-    auto dropped = [&](const char* what, hipError_t e) { impl.release(); return done(fail(MI355PT_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e))); };
-    hipError_t e;
-    hipStream_t stream = nullptr;
-#if !PT_NODE_Q16
-    const bool has_tree = d.root >= 0 && rb.n_entries > 0;
     // the staging buffer in the plan's layout
     std::vector<float> staging(plan.staging_floats);
     for (size_t k = 0; k < changed.size(); ++k) {
@@ -153,83 +141,15 @@ int mi355pt_scene_deform_meshes(mi355pt_scene* s, const mi355pt_camera* cam, con
         if (sl.tangent != DEFORM_NO_SLOT) std::memcpy(staging.data() + sl.tangent, c.tangent, (size_t)3 * sl.n_tri * sizeof(float));
     }
     const std::vector<uint32_t> table = deform_table(plan);
-    const size_t n_inst = impl.instances.size();
-    // the call's own buffers (the instance move's among them) and, once per build, the cost of the tree as it stands (nothing on the device
-    // has changed yet, but the description already holds the new arrays, so a failure drops the scene all the same)
-    if ((e = ensure(&impl, &rb.d_moved_bits, (n_inst + 31) / 32)) != hipSuccess || (e = ensure(&impl, &rb.d_light_pdf, light_pdf.size())) != hipSuccess ||
-        (e = ensure(&impl, &rb.d_sah, sah_scratch_floats(rb.n_entries))) != hipSuccess ||
-        (e = ensure(&impl, &rb.d_deform_staging, deform_staging_capacity(mesh_n_vert.data(), mesh_n_tri.data(), mesh_n_tri.size()))) != hipSuccess ||
-        (e = ensure(&impl, &rb.d_deform_table, deform_table_slots_at(n_inst) + impl.meshes.size() * DEFORM_SLOT_WORDS)) != hipSuccess ||
-        (e = ensure(&impl, &rb.d_mesh_idx, rb.mesh_idx_offset.back())) != hipSuccess) return dropped("hipMalloc", e);
-    if (!rb.sah_built_valid) {
-        rb.sah_built = 0.0f;
-        if (has_tree) {
-            if ((e = launch_sah_cost(d.nodes, d.root, rb.d_entries, rb.n_entries, rb.d_sah, stream)) != hipSuccess) return dropped("launch_sah_cost", e);
-            if ((e = hipMemcpy(&rb.sah_built, rb.d_sah, sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess) return dropped("hipMemcpy", e);
-        }
-        rb.sah_built_valid = true;
-    }
-    std::vector<uint32_t> bits((n_inst + 31) / 32, 0u);
-    for (size_t i = 0; i < plan.moved.size(); ++i) if (plan.moved[i]) bits[i >> 5] |= 1u << (i & 31u);
-    for (const DeformUpdate& u : changed) {                       // a mesh's index buffer: once per build
-        if (rb.mesh_idx_uploaded[u.geom]) continue;
-        if ((e = hipMemcpy(rb.d_mesh_idx + rb.mesh_idx_offset[u.geom], impl.meshes[u.geom].idx.data(), (size_t)3 * u.n_tri * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess) return dropped("hipMemcpy", e);
-        rb.mesh_idx_uploaded[u.geom] = 1;
-    }
-    if ((e = hipMemcpy(rb.d_deform_staging, staging.data(), staging.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return dropped("hipMemcpy", e);
-    if ((e = hipMemcpy(rb.d_deform_table, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess) return dropped("hipMemcpy", e);
 
-    // from here on the device records change: a HIP error leaves them half deformed, so the scene is dropped
-    if ((e = hipMemcpy((void*)d.instances, rec.instances.data(), rec.instances.size() * sizeof(DevInstance), hipMemcpyHostToDevice)) != hipSuccess) return dropped("hipMemcpy", e);
-    if (!rec.lights.empty() && (e = hipMemcpy((void*)d.lights, rec.lights.data(), rec.lights.size() * sizeof(DevLight), hipMemcpyHostToDevice)) != hipSuccess) return dropped("hipMemcpy", e);
-    if (!rec.light_tris.empty() && (e = hipMemcpy((void*)d.light_tris, rec.light_tris.data(), rec.light_tris.size() * sizeof(DevLightTri), hipMemcpyHostToDevice)) != hipSuccess) return dropped("hipMemcpy", e);
-    if ((e = hipMemcpy(rb.d_moved_bits, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess) return dropped("hipMemcpy", e);
-    if (!light_pdf.empty() && (e = hipMemcpy(rb.d_light_pdf, light_pdf.data(), light_pdf.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return dropped("hipMemcpy", e);
-    if ((e = hipMemset(rb.d_count, 0, sizeof(uint32_t))) != hipSuccess) return dropped("hipMemset", e);
-    Event ev_a, ev_b;
-    if ((e = ev_a.create()) != hipSuccess || (e = ev_b.create()) != hipSuccess) return dropped("hipEventCreate", e);
-    if ((e = ev_a.record(stream)) != hipSuccess) return dropped("hipEventRecord", e);
-    // tris_local is the array DevScene::tris names in local-triangle mode (scene.cpp upload): the traversals read what this launch writes,
-    // and tris_render is re-derived from it by the next one in either mode
-    if ((e = launch_deform_tris((DevTriLocal*)d.tris_local, (DevTriShade*)d.shade, rb.d_deform_table, rb.d_deform_staging, rb.d_mesh_idx, d.n_tris, (uint32_t)n_inst,
-                                (uint32_t)deform_table_slots_at(n_inst), (uint32_t)plan.slots.size(), stream)) != hipSuccess) return dropped("launch_deform_tris", e);
-    ++r.launches;
-    if ((e = launch_rebase_tris(d.tris_local, d.instances, (DevTri*)d.tris_render, d.n_tris, !rb.tris_are_local, rb.d_count, stream)) != hipSuccess) return dropped("launch_rebase_tris", e);
-    ++r.launches;
-    if ((e = launch_shade_refresh((DevTriShade*)d.shade, d.tris_local, d.instances, rb.d_moved_bits, d.lights, rb.d_light_pdf, d.n_tris, (uint32_t)n_inst, d.n_lights,
-                                  (uint32_t)light_pdf.size(), stream)) != hipSuccess) return dropped("launch_shade_refresh", e);
-    ++r.launches;
-    for (size_t h = 0; h + 1 < rb.height_offset.size(); ++h) {      // lowest height first: the kernel boundary orders the levels
-        const uint32_t first = rb.height_offset[h], count = rb.height_offset[h + 1] - first;
-        if (count == 0) continue;
-        if ((e = launch_refit_bvh2_height((DevNode*)d.nodes, d.tris_render, rb.d_entries, first, count, stream)) != hipSuccess) return dropped("launch_refit_bvh2_height", e);
-        ++r.launches;
-    }
-    if (rb.n_slots && d.root >= 0) {
-        if ((e = launch_refit_nodes4((DevNode4*)d.nodes4, d.nodes, rb.d_slot_src, rb.n_slots, d.root, stream)) != hipSuccess) return dropped("launch_refit_nodes4", e);
-        ++r.launches;
-    }
-    if (has_tree) {
-        if ((e = launch_sah_cost(d.nodes, d.root, rb.d_entries, rb.n_entries, rb.d_sah, stream)) != hipSuccess) return dropped("launch_sah_cost", e);
-        r.launches += SAH_COST_LAUNCHES;
-    }
-    if ((e = ev_b.record(stream)) != hipSuccess || (e = ev_b.synchronize()) != hipSuccess) return dropped("hipEventSynchronize", e);
-    float ms = 0.0f;
-    if ((e = ev_b.elapsed_ms(ev_a, &ms)) != hipSuccess) return dropped("hipEventElapsedTime", e);
-    r.device_ms = ms;
-    uint32_t n_degenerate = 0;
-    if ((e = hipMemcpy(&n_degenerate, rb.d_count, sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess) return dropped("hipMemcpy", e);
-    if (n_degenerate) return rebuild(MI355PT_MOVE_DEGENERATE_SET_CHANGED);      // (the build overwrites everything the launches wrote)
-    float sah_after = 0.0f;
-    if (has_tree && (e = hipMemcpy(&sah_after, rb.d_sah, sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess) return dropped("hipMemcpy", e);
-    if (rebuild_above > 0.0f && rb.sah_built > 0.0f && sah_after / rb.sah_built > rebuild_above) return rebuild(MI355PT_MOVE_SAH_DEGRADED);
-    r.sah_built = rb.sah_built; r.sah_after = sah_after;
-#else
-    return rebuild(MI355PT_MOVE_UNSUPPORTED_BUILD);
-#endif
-    // the caches the next move (of the camera, of instances, of vertices) starts from
-    rb.lights = rec.lights;
-    rb.light_tris = rec.light_tris;
+    // from here on the device: a HIP error drops the scene, since the description already holds the new arrays
+    const DeformStage stage{staging, table, (uint32_t)plan.slots.size(), changed, deform_staging_capacity(mesh_n_vert.data(), mesh_n_tri.data(), mesh_n_tri.size()),
+                            deform_table_slots_at(impl.instances.size()) + impl.meshes.size() * DEFORM_SLOT_WORDS};
+    const SceneUpdateResult res = scene_update_step(&impl, SceneUpdate{rec, !rb.tris_are_local, plan.moved.data(), &light_pdf, true, rebuild_above, &stage});
+    r.launches = res.launches; r.device_ms = res.device_ms;
+    if (res.outcome == SceneUpdateResult::DEVICE_ERROR) return done(fail(MI355PT_E_DEVICE, res.what));
+    if (res.outcome != SceneUpdateResult::DONE) return rebuild(res.outcome == SceneUpdateResult::SAH_DEGRADED ? MI355PT_MOVE_SAH_DEGRADED : MI355PT_MOVE_DEGENERATE_SET_CHANGED);
+    r.sah_built = res.sah_built; r.sah_after = res.sah_after;
     r.reason = MI355PT_MOVE_REBASED;
     return done(MI355PT_OK);
 }

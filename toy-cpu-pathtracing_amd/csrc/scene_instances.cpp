@@ -1,26 +1,16 @@
-// Moving instances of a built scene (include/mi355pt_instances.h): the dynamic mark and the move itself.  Host C++ only; the kernels are
-// pt_kernels_rebase.hip (positions, both trees) and pt_kernels_instances.hip (shading records, SAH cost), the arithmetic both sides share
-// instance_move_plan.hpp and rebase_plan.hpp.  The side tables are RebaseState's (scene.hpp, scene_rebase.cpp prepare_rebase); the host
-// form the tests hold the move to is mi355pt_scene_debug_pinned_digest (scene_rebase.cpp).
+// Moving instances of a built scene (include/mi355pt_instances.h): the dynamic mark and the move itself.  Host C++ only; the device half
+// is scene_update.cpp's step, the kernels are pt_kernels_rebase.hip (positions, both trees) and pt_kernels_instances.hip (shading records,
+// SAH cost), the arithmetic both sides share instance_move_plan.hpp and rebase_plan.hpp.  The side tables are RebaseState's (scene.hpp,
+// scene_rebase.cpp prepare_rebase); the host form the tests hold the move to is mi355pt_scene_debug_pinned_digest (scene_debug.cpp).
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "../../include/mi355pt_debug.h"
-#include "api_internal.hpp"
-#include "instance_move_plan.hpp"
-#include "scene_lower.hpp"
+#include "scene_update.hpp"
 
 using namespace pt;
-
-namespace {
-
-double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-
-}  // namespace
 
 extern "C" {
 
@@ -71,79 +61,15 @@ int mi355pt_scene_move_instances(mi355pt_scene* s, const mi355pt_camera* cam, co
     std::vector<float> light_pdf;
     std::string err;
     if (int rc = lower_camera_records(impl, cam, rb.bounds, rb.lights, rb.light_tris, &rec, &err, moved.data(), &light_pdf)) return done(fail(rc, err));
-    bool same_class = rec.tris_are_local == rb.tris_are_local && !rb.tris_are_local && rec.instances.size() == rb.identity.size();   // (local-triangle mode: every instance shares ONE translation)
-    for (size_t i = 0; same_class && i < rec.instances.size(); ++i) same_class = (rec.instances[i].identity != 0) == (rb.identity[i] != 0);
-    if (!same_class) return rebuild(MI355PT_MOVE_INSTANCE_CLASS_CHANGED);
-    for (size_t k = 0; k + 1 < rb.left_out.size(); k += 2)        // a triangle the tree leaves out may no longer be degenerate
-        if (moved[rb.left_out[k]] && !render_triangle_degenerate(impl, rec.instances[rb.left_out[k]], rb.left_out[k], rb.left_out[k + 1])) return rebuild(MI355PT_MOVE_DEGENERATE_SET_CHANGED);
+    if (rb.tris_are_local || !same_lowering_class(rec.instances, rec.tris_are_local, rb.identity, rb.tris_are_local)) return rebuild(MI355PT_MOVE_INSTANCE_CLASS_CHANGED);   // (local-triangle mode: every instance shares ONE translation)
+    if (!left_out_stay_degenerate(impl, rec.instances, moved.data())) return rebuild(MI355PT_MOVE_DEGENERATE_SET_CHANGED);   // a triangle the tree leaves out may no longer be degenerate
 
-    DevScene& d = impl.dev;
-    auto dropped = [&](const char* what, hipError_t e) { impl.release(); return done(fail(MI355PT_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e))); };
-    hipError_t e;
-    hipStream_t stream = nullptr;
-#if !PT_NODE_Q16
-    const bool has_tree = d.root >= 0 && rb.n_entries > 0;
-    // the move's own buffers and, once per build, the cost of the tree as it stands (nothing of the scene has changed yet: a failure here
-    // leaves it as it was, but the description already holds the new matrices, so the scene is dropped all the same)
-    if ((e = ensure(&impl, &rb.d_moved_bits, (impl.instances.size() + 31) / 32)) != hipSuccess || (e = ensure(&impl, &rb.d_light_pdf, light_pdf.size())) != hipSuccess ||
-        (e = ensure(&impl, &rb.d_sah, sah_scratch_floats(rb.n_entries))) != hipSuccess) return dropped("hipMalloc", e);
-    if (!rb.sah_built_valid) {
-        rb.sah_built = 0.0f;
-        if (has_tree) {
-            if ((e = launch_sah_cost(d.nodes, d.root, rb.d_entries, rb.n_entries, rb.d_sah, stream)) != hipSuccess) return dropped("launch_sah_cost", e);
-            if ((e = hipMemcpy(&rb.sah_built, rb.d_sah, sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess) return dropped("hipMemcpy", e);
-        }
-        rb.sah_built_valid = true;
-    }
-    std::vector<uint32_t> bits((impl.instances.size() + 31) / 32, 0u);
-    for (size_t i = 0; i < moved.size(); ++i) if (moved[i]) bits[i >> 5] |= 1u << (i & 31u);
-
-    // from here on the device records change: a HIP error leaves them half moved, so the scene is dropped
-    if ((e = hipMemcpy((void*)d.instances, rec.instances.data(), rec.instances.size() * sizeof(DevInstance), hipMemcpyHostToDevice)) != hipSuccess) return dropped("hipMemcpy", e);
-    if (!rec.lights.empty() && (e = hipMemcpy((void*)d.lights, rec.lights.data(), rec.lights.size() * sizeof(DevLight), hipMemcpyHostToDevice)) != hipSuccess) return dropped("hipMemcpy", e);
-    if (!rec.light_tris.empty() && (e = hipMemcpy((void*)d.light_tris, rec.light_tris.data(), rec.light_tris.size() * sizeof(DevLightTri), hipMemcpyHostToDevice)) != hipSuccess) return dropped("hipMemcpy", e);
-    if ((e = hipMemcpy(rb.d_moved_bits, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess) return dropped("hipMemcpy", e);
-    if (!light_pdf.empty() && (e = hipMemcpy(rb.d_light_pdf, light_pdf.data(), light_pdf.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return dropped("hipMemcpy", e);
-    if ((e = hipMemset(rb.d_count, 0, sizeof(uint32_t))) != hipSuccess) return dropped("hipMemset", e);
-    Event ev_a, ev_b;
-    if ((e = ev_a.create()) != hipSuccess || (e = ev_b.create()) != hipSuccess) return dropped("hipEventCreate", e);
-    if ((e = ev_a.record(stream)) != hipSuccess) return dropped("hipEventRecord", e);
-    if ((e = launch_rebase_tris(d.tris_local, d.instances, (DevTri*)d.tris_render, d.n_tris, true, rb.d_count, stream)) != hipSuccess) return dropped("launch_rebase_tris", e);
-    ++r.launches;
-    if ((e = launch_shade_refresh((DevTriShade*)d.shade, d.tris_local, d.instances, rb.d_moved_bits, d.lights, rb.d_light_pdf, d.n_tris, (uint32_t)impl.instances.size(),
-                                  d.n_lights, (uint32_t)light_pdf.size(), stream)) != hipSuccess) return dropped("launch_shade_refresh", e);
-    ++r.launches;
-    for (size_t h = 0; h + 1 < rb.height_offset.size(); ++h) {      // lowest height first: the kernel boundary orders the levels
-        const uint32_t first = rb.height_offset[h], count = rb.height_offset[h + 1] - first;
-        if (count == 0) continue;
-        if ((e = launch_refit_bvh2_height((DevNode*)d.nodes, d.tris_render, rb.d_entries, first, count, stream)) != hipSuccess) return dropped("launch_refit_bvh2_height", e);
-        ++r.launches;
-    }
-    if (rb.n_slots && d.root >= 0) {
-        if ((e = launch_refit_nodes4((DevNode4*)d.nodes4, d.nodes, rb.d_slot_src, rb.n_slots, d.root, stream)) != hipSuccess) return dropped("launch_refit_nodes4", e);
-        ++r.launches;
-    }
-    if (has_tree) {
-        if ((e = launch_sah_cost(d.nodes, d.root, rb.d_entries, rb.n_entries, rb.d_sah, stream)) != hipSuccess) return dropped("launch_sah_cost", e);
-        r.launches += SAH_COST_LAUNCHES;
-    }
-    if ((e = ev_b.record(stream)) != hipSuccess || (e = ev_b.synchronize()) != hipSuccess) return dropped("hipEventSynchronize", e);
-    float ms = 0.0f;
-    if ((e = ev_b.elapsed_ms(ev_a, &ms)) != hipSuccess) return dropped("hipEventElapsedTime", e);
-    r.device_ms = ms;
-    uint32_t n_degenerate = 0;
-    if ((e = hipMemcpy(&n_degenerate, rb.d_count, sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess) return dropped("hipMemcpy", e);
-    if (n_degenerate) return rebuild(MI355PT_MOVE_DEGENERATE_SET_CHANGED);      // (the build overwrites everything the launches wrote)
-    float sah_after = 0.0f;
-    if (has_tree && (e = hipMemcpy(&sah_after, rb.d_sah, sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess) return dropped("hipMemcpy", e);
-    if (rebuild_above > 0.0f && rb.sah_built > 0.0f && sah_after / rb.sah_built > rebuild_above) return rebuild(MI355PT_MOVE_SAH_DEGRADED);
-    r.sah_built = rb.sah_built; r.sah_after = sah_after;
-#else
-    return rebuild(MI355PT_MOVE_UNSUPPORTED_BUILD);
-#endif
-    // the caches the next move (of the camera or of instances) starts from
-    rb.lights = rec.lights;
-    rb.light_tris = rec.light_tris;
+    // from here on the device: a HIP error drops the scene, since the description already holds the new matrices
+    const SceneUpdateResult res = scene_update_step(&impl, SceneUpdate{rec, true, moved.data(), &light_pdf, true, rebuild_above});
+    r.launches = res.launches; r.device_ms = res.device_ms;
+    if (res.outcome == SceneUpdateResult::DEVICE_ERROR) return done(fail(MI355PT_E_DEVICE, res.what));
+    if (res.outcome != SceneUpdateResult::DONE) return rebuild(res.outcome == SceneUpdateResult::SAH_DEGRADED ? MI355PT_MOVE_SAH_DEGRADED : MI355PT_MOVE_DEGENERATE_SET_CHANGED);
+    r.sah_built = res.sah_built; r.sah_after = res.sah_after;
     r.reason = MI355PT_MOVE_REBASED;
     return done(MI355PT_OK);
 }

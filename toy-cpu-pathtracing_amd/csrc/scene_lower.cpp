@@ -707,6 +707,19 @@ bool render_triangle_degenerate(const SceneImpl& scene,const DevInstance& di, ui
     return degenerate(p[0], p[1], p[2]);
 }
 
+bool same_lowering_class(const std::vector<DevInstance>& instances, bool tris_are_local, const std::vector<uint8_t>& identity, bool built_local) {
+    if (tris_are_local != built_local || instances.size() != identity.size()) return false;
+    for (size_t i = 0; i < instances.size(); ++i) if ((instances[i].identity != 0) != (identity[i] != 0)) return false;
+    return true;
+}
+
+bool left_out_stay_degenerate(const SceneImpl& scene, const std::vector<DevInstance>& instances, const uint8_t* moved) {
+    const std::vector<uint32_t>& lo = scene.rebase.left_out;
+    for (size_t k = 0; k + 1 < lo.size(); k += 2)
+        if ((!moved || moved[lo[k]]) && !render_triangle_degenerate(scene, instances[lo[k]], lo[k], lo[k + 1])) return false;
+    return true;
+}
+
 int lower_scene(const SceneImpl& scene, LoweredGeometry&& g, BvhOut&& bvh, const float* cmf4, LoweredScene* ls, LowerReport* rep, std::string* err) {
     *ls = LoweredScene{};
     reorder_to_leaves(g, bvh.order, ls);

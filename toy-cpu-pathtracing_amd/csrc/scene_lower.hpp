@@ -100,6 +100,10 @@ bool instance_transform_ok(const SceneImpl& scene, const mi355pt_camera* cam, co
 void keep_topology(const LoweredGeometry& geo, const BvhOut& bvh, const mi355pt_camera* cam, bool gpu_built, RebaseState* rb);
 // degenerate() on the render-space vertices of triangle `tri` of instance `instance`, whose lowered record is `di`
 bool render_triangle_degenerate(const SceneImpl& scene, const DevInstance& di, uint32_t instance, uint32_t tri);
+// The host gates of an update in place.  Same lowering class: `instances` / `tris_are_local` have the classes `identity` (DevInstance::identity
+// per instance) / `built_local` name.  Every triangle the built tree leaves out (RebaseState::left_out) is still degenerate; with `moved`, of the marked instances only
+bool same_lowering_class(const std::vector<DevInstance>& instances, bool tris_are_local, const std::vector<uint8_t>& identity, bool built_local);
+bool left_out_stay_degenerate(const SceneImpl& scene, const std::vector<DevInstance>& instances, const uint8_t* moved = nullptr);
 
 // What NEW VERTICES of a mesh change besides (mi355pt_scene_deform_meshes, scene_deform.cpp): one mesh's entry of mesh_local_bounds again,
 // and degenerate() on the LOCAL vertices of triangle `tri` of a mesh — the set the tree leaves out in local-triangle mode.  With the
