@@ -1,6 +1,6 @@
 """GPU tests of the per-pixel motion vectors (include/mi355pt_flow.h): the mark and its lifecycle, the flow pass (csrc/pt_kernels_flow.hip)
 against the NumPy restatement of tests/flow_reference.py fed the kernel's own hits — BIT EQUALITY on every record — and against the
-oracle's centre-ray hits (tests/flow_reference.cpp), and the flow-aware accumulations (csrc/pt_kernels_temporal_flow.hip) against the
+oracle's centre-ray hits (tests/flow_reference.cpp), and the flow-aware accumulations (csrc/pt_kernels_temporal.hip) against the
 restatement, bit for bit; then what the records buy on a deforming mesh.  The outputs start as NaN or 0xff, so a value the kernels leave
 out shows.  One line per comparison goes to the file MI355PT_FRAME_LOG names (profiles/flow_parity.jsonl)."""
 import json

@@ -1,5 +1,5 @@
 """The first-frame rule of the one driver behind the mi355pt_temporal_accumulate* entry points (csrc/api_temporal.cpp): without a previous
-frame every device form — rectified or not, whatever carries the hits back — is the plain temporal_accumulate_kernel, and a scratch stays
+frame every device form — rectified or not, whatever carries the hits back — is the plain first-frame instance of temporal_kernel, and a scratch stays
 as it is.  The forms with a previous frame are held to the restatements by tests/test_temporal_gpu.py, test_temporal_rectify_gpu.py,
 test_motion_gpu.py and test_flow_gpu.py."""
 import os

@@ -5,7 +5,7 @@ frame; then the scene is marked, the hero takes a translation and a yaw on the d
 current frame of every timed call (tools/flow_rate.py's setup).  After WARMUP calls of each, RUNS calls of each, ALTERNATING, each call
 bracketed by HIP events:
   probe_{static,table,table_ids,flow,flow_ids}   mi355pt_temporal_budget_device (with d_pred_length), beside the accumulation of the same carry
-                           with the half film: accumulate_static (temporal_accumulate_kernel), accumulate_table_ids, accumulate_flow_ids;
+                           with the half film: accumulate_static (temporal_kernel, static carry), accumulate_table_ids, accumulate_flow_ids;
                            probe_first is the probe without a previous frame
   copy_probe               a device-to-device copy of the bytes the static probe MUST move per pixel: 36 of the current frame (position,
                            normal, hit), 4 x (8 + 4 + 12 + 12) = 144 of the four taps' hit.y, length, position and normal at most — neighbouring
@@ -24,8 +24,8 @@ usage: tools/budget_rate.py [RUNS (default 30, at least 20)] [OUTPUT.json]
 import csv, importlib, json, math, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if len(sys.argv) > 1 and sys.argv[1] == "--merge-kernel-stats":
-    want = ("budget_select_kernel", "adaptive_compact_kernel", "adaptive_err_kernel", "budget_probe_kernel", "temporal_accumulate_kernel",
-            "temporal_accumulate_motion_kernel", "temporal_accumulate_flow_kernel", "pair_normalize_tiles_kernel", "length_credit_kernel")
+    want = ("budget_select_kernel", "adaptive_compact_kernel", "adaptive_err_kernel", "budget_probe_kernel", "temporal_kernel",
+            "pair_normalize_tiles_kernel", "length_credit_kernel")
     rows = {}
     for r in csv.DictReader(open(sys.argv[2])):
         name = r.get("Name") or r.get("KernelName") or ""

@@ -101,17 +101,16 @@ int probe_run(const mi355pt_temporal_frame* cur, const mi355pt_temporal_frame* p
         a.sx = view->sx; a.sy = view->sy; a.cx = view->cx; a.cy = view->cy;
     }
     a.pos_tol = tp->pos_tol; a.normal_cos = tp->normal_cos; a.min_weight = tp->min_weight; a.max_history = tp->max_history;
-    BudgetCarryDev carry{};
+    TemporalCarry carry;
     if (mo && (mo->table || mo->flow)) {
-        carry.ids_cur = mo->ids_cur; carry.ids_prev = mo->ids_prev;
-        carry.table = (const MotionXformDev*)mo->table; carry.last_entry = mo->table ? mo->n_entries - 1u : 0u;
-        carry.flow = (const FlowPixelDev*)mo->flow;
+        carry.kind = mo->table ? TemporalCarry::TABLE : TemporalCarry::FLOW;
+        carry.ids_cur = mo->ids_cur; carry.ids_prev = mo->ids_prev; carry.table = mo->table; carry.n_entries = mo->n_entries; carry.flow = mo->flow;
     }
     const BudgetTilesDev tiles{0u, 0u, bp->base_spp, bp->max_spp, bp->target_history};
     const TemporalFrameDev dc = probe_frame_dev(*cur);
     TemporalFrameDev dp;
     if (prev) dp = probe_frame_dev(*prev);
-    HIP_TRY(launch_budget_probe(dc, prev ? &dp : nullptr, a, carry, tiles, d_pred, d_tile_len, d_tile_spp, stream));
+    HIP_TRY(launch_budget_probe(dc, prev ? &dp : nullptr, a, carry_dev(carry), tiles, d_pred, d_tile_len, d_tile_spp, stream));
     return MI355PT_OK;
 }
 

@@ -152,12 +152,21 @@ struct TemporalCall {
 // ... how a pixel's hit is carried one frame back: by the view alone, through the per-instance table or through the per-pixel records
 // (`align`: what is asked of the table or the records, 16 for a device form, 1 for a host form) ...
 struct TemporalCarry {
-    enum Kind { NONE, TABLE, FLOW } kind = NONE;
+    enum Kind { NONE = CARRY_STATIC, TABLE = CARRY_TABLE, FLOW = CARRY_FLOW } kind = NONE;
     const uint32_t *ids_cur = nullptr, *ids_prev = nullptr;
     const mi355pt_motion_xform* table = nullptr; uint32_t n_entries = 0;
     const mi355pt_flow_pixel* flow = nullptr;
     size_t align = 1;
 };
+// a checked carry whose buffers are on the device, as the kernels and the budget's probe take it
+inline TemporalCarryDev carry_dev(const TemporalCarry& c) {
+    TemporalCarryDev d;
+    d.kind = (TemporalCarryKind)c.kind;
+    d.ids_cur = c.ids_cur; d.ids_prev = c.ids_prev;
+    d.table = (const MotionXformDev*)c.table; d.last_entry = c.table ? c.n_entries - 1u : 0u;
+    d.flow = (const FlowPixelDev*)c.flow;
+    return d;
+}
 // ... and, for a rectified form, its parameters (a host form has no scratch: the driver allocates one)
 struct TemporalRectify { const mi355pt_temporal_rectify_params* rp; void* scratch = nullptr; size_t scratch_bytes = 0; };
 // The checks in their one order — temporal_check, the rectify parameters, the scratch (device form), the carry's own —, then the launches on

@@ -1,8 +1,7 @@
 // The mi355pt_temporal.h and mi355pt_temporal_rectify.h surfaces of libmi355pt.so: the view of a camera pair (host arithmetic), the four
 // entry points of the temporal reprojection and of its rectified form — and the one driver behind them and behind the eight carry forms of
 // api_motion.cpp and api_flow.cpp (api_internal.hpp): the checks in their one order, the launches with the first-frame rule,
-// the host forms' staging.  Host C++ only, like api.cpp; the kernels are pt_kernels_temporal.hip, pt_kernels_temporal_rectify.hip and
-// pt_kernels_temporal_flow.hip.
+// the host forms' staging.  Host C++ only, like api.cpp; the kernels are pt_kernels_temporal.hip and pt_kernels_temporal_rectify.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -118,28 +117,16 @@ int call_check(const TemporalCall& c, const TemporalCarry& carry, const Temporal
 int run_device(const TemporalCall& c, const TemporalCarry& carry, const TemporalRectify* rect, hipStream_t stream) {
     const TemporalArgs a = temporal_args(c.spp, c.view, c.width, c.height, c.tp);
     const TemporalFrameDev dc = frame_dev(*c.cur);
-    if (!c.prev) {
-        HIP_TRY(launch_temporal_accumulate(dc, nullptr, a, c.out_film, c.out_half, c.out_length, stream));
+    const TemporalCarryDev cv = carry_dev(carry);
+    const TemporalOutsDev outs{c.out_film, c.out_half, c.out_length};
+    TemporalFrameDev dp;
+    if (c.prev) dp = frame_dev(*c.prev);
+    if (!c.prev || !rect) {
+        HIP_TRY(launch_temporal_accumulate(dc, c.prev ? &dp : nullptr, a, cv, outs, stream));
         return MI355PT_OK;
     }
-    const TemporalFrameDev dp = frame_dev(*c.prev);
-    const MotionArgs mo{carry.ids_cur, carry.ids_prev, (const MotionXformDev*)carry.table, carry.n_entries - 1u};
-    const FlowArgs fl{carry.ids_cur, carry.ids_prev, (const FlowPixelDev*)carry.flow};
-    switch (carry.kind) {
-        case TemporalCarry::NONE:
-            if (rect) HIP_TRY(launch_temporal_gather(dc, dp, a, rect->scratch, stream));
-            else HIP_TRY(launch_temporal_accumulate(dc, &dp, a, c.out_film, c.out_half, c.out_length, stream));
-            break;
-        case TemporalCarry::TABLE:
-            if (rect) HIP_TRY(launch_temporal_gather_motion(dc, dp, a, mo, rect->scratch, stream));
-            else HIP_TRY(launch_temporal_accumulate_motion(dc, dp, a, mo, c.out_film, c.out_half, c.out_length, stream));
-            break;
-        case TemporalCarry::FLOW:
-            if (rect) HIP_TRY(launch_temporal_gather_flow(dc, dp, a, fl, rect->scratch, stream));
-            else HIP_TRY(launch_temporal_accumulate_flow(dc, dp, a, fl, c.out_film, c.out_half, c.out_length, stream));
-            break;
-    }
-    if (rect) HIP_TRY(launch_temporal_rectify_blend(dc, a, rect->rp->radius, rect->rp->gamma, rect->scratch, c.out_film, c.out_half, c.out_length, stream));
+    HIP_TRY(launch_temporal_gather(dc, dp, a, cv, rect->scratch, stream));
+    HIP_TRY(launch_temporal_rectify_blend(dc, a, rect->rp->radius, rect->rp->gamma, rect->scratch, c.out_film, c.out_half, c.out_length, stream));
     return MI355PT_OK;
 }
 

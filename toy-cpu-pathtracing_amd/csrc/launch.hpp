@@ -69,10 +69,10 @@ size_t denoise_var_scratch_bytes(uint32_t width, uint32_t height);
 hipError_t launch_denoise_var(const float* d_beauty, const float* d_half, uint32_t spp_b, const uint32_t* d_tile_spp, const float* d_albedo, uint32_t spp_a,
                               const float* d_normal, uint32_t spp_n, uint32_t width, uint32_t height, uint32_t levels, float sigma_lum, float sigma_normal,
                               float sigma_albedo, float albedo_eps, float lum_eps, void* d_scratch, float* d_out, hipStream_t);
-// pt_kernels_temporal.hip, pt_kernels_temporal_rectify.hip, pt_kernels_temporal_flow.hip: the temporal reprojection
-// (include/mi355pt_temporal.h, mi355pt_temporal_rectify.h, mi355pt_motion.h, mi355pt_flow.h), every launch on the grid of
-// denoise_grid_blocks; api_temporal.cpp's driver composes them.  A frame's films as the kernels take them (half == nullptr: no half film;
-// length is read of the previous frame only).  Every launcher fills its own copy of TemporalArgs::blocks_x
+// pt_kernels_temporal.hip, pt_kernels_temporal_rectify.hip: the temporal reprojection (include/mi355pt_temporal.h,
+// mi355pt_temporal_rectify.h, mi355pt_motion.h, mi355pt_flow.h), every launch on the grid of denoise_grid_blocks; api_temporal.cpp's driver
+// composes them.  A frame's films as the kernels take them (half == nullptr: no half film; length is read of the previous frame only).
+// Every launcher fills its own copy of TemporalArgs::blocks_x
 struct TemporalFrameDev { const float *film = nullptr, *half = nullptr, *length = nullptr, *position = nullptr, *shading_normal = nullptr, *hit = nullptr; };
 struct TemporalArgs {
     uint32_t width, height, blocks_x;
@@ -81,41 +81,38 @@ struct TemporalArgs {
     float delta[3], rows[9], sx, sy, cx, cy;
     float pos_tol, normal_cos, min_weight, max_history;
 };
-// How a pixel's hit is carried into the previous frame beside the view: a per-instance table (a record as the kernels load it: six 16-byte
-// loads, so the table is 16-byte aligned; last_entry = n_entries - 1, the clamp of a pixel's id) or a 32-byte record per pixel (two
-// 16-byte loads; ids_cur is read only with ids_prev).  ids_prev == nullptr: no id test of the taps.  With either, args.delta is not read
+// How a pixel's hit is carried into the previous frame beside the view: not at all (the static world, args.delta), through a per-instance
+// table (a record as the kernels load it: six 16-byte loads, so the table is 16-byte aligned; last_entry = n_entries - 1, the clamp of a
+// pixel's id) or through a 32-byte record per pixel (two 16-byte loads; ids_cur is read only with ids_prev).  ids_prev == nullptr: no id
+// test of the taps.  With a table or records, args.delta is not read.  The kernels and the budget's probe take the same struct
 struct MotionXformDev { float a[9], b[3], n[9], pad[3]; };
 static_assert(sizeof(MotionXformDev) == 96, "a motion record is six float4");
-struct MotionArgs { const uint32_t* ids_cur; const uint32_t* ids_prev; const MotionXformDev* table; uint32_t last_entry; };
 struct FlowPixelDev { float d[3]; uint32_t id; float dn[3]; uint32_t pad; };
 static_assert(sizeof(FlowPixelDev) == 32, "a flow record is two float4");
-struct FlowArgs { const uint32_t* ids_cur; const uint32_t* ids_prev; const FlowPixelDev* flow; };
-// The accumulation in one launch, each carry's kernels in its unit (temporal, temporal, flow).  prev == nullptr: the first frame, which
-// every form sends to the plain kernel; the table and the flow kernels run WITH a previous frame only
-hipError_t launch_temporal_accumulate(const TemporalFrameDev& cur, const TemporalFrameDev* prev, TemporalArgs args, float* d_out_film, float* d_out_half,
-                                      float* d_out_length, hipStream_t);
-hipError_t launch_temporal_accumulate_motion(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const MotionArgs& motion,
-                                             float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
-hipError_t launch_temporal_accumulate_flow(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const FlowArgs& flow,
-                                           float* d_out_film, float* d_out_half, float* d_out_length, hipStream_t);
-// The rectified accumulation of a frame WITH a previous frame in two launches: a carry's gather (rectify, rectify, flow) into d_scratch
-// (TEMPORAL_RECTIFY_RECORD_BYTES per pixel, 16-byte aligned), then the one rectifying blend over those records.  radius is 1 .. 3
+enum TemporalCarryKind : uint32_t { CARRY_STATIC = 0, CARRY_TABLE = 1, CARRY_FLOW = 2 };
+struct TemporalCarryDev {
+    const uint32_t *ids_cur = nullptr, *ids_prev = nullptr;
+    const MotionXformDev* table = nullptr; uint32_t last_entry = 0;
+    TemporalCarryKind kind = CARRY_STATIC;
+    const FlowPixelDev* flow = nullptr;
+};
+struct TemporalOutsDev { float *film = nullptr, *half = nullptr, *length = nullptr; };
+// The accumulation in one launch.  prev == nullptr: the first frame, which reprojects nothing whatever the carry (it is not read)
+hipError_t launch_temporal_accumulate(const TemporalFrameDev& cur, const TemporalFrameDev* prev, TemporalArgs args, const TemporalCarryDev& carry,
+                                      const TemporalOutsDev& outs, hipStream_t);
+// The rectified accumulation of a frame WITH a previous frame in two launches: the gather into d_scratch (TEMPORAL_RECTIFY_RECORD_BYTES per
+// pixel, 16-byte aligned), then the rectifying blend over those records.  radius is 1 .. 3
 constexpr size_t TEMPORAL_RECTIFY_RECORD_BYTES = 32;
-hipError_t launch_temporal_gather(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, void* d_scratch, hipStream_t);
-hipError_t launch_temporal_gather_motion(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const MotionArgs& motion, void* d_scratch,
-                                         hipStream_t);
-hipError_t launch_temporal_gather_flow(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const FlowArgs& flow, void* d_scratch,
-                                       hipStream_t);
+hipError_t launch_temporal_gather(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const TemporalCarryDev& carry, void* d_scratch,
+                                  hipStream_t);
 hipError_t launch_temporal_rectify_blend(const TemporalFrameDev& cur, TemporalArgs args, uint32_t radius, float gamma, const void* d_scratch, float* d_out_film,
                                          float* d_out_half, float* d_out_length, hipStream_t);
-// pt_kernels_budget.hip: the sample budget by reprojected history (include/mi355pt_budget.h).  How the probe carries a pixel: table != nullptr
-// the per-instance table (last_entry = n_entries - 1), flow != nullptr the per-pixel records, neither the static world (args.delta);
-// ids_prev == nullptr: no id test of the taps.  The probe's per-tile part: the launcher fills tiles_x and n_tiles
-struct BudgetCarryDev { const uint32_t* ids_cur; const uint32_t* ids_prev; const MotionXformDev* table; uint32_t last_entry; const FlowPixelDev* flow; };
+// pt_kernels_budget.hip: the sample budget by reprojected history (include/mi355pt_budget.h); the probe carries a pixel as the
+// accumulation does (TemporalCarryDev).  The probe's per-tile part: the launcher fills tiles_x and n_tiles
 struct BudgetTilesDev { uint32_t tiles_x, n_tiles, base_spp, max_spp; float target_history; };
 // ONE launch: per pixel the history length the accumulation will gather (d_pred, nullptr: not wanted), per tile its minimum and the
 // count budget_plan.hpp's formula gives.  prev == nullptr: the first frame, no G-buffer is read.  args.spp and args.half_spp are not read
-hipError_t launch_budget_probe(const TemporalFrameDev& cur, const TemporalFrameDev* prev, TemporalArgs args, const BudgetCarryDev& carry, BudgetTilesDev tiles,
+hipError_t launch_budget_probe(const TemporalFrameDev& cur, const TemporalFrameDev* prev, TemporalArgs args, const TemporalCarryDev& carry, BudgetTilesDev tiles,
                                float* d_pred, float* d_tile_len, uint32_t* d_tile_spp, hipStream_t);
 // TWO launches: the flags "clamped tile_spp > level_spp" into d_scratch (one u32 per tile) with H := F on the flagged tiles, then
 // launch_adaptive_compact into d_list and d_count

@@ -1,14 +1,17 @@
 // The sample budget by reprojected history (include/mi355pt_budget.h, which is normative for the arithmetic and its order): wave64 kernels
-// for gfx950.  EXTENSION, no reference counterpart.  A unit of its own: the temporal units keep their text and their device code.
-//   budget_probe_kernel<MOTION, HAS_PREV_IDS>   the GEOMETRIC half of the temporal gather (pt_temporal_gather.inc, restated here without the
-//                            films): one wave per 8x8 tile, lane = pixel (lane & 7, lane >> 3) of the tile — adaptive_err_kernel's mapping —,
-//                            four tiles per 256-thread block, grid-stride over the tiles.  Per lane the projection and four clamped,
-//                            unconditional tap loads of hit.y, length, position and shading_normal (with ids also the id): no film or half
-//                            loads at all.  A lane outside the frame runs the clamped pixel of the frame's edge and is selected away.
-//                            Validity is decided by selects, never by branches around loads.  The tile's minimum is a xor butterfly over
-//                            32, 16, .. 1 lanes (fminf of values that are >= 0 or +inf commutes and associates: every lane holds the
-//                            minimum); lane 0 writes the tile's two words.  MOTION: 0 the static world, 1 the per-instance table
-//                            (mi355pt_motion.h), 2 the per-pixel records (mi355pt_flow.h).
+// for gfx950.  EXTENSION, no reference counterpart.
+//   budget_probe_kernel<CARRY, HAS_PREV_IDS>   the GEOMETRIC half of the temporal gather (the body of temporal_kernel in
+//                            pt_kernels_temporal.hip, restated here without the films — text of its own, because with the shared part
+//                            as functions the probe lost one to three waves per SIMD): one wave per 8x8 tile, lane =
+//                            pixel (lane & 7, lane >> 3) of the tile — adaptive_err_kernel's mapping —, four tiles per 256-thread block,
+//                            grid-stride over the tiles.  Per lane the projection and four clamped, unconditional tap loads of hit.y,
+//                            length, position and shading_normal (with ids also the id): no film or half loads at all.  A lane outside
+//                            the frame runs the clamped pixel of the frame's edge and is selected away.  Validity is decided by selects
+//                            on loaded values: a branch the compiler forms stands around arithmetic only, never around a load.  The
+//                            tile's minimum is a xor butterfly over 32, 16, .. 1 lanes (fminf of values that are >= 0 or +inf commutes
+//                            and associates: every lane holds the minimum); lane 0 writes the tile's two words.  CARRY, as
+//                            TemporalCarryDev::kind: 0 the static world, 1 the per-instance table (mi355pt_motion.h), 2 the per-pixel
+//                            records (mi355pt_flow.h).
 //   budget_fill_kernel       the probe without a previous frame: every P is 0, every tile gets budget_spp(0); no G-buffer is read.
 //   budget_select_kernel     one wave per tile: the flag "clamped tile_spp > level" for adaptive_compact_kernel, and H := F on the flagged
 //                            tiles' in-frame pixels — the copy adaptive_err_kernel does for its active tiles.
@@ -32,8 +35,8 @@ namespace {
 
 constexpr uint32_t BG_BLOCK = 256, BG_TILES_PER_BLOCK = BG_BLOCK / 64;
 
-template <int MOTION, bool HAS_PREV_IDS>
-__global__ __launch_bounds__(BG_BLOCK) void budget_probe_kernel(TemporalFrameDev cur, TemporalFrameDev prev, TemporalArgs a, BudgetCarryDev mv, BudgetTilesDev bt,
+template <int CARRY, bool HAS_PREV_IDS>
+__global__ __launch_bounds__(BG_BLOCK) void budget_probe_kernel(TemporalFrameDev cur, TemporalFrameDev prev, TemporalArgs a, TemporalCarryDev cv, BudgetTilesDev bt,
                                                                 float* __restrict__ pred, float* __restrict__ tile_len, uint32_t* __restrict__ tile_spp) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const int wm1 = (int)a.width - 1, hm1 = (int)a.height - 1;
@@ -47,22 +50,22 @@ __global__ __launch_bounds__(BG_BLOCK) void budget_probe_kernel(TemporalFrameDev
         // geometry of p, as the gather's (h == 0 makes NaNs and infinities: `ok` selects them away)
         uint32_t idc = 0u;
         float4 r0, r1, r2, r3, r4, r5;
-        if constexpr (MOTION == 2) {
-            const float4* const frec = (const float4*)(mv.flow + p);
+        if constexpr (CARRY == 2) {
+            const float4* const frec = (const float4*)(cv.flow + p);
             r0 = frec[0]; r1 = frec[1];
-            if constexpr (HAS_PREV_IDS) idc = mv.ids_cur[p];
-        } else if constexpr (MOTION == 1) {
-            idc = mv.ids_cur[p];
-            const float4* const mrec = (const float4*)(mv.table + (idc < mv.last_entry ? idc : mv.last_entry));
+            if constexpr (HAS_PREV_IDS) idc = cv.ids_cur[p];
+        } else if constexpr (CARRY == 1) {
+            idc = cv.ids_cur[p];
+            const float4* const mrec = (const float4*)(cv.table + (idc < cv.last_entry ? idc : cv.last_entry));
             r0 = mrec[0]; r1 = mrec[1]; r2 = mrec[2]; r3 = mrec[3]; r4 = mrec[4]; r5 = mrec[5];
         }
         const float3u P = tp_load3(cur.position, p), N = tp_load3(cur.shading_normal, p);
         const float hx = cur.hit[3 * p], h = cur.hit[3 * p + 1];
         float Xx, Xy, Xz, nx, ny, nz;
-        if constexpr (MOTION == 2) {
+        if constexpr (CARRY == 2) {
             Xx = P.x / h + r0.x; Xy = P.y / h + r0.y; Xz = P.z / h + r0.z;                                           // Xp = X + d
             nx = (2.0f * (N.x / h) - 1.0f) + r1.x; ny = (2.0f * (N.y / h) - 1.0f) + r1.y; nz = (2.0f * (N.z / h) - 1.0f) + r1.z;
-        } else if constexpr (MOTION == 1) {
+        } else if constexpr (CARRY == 1) {
             // a = r0.xyzw r1.xyzw r2.x,  b = r2.yzw,  n = r3.xyzw r4.xyzw r5.x: Xp = a X + b, nrm = n nrm
             const float X0 = P.x / h, X1 = P.y / h, X2 = P.z / h;
             Xx = tp_dot(r0.x, r0.y, r0.z, X0, X1, X2) + r2.y; Xy = tp_dot(r0.w, r1.x, r1.y, X0, X1, X2) + r2.z;
@@ -102,7 +105,7 @@ __global__ __launch_bounds__(BG_BLOCK) void budget_probe_kernel(TemporalFrameDev
             hq[k] = prev.hit[3 * q + 1];
             len[k] = prev.length[q];
             Pq[k] = tp_load3(prev.position, q); Nq[k] = tp_load3(prev.shading_normal, q);
-            if constexpr (MOTION != 0 && HAS_PREV_IDS) idq[k] = mv.ids_prev[q];
+            if constexpr (CARRY != 0 && HAS_PREV_IDS) idq[k] = cv.ids_prev[q];
         }
         // A tap's values are needed only where the tests before them pass, and the compiler would sink their loads into a branch on that
         // (it turns a select whose operand is a load into control flow).  As the gather's tp_keep: the loaded values are pinned here, after
@@ -111,7 +114,7 @@ __global__ __launch_bounds__(BG_BLOCK) void budget_probe_kernel(TemporalFrameDev
         for (int k = 0; k < 4; ++k) {
             tp_keep(Pq[k]); tp_keep(Nq[k]);
             asm volatile("" : "+v"(hq[k]), "+v"(len[k]));
-            if constexpr (MOTION != 0 && HAS_PREV_IDS) asm volatile("" : "+v"(idq[k]));
+            if constexpr (CARRY != 0 && HAS_PREV_IDS) asm volatile("" : "+v"(idq[k]));
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -119,7 +122,7 @@ __global__ __launch_bounds__(BG_BLOCK) void budget_probe_kernel(TemporalFrameDev
             const float pd = fabsf(tp_dot(ex, ey, ez, nx, ny, nz));
             const float qnx = 2.0f * (Nq[k].x / hq[k]) - 1.0f, qny = 2.0f * (Nq[k].y / hq[k]) - 1.0f, qnz = 2.0f * (Nq[k].z / hq[k]) - 1.0f;
             const float nd = tp_dot(nx, ny, nz, qnx, qny, qnz);
-            const bool same = !(MOTION != 0 && HAS_PREV_IDS) || idq[k] == idc;      // the tap shows the pixel's instance (always, without the previous frame's ids)
+            const bool same = !(CARRY != 0 && HAS_PREV_IDS) || idq[k] == idc;      // the tap shows the pixel's instance (always, without the previous frame's ids)
             const bool valid = ok && inside[k] && hq[k] > 0.0f && len[k] > 0.0f && pd <= tol && nd >= a.normal_cos && same;
             w[k] = valid ? bw[k] : 0.0f;
             len[k] = valid ? len[k] : 0.0f;
@@ -195,7 +198,7 @@ uint32_t pixel_grid(uint32_t width, uint32_t height) { return (uint32_t)std::min
 }  // namespace
 
 // ---- host side (declared in launch.hpp; called from api_budget.cpp, which has checked every argument) ----
-hipError_t launch_budget_probe(const TemporalFrameDev& cur, const TemporalFrameDev* prev, TemporalArgs args, const BudgetCarryDev& carry, BudgetTilesDev tiles,
+hipError_t launch_budget_probe(const TemporalFrameDev& cur, const TemporalFrameDev* prev, TemporalArgs args, const TemporalCarryDev& carry, BudgetTilesDev tiles,
                                float* d_pred, float* d_tile_len, uint32_t* d_tile_spp, hipStream_t stream) {
     tiles.n_tiles = adaptive_tile_count(args.width, args.height);
     tiles.tiles_x = (args.width + 7u) / 8u;
@@ -207,11 +210,11 @@ hipError_t launch_budget_probe(const TemporalFrameDev& cur, const TemporalFrameD
     }
     const dim3 grid(tile_grid(tiles.n_tiles)), block(BG_BLOCK);
     const bool ids = carry.ids_prev != nullptr;
-#define PT_BG_LAUNCH(MOTION, IDS) \
-    hipLaunchKernelGGL((budget_probe_kernel<MOTION, IDS>), grid, block, 0, stream, cur, *prev, args, carry, tiles, d_pred, d_tile_len, d_tile_spp)
-    if (carry.flow) { if (ids) PT_BG_LAUNCH(2, true); else PT_BG_LAUNCH(2, false); }
-    else if (carry.table) { if (ids) PT_BG_LAUNCH(1, true); else PT_BG_LAUNCH(1, false); }
-    else PT_BG_LAUNCH(0, false);
+#define PT_BG_LAUNCH(CARRY, IDS) \
+    hipLaunchKernelGGL((budget_probe_kernel<CARRY, IDS>), grid, block, 0, stream, cur, *prev, args, carry, tiles, d_pred, d_tile_len, d_tile_spp)
+    if (carry.kind == CARRY_FLOW) { if (ids) PT_BG_LAUNCH(CARRY_FLOW, true); else PT_BG_LAUNCH(CARRY_FLOW, false); }
+    else if (carry.kind == CARRY_TABLE) { if (ids) PT_BG_LAUNCH(CARRY_TABLE, true); else PT_BG_LAUNCH(CARRY_TABLE, false); }
+    else PT_BG_LAUNCH(CARRY_STATIC, false);
 #undef PT_BG_LAUNCH
     return hipGetLastError();
 }

@@ -1,10 +1,10 @@
 // The rectified temporal accumulation of include/mi355pt_temporal_rectify.h as two HIP kernels for gfx950.  EXTENSION, no reference
 // counterpart.  Both run one thread per pixel on the grid of the temporal unit (64 x 4 blocks), without atomics and without scratch memory.
 //
-// 1. temporal_gather_kernel: the gather of pt_kernels_temporal.hip (the same body, pt_temporal_gather.inc) with another epilogue: instead
-//    of blending it writes hist1, hist2 (hist, 0 without a half film) and "L, or 0 without history" as one 32-byte record per pixel — two
+// 1. pt_kernels_temporal.hip's temporal_kernel<.., RECORD = true>: the gather of the accumulation with another epilogue: instead of
+//    blending it writes hist1, hist2 (hist, 0 without a half film) and "L, or 0 without history" as one 32-byte record per pixel — two
 //    16-byte stores — into the caller's scratch.  It does not read the current film.
-// 2. temporal_rectify_kernel: an LDS stencil.  A workgroup loads its 64 x 4 tile plus an apron of RADIUS pixels (indices clamped to the
+// 2. temporal_rectify_kernel, this unit: an LDS stencil.  A workgroup loads its 64 x 4 tile plus an apron of RADIUS pixels (indices clamped to the
 //    frame; a pixel outside it is no member) and keeps per tile pixel the cleaned current value v, the history mean g (both 0 for a
 //    non-member) and the membership flag as PLANES of (64 + 2 RADIUS) x (4 + 2 RADIUS) words: the 64 lanes of a wave then read consecutive
 //    words at every window offset.  After the barrier each thread forms the window sums in the header's order — row sums left to right
@@ -25,46 +25,6 @@
 namespace pt {
 
 namespace {
-
-template <bool HAS_HALF, bool HAS_PREV>
-__global__ __launch_bounds__(DN_BLOCK_X * DN_BLOCK_Y) void temporal_gather_kernel(TemporalFrameDev cur, TemporalFrameDev prev, TemporalArgs a,
-                                                                                  float4* __restrict__ record) {
-#define PT_TP_RECORD true
-#define PT_TP_MOTION false
-#include "pt_temporal_gather.inc"
-#undef PT_TP_MOTION
-#undef PT_TP_RECORD
-
-    tp_write_record(record, p, m1, m2, L);
-}
-
-// The motion-aware twin of the gather (include/mi355pt_motion.h): the same body with PT_TP_MOTION, the same record.  The rectifying
-// kernel below reads the records of either
-template <bool HAS_HALF, bool HAS_PREV, bool HAS_PREV_IDS>
-__global__ __launch_bounds__(DN_BLOCK_X * DN_BLOCK_Y) void temporal_gather_motion_kernel(TemporalFrameDev cur, TemporalFrameDev prev, TemporalArgs a,
-                                                                                         MotionArgs mo, float4* __restrict__ record) {
-#define PT_TP_RECORD true
-#define PT_TP_MOTION true
-#include "pt_temporal_gather.inc"
-#undef PT_TP_MOTION
-#undef PT_TP_RECORD
-
-    tp_write_record(record, p, m1, m2, L);
-}
-
-// the cleaned current values of pixel p: (c1, c2) with a half film, (c, 0) without — as the gather's body forms them
-template <bool HAS_HALF>
-__device__ __forceinline__ void tr_current(const TemporalFrameDev& cur, const TemporalArgs& a, size_t p, float c1[3], float c2[3]) {
-    const float3u B = tp_load3(cur.film, p);
-    c2[0] = 0.0f; c2[1] = 0.0f; c2[2] = 0.0f;
-    if constexpr (HAS_HALF) {
-        const float3u H = tp_load3(cur.half, p);
-        c1[0] = dn_clean(H.x, a.half_spp); c1[1] = dn_clean(H.y, a.half_spp); c1[2] = dn_clean(H.z, a.half_spp);
-        c2[0] = dn_clean(B.x - H.x, a.half_spp); c2[1] = dn_clean(B.y - H.y, a.half_spp); c2[2] = dn_clean(B.z - H.z, a.half_spp);
-    } else {
-        c1[0] = dn_clean(B.x, a.spp); c1[1] = dn_clean(B.y, a.spp); c1[2] = dn_clean(B.z, a.spp);
-    }
-}
 
 constexpr int TR_PLANES = 7;       // v.x v.y v.z  g.x g.y g.z  member
 
@@ -87,7 +47,7 @@ __global__ __launch_bounds__(DN_BLOCK_X * DN_BLOCK_Y) void temporal_rectify_kern
         const size_t q = (size_t)cy * a.width + (size_t)cx;
         const float4 ra = record[2 * q], rb = record[2 * q + 1];
         float c1[3], c2[3];
-        tr_current<HAS_HALF>(cur, a, q, c1, c2);
+        tp_current<HAS_HALF>(cur, a, q, c1, c2);
         const bool member = inside && rb.z > 0.0f;
         const float h1[3] = {ra.x, ra.y, ra.z}, h2[3] = {ra.w, rb.x, rb.y};
 #pragma unroll
@@ -107,7 +67,7 @@ __global__ __launch_bounds__(DN_BLOCK_X * DN_BLOCK_Y) void temporal_rectify_kern
     // the pixel's own values
     const float4 ra = record[2 * p], rb = record[2 * p + 1];
     float c1[3], c2[3];
-    tr_current<HAS_HALF>(cur, a, p, c1, c2);
+    tp_current<HAS_HALF>(cur, a, p, c1, c2);
     const float h1[3] = {ra.x, ra.y, ra.z}, h2[3] = {ra.w, rb.x, rb.y};
     const bool has = rb.z > 0.0f;
     const float alpha = 1.0f / rb.z;
@@ -159,13 +119,7 @@ __global__ __launch_bounds__(DN_BLOCK_X * DN_BLOCK_Y) void temporal_rectify_kern
         }
     }
 
-    out_length[p] = has ? rb.z : 1.0f;
-    if constexpr (HAS_HALF) {
-        out_half[3 * p] = m1[0]; out_half[3 * p + 1] = m1[1]; out_half[3 * p + 2] = m1[2];
-        out_film[3 * p] = m1[0] + m2[0]; out_film[3 * p + 1] = m1[1] + m2[1]; out_film[3 * p + 2] = m1[2] + m2[2];
-    } else {
-        out_film[3 * p] = m1[0]; out_film[3 * p + 1] = m1[1]; out_film[3 * p + 2] = m1[2];
-    }
+    tp_write_blend<HAS_HALF>(out_film, out_half, out_length, p, m1, m2, has ? rb.z : 1.0f);
 }
 
 template <bool HAS_HALF>
@@ -182,14 +136,7 @@ void launch_rectify_radius(uint32_t radius, const TpShape& sh, hipStream_t strea
 }  // namespace
 
 // ---- host side (declared in launch.hpp; called from api_temporal.cpp's driver, which has checked every argument) ----
-hipError_t launch_temporal_gather(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, void* d_scratch, hipStream_t stream) {
-    const TpShape sh = tp_shape(args);
-    if (cur.half != nullptr) hipLaunchKernelGGL((temporal_gather_kernel<true, true>), sh.grid, sh.block, 0, stream, cur, prev, args, (float4*)d_scratch);
-    else hipLaunchKernelGGL((temporal_gather_kernel<false, true>), sh.grid, sh.block, 0, stream, cur, prev, args, (float4*)d_scratch);
-    return hipGetLastError();
-}
-
-// the second launch of every rectified form, over the records one of the three gathers has written
+// the second launch of every rectified form, over the records launch_temporal_gather has written
 hipError_t launch_temporal_rectify_blend(const TemporalFrameDev& cur, TemporalArgs args, uint32_t radius, float gamma, const void* d_scratch, float* d_out_film,
                                          float* d_out_half, float* d_out_length, hipStream_t stream) {
     if (radius < 1 || radius > 3) return hipErrorInvalidValue;
@@ -197,16 +144,6 @@ hipError_t launch_temporal_rectify_blend(const TemporalFrameDev& cur, TemporalAr
     const float4* record = (const float4*)d_scratch;
     if (cur.half != nullptr) launch_rectify_radius<true>(radius, sh, stream, cur, args, gamma, record, d_out_film, d_out_half, d_out_length);
     else launch_rectify_radius<false>(radius, sh, stream, cur, args, gamma, record, d_out_film, d_out_half, d_out_length);
-    return hipGetLastError();
-}
-
-hipError_t launch_temporal_gather_motion(const TemporalFrameDev& cur, const TemporalFrameDev& prev, TemporalArgs args, const MotionArgs& motion, void* d_scratch,
-                                         hipStream_t stream) {
-    const TpShape sh = tp_shape(args);
-    tp_dispatch(cur.half != nullptr, motion.ids_prev != nullptr, [&](auto half, auto ids) {
-        hipLaunchKernelGGL((temporal_gather_motion_kernel<decltype(half)::value, true, decltype(ids)::value>), sh.grid, sh.block, 0, stream, cur, prev, args, motion,
-                           (float4*)d_scratch);
-    });
     return hipGetLastError();
 }
 

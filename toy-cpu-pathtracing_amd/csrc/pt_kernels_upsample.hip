@@ -6,7 +6,7 @@
 //   upsample_kernel          the DIRECT GATHER, built first: a full pixel reads its own guide values and the 2 x 2 low taps around it from
 //                            global memory.  The taps' loads are UNCONDITIONAL, at indices clamped to the low frame: whether a tap is valid (in
 //                            frame, same surface: plane distance, normal, emitter share; background to background) is a select on the loaded
-//                            values, never a branch around loads — as pt_temporal_gather.inc, whose helpers this unit takes.  A low tap is read
+//                            values, never a branch around loads — as pt_kernels_temporal.hip, whose helpers (pt_temporal_gather.hpp) this unit takes.  A low tap is read
 //                            by up to 16 full pixels, and each of them repeats the tap's divisions.
 //   upsample_staged_kernel   the block's 34 x 4 low pixels and what is derived from them, once, in LDS.  tools/upsample_rate.py found the direct
 //                            gather at 1.9 - 2.7 times a copy of its compulsory bytes, the staged form at 1.25 - 1.43 times and 0.54 - 0.68 of
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(DN_BLOCK_X * DN_BLOCK_Y) void upsample_kernel(const
         f[k] = tp_load3(low_film, q);
         if constexpr (HAS_HALF) g[k] = tp_load3(low_half, q);
     }
-    // the compiler would sink the loads of values that only a valid tap needs into a branch on its validity (pt_temporal_gather.inc):
+    // the compiler would sink the loads of values that only a valid tap needs into a branch on its validity (pt_kernels_temporal.hip):
     // tp_keep pins them here, after all four taps' loads have been issued
 #pragma unroll
     for (int k = 0; k < 4; ++k) {

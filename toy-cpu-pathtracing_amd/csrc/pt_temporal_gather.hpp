@@ -1,8 +1,8 @@
-// What the three units of the temporal reprojection share beside the gather's body (pt_temporal_gather.inc): pt_kernels_temporal.hip blends
-// the gathered history with the current frame at once (include/mi355pt_temporal.h), pt_kernels_temporal_rectify.hip writes it to a scratch
-// record per pixel and rectifies it against the current frame's local mean in a second launch (include/mi355pt_temporal_rectify.h),
-// pt_kernels_temporal_flow.hip does either with a motion record per pixel (include/mi355pt_flow.h).  Device helpers, the record epilogue of
-// the gather's body (the blend's stays spelled out in its kernels: as a function it changes their schedule), and the launch shape and template dispatch of the units' host launchers.
+// What the units of the temporal reprojection share beside the gather itself (the body of temporal_kernel in pt_kernels_temporal.hip, which
+// blends the gathered history with the current frame at once — include/mi355pt_temporal.h — or writes it to a scratch record per pixel
+// that pt_kernels_temporal_rectify.hip rectifies against the current frame's local mean in a second launch —
+// include/mi355pt_temporal_rectify.h).  Device helpers, the cleaned current values, the two store epilogues, and the launch shape and
+// template dispatch of the units' host launchers.  pt_kernels_budget.hip and pt_kernels_upsample.hip take the device helpers too.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,14 +25,41 @@ __device__ __forceinline__ float3u tp_load3(const float* __restrict__ film, size
 __device__ __forceinline__ void tp_keep(float3u& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z)); }
 __device__ __forceinline__ float tp_dot(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
 
-// the gather's epilogue: pixel p's scratch record, two 16-byte stores
+// the cleaned current values of pixel p: (c1, c2) with a half film, (c, 0) without
+template <bool HAS_HALF>
+__device__ __forceinline__ void tp_current(const TemporalFrameDev& cur, const TemporalArgs& a, size_t p, float c1[3], float c2[3]) {
+    const float3u B = tp_load3(cur.film, p);
+    c2[0] = 0.0f; c2[1] = 0.0f; c2[2] = 0.0f;
+    if constexpr (HAS_HALF) {
+        const float3u H = tp_load3(cur.half, p);
+        c1[0] = dn_clean(H.x, a.half_spp); c1[1] = dn_clean(H.y, a.half_spp); c1[2] = dn_clean(H.z, a.half_spp);
+        c2[0] = dn_clean(B.x - H.x, a.half_spp); c2[1] = dn_clean(B.y - H.y, a.half_spp); c2[2] = dn_clean(B.z - H.z, a.half_spp);
+    } else {
+        c1[0] = dn_clean(B.x, a.spp); c1[1] = dn_clean(B.y, a.spp); c1[2] = dn_clean(B.z, a.spp);
+    }
+}
+
+// ---- the two store epilogues ----
+// the blend's: pixel p of the accumulated films (out_half with a half film only) and of the history length
+template <bool HAS_HALF>
+__device__ __forceinline__ void tp_write_blend(float* __restrict__ out_film, float* __restrict__ out_half, float* __restrict__ out_length, size_t p,
+                                               const float m1[3], const float m2[3], float L) {
+    out_length[p] = L;
+    if constexpr (HAS_HALF) {
+        out_half[3 * p] = m1[0]; out_half[3 * p + 1] = m1[1]; out_half[3 * p + 2] = m1[2];
+        out_film[3 * p] = m1[0] + m2[0]; out_film[3 * p + 1] = m1[1] + m2[1]; out_film[3 * p + 2] = m1[2] + m2[2];
+    } else {
+        out_film[3 * p] = m1[0]; out_film[3 * p + 1] = m1[1]; out_film[3 * p + 2] = m1[2];
+    }
+}
+// the gather's: pixel p's scratch record, two 16-byte stores
 static_assert(TEMPORAL_RECTIFY_RECORD_BYTES == 2 * sizeof(float4), "a scratch record is two float4");
 __device__ __forceinline__ void tp_write_record(float4* record, size_t p, const float m1[3], const float m2[3], float L) {
     record[2 * p] = make_float4(m1[0], m1[1], m1[2], m2[0]);
     record[2 * p + 1] = make_float4(m2[1], m2[2], L, 0.0f);
 }
 
-// ---- host side: what every launcher of the three units starts with ----
+// ---- host side: what the launchers of the temporal units start with ----
 // the launch shape of all their kernels, one thread per pixel; fills args.blocks_x, which the kernels find their block with
 struct TpShape { dim3 grid, block; };
 inline TpShape tp_shape(TemporalArgs& args) {
