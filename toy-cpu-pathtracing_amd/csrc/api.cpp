@@ -145,7 +145,10 @@ static int launch_range(const mi355pt_scene* s, const mi355pt_camera* cam, const
     if (d_list) set_tile_list(dp, d_list);
     dp.stats_mode = p->collect_stats;
     // (the AOV kernel counts its samples, primary rays and hits in every launch that is given a stats block)
-    return timed_launch(lc, slot, stream, stats, want_stats || aov, [&](unsigned* d_counter, DevStats* d_stats) {
+    // (a production launch that is given a stats block after mi355pt_debug_unlock(1) counts the rays it did not trace — path_end_plan.hpp — into
+    // wave_steps[7]; every other production launch passes its kernel no stats pointer)
+    const bool count_ends = stats && !want_stats && !aov && g_debug_unlocked;
+    return timed_launch(lc, slot, stream, stats, want_stats || aov || count_ends, [&](unsigned* d_counter, DevStats* d_stats) {
         if ((rc = grow_device_buffer(&lc->d_partial, &lc->partial_bytes, plan.partial_floats * sizeof(float), stream))) return rc;
         // (one stream at a time per scene, like d_partial: the queues are empty between launches, so consecutive launches share them)
         // (sized by what the selected kernel's queues use per wave; the buffer only grows: a context that launches several kernels holds the largest)
@@ -158,8 +161,9 @@ static int launch_range(const mi355pt_scene* s, const mi355pt_camera* cam, const
             dev.cam_lists = use_camera_lists(key, dp.block_log2, camera_lists_enabled()) ? 1u : 0u;
             dev.queue_stage = use_queue_staging(key, queue_staging_enabled()) ? 1u : 0u;
             dev.light_queue = use_light_queue(key, light_queue_enabled()) ? 1u : 0u;
+            dev.early_path_end = use_early_path_end(key, early_path_end_enabled()) ? 1u : 0u;
             HIP_TRY(launch_pt(key, dev, dc, dp, plan.n_tiles,
-                              lc->d_hash, d_accum, lc->d_partial, d_counter, d_list ? nullptr : d_stats, plan.grid, stream, pout, lc->d_defer));
+                              lc->d_hash, d_accum, lc->d_partial, d_counter, (want_stats && !d_list) || count_ends ? d_stats : nullptr, plan.grid, stream, pout, lc->d_defer));
         }
         return (int)MI355PT_OK;
     });

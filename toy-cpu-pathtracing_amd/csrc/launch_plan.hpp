@@ -242,4 +242,13 @@ inline bool use_light_queue(const KernelKey& key, bool enabled) { return enabled
 // the host-side switch, read per launch: MI355PT_NO_LIGHT_QUEUE=1 (any value but "0") evaluates every emitter hit in place; default on
 inline bool light_queue_enabled() { const char* e = getenv("MI355PT_NO_LIGHT_QUEUE"); return !(e && e[0] != '\0' && !(e[0] == '0' && e[1] == '\0')); }
 
+// ---- the early end of roulette-doomed paths (path_end_plan.hpp, pt_kernel_body.inc) ----
+// Do the kernels with one tail queue end a doomed path without tracing its last ray when that ray cannot matter (DevScene::early_path_end)?
+// With 0 they take the same decision in the same place — the roulette draw moved to the pass with it — and trace every ray: the control for
+// the samples' values, not the speed of a build without the code.  The kernels without the code (two queues, the instrumented ones, the
+// plain path tracer) ignore the flag.  `enabled`: early_path_end_enabled().
+inline bool use_early_path_end(const KernelKey& key, bool enabled) { return enabled && !key.stats; }
+// the host-side switch, read per launch: MI355PT_NO_EARLY_PATH_END=1 (any value but "0") traces every ray; default on
+inline bool early_path_end_enabled() { const char* e = getenv("MI355PT_NO_EARLY_PATH_END"); return !(e && e[0] != '\0' && !(e[0] == '0' && e[1] == '\0')); }
+
 }  // namespace pt

@@ -244,9 +244,12 @@ struct DevScene {
     uint32_t n_envs;
     uint16_t queue_stage;         // 1: the kernels with one tail queue hand a pass its fresh records through LDS (tail_queue_plan.hpp).  0 in the lowered
                                   // scene; set per launch like cam_lists (launch_plan.hpp use_queue_staging)
-    uint16_t light_queue;         // 1: the kernels with one tail queue evaluate emitter hits 64 at a time from the wave's light-hit queue (pt_kernel.hpp);
-                                  // 0: in place.  0 in the lowered scene; set per launch (launch_plan.hpp use_light_queue).  (The two flags share one
-                                  // dword: DevScene keeps its size, and the kernels that read neither keep their code)
+    uint8_t light_queue;          // 1: the kernels with one tail queue evaluate emitter hits 64 at a time from the wave's light-hit queue (pt_kernel.hpp);
+                                  // 0: in place.  0 in the lowered scene; set per launch (launch_plan.hpp use_light_queue).  (The three flags share one
+                                  // dword: DevScene keeps its size, and the kernels that read none of them keep their code)
+    uint8_t early_path_end;       // 1: the same kernels end a roulette-doomed path without tracing its last ray when that ray cannot reach an emitter
+                                  // (path_end_plan.hpp); 0: the decision is taken, every ray is traced.  0 in the lowered scene; set per launch
+                                  // (launch_plan.hpp use_early_path_end)
 };
 
 struct DevCamera {

@@ -61,6 +61,7 @@
     unsigned long long tp[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long dvc[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // mi355pt_stats.divergence[4..11]
     unsigned long long t_loop0 = 0;
+    uint32_t n_early = 0u;                                          // wave-uniform: rays not traced (EARLY PATH END; the kernels with one tail queue)
     if (STATS) t_loop0 = __builtin_amdgcn_s_memtime();
 
     for (;;) {
@@ -335,7 +336,8 @@
                     ShadeCtx C0;
                     C0.cont = false;
                     if constexpr (LIGHTQ) {
-                        if (front && !lq_push && !lq_void) end_path = shade_vertex_head<STATS, FEAT, 3>(P, sc, prm, sctx, got, hit, sh, st, tsa, C0);
+                        // (PHASE 4: the roulette of this vertex was decided, draw included, by the pass that spawned the ray — EARLY PATH END below)
+                        if (front && !lq_push && !lq_void) end_path = shade_vertex_head<STATS, FEAT, 4>(P, sc, prm, sctx, got, hit, sh, st, tsa, C0);
                         if (lq_void) end_path = true;
                     } else {
                         if (front) end_path = shade_vertex_head<STATS, FEAT, 1>(P, sc, prm, sctx, got, hit, sh, st, tsa, C0);
@@ -428,6 +430,7 @@
                     if constexpr (STAGE) sp = tq_stage_pop(stage ? q_count - n_on1 : q_count, stage ? n_on1 : 0u, n1, r - n2);
                     q2_count -= n2; q_count -= n1;
                     bool ep = false;
+                    bool ended_early = false;                       // (one queue: this lane's path ended without its last ray, EARLY PATH END below)
                     if constexpr ((FEAT & FEAT_CC) != 0u) {
                         ShadeCtx C;
                         shade_ctx_idle_cc(C);
@@ -458,11 +461,43 @@
                         C.cont = false; C.need_cc = false; C.cc_fc = 0.0f;
                         shade_vertex_head<STATS, FEAT, 2>(P, sc, prm, sctx, true, hit, sh, st, tsa, C);
                         if (C.cont) ep = shade_vertex_tail<STATS, FEAT>(P, sc, prm, sctx, sh, st, tsb, C);
+                        // EARLY PATH END (path_end_plan.hpp).  The roulette and the depth test of the NEXT vertex read nothing the ray finds: the
+                        // decision is taken here, and the draw made here, at the dimension the front would have drawn at.  A doomed path's ray can
+                        // only add an emitter's radiance to L (or the NaN of a non-finite throughput): when it can do neither — no environment
+                        // light, the non-emitter term an exact zero, the ray past every area light's padded box; under NEE after a non-specular
+                        // sample an emitter adds nothing either — the path ends now, as one whose BSDF sample failed ends (`dying` below, if a
+                        // connection is pending).  Every other doomed path is traced and carries the decision to its front (PHASE 4).
+                        // sc.early_path_end == 0 (launch_plan.hpp use_early_path_end): same decision, same draw, every ray traced.
+                        if (C.cont && !ep) {
+                            const float p_next = path_end_pmax(P.T, P.pf, P.p_pdf);
+                            float ur = 0.0f;
+                            if (path_end_draws(p_next, prm.rr_gate)) ur = get_1d(P.smp, sctx);
+                            if (path_end_doomed(p_next, ur, prm.rr_gate, P.depth, prm.max_depth)) {
+                                P.depth |= PATH_DOOMED_BIT;
+                                bool skip = sc.early_path_end != 0u && sc.n_envs == 0u;
+                                if (skip && !emitter_hit_is_void<STATS>(prm, false, P.prev_spec)) {
+                                    const float w = (prm.strategy == 2u && !P.prev_spec) ? balance_heuristic(P.p_pdf, 0.0f) : 1.0f;   // the front's
+                                    skip = path_end_term_is_zero(P.T, w);
+                                    const float o[3] = {P.ro.x, P.ro.y, P.ro.z}, d[3] = {P.rd.x, P.rd.y, P.rd.z};
+                                    for (uint32_t li = 0u; li < sc.n_lights; ++li) {          // wave-uniform records
+                                        const float4* bx = (const float4*)light_box_of(sc.lights, sc.n_lights, li);
+                                        const float4 b0 = bx[0], b1 = bx[1];
+                                        const float lo[3] = {b0.x, b0.y, b0.z}, hi[3] = {b1.x, b1.y, b1.z};
+                                        if (light_box_may_reach(o, d, lo, hi, b0.w)) skip = false;
+                                    }
+                                }
+                                if (skip) { ep = true; ended_early = true; }
+                            }
+                        }
                     }
+                    if constexpr (STAGE) n_early += (uint32_t)__popcll(__ballot(ended_early));
                     park(P, take);
                     if (sh.on && sh.c[0] == 0.0f && sh.c[1] == 0.0f && sh.c[2] == 0.0f && sh.c[3] == 0.0f) sh.on = false;
                     if (!active) sh.on = false;
-                    if (take) { dying = sh.on && ep; if (dying) ep = false; }
+                    // (a path that ended early keeps its lane until the next front, connection or not, like the doomed path it was: a lane freed
+                    // here starts a camera path in the iteration that follows a pass, where no other lane is free — the hand-out, the Sobol
+                    // prefixes and the candidate test for a handful of lanes, every cycle.  Measured: with the lanes freed C2 LOSES 3.3 %)
+                    if (take) { dying = (sh.on && ep) || ended_early; if (dying) ep = false; }
                     if (take && ep) { finish_path(); active = false; }
                 }
             } else
@@ -598,3 +633,5 @@
         for (int i = 0; i < 8; ++i) atomicAdd(&stats->divergence[4 + i], dvc[i]);
     }
     if (STATS) flush_stats(stats, st);
+    // (a production launch is given a stats block only by a caller that asked for this count: api.cpp launch_range)
+    if (!STATS && n_early != 0u && stats != nullptr && lane == 0) atomicAdd(&stats->wave_steps[7], (unsigned long long)n_early);

@@ -2,6 +2,7 @@
 // device functions shared by the kernel variants in pt_kernels.hip.  All state lives in registers.
 #pragma once
 #include "launch.hpp"
+#include "path_end_plan.hpp"
 #include "pt_device.hpp"
 #include "pt_ggx.hpp"
 
@@ -419,6 +420,8 @@ PT_DEV void shade_ctx_idle_cc(ShadeCtx& C) {
 // (P, hit) compute exactly what 0 computes: the sampler's dimensions are consumed in the same order.
 // 3 = the front as in 1 for a caller that has taken the paths whose hit is on an emitter out (the kernels with the light-hit queue,
 // pt_kernel.hpp: emitter_hit is all such a path has left, and they call it themselves): no emitter code in the front at all.
+// 4 = 3 without the roulette draw: the pass that ran the previous vertex's tail has made it and taken the decision (path_end_plan.hpp); a
+// doomed path arrives with PATH_DOOMED_BIT in its depth, adds the term of its hit and ends.  What every kernel with the light-hit queue runs.
 // (PHASES 0 and 1 keep the emitter evaluation as the statements they were compiled from — emitter_contribution restates them —: calling
 // the function from here re-schedules every kernel without the queue, scratch +8 ... +68 B per lane on the gfx950 disassembly, and those
 // kernels are measured as they are.  A change to one side belongs on the other as well.)
@@ -486,11 +489,11 @@ PT_DEV bool shade_vertex_head(Path& P, const DevScene& sc, const DevParams& prm,
         // PHASE 1 (the front of the tail queue's vertex) knows the material TYPE from the hit (DevTri::pad[0], Hit::mclass) and needs the surface
         // for emitters only: every other lane skips the ten loads and the normalisations here — the back of the vertex computes the surface once
         Surface sf; const DevMaterial* mat = nullptr; uint32_t mtype;
-        if (PHASE == 1 || PHASE == 3) {
+        if (PHASE == 1 || PHASE == 3 || PHASE == 4) {
             mtype = hit.mclass & 7u;
             if (PHASE == 1 && mtype == MT_EMISSIVE) { sf = load_surface(sc, hit, rd); mat = sc.materials + sf.material; }
         } else { sf = load_surface(sc, hit, rd); mat = sc.materials + sf.material; mtype = mat->type; }
-        const bool emissive = PHASE != 2 && PHASE != 3 && mtype == MT_EMISSIVE;   // (PHASE 2: the path went on, so the surface is not an emitter; 3: the caller's word)
+        const bool emissive = PHASE != 2 && PHASE != 3 && PHASE != 4 && mtype == MT_EMISSIVE;   // (PHASE 2: the path went on, so the surface is not an emitter; 3, 4: the caller's word)
         float Le[4] = {0, 0, 0, 0};
         if constexpr (PHASE != 2) {
         if (emissive) {                                                      // evaluate_emissive_surface :54-73
@@ -572,6 +575,15 @@ PT_DEV bool shade_vertex_head(Path& P, const DevScene& sc, const DevParams& prm,
             for (int i = 0; i < 4; ++i) T[i] = T[i] * (pf[i] * tf);
             // apply_russian_roulette (:76-92)
             float p = fmaxf(fmaxf(fmaxf(fmaxf(-INFINITY, T[0]), T[1]), T[2]), T[3]);
+            if constexpr (PHASE == 4) {
+                // the pass that spawned the ray has taken this decision, and made the draw at this very dimension (path_end_plan.hpp): the
+                // path carries the outcome in its depth word.  A path that survives divides by p as below
+                if ((depth & PATH_DOOMED_BIT) != 0u) end_path = true;
+                else if (!(p >= prm.rr_gate) && p != 0.0f) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) T[i] = T[i] / p;
+                }
+            } else
             if (!(p >= prm.rr_gate)) {                                         // rr_gate = 1 (the reference) unless a test asks for slack
                 float ur = get_1d(smp, sctx);
                 if (ur < p) {
@@ -589,7 +601,7 @@ PT_DEV bool shade_vertex_head(Path& P, const DevScene& sc, const DevParams& prm,
             if (depth > prm.max_depth || emissive) end_path = true;           // as_bsdf_material() == None (:199-202)
         }
         }   // PHASE != 2
-        if (PHASE != 1 && PHASE != 3 && !end_path) {
+        if (PHASE != 1 && PHASE != 3 && PHASE != 4 && !end_path) {
             if (STATS) { st.bounces++; tsa = __builtin_amdgcn_s_memtime(); }
             Frame fr, fw_num;
             if constexpr (numeric_frames<FEAT>()) shading_frames_numeric(sf.ns, sf.tangent, fr, fw_num);

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "path_end_plan.hpp"
 #include "scene_lower.hpp"
 
 namespace pt {
@@ -58,7 +59,12 @@ int SceneImpl::upload(const LoweredScene& ls, std::string* err) {
     dev.tris = dev.tris_are_local ? dev.tris_local : dev.tris_render;
     if ((rc = upload_array(this, ls.cc_albedo, &dev.cc_albedo, err))) return rc;
     if ((rc = upload_array(this, ls.materials, &dev.materials, err))) return rc;
-    if ((rc = upload_array(this, ls.lights, &dev.lights, err))) return rc;
+    {   // the light records, and behind them one box record per light (path_end_plan.hpp light_boxes: what a doomed path's ray is tested against)
+        const std::vector<unsigned char> bytes = light_allocation(ls.lights, ls.light_tris, ls.dev.tri_shift);
+        const unsigned char* p = nullptr;
+        if ((rc = upload_array(this, bytes, &p, err))) return rc;
+        dev.lights = (const DevLight*)p;
+    }
     if ((rc = upload_array(this, ls.light_tris, &dev.light_tris, err))) return rc;
     if ((rc = upload_array(this, ls.light_uvs, &dev.light_uvs, err))) return rc;
     if ((rc = upload_array(this, ls.luts, &dev.luts, err))) return rc;

@@ -795,7 +795,7 @@ void lowering_digests(const LoweredScene& ls, const LowerReport& rep, std::vecto
     const DevScene& dev = ls.dev;
     put(dev.grid_org, 12); put(dev.grid_cell, 12); put(dev.tri_shift, 12); put(&dev.tris_are_local, 4); put(dev.shared_mw, 12); put(&dev.pad_mw, 4);
     put(&dev.n_nodes, 4); put(&dev.n_tris, 4); put(&dev.n_lights, 4); put(&dev.n_materials, 4); put(&dev.root, 4); put(&dev.root4, 4);
-    put(&dev.n_nodes4, 4); put(&dev.cam_lists, 4); put(&dev.n_envs, 4); put(&dev.queue_stage, 2); put(&dev.light_queue, 2);
+    put(&dev.n_nodes4, 4); put(&dev.cam_lists, 4); put(&dev.n_envs, 4); put(&dev.queue_stage, 2); put(&dev.light_queue, 1); put(&dev.early_path_end, 1);
     const uint32_t feat = ls.features; const uint64_t ndeg = rep.n_degenerate, nn4 = dev.n_nodes4; const int32_t depth = rep.bvh_depth, need = rep.stack_need;
     put(&feat, 4); put(&ndeg, 8); put(&depth, 4); put(&nn4, 8); put(&need, 4); put(rep.collapse_method, std::strlen(rep.collapse_method));
     add("scalars", b.data(), b.size());

@@ -2,6 +2,8 @@
 // Host C++ only; the kernels are pt_kernels_rebase.hip (positions, both trees), pt_kernels_instances.hip (shading records, SAH cost), pt_kernels_deform.hip.
 #include "scene_update.hpp"
 
+#include "path_end_plan.hpp"
+
 namespace pt {
 
 SceneUpdateResult scene_update_step(SceneImpl* impl, const SceneUpdate& u) {
@@ -41,10 +43,19 @@ SceneUpdateResult scene_update_step(SceneImpl* impl, const SceneUpdate& u) {
         STEP_TRY("hipMemcpy", hipMemcpy(rb.d_deform_table, u.deform->table.data(), u.deform->table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
 
+    // (the light allocation is n_lights records and n_lights boxes, path_end_plan.hpp light_allocation_bytes: the copies below rely on the count)
+    if (!u.rec.lights.empty() && u.rec.lights.size() != (size_t)d.n_lights) return dropped("scene_update_step: light list changed since the build", hipErrorInvalidValue);
     // from here on the device records change
     STEP_TRY("hipMemcpy", hipMemcpy((void*)d.instances, u.rec.instances.data(), u.rec.instances.size() * sizeof(DevInstance), hipMemcpyHostToDevice));
     if (!u.rec.lights.empty()) STEP_TRY("hipMemcpy", hipMemcpy((void*)d.lights, u.rec.lights.data(), u.rec.lights.size() * sizeof(DevLight), hipMemcpyHostToDevice));
     if (!u.rec.light_tris.empty()) STEP_TRY("hipMemcpy", hipMemcpy((void*)d.light_tris, u.rec.light_tris.data(), u.rec.light_tris.size() * sizeof(DevLightTri), hipMemcpyHostToDevice));
+    if (!u.rec.lights.empty()) {
+        // the lights' boxes, behind the light records (scene.cpp upload): from the triangles written above, in the same step
+        const float zero[3] = {0.0f, 0.0f, 0.0f};
+        std::vector<float> boxes;
+        light_boxes(u.rec.lights, u.rec.light_tris, u.rec.tris_are_local ? u.rec.shared_iw : zero, &boxes);
+        STEP_TRY("hipMemcpy", hipMemcpy((void*)light_box_of(d.lights, d.n_lights, 0u), boxes.data(), boxes.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
     if (u.moved) {
         std::vector<uint32_t> bits((n_inst + 31) / 32, 0u);
         for (size_t i = 0; i < n_inst; ++i) if (u.moved[i]) bits[i >> 5] |= 1u << (i & 31u);
