@@ -1,10 +1,12 @@
 // CPU check of csrc/camera_candidates.hpp (tests/test_camera_candidates.py compiles and runs it; plain g++, -ffp-contract=off like the library).
 //
-//   camera_candidates_check <seed> <n_tris> <frame_w> <frame_h>
+//   camera_candidates_check <seed> <n_tris> <frame_w> <frame_h> [<dir_x> <dir_y> <dir_z> <up_x> <up_y> <up_z> <fov_deg>]
 //
 // Builds a seeded synthetic scene — random triangles all round the render-space origin (in front of the camera, behind it, straddling the
 // pyramids' side planes, a few large ones whose boxes contain the apex), a 4-wide tree over them with 1 .. 3 triangles per leaf, 2 .. 4 children
-// per node, unused slots as point boxes at +FLT_MAX and every box padded like the lowered tree's — and a random camera.  For a set of pixel
+// per node, unused slots as point boxes at +FLT_MAX and every box padded like the lowered tree's — and a random camera, or, with the seven
+// optional arguments, the camera launch_plan.hpp make_camera builds from that direction, up and field of view (tests/camera_cases.py: rolled,
+// along an axis, 1 to 170 degrees wide; the scene of the seed stays the same).  For a set of pixel
 // rectangles (frame corners, frame edges, interior; 1x1 up to 8x8) it walks the tree with the header and shoots camera rays with
 // regen_path's arithmetic through the rectangle's corners, edges and interior.  Every triangle a brute-force loop of the kernels' watertight
 // test (restated below from pt_device.hpp intersect_triangle<false>, limit FLT_MAX) hits must be in the rectangle's list.  With the exact
@@ -19,6 +21,7 @@
 #include <vector>
 
 #include "camera_candidates.hpp"
+#include "launch_plan.hpp"
 
 using namespace pt;
 
@@ -134,7 +137,10 @@ struct Builder {
 #define FAIL(...) do { std::printf(__VA_ARGS__); std::printf("\n"); return 1; } while (0)
 
 int main(int argc, char** argv) {
-    if (argc != 5) { std::fprintf(stderr, "usage: %s <seed> <n_tris> <frame_w> <frame_h>\n", argv[0]); return 2; }
+    if (argc != 5 && argc != 12) {
+        std::fprintf(stderr, "usage: %s <seed> <n_tris> <frame_w> <frame_h> [<dir_x> <dir_y> <dir_z> <up_x> <up_y> <up_z> <fov_deg>]\n", argv[0]);
+        return 2;
+    }
     const uint32_t seed = (uint32_t)std::atoi(argv[1]), n_tris = (uint32_t)std::atoi(argv[2]), W = (uint32_t)std::atoi(argv[3]), H = (uint32_t)std::atoi(argv[4]);
     std::mt19937 rng(seed);
     std::uniform_real_distribution<float> U(0.0f, 1.0f);
@@ -148,6 +154,12 @@ int main(int argc, char** argv) {
         cam.s[0] = s.x; cam.s[1] = s.y; cam.s[2] = s.z; cam.u[0] = u.x; cam.u[1] = u.y; cam.u[2] = u.z; cam.f[0] = f.x; cam.f[1] = f.y; cam.f[2] = f.z;
         cam.tan_half_fov = std::tan((30.0f + 60.0f * U(rng)) * 0.5f * 3.14159265f / 180.0f);
         cam.aspect = (float)W / (float)H; cam.width = W; cam.height = H;
+    }
+    if (argc == 12) {                                                      // (after the random one, so that the seed's scene does not change)
+        mi355pt_camera c{};
+        for (int a = 0; a < 3; ++a) { c.direction[a] = (float)std::atof(argv[5 + a]); c.up[a] = (float)std::atof(argv[8 + a]); }
+        c.fov_deg = (float)std::atof(argv[11]); c.width = W; c.height = H;
+        cam = make_camera(&c);
     }
     // triangles all round the origin: small ones at every distance, every 16th a large one (its box may contain the apex)
     std::vector<DevTri> tris(n_tris);

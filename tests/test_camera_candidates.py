@@ -23,8 +23,9 @@ def build_checker(tmp_path_factory, name, extra):
     subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Werror"] + extra +
                    ["-I", os.path.join(ROOT, "toy-cpu-pathtracing_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tests", "camera_candidates_check.cpp")], check=True)
 
-    def run(seed, n_tris, w, h):
-        r = subprocess.run([exe, str(seed), str(n_tris), str(w), str(h)], capture_output=True, text=True)
+    def run(seed, n_tris, w, h, *camera):
+        """camera: nothing, or the seven optional arguments (direction, up, fov in degrees)"""
+        r = subprocess.run([exe, str(seed), str(n_tris), str(w), str(h)] + [repr(float(v)) for v in camera], capture_output=True, text=True)
         assert r.returncode == 0, r.stdout + r.stderr
         tag, *vals = r.stdout.split()
         assert tag == "ok", r.stdout
