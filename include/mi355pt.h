@@ -409,6 +409,15 @@ const char* mi355pt_version(void);
  * header, which this one always includes (ahead of the variance-guided denoiser's, which stays the last one). */
 #include "mi355pt_budget.h"
 
+/* ---------------- lights and materials of a built scene ---------------- */
+/* EXTENSION, no reference counterpart: mi355pt_material_edit, mi355pt_light_edit, mi355pt_env_edit, mi355pt_scene_edits,
+ * mi355pt_edit_result and mi355pt_scene_edit — new descriptions for materials, delta lights and environment lights of the built scene,
+ * applied in place: the small records lowered again with the lowering's own functions and uploaded into the existing allocations, one
+ * launch over the triangles' class words when a material changed its queue sort class, the feature set the kernel selector reads
+ * replaced.  No triangle and no box changes.  Declared in its own header, which this one always includes (ahead of the variance-guided
+ * denoiser's, which stays the last one). */
+#include "mi355pt_edit.h"
+
 /* ---------------- variance-guided denoiser ---------------- */
 /* EXTENSION, no reference counterpart: a second filter beside the one above, which it leaves as it is — mi355pt_denoise_var_params,
  * mi355pt_denoise_var_params_default, mi355pt_denoise_var_scratch_bytes, mi355pt_denoise_var_device and mi355pt_denoise_var: an a-trous

@@ -83,6 +83,11 @@ int mi355pt_scene_debug_set_instance_transform(mi355pt_scene* s, uint32_t instan
  * and its normalisation of the normals: the description update alone, so that mi355pt_scene_debug_pinned_digest and
  * mi355pt_scene_debug_pinned_export give the host form of a deformation without a device.  Refuses a built scene with MI355PT_E_INVALID. */
 int mi355pt_scene_debug_set_mesh_vertices(mi355pt_scene* s, const mi355pt_mesh_update* updates, uint32_t n);
+/* ... and mi355pt_scene_debug_apply_edits replaces material, delta-light and environment-light descriptions of such a scene, as
+ * mi355pt_scene_edit (include/mi355pt_edit.h) does on a built one, with that call's checks of the edits (ids, the add calls' validators,
+ * texture and LUT ids of the pin, non-finite values, singular light matrices): the description update alone, so that
+ * mi355pt_scene_debug_pinned_digest gives the host form of an edit without a device.  Refuses a built scene with MI355PT_E_INVALID. */
+int mi355pt_scene_debug_apply_edits(mi355pt_scene* s, const mi355pt_scene_edits* edits);
 /* The host form of the SAH cost mi355pt_scene_move_instances reports (csrc/instance_move_plan.hpp sah_cost_host): node records as
  * mi355pt_scene_export_bvh gives them, the entries of mi355pt_scene_debug_pinned_export.  No device. */
 int mi355pt_debug_sah_cost(const void* nodes, uint32_t n_nodes, int32_t root, const uint32_t* entries, uint32_t n_entries, float* out_cost);

@@ -77,6 +77,10 @@ namespace pt {
 extern bool g_debug_unlocked;      // mi355pt_debug_unlock: lets mi355pt_params.rr_gate_slack through
 void cie_cmf4(float out[470 * 4]);   // the CIE colour matching functions SceneImpl::build takes: [470][4] (xbar, ybar, zbar, 0) (api.cpp)
 int fail(int code, const std::string& msg);   // sets the thread's mi355pt_last_error (api.cpp) and returns `code`
+// api_scene.cpp: the validators mi355pt_scene_add_material / mi355pt_scene_add_delta_light share with mi355pt_scene_edit (scene_edit.cpp):
+// the descriptor as the description's record (the light's: its hidden emissive material), or the refusal's code with its text in *err
+int lower_material_desc(const SceneImpl& im, const mi355pt_material_desc& d, DevMaterial* out, std::string* err);
+int lower_light_desc(const SceneImpl& im, const mi355pt_light_desc& d, DevMaterial* hidden, std::string* err);
 #define HIP_TRY(expr)                                                                                   \
     do {                                                                                                \
         hipError_t _e = (expr);                                                                         \

@@ -8,6 +8,92 @@
 
 using namespace pt;
 
+// The ONE validator of a material descriptor: mi355pt_scene_add_material's and mi355pt_scene_edit's (scene_edit.cpp).  *out: the record of
+// the description (the build's finish_materials adds the texture descriptors and the coat table's offset); *err: the refusal's text
+int pt::lower_material_desc(const SceneImpl& im, const mi355pt_material_desc& d, DevMaterial* out, std::string* err) {
+    auto bad_rc = [&](int code, const std::string& msg) { *err = msg; return code; };
+    auto bad = [&](const char* msg) { return bad_rc(MI355PT_E_INVALID, msg); };
+    DevMaterial m{};
+    int rc;
+    m.type = d.type;
+    m.normal_tex = d.normal_tex; m.normal_flip_y = d.normal_flip_y; m.thin = d.thin;
+    m.intensity = d.intensity; m.roughness = d.roughness; m.metallic = d.metallic; m.ior = d.ior;
+    m.cc_ior = d.clearcoat_ior; m.cc_roughness = d.clearcoat_roughness; m.cc_thickness = d.clearcoat_thickness;
+    m.metallic_tex = m.roughness_tex = m.cc_thickness_tex = 0xffffffffu;
+    m.intensity_avg = d.intensity;
+    if (d.type == MI355PT_MAT_EMISSIVE && d.intensity_tex != MI355PT_NONE) {
+        // FloatParameter::texture intensity (emissive_material.rs:55-56,69-76): the device reads it at the hit / sampled uv through the
+        // material's metallic_tex slot; the light-pick weight uses ONE value, the texture at uv (0.5, 0.5), computed here with the device's
+        // bilinear arithmetic (texture/sampler.rs:81-107: red channel of the gamma-encoded texel / 255)
+        if (d.intensity_tex >= im.textures.size()) return bad("bad intensity texture id");
+        m.metallic_tex = d.intensity_tex;
+        const SceneImpl::Tex& t = im.textures[d.intensity_tex];
+        const float u = std::fabs(0.5f - std::trunc(0.5f)), v = 1.0f - std::fabs(0.5f - std::trunc(0.5f));
+        const float x = u * ((float)t.w - 1.0f), y = v * ((float)t.h - 1.0f);
+        const uint32_t x0 = (uint32_t)std::floor(x), y0 = (uint32_t)std::floor(y), x1 = std::min(x0 + 1u, t.w - 1u), y1 = std::min(y0 + 1u, t.h - 1u);
+        const float fx = x - (float)x0, fy = y - (float)y0;
+        auto red = [&](uint32_t xx, uint32_t yy) { return (float)t.rgb[((size_t)yy * t.w + xx) * 3] / 255.0f; };
+        const float top = red(x0, y0) * (1.0f - fx) + red(x1, y0) * fx, bottom = red(x0, y1) * (1.0f - fx) + red(x1, y1) * fx;
+        m.intensity_avg = top * (1.0f - fy) + bottom * fy;
+    }
+    if (d.type == MI355PT_MAT_CLEARCOAT && d.clearcoat_thickness_tex != MI355PT_NONE) {
+        if (d.clearcoat_thickness_tex >= im.textures.size()) return bad("bad clearcoat thickness texture id");
+        m.cc_thickness_tex = d.clearcoat_thickness_tex;
+    }
+    if (d.type == MI355PT_MAT_GLASS || d.type == MI355PT_MAT_PLASTIC) {   // roughness: FloatParameter (glass_material.rs:42, plastic_material.rs:43)
+        if (d.roughness_tex != MI355PT_NONE && d.roughness_tex >= im.textures.size()) return bad("bad roughness texture id");
+        m.roughness_tex = d.roughness_tex;
+    }
+    if (d.type == MI355PT_MAT_SIMPLE_PBR || d.type == MI355PT_MAT_CLEARCOAT || d.type == MI355PT_MAT_METAL) {
+        if ((d.metallic_tex != MI355PT_NONE && d.metallic_tex >= im.textures.size()) || (d.roughness_tex != MI355PT_NONE && d.roughness_tex >= im.textures.size()))
+            return bad("bad metallic/roughness texture id");
+        m.metallic_tex = d.type == MI355PT_MAT_METAL ? 0xffffffffu : d.metallic_tex; m.roughness_tex = d.roughness_tex;
+    }
+    if (d.normal_tex != MI355PT_NONE && d.normal_tex >= im.textures.size()) return bad("bad normal texture id");
+    switch (d.type) {
+        case MI355PT_MAT_LAMBERT:
+            if ((rc = im.lower_spectrum(d.color, &m.color, true, err))) return bad_rc(rc, *err);
+            break;
+        case MI355PT_MAT_EMISSIVE:
+            // SpectrumParameter::Texture radiance (emissive_material.rs:48-79): an sRGB texture of any SpectrumType, looked up at the hit / sampled uv
+            if ((rc = im.lower_spectrum(d.color, &m.color, 2, err))) return bad_rc(rc, "emissive radiance: " + *err);
+            break;
+        case MI355PT_MAT_GLASS:
+        case MI355PT_MAT_PLASTIC:
+            if ((rc = im.lower_spectrum(d.eta, &m.eta, false, err))) return bad_rc(rc, "eta: " + *err);
+            if ((rc = im.lower_spectrum(d.color, &m.color, d.type == MI355PT_MAT_PLASTIC, err))) return bad_rc(rc, *err);
+            break;
+        case MI355PT_MAT_CLEARCOAT:
+            if ((rc = im.lower_spectrum(d.color, &m.color, true, err))) return bad_rc(rc, *err);
+            if ((rc = im.lower_spectrum(d.clearcoat_tint, &m.cc_tint, true, err))) return bad_rc(rc, "clearcoat tint: " + *err);
+            break;
+        case MI355PT_MAT_SIMPLE_PBR:      // SimplePbrMaterial == the clearcoat material's base layer: thickness 0 takes exactly that path
+            m.type = MT_CLEARCOAT; m.cc_thickness = 0.0f; m.cc_ior = 1.5f; m.cc_roughness = 0.0f;
+            m.cc_tint.kind = SPK_CONSTANT; m.cc_tint.c[0] = 1.0f;
+            if ((rc = im.lower_spectrum(d.color, &m.color, true, err))) return bad_rc(rc, *err);
+            break;
+        case MI355PT_MAT_METAL:
+            if ((rc = im.lower_spectrum(d.eta, &m.eta, false, err))) return bad_rc(rc, "eta: " + *err);
+            if ((rc = im.lower_spectrum(d.k, &m.cc_tint, false, err))) return bad_rc(rc, "k: " + *err);
+            break;
+        default:
+            return bad("material type not implemented on the device yet");
+    }
+    *out = m;
+    return MI355PT_OK;
+}
+
+// ... and of a delta light's: the hidden emissive material that carries the light's spectrum with intensity 1
+int pt::lower_light_desc(const SceneImpl& im, const mi355pt_light_desc& d, DevMaterial* hidden, std::string* err) {
+    if (d.kind < MI355PT_LIGHT_POINT || d.kind > MI355PT_LIGHT_DIRECTIONAL) { *err = "bad light kind"; return MI355PT_E_INVALID; }
+    DevMaterial m{};
+    m.type = MT_EMISSIVE; m.normal_tex = 0xffffffffu; m.metallic_tex = m.roughness_tex = m.cc_thickness_tex = 0xffffffffu; m.intensity = 1.0f; m.intensity_avg = 1.0f;
+    std::string why;
+    if (int rc = im.lower_spectrum(d.spectrum, &m.color, false, &why)) { *err = "light spectrum: " + why; return rc; }
+    *hidden = m;
+    return MI355PT_OK;
+}
+
 extern "C" {
 
 int mi355pt_scene_create(mi355pt_scene** out) {
@@ -60,84 +146,17 @@ int mi355pt_scene_add_material(mi355pt_scene* s, const mi355pt_material_desc* d,
     SceneImpl& im = s->impl;
     DevMaterial m{};
     std::string err;
-    int rc;
-    m.type = d->type;
-    m.normal_tex = d->normal_tex; m.normal_flip_y = d->normal_flip_y; m.thin = d->thin;
-    m.intensity = d->intensity; m.roughness = d->roughness; m.metallic = d->metallic; m.ior = d->ior;
-    m.cc_ior = d->clearcoat_ior; m.cc_roughness = d->clearcoat_roughness; m.cc_thickness = d->clearcoat_thickness;
-    m.metallic_tex = m.roughness_tex = m.cc_thickness_tex = 0xffffffffu;
-    m.intensity_avg = d->intensity;
-    if (d->type == MI355PT_MAT_EMISSIVE && d->intensity_tex != MI355PT_NONE) {
-        // FloatParameter::texture intensity (emissive_material.rs:55-56,69-76): the device reads it at the hit / sampled uv through the
-        // material's metallic_tex slot; the light-pick weight uses ONE value, the texture at uv (0.5, 0.5), computed here with the device's
-        // bilinear arithmetic (texture/sampler.rs:81-107: red channel of the gamma-encoded texel / 255)
-        if (d->intensity_tex >= im.textures.size()) return fail(MI355PT_E_INVALID, "bad intensity texture id");
-        m.metallic_tex = d->intensity_tex;
-        const SceneImpl::Tex& t = im.textures[d->intensity_tex];
-        const float u = std::fabs(0.5f - std::trunc(0.5f)), v = 1.0f - std::fabs(0.5f - std::trunc(0.5f));
-        const float x = u * ((float)t.w - 1.0f), y = v * ((float)t.h - 1.0f);
-        const uint32_t x0 = (uint32_t)std::floor(x), y0 = (uint32_t)std::floor(y), x1 = std::min(x0 + 1u, t.w - 1u), y1 = std::min(y0 + 1u, t.h - 1u);
-        const float fx = x - (float)x0, fy = y - (float)y0;
-        auto red = [&](uint32_t xx, uint32_t yy) { return (float)t.rgb[((size_t)yy * t.w + xx) * 3] / 255.0f; };
-        const float top = red(x0, y0) * (1.0f - fx) + red(x1, y0) * fx, bottom = red(x0, y1) * (1.0f - fx) + red(x1, y1) * fx;
-        m.intensity_avg = top * (1.0f - fy) + bottom * fy;
-    }
-    if (d->type == MI355PT_MAT_CLEARCOAT && d->clearcoat_thickness_tex != MI355PT_NONE) {
-        if (d->clearcoat_thickness_tex >= im.textures.size()) return fail(MI355PT_E_INVALID, "bad clearcoat thickness texture id");
-        m.cc_thickness_tex = d->clearcoat_thickness_tex;
-    }
-    if (d->type == MI355PT_MAT_GLASS || d->type == MI355PT_MAT_PLASTIC) {   // roughness: FloatParameter (glass_material.rs:42, plastic_material.rs:43)
-        if (d->roughness_tex != MI355PT_NONE && d->roughness_tex >= im.textures.size()) return fail(MI355PT_E_INVALID, "bad roughness texture id");
-        m.roughness_tex = d->roughness_tex;
-    }
-    if (d->type == MI355PT_MAT_SIMPLE_PBR || d->type == MI355PT_MAT_CLEARCOAT || d->type == MI355PT_MAT_METAL) {
-        if ((d->metallic_tex != MI355PT_NONE && d->metallic_tex >= im.textures.size()) || (d->roughness_tex != MI355PT_NONE && d->roughness_tex >= im.textures.size()))
-            return fail(MI355PT_E_INVALID, "bad metallic/roughness texture id");
-        m.metallic_tex = d->type == MI355PT_MAT_METAL ? 0xffffffffu : d->metallic_tex; m.roughness_tex = d->roughness_tex;
-    }
-    if (d->normal_tex != MI355PT_NONE && d->normal_tex >= im.textures.size()) return fail(MI355PT_E_INVALID, "bad normal texture id");
-    switch (d->type) {
-        case MI355PT_MAT_LAMBERT:
-            if ((rc = im.lower_spectrum(d->color, &m.color, true, &err))) return fail(rc, err);
-            break;
-        case MI355PT_MAT_EMISSIVE:
-            // SpectrumParameter::Texture radiance (emissive_material.rs:48-79): an sRGB texture of any SpectrumType, looked up at the hit / sampled uv
-            if ((rc = im.lower_spectrum(d->color, &m.color, 2, &err))) return fail(rc, "emissive radiance: " + err);
-            break;
-        case MI355PT_MAT_GLASS:
-        case MI355PT_MAT_PLASTIC:
-            if ((rc = im.lower_spectrum(d->eta, &m.eta, false, &err))) return fail(rc, "eta: " + err);
-            if ((rc = im.lower_spectrum(d->color, &m.color, d->type == MI355PT_MAT_PLASTIC, &err))) return fail(rc, err);
-            break;
-        case MI355PT_MAT_CLEARCOAT:
-            if ((rc = im.lower_spectrum(d->color, &m.color, true, &err))) return fail(rc, err);
-            if ((rc = im.lower_spectrum(d->clearcoat_tint, &m.cc_tint, true, &err))) return fail(rc, "clearcoat tint: " + err);
-            break;
-        case MI355PT_MAT_SIMPLE_PBR:      // SimplePbrMaterial == the clearcoat material's base layer: thickness 0 takes exactly that path
-            m.type = MT_CLEARCOAT; m.cc_thickness = 0.0f; m.cc_ior = 1.5f; m.cc_roughness = 0.0f;
-            m.cc_tint.kind = SPK_CONSTANT; m.cc_tint.c[0] = 1.0f;
-            if ((rc = im.lower_spectrum(d->color, &m.color, true, &err))) return fail(rc, err);
-            break;
-        case MI355PT_MAT_METAL:
-            if ((rc = im.lower_spectrum(d->eta, &m.eta, false, &err))) return fail(rc, "eta: " + err);
-            if ((rc = im.lower_spectrum(d->k, &m.cc_tint, false, &err))) return fail(rc, "k: " + err);
-            break;
-        default:
-            return fail(MI355PT_E_INVALID, "material type not implemented on the device yet");
-    }
+    if (int rc = lower_material_desc(im, *d, &m, &err)) return fail(rc, err);
     im.materials.push_back(m);
     *out = (uint32_t)im.materials.size() - 1;
     return MI355PT_OK;
 }
 int mi355pt_scene_add_delta_light(mi355pt_scene* s, const mi355pt_light_desc* d) {
     if (!s || !d) return fail(MI355PT_E_INVALID, "null argument");
-    if (d->kind < MI355PT_LIGHT_POINT || d->kind > MI355PT_LIGHT_DIRECTIONAL) return fail(MI355PT_E_INVALID, "bad light kind");
     SceneImpl& im = s->impl;
-    DevMaterial m{};                        // hidden emissive material: carries the light's spectrum with intensity 1
+    DevMaterial m{};
     std::string err;
-    int rc;
-    m.type = MT_EMISSIVE; m.normal_tex = 0xffffffffu; m.metallic_tex = m.roughness_tex = m.cc_thickness_tex = 0xffffffffu; m.intensity = 1.0f; m.intensity_avg = 1.0f;
-    if ((rc = im.lower_spectrum(d->spectrum, &m.color, false, &err))) return fail(rc, "light spectrum: " + err);
+    if (int rc = lower_light_desc(im, *d, &m, &err)) return fail(rc, err);
     im.materials.push_back(m);
     HostDeltaLight hl{*d, (uint32_t)im.materials.size() - 1, (uint32_t)im.instances.size()};
     im.delta_lights.push_back(hl);

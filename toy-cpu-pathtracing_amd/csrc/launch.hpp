@@ -204,6 +204,11 @@ constexpr uint32_t SAH_COST_LAUNCHES = 2;
 // index pool d_mesh_idx; the triangles of every other instance are not written
 hipError_t launch_deform_tris(DevTriLocal* d_local, DevTriShade* d_shade, const uint32_t* d_table, const float* d_staging, const uint32_t* d_mesh_idx, uint32_t n_tris,
                               uint32_t n_instances, uint32_t slots_at, uint32_t n_slots, hipStream_t);
+// pt_kernels_edit.hip: a material edit on a built scene (include/mi355pt_edit.h, scene_edit.cpp; launched from scene_update.cpp).  launch_reclass_tris: the class word of
+// the leaf-order triangles whose material has a class in d_table (scene_edit_plan.hpp edit_class_table: n_materials words, EDIT_CLASS_UNCHANGED
+// = not written), in d_local, in d_render and, where it is given, in d_walked (DevScene::tris when it is neither of the two; nullptr otherwise)
+hipError_t launch_reclass_tris(DevTriLocal* d_local, DevTri* d_render, DevTri* d_walked, const DevTriShade* d_shade, const uint32_t* d_table, uint32_t n_tris,
+                               uint32_t n_materials, hipStream_t);
 
 // Resident 64-thread blocks (= waves) of `kernel` on the current device: the persistent grid size of the EXACT instantiation a launch takes
 // (the register count, and so the occupancy, differs between instantiations and between translation units with their own backend flags).

@@ -66,6 +66,13 @@ struct RebaseState {
     std::vector<DevNode4> tree_nodes4;        // ... and its 4-wide collapse (links and used slots; the boxes follow a refit)
     int32_t tree_root4 = 0;
     std::vector<uint32_t> kept;               // build index -> triangle of the build, when it left triangles out (else the identity, not stored)
+    // mi355pt_scene_edit (scene_edit.cpp): the lowered records an edit compares with and starts from, as the build uploaded them
+    std::vector<DevMaterial> materials;       // the device copy (texture descriptors, coat table offsets, the environments' integrated spectra)
+    std::vector<float> cc_albedo;
+    std::vector<DevTexture> textures;         // the build's textures and LUTs: an edit names no later one
+    uint32_t n_luts = 0;
+    std::vector<DevEnv> envs;                 // the three pointers of each are null
+    uint32_t* d_class_table = nullptr;        // one word per material (in SceneImpl::allocs, made by the build)
     // mi355pt_scene_move_instances (scene_instances.cpp, scene_update.cpp): allocated / computed by the first move after a build (all in SceneImpl::allocs)
     uint32_t n_entries = 0;                   // RebasePlan::entries.size()
     float* d_sah = nullptr;                   // launch_sah_cost's scratch

@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "instance_move_plan.hpp"
+#include "scene_edit_plan.hpp"
 
 namespace pt {
 
@@ -175,16 +176,15 @@ AreaTables area_light_tables(const HostMesh& mesh, const float* l2w) {
     return t;
 }
 
+inline EditMaterialKey material_key(const DevMaterial& m) { return EditMaterialKey{m.type, m.color.kind, m.cc_tint.kind, m.eta.kind}; }
+
 // The records of one instance's triangles, in mesh order; `areas`: the instance is an area light, `light_index` its place in the light list
 void lower_triangles(const SceneImpl& scene, uint32_t ii, const float* l2r, const DevInstance& di, const AreaTables* areas, uint32_t light_index,
                      LoweredGeometry* g, std::vector<uint8_t>* deg_render, std::vector<uint8_t>* deg_local) {
     const HostInstance& inst = scene.instances[ii];
     const HostMesh& mesh = scene.meshes[inst.geom];
-    // sort class of the deferral queue (pt_kernel.hpp): material type, + 8 if the material has a SPECTRUM texture (texel fetches +
-    // the rgb2spec lookup: the long branch).  Normal / roughness maps alone do not make a class: measured -4 % on scene 5.
-    const DevMaterial& dm = scene.materials[inst.mat];
-    const bool tex = dm.color.kind == SPK_TEXTURE || dm.cc_tint.kind == SPK_TEXTURE || dm.eta.kind == SPK_TEXTURE;
-    const uint32_t mclass = dm.type | (tex ? 8u : 0u);
+    // sort class of the deferral queue (pt_kernel.hpp), stated in scene_edit_plan.hpp: an edit of the material recomputes it (reclass_tris_kernel)
+    const uint32_t mclass = edit_material_class(material_key(scene.materials[inst.mat]));
     for (uint32_t t = 0; t < mesh.n_tri; ++t) {
         const uint32_t vi[3] = {mesh.idx[3 * t], mesh.idx[3 * t + 1], mesh.idx[3 * t + 2]};
         V3 p[3], pl[3];
@@ -346,8 +346,12 @@ int lower_environment(const SceneImpl& scene, const SceneImpl::HostEnv& env, con
 
 // The device copy of the materials: texture descriptors ride in the records that name the texture (layout.hpp), and every clearcoat
 // material gets the coat's directional-albedo table (mi355pt_params.albedo_lut) and names its offset
-void finish_materials(LoweredScene* ls) {
-    for (DevMaterial& m : ls->materials) {
+// `reuse` (an edit of a built scene, lower_edit_records): a clearcoat material that is not marked in reuse->changed and was a clearcoat
+// material in reuse->materials takes its row from reuse->cc_albedo — the row is a function of the record — instead of integrating it again
+struct CoatRows { const std::vector<DevMaterial>& materials; const std::vector<float>& cc_albedo; const uint8_t* changed; };
+void finish_materials(LoweredScene* ls, const CoatRows* reuse = nullptr) {
+    for (size_t mi = 0; mi < ls->materials.size(); ++mi) {
+        DevMaterial& m = ls->materials[mi];
         m.normal_desc = m.normal_tex != 0xffffffffu ? ls->textures[m.normal_tex] : DevTexture{0, 0, 0, 0};
         for (DevSpectrum* sp : {&m.color, &m.eta, &m.cc_tint})
             if (sp->kind == SPK_TEXTURE) { const DevTexture& t = ls->textures[sp->id]; sp->pad[0] = t.offset; sp->pad[1] = t.w; sp->pad[2] = t.h; }
@@ -356,7 +360,11 @@ void finish_materials(LoweredScene* ls) {
         float r = (m.cc_ior - 1.0f) / (m.cc_ior + 1.0f);
         m.cc_albedo_lut = (uint32_t)ls->cc_albedo.size();
         ls->cc_albedo.resize(ls->cc_albedo.size() + 64);
-        coat_albedo_table(m.cc_roughness * m.cc_roughness, r * r, ls->cc_albedo.data() + m.cc_albedo_lut);
+        if (reuse && !reuse->changed[mi] && mi < reuse->materials.size() && reuse->materials[mi].type == MT_CLEARCOAT &&
+            (size_t)reuse->materials[mi].cc_albedo_lut + 64 <= reuse->cc_albedo.size())
+            std::memcpy(ls->cc_albedo.data() + m.cc_albedo_lut, reuse->cc_albedo.data() + reuse->materials[mi].cc_albedo_lut, 64 * sizeof(float));
+        else
+            coat_albedo_table(m.cc_roughness * m.cc_roughness, r * r, ls->cc_albedo.data() + m.cc_albedo_lut);
     }
     if (ls->cc_albedo.empty()) ls->cc_albedo.assign(64, 0.0f);
 }
@@ -672,7 +680,41 @@ int lower_camera_records(const SceneImpl& scene, const mi355pt_camera* cam, cons
     if (g.lights.size() != built_lights.size() || lt != out->light_tris.size()) { *err = "internal error: light list changed since the build"; return MI355PT_E_INVALID; }
     set_directional_areas(sb_lo, sb_hi, &g.lights);
     out->lights = std::move(g.lights);
+    out->env_light_index = std::move(g.env_light_index); out->env_l2r = std::move(g.env_l2r);
     out->tris_are_local = all_shared && have_shared && scene.lowering < 1;   // (a dynamic instance is never `shared`: its identity is 0)
+    return MI355PT_OK;
+}
+
+// ---------------- new materials, lights and environments on a built scene (scene_edit.cpp) ----------------
+
+void material_keys(const std::vector<DevMaterial>& materials, std::vector<EditMaterialKey>* out) {
+    out->resize(materials.size());
+    for (size_t i = 0; i < materials.size(); ++i) (*out)[i] = material_key(materials[i]);
+}
+
+// lower_scene's steps between pack_textures and the tree, on the description as it is now: the same functions in the same order
+int lower_edit_records(const SceneImpl& scene, const mi355pt_camera* cam, const RebaseState& built, const uint8_t* material_changed, const uint8_t* env_edited,
+                       EditRecords* out, std::string* err) {
+    *out = EditRecords{};
+    CameraRecords rec;
+    if (int rc = lower_camera_records(scene, cam, built.bounds, built.lights, built.light_tris, &rec, err)) return rc;
+    if (built.materials.size() != scene.materials.size() || built.envs.size() != scene.envs.size()) { *err = "internal error: material or environment list changed since the build"; return MI355PT_E_INVALID; }
+    LoweredScene ls;
+    ls.textures = built.textures;
+    ls.materials = scene.materials;
+    out->envs = built.envs;
+    out->env_tables.resize(scene.envs.size());
+    for (size_t ek = 0; ek < scene.envs.size(); ++ek) {
+        const uint32_t li = rec.env_light_index[ek], hidden = rec.lights[li].material;
+        if (!env_edited[ek]) { ls.materials[hidden] = built.materials[hidden]; continue; }        // the integrated spectrum the build computed
+        if (int rc = lower_environment(scene, scene.envs[ek], rec.env_l2r[ek].data(), li, &out->env_tables[ek], &out->envs[ek], &ls.materials[hidden], err)) return rc;
+    }
+    const CoatRows reuse{built.materials, built.cc_albedo, material_changed};
+    finish_materials(&ls, &reuse);
+    out->materials = std::move(ls.materials);
+    out->cc_albedo = std::move(ls.cc_albedo);
+    out->lights = std::move(rec.lights);
+    out->features = scene_features(scene, out->lights.size());
     return MI355PT_OK;
 }
 

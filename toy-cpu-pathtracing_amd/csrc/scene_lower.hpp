@@ -85,6 +85,8 @@ struct CameraRecords {
     std::vector<DevLightTri> light_tris;
     bool tris_are_local = false;
     float shared_iw[3] = {0, 0, 0}, shared_mw[3] = {0, 0, 0};
+    std::vector<uint32_t> env_light_index;     // as in LoweredGeometry: what lower_environment takes beside the description
+    std::vector<std::array<float, 16>> env_l2r;
 };
 int lower_camera_records(const SceneImpl& scene, const mi355pt_camera* cam, const std::vector<MeshBounds>& bounds, const std::vector<DevLight>& built_lights,
                          const std::vector<DevLightTri>& built_light_tris, CameraRecords* out, std::string* err, const uint8_t* moved = nullptr,
@@ -110,6 +112,24 @@ bool left_out_stay_degenerate(const SceneImpl& scene, const std::vector<DevInsta
 // instances of the deformed meshes marked in `moved`, lower_camera_records gives an emissive one its area tables from the new vertices
 void mesh_local_bounds_of(const SceneImpl& scene, uint32_t geom, MeshBounds* out);
 bool local_triangle_degenerate(const HostMesh& mesh, uint32_t tri);
+
+// What NEW DESCRIPTIONS of materials, delta lights and environment lights change (mi355pt_scene_edit, scene_edit.cpp), for a description
+// whose emitter set and clearcoat count are the build's: the device copy of the materials and the coat-albedo table (finish_materials; a
+// clearcoat material not marked in `material_changed` keeps the row `built` holds), the light list (lower_camera_records: lower_delta_light
+// with set_directional_areas over the cached mesh bounds), for every environment marked in `env_edited` its record, its tables and the
+// integrated spectrum of its hidden material (lower_environment; the others keep the records of `built`), and scene_features
+struct EditMaterialKey;   // scene_edit_plan.hpp
+struct EditRecords {
+    std::vector<DevMaterial> materials;
+    std::vector<float> cc_albedo;
+    std::vector<DevLight> lights;
+    std::vector<DevEnv> envs;                                // the three pointers of each are null
+    std::vector<LoweredScene::EnvTables> env_tables;         // of the marked environments; the others' stay empty
+    uint32_t features = 0;
+};
+int lower_edit_records(const SceneImpl& scene, const mi355pt_camera* cam, const RebaseState& built, const uint8_t* material_changed, const uint8_t* env_edited,
+                       EditRecords* out, std::string* err);
+void material_keys(const std::vector<DevMaterial>& materials, std::vector<EditMaterialKey>* out);   // what scene_edit_plan.hpp reads of each record
 
 // scene_info's text; ms = {bvh_ms, bvh_device_ms, collapse_ms} or null to leave the three timings out (what the digests are recorded with)
 std::string lowering_info(const LoweredScene& ls, const LowerReport& rep, bool gpu_builder, const double* ms);

@@ -35,7 +35,8 @@ int SceneImpl::prepare_rebase(const LoweredScene& ls, const LowerReport& rep, st
     if (!make_rebase_plan(ls.nodes, ls.dev.root, ls.nodes4, ls.dev.root4, ls.tris_render.size(), &plan)) return MI355PT_OK;   // (a tree the plan does not cover: a move builds again)
     int rc;
     if (on_device && ((rc = upload_words(this, plan.entries, &rb.d_entries, err)) || (rc = upload_words(this, plan.slot_src, &rb.d_slot_src, err)) ||
-                      (rc = upload_words(this, std::vector<uint32_t>(4, 0u), &rb.d_count, err)))) return rc;
+                      (rc = upload_words(this, std::vector<uint32_t>(4, 0u), &rb.d_count, err)) ||
+                      (rc = upload_words(this, std::vector<uint32_t>(ls.materials.size(), 0xffffffffu), &rb.d_class_table, err)))) return rc;
     rb.height_offset = plan.height_offset;
     rb.n_slots = (uint32_t)plan.slot_src.size();
     rb.n_entries = (uint32_t)plan.entries.size();
@@ -46,6 +47,7 @@ int SceneImpl::prepare_rebase(const LoweredScene& ls, const LowerReport& rep, st
     mesh_local_bounds(*this, &rb.bounds);
     rb.lights = ls.lights;
     rb.light_tris = ls.light_tris;
+    rb.materials = ls.materials; rb.cc_albedo = ls.cc_albedo; rb.textures = ls.textures; rb.n_luts = (uint32_t)luts.size(); rb.envs = ls.envs;
     rb.pinned = true;
     rb.ready = on_device;
 #endif

@@ -17,6 +17,54 @@ SceneUpdateResult scene_update_step(SceneImpl* impl, const SceneUpdate& u) {
     RebaseState& rb = impl->rebase;
     DevScene& d = impl->dev;
     hipStream_t stream = nullptr;
+    if (u.edit) {
+        // an edit of materials and lights: uploads into the build's allocations, each of the array's built size, and at most one launch
+        const EditStage& e = *u.edit;
+        size_t n_cc = 0;
+        for (const DevMaterial& m : rb.materials) if (m.type == MT_CLEARCOAT) ++n_cc;
+        if ((e.materials && e.materials->size() != (size_t)d.n_materials) || (e.cc_albedo && e.cc_albedo->size() != std::max<size_t>(n_cc, 1) * 64) ||
+            (e.lights && e.lights->size() != (size_t)d.n_lights) || (e.envs && (e.envs->size() != (size_t)d.n_envs || !e.env_tables || !e.env_map_changed)) ||
+            (e.class_table && (e.class_table->size() != (size_t)d.n_materials || !rb.d_class_table)))
+            return dropped("scene_update_step: a record list changed size since the build", hipErrorInvalidValue);
+        if (e.envs) {
+            std::vector<DevEnv> envs(d.n_envs);                                // the built records name the tables on the device
+            if (d.n_envs) STEP_TRY("hipMemcpy", hipMemcpy(envs.data(), d.envs, envs.size() * sizeof(DevEnv), hipMemcpyDeviceToHost));
+            for (size_t k = 0; k < envs.size(); ++k) {
+                const DevEnv& built = envs[k];
+                DevEnv ne = (*e.envs)[k];
+                if (ne.w != built.w || ne.h != built.h) return dropped("scene_update_step: an environment map changed size since the build", hipErrorInvalidValue);
+                ne.texels = built.texels; ne.marginal = built.marginal; ne.conditional = built.conditional;
+                if (e.env_map_changed[k]) {
+                    const LoweredScene::EnvTables& t = (*e.env_tables)[k];
+                    const size_t px = (size_t)ne.w * ne.h;
+                    if (t.texels.size() != px * 4 || t.marginal.size() != (size_t)ne.h || t.conditional.size() != px) return dropped("scene_update_step: environment tables of another size", hipErrorInvalidValue);
+                    STEP_TRY("hipMemcpy", hipMemcpy((void*)ne.texels, t.texels.data(), t.texels.size() * sizeof(float), hipMemcpyHostToDevice));
+                    STEP_TRY("hipMemcpy", hipMemcpy((void*)ne.marginal, t.marginal.data(), t.marginal.size() * sizeof(float), hipMemcpyHostToDevice));
+                    STEP_TRY("hipMemcpy", hipMemcpy((void*)ne.conditional, t.conditional.data(), t.conditional.size() * sizeof(float), hipMemcpyHostToDevice));
+                }
+                envs[k] = ne;
+            }
+            if (d.n_envs) STEP_TRY("hipMemcpy", hipMemcpy((void*)d.envs, envs.data(), envs.size() * sizeof(DevEnv), hipMemcpyHostToDevice));
+        }
+        if (e.cc_albedo) STEP_TRY("hipMemcpy", hipMemcpy((void*)d.cc_albedo, e.cc_albedo->data(), e.cc_albedo->size() * sizeof(float), hipMemcpyHostToDevice));
+        if (e.materials) STEP_TRY("hipMemcpy", hipMemcpy((void*)d.materials, e.materials->data(), e.materials->size() * sizeof(DevMaterial), hipMemcpyHostToDevice));
+        // (the lights' boxes behind the records are the emissive triangles': no edit moves them)
+        if (e.lights) STEP_TRY("hipMemcpy", hipMemcpy((void*)d.lights, e.lights->data(), e.lights->size() * sizeof(DevLight), hipMemcpyHostToDevice));
+        if (e.class_table) {
+            STEP_TRY("hipMemcpy", hipMemcpy(rb.d_class_table, e.class_table->data(), e.class_table->size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            Event ev_a, ev_b;
+            STEP_TRY("hipEventCreate", ev_a.create()); STEP_TRY("hipEventCreate", ev_b.create());
+            STEP_TRY("hipEventRecord", ev_a.record(stream));
+            // DevScene::tris is one of the two arrays (scene.cpp upload); were it a third, it would carry the class too
+            DevTri* walked = d.tris != d.tris_local && d.tris != d.tris_render ? (DevTri*)d.tris : nullptr;
+            STEP_TRY("launch_reclass_tris", launch_reclass_tris((DevTriLocal*)d.tris_local, (DevTri*)d.tris_render, walked, d.shade, rb.d_class_table, d.n_tris, d.n_materials, stream));
+            ++r.launches;
+            STEP_TRY("hipEventRecord", ev_b.record(stream)); STEP_TRY("hipEventSynchronize", ev_b.synchronize());
+            float ms = 0.0f;
+            STEP_TRY("hipEventElapsedTime", ev_b.elapsed_ms(ev_a, &ms)); r.device_ms = ms;
+        }
+        return r;
+    }
     const size_t n_inst = impl->instances.size(), n_pdf = u.light_pdf ? u.light_pdf->size() : 0;
     const bool has_tree = u.sah && d.root >= 0 && rb.n_entries > 0;
 
@@ -105,7 +153,10 @@ SceneUpdateResult scene_update_step(SceneImpl* impl, const SceneUpdate& u) {
         r.sah_built = rb.sah_built;
         if (u.rebuild_above > 0.0f && rb.sah_built > 0.0f && r.sah_after / rb.sah_built > u.rebuild_above) { r.outcome = SceneUpdateResult::SAH_DEGRADED; return r; }
     }
-    if (u.moved) { rb.lights = u.rec.lights; rb.light_tris = u.rec.light_tris; }      // the caches the next update starts from
+    // the caches the next update starts from: what the device holds now (a camera move re-lowers the delta lights' render-space positions
+    // too, and mi355pt_scene_edit compares its records with these)
+    if (!u.rec.lights.empty()) rb.lights = u.rec.lights;
+    if (!u.rec.light_tris.empty()) rb.light_tris = u.rec.light_tris;
     return r;
 #endif
 #undef STEP_TRY

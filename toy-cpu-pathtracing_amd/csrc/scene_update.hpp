@@ -1,5 +1,6 @@
 // The one device step (scene_update.cpp) behind the three in-place updates of a built scene: mi355pt_scene_move_camera
-// (scene_rebase.cpp), mi355pt_scene_move_instances (scene_instances.cpp), mi355pt_scene_deform_meshes (scene_deform.cpp).  An entry point keeps its
+// (scene_rebase.cpp), mi355pt_scene_move_instances (scene_instances.cpp), mi355pt_scene_deform_meshes (scene_deform.cpp) — and, as a stage of
+// its own that touches no geometry, behind mi355pt_scene_edit (scene_edit.cpp).  An entry point keeps its
 // checks, the description, the host records and the host gates; everything that touches the device after them is the step's.  Not installed, not an ABI.
 #pragma once
 #include "api_internal.hpp"
@@ -17,6 +18,19 @@ struct DeformStage {
     size_t staging_capacity, table_capacity;    // in floats / words, for every mesh of the scene at once
 };
 
+// an edit of materials and lights (scene_edit.cpp) in place of the geometry stages: the arrays that differ from the built ones (nullptr =
+// as built, not uploaded), each of the built array's size, and the class table when a material changed class.  With this stage the step
+// uploads and launches nothing else: no triangle position, no box and no instance record changes
+struct EditStage {
+    const std::vector<DevMaterial>* materials = nullptr;
+    const std::vector<float>* cc_albedo = nullptr;
+    const std::vector<DevLight>* lights = nullptr;
+    const std::vector<DevEnv>* envs = nullptr;                               // the records without their pointers, which the step keeps
+    const std::vector<LoweredScene::EnvTables>* env_tables = nullptr;        // with env_map_changed: the tables of the marked environments
+    const uint8_t* env_map_changed = nullptr;                                // per environment, with envs
+    const std::vector<uint32_t>* class_table = nullptr;                      // scene_edit_plan.hpp edit_class_table; nullptr: no class changed, no launch
+};
+
 struct SceneUpdate {
     const CameraRecords& rec;                   // uploaded into the existing allocations
     bool count_degenerate;                      // launch_rebase_tris counts the triangles that became degenerate
@@ -25,6 +39,7 @@ struct SceneUpdate {
     bool sah = false;                           // take sah_built (once per build, ahead of everything) and sah_after, compare with rebuild_above
     float rebuild_above = 0.0f;
     const DeformStage* deform = nullptr;
+    const EditStage* edit = nullptr;            // with it, `rec` and everything above are not read
 };
 
 struct SceneUpdateResult {

@@ -248,6 +248,50 @@ class MeshUpdate(C.Structure):
     _fields_ = [("geom", C.c_uint32), ("pos", C.POINTER(C.c_float)), ("nrm", C.POINTER(C.c_float)), ("tri_tangent", C.POINTER(C.c_float))]
 
 
+# mi355pt_edit_result.reason (include/mi355pt_edit.h): "rebased" (edited in place) and "unsupported_build" of MOVE_REASON, and three of its own
+EDIT_REASON = DEFORM_REASON + ["same_records", "emitter_set_changed", "table_shape_changed"]
+
+
+class MaterialEdit(C.Structure):
+    """mi355pt_material_edit (include/mi355pt_edit.h)"""
+    _fields_ = [("mat", C.c_uint32), ("desc", MaterialDesc)]
+
+
+class LightEdit(C.Structure):
+    """mi355pt_light_edit (include/mi355pt_edit.h)"""
+    _fields_ = [("light", C.c_uint32), ("desc", LightDesc)]
+
+
+class EnvEdit(C.Structure):
+    """mi355pt_env_edit (include/mi355pt_edit.h)"""
+    _fields_ = [("env", C.c_uint32), ("intensity", C.c_float), ("local_to_world", C.POINTER(C.c_float)), ("rgb", C.POINTER(C.c_float))]
+
+
+class SceneEdits(C.Structure):
+    """mi355pt_scene_edits (include/mi355pt_edit.h)"""
+    _fields_ = [("materials", C.POINTER(MaterialEdit)), ("n_materials", C.c_uint32), ("lights", C.POINTER(LightEdit)), ("n_lights", C.c_uint32),
+                ("envs", C.POINTER(EnvEdit)), ("n_envs", C.c_uint32)]
+
+
+class EditResult(C.Structure):
+    """mi355pt_edit_result (include/mi355pt_edit.h)"""
+    _fields_ = [("rebuilt", C.c_uint32), ("reason", C.c_uint32), ("launches", C.c_uint32), ("features_before", C.c_uint32), ("features_after", C.c_uint32),
+                ("host_ms", C.c_double), ("device_ms", C.c_double)]
+
+    def as_dict(self):
+        return {"rebuilt": int(self.rebuilt), "reason": EDIT_REASON[self.reason], "launches": int(self.launches), "features_before": int(self.features_before),
+                "features_after": int(self.features_after), "host_ms": float(self.host_ms), "device_ms": float(self.device_ms)}
+
+
+def make_light_desc(kind, intensity, spectrum, local_to_world=None, angle_inner=0.0, angle_outer=0.0):
+    """mi355pt_light_desc from a row-major 4 x 4 matrix, as SceneHandle.add_delta_light takes its arguments"""
+    m = np.eye(4, dtype=np.float32) if local_to_world is None else np.asarray(local_to_world, dtype=np.float32)
+    d = LightDesc(); d.kind = kind; d.intensity = intensity; d.angle_inner = angle_inner; d.angle_outer = angle_outer
+    d.spectrum = spectrum
+    d.local_to_world = (C.c_float * 16)(*np.ascontiguousarray(m.T.reshape(-1)))   # column-major
+    return d
+
+
 def make_camera(position, direction, up, width, height, fov_deg=45.0):
     return Camera((C.c_float * 3)(*position), (C.c_float * 3)(*direction), (C.c_float * 3)(*up), fov_deg, width, height)
 
@@ -263,7 +307,7 @@ def _ptr(a, ty):
 
 
 # every symbol include/mi355pt.h declares (tests/test_abi.py checks the built library exports all of them) ...
-DEBUG_SYMBOLS = ["debug_unlock", "scene_debug_set_lowering", "scene_debug_lowering_digest", "scene_debug_camera_candidates", "scene_debug_move_digest", "scene_debug_move_export", "scene_debug_device_digest", "scene_debug_pinned_digest", "scene_debug_pinned_export", "scene_debug_pin_host_tree", "scene_debug_set_instance_transform", "scene_debug_set_mesh_vertices", "debug_sah_cost", "scene_export_bvh", "probe_bvh_collapse", "probe_bvh_collapse_nodes", "probe_sobol", "probe_sincos", "probe_intersect", "probe_occluded",
+DEBUG_SYMBOLS = ["debug_unlock", "scene_debug_set_lowering", "scene_debug_lowering_digest", "scene_debug_camera_candidates", "scene_debug_move_digest", "scene_debug_move_export", "scene_debug_device_digest", "scene_debug_pinned_digest", "scene_debug_pinned_export", "scene_debug_pin_host_tree", "scene_debug_set_instance_transform", "scene_debug_set_mesh_vertices", "scene_debug_apply_edits", "debug_sah_cost", "scene_export_bvh", "probe_bvh_collapse", "probe_bvh_collapse_nodes", "probe_sobol", "probe_sincos", "probe_intersect", "probe_occluded",
                  "sample_log_records", "render_sample_log", "probe_radiance", "probe_display_meter_ms",
                  "render_flow_debug", "scene_export_flow_mark", "scene_export_triangle_ids"]     # ... and include/mi355pt_debug.h
 ABI_SYMBOLS = [
@@ -301,6 +345,8 @@ MOTION_SYMBOLS = ["render_ids_device", "render_ids", "motion_table", "temporal_a
                   "temporal_accumulate_rectified_motion_device", "temporal_accumulate_rectified_motion"]
 # ... and include/mi355pt_deform.h, the mesh-deformation block (tests/test_deform.py)
 DEFORM_SYMBOLS = ["scene_deform_meshes"]
+# ... and include/mi355pt_edit.h, the lights-and-materials block (tests/test_scene_edit.py)
+EDIT_SYMBOLS = ["scene_edit"]
 # ... and include/mi355pt_flow.h, the per-pixel motion block (tests/test_flow.py)
 FLOW_SYMBOLS = ["scene_flow_mark", "scene_flow_marked", "render_flow_device", "render_flow", "temporal_accumulate_flow_device", "temporal_accumulate_flow",
                 "temporal_accumulate_rectified_flow_device", "temporal_accumulate_rectified_flow"]
@@ -388,6 +434,8 @@ class SceneHandle:
         self.keep = []
         self.material_descs = []       # by material id (delta / environment lights add hidden materials on the library side, after these)
         self.instances = []            # by instance id: (geometry, material, local_to_world as a row-major 4 x 4 float32 array) as described
+        self.light_descs = []          # by delta-light id (the order of add_delta_light calls): the LightDesc as described
+        self.env_lights = []           # by environment-light id: (intensity, rgb (h, w, 3) float32, local_to_world row-major 4 x 4) as described
 
     def close(self):
         if self.h:
@@ -446,11 +494,9 @@ class SceneHandle:
         self.instances.append((geom, mat, m.copy()))
 
     def add_delta_light(self, kind, intensity, spectrum, local_to_world=None, angle_inner=0.0, angle_outer=0.0):
-        m = np.eye(4, dtype=np.float32) if local_to_world is None else np.asarray(local_to_world, dtype=np.float32)
-        d = LightDesc(); d.kind = kind; d.intensity = intensity; d.angle_inner = angle_inner; d.angle_outer = angle_outer
-        d.spectrum = spectrum
-        d.local_to_world = (C.c_float * 16)(*np.ascontiguousarray(m.T.reshape(-1)))   # column-major
+        d = make_light_desc(kind, intensity, spectrum, local_to_world, angle_inner, angle_outer)
         self.b.check(self.b.fn("scene_add_delta_light")(self.h, C.byref(d)), "scene_add_delta_light")
+        self.light_descs.append(d)
 
     def add_environment_light(self, intensity, rgb, illuminant_lut, local_to_world=None):
         rgb = np.ascontiguousarray(rgb, dtype=np.float32)
@@ -459,6 +505,7 @@ class SceneHandle:
         cols = np.ascontiguousarray(m.T.reshape(-1))
         self.b.check(self.b.fn("scene_add_environment_light")(self.h, intensity, _ptr(rgb, C.c_float), rgb.shape[1], rgb.shape[0],
                                                               _ptr(cols, C.c_float), illuminant_lut), "scene_add_environment_light")
+        self.env_lights.append((float(intensity), rgb.copy(), m.copy()))
 
     def set_bvh_builder(self, mode):
         """mi355pt_scene_set_bvh_builder: "auto" | "host" | "gpu" (product only; the oracle has its own BVH)."""
@@ -563,6 +610,42 @@ class SceneHandle:
         fn.argtypes = [C.c_void_p, C.POINTER(MeshUpdate), C.c_uint32]
         ups, keep = self._mesh_updates(meshes)
         self.b.check(fn(self.h, ups, len(meshes)), "scene_debug_set_mesh_vertices")
+
+    def _scene_edits(self, materials=None, lights=None, envs=None):
+        """{mat: MaterialDesc}, {light: LightDesc}, {env: (intensity, local_to_world row-major 4 x 4 or None = keep, rgb (h, w, 3) or None =
+        keep)} -> (a SceneEdits with each list in ascending id order, what it points into)"""
+        materials, lights, envs = materials or {}, lights or {}, envs or {}
+        me, le, ee, keep = (MaterialEdit * max(len(materials), 1))(), (LightEdit * max(len(lights), 1))(), (EnvEdit * max(len(envs), 1))(), []
+        for k, mat in enumerate(sorted(materials)):
+            me[k] = MaterialEdit(mat, materials[mat])
+        for k, light in enumerate(sorted(lights)):
+            le[k] = LightEdit(light, lights[light])
+        for k, env in enumerate(sorted(envs)):
+            intensity, l2w, rgb = envs[env]
+            cols = None if l2w is None else np.ascontiguousarray(np.asarray(l2w, dtype=np.float32).T.reshape(-1))
+            rgb = None if rgb is None else np.ascontiguousarray(rgb, dtype=np.float32)
+            keep += [cols, rgb]
+            ee[k] = EnvEdit(env, intensity, _ptr(cols, C.c_float), _ptr(rgb, C.c_float))
+        keep += [me, le, ee]
+        return SceneEdits(me if materials else None, len(materials), le if lights else None, len(lights), ee if envs else None, len(envs)), keep
+
+    def edit(self, cam, materials=None, lights=None, envs=None):
+        """mi355pt_scene_edit (include/mi355pt_edit.h, product only): new descriptions for materials, delta lights and environment lights
+        of the built scene (_scene_edits' dictionaries), applied in place -> {"rebuilt", "reason" (an EDIT_REASON name), "launches",
+        "features_before", "features_after", "host_ms", "device_ms"}"""
+        fn = self.b.fn("scene_edit")
+        fn.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(SceneEdits), C.POINTER(EditResult)]
+        edits, keep = self._scene_edits(materials, lights, envs)
+        res = EditResult()
+        self.b.check(fn(self.h, C.byref(cam), C.byref(edits), C.byref(res)), "scene_edit")
+        return res.as_dict()
+
+    def debug_apply_edits(self, materials=None, lights=None, envs=None):
+        """mi355pt_scene_debug_apply_edits (host only, product only): edit's description update alone, on an unbuilt scene"""
+        fn = self.b.fn("scene_debug_apply_edits")
+        fn.argtypes = [C.c_void_p, C.POINTER(SceneEdits)]
+        edits, keep = self._scene_edits(materials, lights, envs)
+        self.b.check(fn(self.h, C.byref(edits)), "scene_debug_apply_edits")
 
     def debug_pin_host_tree(self, cam):
         """mi355pt_scene_debug_pin_host_tree (host only, product only): what a build keeps on the host, for an unbuilt scene"""

@@ -55,6 +55,15 @@ struct Args {   // main.rs:20-53
     // instance's local_to_world is the scene's with T . R_y applied k times (the way --camera-step moves the camera); the instances are marked
     // dynamic before the build and moved on the device between the frames, and the accumulation is the motion-aware one
     std::vector<InstanceTransform> instance_steps;
+    // nor edits of lights and materials of the built scene (mi355pt_edit.h), with --temporal-frames: --light-step ID:dx,dy,dz[:gain] (each frame
+    // translates delta light ID and multiplies its intensity by gain), --emitter-gain MAT:g (each frame multiplies the emissive material's
+    // intensity by g), --env-yaw-step DEG (each frame turns every environment light by DEG degrees about +y), and --scene-edit inplace|rebuild:
+    // mi355pt_scene_edit alone, or followed by mi355pt_scene_build of the edited description (the default, the precedent of --camera-move)
+    struct LightStep { uint32_t id; float d[3]; float gain; };
+    struct EmitterGain { uint32_t mat; float gain; };
+    std::vector<LightStep> light_steps; std::vector<EmitterGain> emitter_gains; bool env_yaw_given = false; float env_yaw_step = 0.0f;
+    bool scene_edit_given = false; std::string scene_edit = "rebuild";
+    bool editing() const { return !light_steps.empty() || !emitter_gains.empty() || env_yaw_given; }
     // nor deforming meshes of the built scene (mi355pt_deform.h): --mesh-wave GEOM:amp,wavelength[,phase_step], repeatable — the scene is
     // built as described, then every vertex of mesh GEOM takes y += amp sin(2 pi x / wavelength + phase_step) with area-weighted vertex
     // normals recomputed on the host, applied on the device before the frame.  --instance-rebuild-above applies to it
@@ -337,6 +346,40 @@ static void follow_camera(Scene& scene, const Camera& moved, const Args& a, uint
     std::fprintf(stderr, "camera move, frame %u: rebuilt=%u host_ms=%.3f device_ms=%.3f\n", frame, r.rebuilt, r.host_ms, r.device_ms);
 }
 
+// --light-step, --emitter-gain, --env-yaw-step: the frame's step once more on top of what the scene holds (mi355pt_scene_edit), at the camera
+// the scene is at; --scene-edit rebuild then builds the edited description again.  One line per frame on stderr
+static void step_scene_edits(Scene& scene, const Camera& at, const Args& a, uint32_t frame) {
+    std::vector<mi355pt_material_edit> mats; std::vector<mi355pt_light_edit> lights; std::vector<mi355pt_env_edit> envs;
+    for (const Args::EmitterGain& g : a.emitter_gains) {
+        mi355pt_material_edit e{g.mat, scene.material_desc(g.mat)};
+        e.desc.intensity *= g.gain;
+        mats.push_back(e);
+    }
+    for (const Args::LightStep& st : a.light_steps) {
+        mi355pt_light_edit e{st.id, scene.light_desc(st.id)};
+        for (int i = 0; i < 3; ++i) e.desc.local_to_world[12 + i] += st.d[i];
+        e.desc.intensity *= st.gain;
+        lights.push_back(e);
+    }
+    std::vector<std::vector<float>> turned;
+    if (a.env_yaw_given) {
+        const double r = (double)a.env_yaw_step * 3.14159265358979323846 / 180.0;
+        const float c = (float)std::cos(r), sn = (float)std::sin(r);
+        const float ry[16] = {c, 0, -sn, 0, 0, 1, 0, 0, sn, 0, c, 0, 0, 0, 0, 1};      // column-major R_y
+        for (uint32_t v = 0; v < scene.env_count(); ++v) {
+            const float* m = scene.env_transform(v);
+            std::vector<float> o(16, 0.0f);
+            for (int col = 0; col < 4; ++col) for (int row = 0; row < 4; ++row) for (int k = 0; k < 4; ++k) o[4 * col + row] += ry[4 * k + row] * m[4 * col + k];
+            turned.push_back(o);
+        }
+        for (uint32_t v = 0; v < scene.env_count(); ++v) envs.push_back(mi355pt_env_edit{v, scene.env_intensity(v), turned[v].data(), nullptr});
+    }
+    const mi355pt_edit_result r = scene.edit(at, mats, lights, envs);
+    std::fprintf(stderr, "scene edit, frame %u: rebuilt=%u reason=%u launches=%u features=%u->%u host_ms=%.3f device_ms=%.3f\n", frame, r.rebuilt, r.reason, r.launches,
+                 r.features_before, r.features_after, r.host_ms, r.device_ms);
+    if (a.scene_edit != "inplace" && !r.rebuilt) scene.build(at);
+}
+
 // One frame of the accumulation on device buffers: the entry point of the carry (ids_cur == nullptr: none; a table of n_entries records, or
 // else flow records) and of --temporal-rectify (rect != nullptr: its parameters, with the scratch).  The name check() gets is the entry
 // point's that ran
@@ -450,6 +493,7 @@ static double render_temporal(Scene& scene, const Camera& camera, mi355pt_params
             const mi355pt_instance_move_result mr = scene.deform_meshes(moved, geoms, pos, nrm, a.instance_rebuild_above);
             std::fprintf(stderr, "mesh deform, frame %u: rebuilt=%u reason=%u host_ms=%.3f device_ms=%.3f\n", k, mr.rebuilt, mr.reason, mr.host_ms, mr.device_ms);
         }
+        if (k > 0 && a.editing()) step_scene_edits(scene, moved, a, k);
         // a move that built the scene again dropped the mark: this frame has no previous one
         const bool first = k == 0 || (flowing && !scene.flow_marked());
         if (flowing && k > 0 && first) std::fprintf(stderr, "flow, frame %u: a move rebuilt the scene, the accumulation restarts\n", k);
@@ -680,6 +724,11 @@ static void usage() {
               "                   [--temporal-budget TARGET] (with --temporal-frames: every frame probes the history length its pixels will find, renders --spp\n"
               "                                         samples everywhere and doubles them, up to --temporal-budget-max-spp, on the 8 x 8 tiles that would not reach\n"
               "                                         TARGET frames' worth; --spp a power of two; not with --half-res)  [--temporal-budget-max-spp M] (8 x --spp)\n"
+              "                   [--light-step ID:dx,dy,dz[:gain]] [--emitter-gain MAT:g] [--env-yaw-step DEG] (repeatable but for the last; with --temporal-frames:\n"
+              "                                         before every frame but the first delta light ID moves by (dx,dy,dz) and its intensity is multiplied by gain, the\n"
+              "                                         emissive material MAT's intensity by g, every environment light turns by DEG degrees about +y)\n"
+              "                   [--scene-edit inplace|rebuild] (how those steps reach the built scene: mi355pt_scene_edit in place, or the edited description built\n"
+              "                                         again (the default).  Without --temporal-rectify the plain accumulation averages the change over its history)\n"
               "                   [--flow] (with --temporal-frames: per-pixel motion vectors — every frame marks the scene, takes --camera-step, --instance-step and\n"
               "                                         --mesh-wave in place (frame k's wave: the original vertices at phase k * phase_step) and accumulates through\n"
               "                                         the flow pass; a move that rebuilds restarts the accumulation; the camera follows as with --camera-move rebase unless\n"
@@ -784,6 +833,35 @@ int main(int argc, char** argv) {
             if (!ok) { std::fprintf(stderr, "error: invalid value '%s' for '--instance-step': ID:tx,ty,tz[:ry_deg], finite numbers, each ID once\n", v.c_str()); return 2; }
             a.instance_steps.push_back(it);
         }
+        else if (k == "--light-step") {
+            const std::string v = val();
+            Args::LightStep st{0, {0, 0, 0}, 1.0f};
+            char tail = 0;
+            int n = std::sscanf(v.c_str(), "%u:%f,%f,%f%c", &st.id, &st.d[0], &st.d[1], &st.d[2], &tail);
+            bool ok = n == 4;
+            if (n == 5 && tail == ':') ok = std::sscanf(v.c_str(), "%u:%f,%f,%f:%f%c", &st.id, &st.d[0], &st.d[1], &st.d[2], &st.gain, &tail) == 5;
+            for (float f : {st.d[0], st.d[1], st.d[2], st.gain}) ok = ok && std::isfinite(f);
+            ok = ok && !v.empty() && v[0] >= '0' && v[0] <= '9';
+            for (const Args::LightStep& o : a.light_steps) ok = ok && o.id != st.id;
+            if (!ok) { std::fprintf(stderr, "error: invalid value '%s' for '--light-step': ID:dx,dy,dz[:gain], finite numbers, each ID once\n", v.c_str()); return 2; }
+            a.light_steps.push_back(st);
+        }
+        else if (k == "--emitter-gain") {
+            const std::string v = val();
+            Args::EmitterGain g{0, 1.0f};
+            char tail = 0;
+            bool ok = std::sscanf(v.c_str(), "%u:%f%c", &g.mat, &g.gain, &tail) == 2 && std::isfinite(g.gain) && !v.empty() && v[0] >= '0' && v[0] <= '9';
+            for (const Args::EmitterGain& o : a.emitter_gains) ok = ok && o.mat != g.mat;
+            if (!ok) { std::fprintf(stderr, "error: invalid value '%s' for '--emitter-gain': MAT:g, a finite number, each MAT once\n", v.c_str()); return 2; }
+            a.emitter_gains.push_back(g);
+        }
+        else if (k == "--env-yaw-step") {
+            const std::string v = val();
+            char tail = 0;
+            a.env_yaw_given = true;
+            if (std::sscanf(v.c_str(), "%f%c", &a.env_yaw_step, &tail) != 1 || !std::isfinite(a.env_yaw_step)) { std::fprintf(stderr, "error: invalid value '%s' for '--env-yaw-step': a finite number of degrees\n", v.c_str()); return 2; }
+        }
+        else if (k == "--scene-edit") { a.scene_edit_given = true; a.scene_edit = val(); }
         else if (k == "--mesh-wave") {
             const std::string v = val();
             Args::MeshWave w{0, 0.0f, 0.0f, 0.0f};
@@ -910,6 +988,12 @@ int main(int argc, char** argv) {
     if (a.camera_step_given && !a.temporal) { std::fprintf(stderr, "error: --camera-step needs --temporal-frames: it moves the camera between the frames\n"); return 2; }
     if (a.camera_move != "rebuild" && a.camera_move != "rebase") { std::fprintf(stderr, "error: invalid value '%s' for '--camera-move' (rebuild or rebase)\n", a.camera_move.c_str()); return 2; }
     if (a.camera_move_given && !a.temporal) { std::fprintf(stderr, "error: --camera-move needs --temporal-frames: it says how the scene follows the camera between the frames\n"); return 2; }
+    if (a.scene_edit != "inplace" && a.scene_edit != "rebuild") { std::fprintf(stderr, "error: invalid value '%s' for '--scene-edit' (inplace or rebuild)\n", a.scene_edit.c_str()); return 2; }
+    if ((a.editing() || a.scene_edit_given) && !a.temporal) { std::fprintf(stderr, "error: --light-step, --emitter-gain, --env-yaw-step and --scene-edit need --temporal-frames: they change the scene between the frames\n"); return 2; }
+    if (a.scene_edit_given && !a.editing()) { std::fprintf(stderr, "error: --scene-edit says how --light-step, --emitter-gain and --env-yaw-step reach the scene: give one of them\n"); return 2; }
+    if (a.editing() && !a.temporal_rectify) std::fprintf(stderr, "note: without --temporal-rectify the plain accumulation averages the change of light over its history\n");
+    std::sort(a.light_steps.begin(), a.light_steps.end(), [](const Args::LightStep& x, const Args::LightStep& y) { return x.id < y.id; });
+    std::sort(a.emitter_gains.begin(), a.emitter_gains.end(), [](const Args::EmitterGain& x, const Args::EmitterGain& y) { return x.mat < y.mat; });
     if (a.temporal && a.temporal_frames == 0) { std::fprintf(stderr, "error: --temporal-frames must be above 0\n"); return 2; }
     if (a.temporal && aov) { std::fprintf(stderr, "error: --temporal-frames with --renderer %s: temporal accumulation is for the path renderers (pt, nee, mis)\n", a.renderer.c_str()); return 2; }
     if (a.temporal && a.gpus > 1) { std::fprintf(stderr, "error: --temporal-frames with --gpus %d: temporal accumulation runs on one GPU\n", a.gpus); return 2; }
@@ -989,6 +1073,11 @@ int main(int argc, char** argv) {
             if (it.id >= scene.instance_count()) { std::fprintf(stderr, "error: invalid value for '--instance-step': scene %u has no instance %u (%u instances)\n", a.scene, it.id, scene.instance_count()); return 2; }
             scene.set_instance_dynamic(it.id);
         }
+        for (const Args::LightStep& st : a.light_steps)
+            if (st.id >= scene.light_count()) { std::fprintf(stderr, "error: invalid value for '--light-step': scene %u has no delta light %u (%u delta lights)\n", a.scene, st.id, scene.light_count()); return 2; }
+        for (const Args::EmitterGain& g : a.emitter_gains)
+            if (!scene.has_material(g.mat) || scene.material_desc(g.mat).type != MI355PT_MAT_EMISSIVE) { std::fprintf(stderr, "error: invalid value for '--emitter-gain': material %u of scene %u is not an emissive material\n", g.mat, a.scene); return 2; }
+        if (a.env_yaw_given && scene.env_count() == 0) { std::fprintf(stderr, "error: --env-yaw-step: scene %u has no environment light\n", a.scene); return 2; }
         for (const Args::MeshWave& w : a.mesh_waves)
             if (w.geom >= scene.mesh_count()) { std::fprintf(stderr, "error: invalid value for '--mesh-wave': scene %u has no mesh %u (%u meshes)\n", a.scene, w.geom, scene.mesh_count()); return 2; }
         std::puts("Start build scene.");                                                // main.rs:103-109

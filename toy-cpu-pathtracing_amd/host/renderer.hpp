@@ -686,6 +686,8 @@ public:
         if (m.type == MI355PT_MAT_CLEARCOAT) md.clearcoat_tint = lower(m.clearcoat_tint);
         uint32_t mat;
         check(mi355pt_scene_add_material(s_, &md, &mat), "mi355pt_scene_add_material");
+        if (material_descs_.size() <= mat) { material_descs_.resize(mat + 1); has_material_.resize(mat + 1, 0); }
+        material_descs_[mat] = md; has_material_[mat] = 1;
         check(mi355pt_scene_add_instance(s_, d.geometry_index.id, mat, d.transform.m), "mi355pt_scene_add_instance");
         instance_l2w_.emplace_back(d.transform.m, d.transform.m + 16);
     }
@@ -708,6 +710,8 @@ public:
         std::vector<float> rgb = load_float_image(d.texture_path, &w, &h);                 // EXR (environment_light.rs:30-41) or PFM
         mi355pt_spectrum d65 = lower_spectrum(presets::cie_illum_d6500());       // rgb_illuminant_spectrum.rs:28
         check(mi355pt_scene_add_environment_light(s_, d.intensity, rgb.data(), w, h, d.transform.m, d65.id), "mi355pt_scene_add_environment_light");
+        EnvDesc e; e.intensity = d.intensity; std::memcpy(e.l2w, d.transform.m, sizeof(e.l2w));
+        envs_.push_back(e);
     }
     void create_primitive(const PointLightPrimitive& d) { add_light(MI355PT_LIGHT_POINT, d.intensity, 0, 0, d.spectrum, d.transform); }
     void create_primitive(const SpotLightPrimitive& d) { add_light(MI355PT_LIGHT_SPOT, d.intensity, d.angle_inner, d.angle_outer, d.spectrum, d.transform); }
@@ -767,6 +771,27 @@ public:
         for (size_t k = 0; k < geoms.size(); ++k) { meshes_[geoms[k]].pos = pos[k]; meshes_[geoms[k]].nrm = nrm[k]; }
         return r;
     }
+    // EXTENSION (include/mi355pt_edit.h): materials, delta lights and environment lights of the built scene take new descriptions in place —
+    // the small records lowered again and uploaded, one launch when a material changed its class —; ids strictly ascending in each list.
+    // The mirror keeps what the scene was described with / last edited to: material_desc(), light_desc(), env_intensity(), env_transform()
+    mi355pt_edit_result edit(const Camera& cam, const std::vector<mi355pt_material_edit>& materials, const std::vector<mi355pt_light_edit>& lights,
+                             const std::vector<mi355pt_env_edit>& envs) {
+        const mi355pt_scene_edits e{materials.data(), (uint32_t)materials.size(), lights.data(), (uint32_t)lights.size(), envs.data(), (uint32_t)envs.size()};
+        mi355pt_edit_result r{};
+        check(mi355pt_scene_edit(s_, &cam.raw(), &e, &r), "mi355pt_scene_edit");
+        for (const mi355pt_material_edit& m : materials) material_descs_[m.mat] = m.desc;
+        for (const mi355pt_light_edit& l : lights) light_descs_[l.light] = l.desc;
+        for (const mi355pt_env_edit& v : envs) { envs_[v.env].intensity = v.intensity; if (v.local_to_world) std::memcpy(envs_[v.env].l2w, v.local_to_world, sizeof(envs_[v.env].l2w)); }
+        return r;
+    }
+    uint32_t material_count() const { return (uint32_t)material_descs_.size(); }
+    bool has_material(uint32_t mat) const { return mat < has_material_.size() && has_material_[mat] != 0; }      // (false: a light's hidden material)
+    const mi355pt_material_desc& material_desc(uint32_t mat) const { return material_descs_[mat]; }
+    uint32_t light_count() const { return (uint32_t)light_descs_.size(); }                                       // delta lights, in creation order
+    const mi355pt_light_desc& light_desc(uint32_t light) const { return light_descs_[light]; }
+    uint32_t env_count() const { return (uint32_t)envs_.size(); }
+    float env_intensity(uint32_t env) const { return envs_[env].intensity; }
+    const float* env_transform(uint32_t env) const { return envs_[env].l2w; }
     uint32_t mesh_count() const { return (uint32_t)meshes_.size(); }
     const TriangleMeshData& mesh(uint32_t geom) const { return meshes_[geom]; }      // as loaded / last deformed
     uint32_t instance_count() const { return (uint32_t)instance_l2w_.size(); }
@@ -785,10 +810,16 @@ public:
 private:
     std::vector<std::vector<float>> instance_l2w_;      // by instance id
     std::vector<TriangleMeshData> meshes_;              // by geometry id
+    struct EnvDesc { float intensity = 1.0f; float l2w[16]; };
+    std::vector<mi355pt_material_desc> material_descs_; // by material id (the lights' hidden materials leave gaps: has_material_)
+    std::vector<uint8_t> has_material_;
+    std::vector<mi355pt_light_desc> light_descs_;       // by delta-light id
+    std::vector<EnvDesc> envs_;                         // by environment-light id
     void add_light(uint32_t kind, float intensity, float a_in, float a_out, const Spectrum& sp, const Transform& t) {
         mi355pt_light_desc ld{}; ld.kind = kind; ld.intensity = intensity; ld.angle_inner = a_in; ld.angle_outer = a_out;
         ld.spectrum = lower_spectrum(sp); std::memcpy(ld.local_to_world, t.m, sizeof(ld.local_to_world));
         check(mi355pt_scene_add_delta_light(s_, &ld), "mi355pt_scene_add_delta_light");
+        light_descs_.push_back(ld);
     }
     uint32_t add_tex(const ImageRgb8& im) { uint32_t id; check(mi355pt_scene_add_tex_rgb8(s_, im.rgb.data(), im.w, im.h, &id), "mi355pt_scene_add_tex_rgb8"); return id; }
     mi355pt_spectrum lower_spectrum(const Spectrum& sp) {
