@@ -418,6 +418,13 @@ const char* mi355pt_version(void);
  * denoiser's, which stays the last one). */
 #include "mi355pt_edit.h"
 
+/* ---------------- bloom ---------------- */
+/* mi355pt_bloom_params, mi355pt_bloom_params_default, mi355pt_bloom_scratch_bytes, mi355pt_bloom_device and mi355pt_bloom: the glare of an
+ * HDR display chain on the device — a bright pass over the linear film, a pyramid of [1 3 3 1] reductions, a bilinear expansion that mixes
+ * the levels, a composite with the film — between the display stage's meter and its tone curve.  Declared in its own header, which this
+ * one always includes (ahead of the variance-guided denoiser's, which stays the last one). */
+#include "mi355pt_bloom.h"
+
 /* ---------------- variance-guided denoiser ---------------- */
 /* EXTENSION, no reference counterpart: a second filter beside the one above, which it leaves as it is — mi355pt_denoise_var_params,
  * mi355pt_denoise_var_params_default, mi355pt_denoise_var_scratch_bytes, mi355pt_denoise_var_device and mi355pt_denoise_var: an a-trous

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generates bindings/rust/mi355pt_sys.rs — the `extern "C"` block and #[repr(C)] structs a maintainer of the reference adds — from
-include/mi355pt.h and the include/mi355pt_denoise.h, include/mi355pt_adaptive.h, include/mi355pt_denoise_var.h, include/mi355pt_gbuffer.h, include/mi355pt_temporal.h, include/mi355pt_temporal_rectify.h, include/mi355pt_upsample.h, include/mi355pt_display.h, include/mi355pt_robust.h, include/mi355pt_rebase.h, include/mi355pt_instances.h, include/mi355pt_motion.h, include/mi355pt_deform.h, include/mi355pt_flow.h, include/mi355pt_budget.h and include/mi355pt_edit.h it includes, so that the documented Rust seam cannot drift from the header (tests/test_abi.py re-parses both and compares).
+include/mi355pt.h and the include/mi355pt_denoise.h, include/mi355pt_adaptive.h, include/mi355pt_denoise_var.h, include/mi355pt_gbuffer.h, include/mi355pt_temporal.h, include/mi355pt_temporal_rectify.h, include/mi355pt_upsample.h, include/mi355pt_display.h, include/mi355pt_robust.h, include/mi355pt_rebase.h, include/mi355pt_instances.h, include/mi355pt_motion.h, include/mi355pt_deform.h, include/mi355pt_flow.h, include/mi355pt_budget.h, include/mi355pt_edit.h and include/mi355pt_bloom.h it includes, so that the documented Rust seam cannot drift from the header (tests/test_abi.py re-parses both and compares).
 The image has no Rust toolchain: the file is generated text, checked structurally, never compiled here.
 usage: tools/gen_rust_binding.py [--check]   (--check: exit 1 if the committed file differs from what the header generates)"""
 import os, re, sys
@@ -23,6 +23,7 @@ DEFORM_HDR = os.path.join(ROOT, "include", "mi355pt_deform.h")   # the mesh-defo
 FLOW_HDR = os.path.join(ROOT, "include", "mi355pt_flow.h")   # the per-pixel motion block, likewise
 BUDGET_HDR = os.path.join(ROOT, "include", "mi355pt_budget.h")   # the sample-budget block, likewise
 EDIT_HDR = os.path.join(ROOT, "include", "mi355pt_edit.h")   # the lights-and-materials block, likewise
+BLOOM_HDR = os.path.join(ROOT, "include", "mi355pt_bloom.h")   # the bloom block, likewise
 OUT = os.path.join(ROOT, "bindings", "rust", "mi355pt_sys.rs")
 
 SCALARS = {"uint32_t": "u32", "int32_t": "i32", "uint64_t": "u64", "int64_t": "i64", "float": "f32", "double": "f64", "uint8_t": "u8",
@@ -105,10 +106,10 @@ def rust_struct_name(cname):
 
 def generate():
     structs, funcs, consts, enums = parse_header()
-    for hdr in (DENOISE_HDR, ADAPTIVE_HDR, DENOISE_VAR_HDR, GBUFFER_HDR, TEMPORAL_HDR, TEMPORAL_RECTIFY_HDR, UPSAMPLE_HDR, DISPLAY_HDR, ROBUST_HDR, REBASE_HDR, INSTANCES_HDR, MOTION_HDR, DEFORM_HDR, FLOW_HDR, BUDGET_HDR, EDIT_HDR):   # what a caller of mi355pt.h sees: all seventeen headers
+    for hdr in (DENOISE_HDR, ADAPTIVE_HDR, DENOISE_VAR_HDR, GBUFFER_HDR, TEMPORAL_HDR, TEMPORAL_RECTIFY_HDR, UPSAMPLE_HDR, DISPLAY_HDR, ROBUST_HDR, REBASE_HDR, INSTANCES_HDR, MOTION_HDR, DEFORM_HDR, FLOW_HDR, BUDGET_HDR, EDIT_HDR, BLOOM_HDR):   # what a caller of mi355pt.h sees: all eighteen headers
         for part, more in zip((structs, funcs, consts, enums), parse_header(hdr)):
             part.update(more) if isinstance(part, dict) else part.extend(more)
-    o = ["// GENERATED by tools/gen_rust_binding.py from include/mi355pt.h (+ mi355pt_denoise.h, mi355pt_adaptive.h, mi355pt_denoise_var.h, mi355pt_gbuffer.h, mi355pt_temporal.h, mi355pt_temporal_rectify.h, mi355pt_upsample.h, mi355pt_display.h, mi355pt_robust.h, mi355pt_rebase.h, mi355pt_instances.h, mi355pt_motion.h, mi355pt_deform.h, mi355pt_flow.h, mi355pt_budget.h, mi355pt_edit.h) — do not edit; `tools/gen_rust_binding.py --check` and",
+    o = ["// GENERATED by tools/gen_rust_binding.py from include/mi355pt.h (+ mi355pt_denoise.h, mi355pt_adaptive.h, mi355pt_denoise_var.h, mi355pt_gbuffer.h, mi355pt_temporal.h, mi355pt_temporal_rectify.h, mi355pt_upsample.h, mi355pt_display.h, mi355pt_robust.h, mi355pt_rebase.h, mi355pt_instances.h, mi355pt_motion.h, mi355pt_deform.h, mi355pt_flow.h, mi355pt_budget.h, mi355pt_edit.h, mi355pt_bloom.h) — do not edit; `tools/gen_rust_binding.py --check` and",
          "// tests/test_abi.py::test_rust_binding_matches_header keep it in step with the header.",
          "// The seam: renderer/src/renderer.rs:120-134 (RendererImage::render) calls mi355pt_render instead of the rayon pixel loop.",
          "#![allow(dead_code, non_upper_case_globals)]", ""]

@@ -168,6 +168,17 @@ hipError_t launch_display_hist(const float* d_film, const DisplayMeterArgs& args
 hipError_t launch_display_finish(const uint32_t* d_scratch, const DisplayMeterArgs& args, const uint32_t* d_prev_record, uint32_t* d_record, uint32_t* d_hist, hipStream_t);
 hipError_t launch_display(const float* d_film, const DisplayArgs& args, const uint32_t* d_record, float* d_out, hipStream_t);
 float display_hable(float x);      // h(x) of the header on the host, the same single-rounded steps as the kernel
+// pt_kernels_bloom.hip: the bloom stage (include/mi355pt_bloom.h) over bloom_plan.hpp's plan: 2 x levels launches on one stream — the
+// reductions 0 -> 1 (with the bright pass and, with firefly, the weights) .. L - 1 -> L into d_scratch (16-byte records, 16-byte aligned;
+// every word that is read is written first), the expansions L -> L - 1 .. 2 -> 1 in place over the levels, and the composite into d_out,
+// which may be d_film.  d_record == nullptr: E is args.exposure.  s0 is the host's f32 1 - scatter
+struct BloomArgs {
+    uint32_t width, height, levels, firefly;
+    float spp;                              // (float)spp
+    float threshold, knee, exposure;
+    float s0, s1, base, intensity;
+};
+hipError_t launch_bloom(const float* d_film, const BloomArgs& args, const uint32_t* d_record, void* d_scratch, float* d_out, hipStream_t);
 // pt_kernels_robust.hip: the robust film (include/mi355pt_robust.h): one launch, one thread per pixel, over n_buckets in {4, 8, 16, 32} films
 // of args.pixels x 3 floats at d_buckets.  d_out_half == nullptr: single output (one set of n_buckets); otherwise pair output (two sets of
 // n_buckets / 2).  d_out_trim == nullptr: not wanted.  The frame has fewer than 2^32 pixels

@@ -201,6 +201,15 @@ ENCODE = {"linear": 0, "srgb": 1}                                               
 DISPLAY_RECORD_WORDS, DISPLAY_HIST_WORDS = 8, 258
 
 
+class BloomParams(C.Structure):
+    """mi355pt_bloom_params (include/mi355pt_bloom.h); Product.bloom_params_default() fills it — a zeroed one is refused"""
+    _fields_ = [("levels", C.c_uint32), ("firefly", C.c_uint32), ("threshold", C.c_float), ("knee", C.c_float), ("scatter", C.c_float), ("base", C.c_float),
+                ("intensity", C.c_float), ("exposure", C.c_float)]
+
+
+BLOOM_MAX_LEVELS = 8
+
+
 class RobustParams(C.Structure):
     """mi355pt_robust_params (include/mi355pt_robust.h); Product.robust_params_default() gives GMON with scale 1, a zeroed one is MEAN"""
     _fields_ = [("mode", C.c_uint32), ("gini_scale", C.c_float)]
@@ -334,6 +343,8 @@ TEMPORAL_RECTIFY_SYMBOLS = ["temporal_rectify_params_default", "temporal_rectify
 UPSAMPLE_SYMBOLS = ["upsample_params_default", "upsample_low_camera", "upsample_device", "upsample"]
 # ... and include/mi355pt_display.h, the display block (tests/test_display.py)
 DISPLAY_SYMBOLS = ["display_params_default", "display_scratch_bytes", "display_meter_device", "display_device", "display_meter", "display"]
+# ... and include/mi355pt_bloom.h, the bloom block (tests/test_bloom.py)
+BLOOM_SYMBOLS = ["bloom_params_default", "bloom_scratch_bytes", "bloom_device", "bloom"]
 # ... and include/mi355pt_robust.h, the robust-film block (tests/test_robust.py)
 ROBUST_SYMBOLS = ["robust_params_default", "robust_combine_device", "robust_combine", "render_buckets_device", "render_robust"]
 # ... and include/mi355pt_rebase.h, the camera-move block (tests/test_rebase.py)
@@ -826,6 +837,12 @@ class Product(Backend):
             lib.mi355pt_display_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DisplayParams), C.c_void_p, C.c_void_p, C.c_void_p]
             lib.mi355pt_display_meter.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DisplayParams), C.c_void_p, C.c_void_p, C.c_void_p]
             lib.mi355pt_display.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DisplayParams), C.c_void_p, C.c_void_p]
+        if hasattr(lib, "mi355pt_bloom_device"):  # (absent from an older build loaded through MI355PT_LIB)
+            lib.mi355pt_bloom_params_default.argtypes = [C.POINTER(BloomParams)]; lib.mi355pt_bloom_params_default.restype = None
+            lib.mi355pt_bloom_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]; lib.mi355pt_bloom_scratch_bytes.restype = C.c_size_t
+            lib.mi355pt_bloom_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(BloomParams), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                 C.c_void_p]
+            lib.mi355pt_bloom.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(BloomParams), C.c_void_p, C.c_void_p]
         if hasattr(lib, "mi355pt_robust_combine_device"):  # (absent from an older build loaded through MI355PT_LIB)
             lib.mi355pt_robust_params_default.argtypes = [C.POINTER(RobustParams)]; lib.mi355pt_robust_params_default.restype = None
             lib.mi355pt_robust_combine_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RobustParams), C.c_void_p, C.c_void_p,
@@ -1378,6 +1395,30 @@ class Product(Backend):
         rec = None if record is None else np.ascontiguousarray(record, dtype=np.uint32)
         out = np.zeros((h, w, 3), np.float32)
         self.check(self.lib.mi355pt_display(f.ctypes.data, w, h, spp, C.byref(params), rec.ctypes.data if rec is not None else None, out.ctypes.data), "display")
+        return out
+
+    # ---- the bloom stage (include/mi355pt_bloom.h): bright pass, blur pyramid, composite; in front of the display stage ----
+    def bloom_params_default(self):
+        p = BloomParams()
+        self.lib.mi355pt_bloom_params_default(C.byref(p))
+        return p
+
+    def bloom_scratch_bytes(self, width, height, levels):
+        return int(self.lib.mi355pt_bloom_scratch_bytes(width, height, levels))
+
+    def bloom_device(self, d_film_ptr, width, height, spp, params, d_record_ptr, d_scratch_ptr, scratch_bytes, d_out_ptr, stream=None):
+        """mi355pt_bloom_device: d_record_ptr None or 0 = the constant params.exposure; d_out_ptr may be d_film_ptr"""
+        self.check(self.lib.mi355pt_bloom_device(C.c_void_p(d_film_ptr), width, height, spp, C.byref(params), C.c_void_p(d_record_ptr or 0),
+                                                            C.c_void_p(d_scratch_ptr), scratch_bytes, C.c_void_p(d_out_ptr), C.c_void_p(stream or 0)), "bloom_device")
+
+    def bloom(self, film, spp, params=None, record=None):
+        """mi355pt_bloom on a host (H, W, 3) float32 film of sums -> (H, W, 3) float32 film of spp 1; record None = the constant params.exposure"""
+        f = np.ascontiguousarray(film, dtype=np.float32)
+        h, w = f.shape[:2]
+        params = params if params is not None else self.bloom_params_default()
+        rec = None if record is None else np.ascontiguousarray(record, dtype=np.uint32)
+        out = np.zeros((h, w, 3), np.float32)
+        self.check(self.lib.mi355pt_bloom(f.ctypes.data, w, h, spp, C.byref(params), rec.ctypes.data if rec is not None else None, out.ctypes.data), "bloom")
         return out
 
     # ---- the robust film (include/mi355pt_robust.h): K bucket films, a per-pixel trimmed mean chosen by their Gini coefficient ----

@@ -43,6 +43,11 @@ struct Args {   // main.rs:20-53
     std::string tone_map; bool white_given = false; float white = 0.0f;
     bool auto_exposure = false, exposure_key_given = false, exposure_adapt_given = false, exposure_trim_given = false;
     float exposure_key = 0.0f, exposure_adapt = 0.0f; uint32_t exposure_trim[2] = {0, 0};
+    // nor the bloom stage (mi355pt_bloom.h): between the meter and the tone curve of whatever device path renders the frame.  Not given = the
+    // defaults (six levels, energy-conserving: base = 1 - intensity, no threshold); --bloom-additive: base 1 and, unless given, a threshold of 1
+    bool bloom = false, bloom_additive = false, bloom_no_firefly = false;
+    bool bloom_levels_given = false, bloom_threshold_given = false, bloom_knee_given = false, bloom_scatter_given = false, bloom_intensity_given = false;
+    uint32_t bloom_levels = 0; float bloom_threshold = 0.0f, bloom_knee = 0.0f, bloom_scatter = 0.0f, bloom_intensity = 0.0f;
     // nor the robust film (mi355pt_robust.h): --spp rendered as K buckets of --spp / K consecutive samples, combined per pixel by a trimmed
     // mean of the bucket means (0 = off).  Mode and scale not given = mi355pt_robust_params_default: GMON, 1
     uint32_t robust_buckets = 0; bool robust_given = false; std::string robust_mode; bool robust_scale_given = false; float robust_scale = 0.0f;
@@ -116,13 +121,38 @@ struct DeviceFilm {
 // made before the display stage existed.  With either, mi355pt_display_device: the chosen curve, sRGB, and — with --auto-exposure — the
 // exposure of a record that mi355pt_display_meter_device wrote: the loops of --temporal-frames meter every frame's accumulated film with
 // the previous frame's record (meter()), every other path meters the film it hands to resolve() there, with no previous record.
+// With --bloom, resolve() first meters the UN-bloomed film (the glare does not feed the exposure), then mi355pt_bloom_device with that record
+// into a buffer of the stage's own — the film it was handed, an accumulated history among them, is never written —, and what follows takes
+// that buffer as a film of spp 1.
 struct DisplayStage {
-    bool on = false, auto_exposure = false, have_record = false;
+    bool on = false, auto_exposure = false, have_record = false, bloom_on = false;
     mi355pt_display_params dp{};
+    mi355pt_bloom_params bp{};
     uint32_t* record = nullptr;
     void* scratch = nullptr;
     size_t scratch_bytes = 0;
-    void release() { (void)hipFree(record); (void)hipFree(scratch); record = nullptr; scratch = nullptr; scratch_bytes = 0; }      // (called in main: no HIP call from a static destructor)
+    float* bloom_out = nullptr;
+    void* bloom_scratch = nullptr;
+    size_t bloom_out_bytes = 0, bloom_scratch_bytes = 0;
+    void release() {      // (called in main: no HIP call from a static destructor)
+        (void)hipFree(record); (void)hipFree(scratch); (void)hipFree(bloom_out); (void)hipFree(bloom_scratch);
+        record = nullptr; scratch = nullptr; scratch_bytes = 0; bloom_out = nullptr; bloom_scratch = nullptr; bloom_out_bytes = bloom_scratch_bytes = 0;
+    }
+    static void grow(void** p, size_t* have, size_t need) {
+        if (need <= *have) return;
+        (void)hipFree(*p); *p = nullptr; *have = 0;
+        if (hipMalloc(p, need) != hipSuccess) throw std::runtime_error("mi355pt: device allocation failed");
+        *have = need;
+    }
+    // the bloomed film of `film`, spp 1, in the stage's own buffer
+    const float* bloomed(const float* film, uint32_t width, uint32_t height, uint32_t spp) {
+        if (on && auto_exposure && !have_record) meter(film, width, height, spp);
+        grow((void**)&bloom_out, &bloom_out_bytes, (size_t)width * height * 3 * sizeof(float));
+        grow(&bloom_scratch, &bloom_scratch_bytes, mi355pt_bloom_scratch_bytes(width, height, bp.levels));
+        check(mi355pt_bloom_device(film, width, height, spp, &bp, on && auto_exposure ? record : nullptr, bloom_scratch, bloom_scratch_bytes, bloom_out, nullptr),
+              "mi355pt_bloom_device");
+        return bloom_out;
+    }
     void meter(const float* film, uint32_t width, uint32_t height, uint32_t spp) {
         if (!on || !auto_exposure) return;
         const size_t need = mi355pt_display_scratch_bytes(width, height);
@@ -137,6 +167,7 @@ struct DisplayStage {
         have_record = true;
     }
     void resolve(const float* film, uint32_t width, uint32_t height, uint32_t spp, float* rgb) {
+        if (bloom_on) { film = bloomed(film, width, height, spp); spp = 1; }
         if (!on) { check(mi355pt_film_resolve_device(film, width * height, spp, rgb, nullptr), "mi355pt_film_resolve_device"); return; }
         if (auto_exposure && !have_record) meter(film, width, height, spp);
         check(mi355pt_display_device(film, width, height, spp, &dp, auto_exposure ? record : nullptr, rgb, nullptr), "mi355pt_display_device");
@@ -706,6 +737,11 @@ static void usage() {
               "                                      frame is metered and blended with the previous frame's exposure)\n"
               "                   [--exposure-key K] (0.18: the value the mean luminance is mapped to)  [--exposure-adapt A] (1; 0 .. 1: the share of the way\n"
               "                                      to the new exposure taken per frame)  [--exposure-trim LO,HI] (102,51: 1/1024ths of the pixels left out)\n"
+              "                   [--bloom] (pt|nee|mis: glare between the exposure and the tone curve of every path that ends on the device — a bright pass,\n"
+              "                              a pyramid of blurs, a composite with the frame, mi355pt_bloom_device; metered before, never fed back into --temporal-frames)\n"
+              "                   [--bloom-levels L] (6; 1 .. 8)  [--bloom-threshold T] (0; exposed units)  [--bloom-knee K] (0.5; 0 .. 1)  [--bloom-scatter S] (0.7; 0 .. 1)\n"
+              "                   [--bloom-intensity I] (0.04; the frame keeps 1 - I)  [--bloom-additive] (the frame keeps 1, I up to 16, T 1 unless given)\n"
+              "                   [--bloom-no-firefly] (no luminance weights in the first reduction)\n"
               "                   [--robust-buckets K] (pt|nee|mis, K = 4|8|16|32 dividing --spp: the frame as K buckets of consecutive samples, combined per\n"
               "                                         pixel by a trimmed mean of the bucket means: firefly rejection; with --denoise, --denoise-variance,\n"
               "                                         --fused-guides, --tone-map and --auto-exposure)\n"
@@ -788,6 +824,30 @@ int main(int argc, char** argv) {
                 std::fprintf(stderr, "error: invalid value '%s' for '--exposure-trim': two counts of 1/1024ths LO,HI whose sum is below 1024\n", v.c_str());
                 return 2;
             }
+        }
+        else if (k == "--bloom") a.bloom = true;
+        else if (k == "--bloom-additive") a.bloom_additive = true;
+        else if (k == "--bloom-no-firefly") a.bloom_no_firefly = true;
+        else if (k == "--bloom-levels") {
+            const std::string v = val();
+            char tail = 0;
+            a.bloom_levels_given = true;
+            if (std::sscanf(v.c_str(), "%u%c", &a.bloom_levels, &tail) != 1 || a.bloom_levels < 1u || a.bloom_levels > MI355PT_BLOOM_MAX_LEVELS) {
+                std::fprintf(stderr, "error: invalid value '%s' for '--bloom-levels': 1 .. 8\n", v.c_str());
+                return 2;
+            }
+        }
+        else if (k == "--bloom-threshold" || k == "--bloom-knee" || k == "--bloom-scatter" || k == "--bloom-intensity") {
+            const std::string v = val();
+            char tail = 0;
+            float x = 0.0f;
+            const bool parsed = std::sscanf(v.c_str(), "%f%c", &x, &tail) == 1;
+            const float hi = k == "--bloom-threshold" ? 0x1p16f : (k == "--bloom-intensity" ? 16.0f : 1.0f);
+            if (!parsed || !(x >= 0.0f && x <= hi)) { std::fprintf(stderr, "error: invalid value '%s' for '%s': a number in [0, %g]\n", v.c_str(), k.c_str(), (double)hi); return 2; }
+            if (k == "--bloom-threshold") { a.bloom_threshold_given = true; a.bloom_threshold = x; }
+            else if (k == "--bloom-knee") { a.bloom_knee_given = true; a.bloom_knee = x; }
+            else if (k == "--bloom-scatter") { a.bloom_scatter_given = true; a.bloom_scatter = x; }
+            else { a.bloom_intensity_given = true; a.bloom_intensity = x; }
         }
         else if (k == "--robust-buckets") { a.robust_given = true; a.robust_buckets = (uint32_t)std::stoul(val()); }
         else if (k == "--robust-mode") a.robust_mode = val();
@@ -923,6 +983,27 @@ int main(int argc, char** argv) {
     if (a.exposure_key_given) display_stage.dp.key = a.exposure_key;
     if (a.exposure_adapt_given) display_stage.dp.adapt = a.exposure_adapt;
     if (a.exposure_trim_given) { display_stage.dp.trim_low = a.exposure_trim[0]; display_stage.dp.trim_high = a.exposure_trim[1]; }
+    // the bloom stage's flags: the sub-flags need --bloom, --bloom needs a path renderer on one GPU
+    if (!a.bloom) {
+        const char* sub = a.bloom_levels_given ? "--bloom-levels" : a.bloom_threshold_given ? "--bloom-threshold" : a.bloom_knee_given ? "--bloom-knee" : a.bloom_scatter_given ? "--bloom-scatter"
+                          : a.bloom_intensity_given ? "--bloom-intensity" : a.bloom_additive ? "--bloom-additive" : a.bloom_no_firefly ? "--bloom-no-firefly" : nullptr;
+        if (sub) { std::fprintf(stderr, "error: %s needs --bloom: it is a parameter of the bloom stage\n", sub); return 2; }
+    } else {
+        if (!a.bloom_additive && a.bloom_intensity_given && a.bloom_intensity > 1.0f) { std::fprintf(stderr, "error: --bloom-intensity above 1 needs --bloom-additive: the frame keeps 1 - intensity otherwise\n"); return 2; }
+        if (aov) { std::fprintf(stderr, "error: --bloom with --renderer %s: the bloom stage takes the film of a path renderer (pt, nee, mis)\n", a.renderer.c_str()); return 2; }
+        if (a.gpus > 1) { std::fprintf(stderr, "error: --bloom with --gpus %d: the bloom stage runs on one GPU\n", a.gpus); return 2; }
+        mi355pt_bloom_params& bp = display_stage.bp;
+        mi355pt_bloom_params_default(&bp);
+        if (a.bloom_levels_given) bp.levels = a.bloom_levels;
+        if (a.bloom_no_firefly) bp.firefly = 0;
+        if (a.bloom_knee_given) bp.knee = a.bloom_knee;
+        if (a.bloom_scatter_given) bp.scatter = a.bloom_scatter;
+        if (a.bloom_intensity_given) bp.intensity = a.bloom_intensity;
+        bp.base = a.bloom_additive ? 1.0f : 1.0f - bp.intensity;
+        bp.threshold = a.bloom_threshold_given ? a.bloom_threshold : (a.bloom_additive ? 1.0f : 0.0f);
+        bp.exposure = display_stage.dp.exposure;
+        display_stage.bloom_on = true;
+    }
     // the robust film: refused here, before anything is loaded; mi355pt_robust_combine_device checks the struct again
     mi355pt_robust_params robust_params;
     mi355pt_robust_params_default(&robust_params);
@@ -1126,7 +1207,7 @@ int main(int argc, char** argv) {
         else if (a.robust_given) kernel_s = render_robust(scene, camera, image.params(sampler, a.albedo_lut), a, robust_params, image.pixels_mut());
         else if (a.denoise_variance) kernel_s = render_denoised_variance(scene, camera, image.params(sampler, a.albedo_lut), a.denoise_guide_spp, a.fused_guides, a.denoise_sigma_lum, image.pixels_mut());
         else kernel_s = a.denoise ? render_denoised(scene, camera, image.params(sampler, a.albedo_lut), a.denoise_guide_spp, a.fused_guides, image.pixels_mut())
-                                    : (display_stage.on ? render_displayed(scene, camera, image.params(sampler, a.albedo_lut), image.pixels_mut()) : image.render(sampler, a.albedo_lut));
+                                    : (display_stage.on || display_stage.bloom_on ? render_displayed(scene, camera, image.params(sampler, a.albedo_lut), image.pixels_mut()) : image.render(sampler, a.albedo_lut));
         double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         std::printf("Finish rendering: %.3f seconds.\n", wall);
         if (kernel_s > 0.0 && a.half_res) std::printf("(beauty launches at %u x %u: device %.3f s; the two G-buffers, the upsample and what follows it are in the wall time above)\n", a.width / 2, a.height / 2, kernel_s);
